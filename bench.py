@@ -9,10 +9,17 @@ Workload: ONE seeded list of N x 10 000 utterances of the S-MFCC set (ctucopy_am
 carries the timing barrier and the max-over-ranks.  Per-GPU work stays fixed as N grows ("weak" scaling); the per-rank
 frame counts in the JSON line show the balance the partition reached.
 
-A step = one pass of the hot path (ctu_engine_run through the C ABI) over the rank's resident batch.  After the timed
-region a sample of the rows it produced is checked against the CPU oracle (and every row for finiteness).
+A step = one pass of the hot path (ctu_engine_run through the C ABI) over the rank's resident batch.  A plain run sets up,
+warms up, times the steps and prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better,
+dtype, ms_per_step, ...).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+  --dump-outputs DIR  after the timed steps, writes what the last step computed: a fixed, seeded sample of 1 000 000 of its
+                      MFCC rows (DIR/mfcc_rows_sample.npy, float32 [n, 13]) and their row numbers in the batch
+                      (DIR/mfcc_rows_sample_index.npy, float64), about 60 MB in all
+  --full              everything else: the CPU baseline before the GPU legs and, after the timed region, a sample of the rows
+                      against the CPU oracle (and every row for finiteness) and the legs below
+
+With --full the line also holds
   roofline     algorithmic HBM bytes (2*wshift + 4*D = 372 B/frame) / measured kernel time vs 8 TB/s, and beside it the
                fractions of the VALU issue rate and of the LDS rate the same launch used (instruction / LDS-cycle counts
                per frame from the committed PMC passes, profiles/traffic.json, only if they are for this kernel)
@@ -24,6 +31,7 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
   configs      BASELINE.json configs[2..4] (PLP-12, exten + Burg-cepstral VAD at 8 kHz, TRAP-DCT) on their synthetic sets:
                ms per pass, frames/s, fraction of the HBM roofline at their own bytes per frame, each checked against the
                oracle on a sample (N=1 only; outside the timed region)
+  validated    finiteness of every row and the worst error of the oracle sample
 """
 import argparse
 import json
@@ -129,8 +137,19 @@ def cpu_baseline(seconds, per_worker, max_procs):
     t0 = time.perf_counter()
     procs = [ctx.Process(target=_cpu_worker, args=(list(range(w, cores * per_worker, cores)), seconds, barrier, q), daemon=True)
              for w in range(cores)]
-    for p in procs:
-        p.start()
+    # the workers never call BLAS, but numpy starts one BLAS thread per hardware thread on import and those spin for a while:
+    # one thread each, so a worker's CPU time is the oracle's alone (the children take the environment at start)
+    saved = {k: os.environ.get(k) for k in ("OPENBLAS_NUM_THREADS", "OMP_NUM_THREADS")}
+    os.environ.update({k: "1" for k in saved})
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     res = []
     for _ in procs:
         try:
@@ -251,6 +270,21 @@ def end_to_end(eng, plan, host, runs=3):
                     "utterance ranges on two streams (file decode and the HTK writer are host work outside the C ABI)"}
 
 
+DUMP_ROWS = 1_000_000  # rows in the --dump-outputs sample: 52 MB of float32 rows and 8 MB of row numbers
+
+
+def dump_outputs(out_dir, rows):
+    """What the last timed step computed: a fixed, seeded sample of its rows (sorted row numbers, the same for the same
+    arguments) as DIR/mfcc_rows_sample.npy (float32 [n, D]) and the row numbers as DIR/mfcc_rows_sample_index.npy (float64)."""
+    import torch
+    n = rows.shape[0]
+    idx = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(20260101).choice(n, size=DUMP_ROWS, replace=False))
+    sample = rows[torch.from_numpy(idx).to(rows.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "mfcc_rows_sample.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(out_dir, "mfcc_rows_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,7 +296,12 @@ def main():
     ap.add_argument("--cpu-procs", type=int, default=512, help="upper bound on CPU-baseline processes")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the e2e and configs legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline (before the GPU legs) and, after the timed region, the oracle check, roofline, e2e and configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of the last timed step's rows to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -272,7 +311,7 @@ def main():
 
     # The CPU leg first: its processes are spawned while this one has neither torch nor the HIP runtime in it
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         assert "torch" not in sys.modules
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_utts, args.cpu_procs)
 
@@ -316,10 +355,12 @@ def main():
         eng.run_device(plan, pcm, rows, stream=stream)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows)
     # per-launch kernel time from HIP events recorded by the library on this stream (separate short loop,
     # outside the timed region, because reading an event blocks the host)
     kernel_ms = []
-    for _ in range(min(args.steps, 10)):
+    for _ in range(min(args.steps, 10) if args.full else 0):
         eng.run_device(plan, pcm, rows, stream=stream)
         kernel_ms.append(eng.last_kernel_ms())
     dt, total_frames = shard.reduce_timing(dt, plan.total_frames, device=dev)
@@ -331,15 +372,16 @@ def main():
         per_rank = [int(x) for x in t.tolist()]
 
     # ---- what was timed is checked: every row finite, a sample of utterances against the CPU oracle
-    finite = bool(torch.isfinite(rows).all().item())
+    finite = bool(torch.isfinite(rows).all().item()) if args.full else None
     checked, worst = 0, 0.0
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle.oracle import Oracle
         checked, worst, _ = _validate(rows, plan, host, Oracle(CFG), 24, 1)
         if not finite or worst > 1e-4:
             raise SystemExit(f"bench validation failed: finite={finite}, worst error {worst:.3e} over {checked} frames")
 
-    if rank == 0:
+    roof = None
+    if rank == 0 and args.full:
         d = eng.dims
         kname = eng.kernel_name()
         bytes_per_frame = 2 * d.wshift + 4 * d.row_floats
@@ -379,6 +421,7 @@ def main():
                 if "mfma_busy_cycles_per_frame" in pm:  # matrix-pipe cycles summed over SIMDs: 1024 pipes at 2.4 GHz
                     roof["mfma_frac"] = fps_kernel * pm["mfma_busy_cycles_per_frame"] / (256 * 4 * 2.4e9)
                 roof["limiter"] = pm.get("limiter")
+    if rank == 0:
         result = {
             "metric": "frames/sec (16 kHz, 25 ms/10 ms, MFCC-13)",
             "value": total_frames * args.steps / dt,
@@ -396,12 +439,13 @@ def main():
                                    "512-pt FFT, 26 mel -> MFCC-13 (-preset mfcc -preem 0.97), device-resident, LPT-sharded",
                        "frames_per_rank": per_rank, "pcm_bytes_per_gpu": plan.total_samples * 2,
                        "parallelism": f"utterance shard x{world} (LPT), no collective"},
-            "roofline": roof,
-            "validated": {"rows_finite": finite, "oracle_frames_checked": checked, "worst_rel_err": worst, "tol": 1e-4},
         }
+        if args.full:
+            result["roofline"] = roof
+            result["validated"] = {"rows_finite": finite, "oracle_frames_checked": checked, "worst_rel_err": worst, "tol": 1e-4}
         if cpu is not None:
             result["cpu_baseline"] = cpu
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             try:
                 result["e2e"] = end_to_end(eng, plan, host)
             except Exception as e:  # noqa: BLE001

@@ -36,3 +36,8 @@ def synth_utt(seed, nsamples, fs=16000, noise=300.0):
     x *= 6000 * (0.6 + 0.4 * np.sin(2 * np.pi * 4 * t))
     x += rng.normal(0, noise, nsamples)
     return np.clip(np.round(x), -32768, 32767).astype(np.int16)
+
+
+def ref_outputs():
+    """What the reference's own FFTW-free pieces computed on the inputs of the *_ref tests (made by tests/golden/make_ref_fixtures.py)."""
+    return np.load(os.path.join(GOLDEN, "ref_outputs.npz"))

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final_$TAG
 mkdir -p $O
 cd $R
-python3 bench.py > $O/bench_full.json 2> $O/bench_full.err
+python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --no-cpu --no-extra > $O/trace.log 2>&1
 P="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-extra"
