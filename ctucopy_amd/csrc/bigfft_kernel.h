@@ -35,7 +35,8 @@ struct BigParams {
     const int *chain_first;
     float nr_p, nr_a;
     float2 *xri;             // speech output (-format_out raw|wave): the frame's complex spectrum [K] and, in pnr, the magnitudes the NR left [K]
-    float *pnr;              // go to the plan's scratch for bigsynth_kernel; nothing is projected.  NULL on the feature path
+    float *pnr;              // go to the plan's scratch for bigsynth_kernel; nothing is projected (xri_only).  NULL on the feature path,
+    int xri_only;            // except with the Burg-cepstral VAD criterion (bigburg_kernel.h): the same export, the projection kept
     const float *dc1;        // -remove_dc1 (bigfft_kernel): the frames' offsets (decode_kernels.h), or NULL; dc1_J = floor(window / wshift) <= 8
     int dc1_J;
     float *vad_en;           // wave1k_kernel: the VAD's energy criterion per frame (sum of squares of the vector the NR left, src/vad/vad.cc:96-107), or NULL
@@ -224,10 +225,13 @@ __global__ __launch_bounds__(256) void bigfft_kernel(const BigParams p) {
                 }
                 lds_barrier();
             }
-            if (p.xri) {  // speech output: what the NR left of the magnitudes; the inverse transform is bigsynth_kernel's
+            if (p.xri) {  // what the NR left of the magnitudes: for speech output (the inverse transform is bigsynth_kernel's, nothing is
+                          // projected) or for the Burg-cepstral VAD criterion (bigburg_kernel; the rows are computed as well)
                 for (int k = tid; k < K; k += 256) p.pnr[(rec.rbase + f) * K + k] = P[k];
-                lds_barrier();  // P and the FFT buffers are rewritten by the next frame
-                continue;
+                if (p.xri_only) {
+                    lds_barrier();  // P and the FFT buffers are rewritten by the next frame
+                    continue;
+                }
             }
             if (p.vad_en) {  // the VAD's energy criterion on the vector the NR left (frontend_kernel's vad_export == 2)
                 double s = 0.0;
@@ -350,6 +354,42 @@ __global__ __launch_bounds__(256) void bigfft_kernel(const BigParams p) {
     }
 }
 
+// The unnormalised Hermitian -> real transform of N = 2 Nc points through LDS, shared by bigsynth_kernel and bigburg_kernel
+// (bigburg_kernel.h): A holds the halfcomplex bins X[0 .. Nc] (written by the caller, not yet synchronised), Bf is the second
+// buffer, ltw the forward twiddles (cos, -sin)(2 pi m / N).  The packed half-size form
+//   Z[k] = (X[k] + X*[Nc-k]) + i e^{+2 pi i k / N} (X[k] - X*[Nc-k]),  z = IDFT_Nc(Z),  x[2n] = Re z[n], x[2n+1] = Im z[n]
+// with bigfft_kernel's Stockham radix-2 passes on the conjugate twiddles.  Returns the buffer that holds z, synchronised.
+__device__ __forceinline__ const float2 *big_hc2r_lds(float2 *A, float2 *Bf, const float2 *ltw, int Nc, int tid) {
+    lds_barrier();
+    for (int k = tid; k < Nc; k += 256) {
+        const float2 a = A[k], b = A[Nc - k];
+        const float2 sm = make_float2(a.x + b.x, a.y - b.y);  // X[k] + conj(X[M-k])
+        const float2 df = make_float2(a.x - b.x, a.y + b.y);  // X[k] - conj(X[M-k])
+        const float2 w = make_float2(ltw[k].x, -ltw[k].y);    // e^{+2 pi i k / N}
+        const float2 t = make_float2(-(w.x * df.y + w.y * df.x), w.x * df.x - w.y * df.y);  // i w df
+        Bf[k] = make_float2(sm.x + t.x, sm.y + t.y);
+    }
+    lds_barrier();
+    float2 *src = Bf, *dst = A;
+    for (int Ns = 1; Ns < Nc; Ns <<= 1) {
+        const int tstep = Nc / Ns;  // conj of W_{2Ns}^k = W_wfft^(k * Nc / Ns)
+        for (int j = tid; j < (Nc >> 1); j += 256) {
+            const int k = j & (Ns - 1);
+            const float2 w = make_float2(ltw[k * tstep].x, -ltw[k * tstep].y);
+            const float2 a = src[j], b0 = src[j + (Nc >> 1)];
+            const float2 b = make_float2(b0.x * w.x - b0.y * w.y, b0.x * w.y + b0.y * w.x);
+            const int j0 = ((j - k) << 1) + k;
+            dst[j0] = make_float2(a.x + b.x, a.y + b.y);
+            dst[j0 + Ns] = make_float2(a.x - b.x, a.y - b.y);
+        }
+        lds_barrier();
+        float2 *t_ = src;
+        src = dst;
+        dst = t_;
+    }
+    return src;
+}
+
 // Speech output on 1024 .. 4096-point frames (sigOUT, src/io/out.cc:405-434; signal_kernels.h has the 256 / 512-point form): a workgroup
 // per frame.  Every bin keeps its direction and takes the magnitude the NR left, times 1/N (DC and Nyquist as positive reals: the
 // reference stores them before its sign fix-up, out.cc:416-419); Hermitian -> real by the packed half-size inverse transform
@@ -380,33 +420,7 @@ __global__ __launch_bounds__(256) void bigsynth_kernel(const float2 *__restrict_
             }
             A[k] = v;
         }
-        lds_barrier();
-        for (int k = tid; k < Nc; k += 256) {
-            const float2 a = A[k], b = A[Nc - k];
-            const float2 sm = make_float2(a.x + b.x, a.y - b.y);  // X[k] + conj(X[M-k])
-            const float2 df = make_float2(a.x - b.x, a.y + b.y);  // X[k] - conj(X[M-k])
-            const float2 w = make_float2(ltw[k].x, -ltw[k].y);    // e^{+2 pi i k / N}
-            const float2 t = make_float2(-(w.x * df.y + w.y * df.x), w.x * df.x - w.y * df.y);  // i w df
-            Bf[k] = make_float2(sm.x + t.x, sm.y + t.y);
-        }
-        lds_barrier();
-        float2 *src = Bf, *dst = A;
-        for (int Ns = 1; Ns < Nc; Ns <<= 1) {
-            const int tstep = Nc / Ns;  // conj of W_{2Ns}^k = W_wfft^(k * Nc / Ns)
-            for (int j = tid; j < (Nc >> 1); j += 256) {
-                const int k = j & (Ns - 1);
-                const float2 w = make_float2(ltw[k * tstep].x, -ltw[k * tstep].y);
-                const float2 a = src[j], b0 = src[j + (Nc >> 1)];
-                const float2 b = make_float2(b0.x * w.x - b0.y * w.y, b0.x * w.y + b0.y * w.x);
-                const int j0 = ((j - k) << 1) + k;
-                dst[j0] = make_float2(a.x + b.x, a.y + b.y);
-                dst[j0 + Ns] = make_float2(a.x - b.x, a.y - b.y);
-            }
-            lds_barrier();
-            float2 *t_ = src;
-            src = dst;
-            dst = t_;
-        }
+        const float2 *src = big_hc2r_lds(A, Bf, ltw, Nc, tid);
         float *yo = ybuf + f * window;  // any window: 25 ms at 44.1 kHz are 1103 samples, rows of odd length are not 8-byte aligned
         for (int n = tid; n < window; n += 256) yo[n] = (n & 1) ? src[n >> 1].y : src[n >> 1].x;
         lds_barrier();

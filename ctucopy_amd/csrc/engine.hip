@@ -43,6 +43,7 @@
 #include "bigfft_kernel.h"
 #include "lp_tail_kernel.h"
 #include "wave1k_kernel.h"
+#include "bigburg_kernel.h"
 
 namespace {
 
@@ -284,7 +285,6 @@ std::string unsupported_reason(const ctu::Design &d) {
             if (nc > 32 || nc < 2) return "more than 32 (or fewer than 2) VAD cepstral coefficients";
         }
         if (o.vad_filter_order > 31) return "VAD filter order above 31";
-        if (o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "lpc" && d.window <= 128) return "Burg-cepstral VAD with an FFT size below 256 (the detector's inverse transform has the reference's size)";
     }
     if (d.wfft >= 1024) {  // bigfft_kernel.h: the plain chain
         if (d.wfft > 4096) return "FFT size above 4096";
@@ -292,10 +292,9 @@ std::string unsupported_reason(const ctu::Design &d) {
         // exten on the spectrum at 1024 .. 4096 points: wave1k_kernel / bigfft_kernel carry the recurrence along chains of whole utterances
         const bool big_exten = o.nr_mode == "exten" && !o.nr_when_afterFB && !d.signal_out;
         if ((o.nr_mode != "none" || o.nr_when_afterFB) && !big_exten) return "noise reduction with an FFT size above 512 (exten on the spectrum excepted)";
-        // the VAD on 1024-point frames: the criteria that need no spectrum behind the front end - the energy of the vector the NR left
-        // (wave1k_kernel stores it per frame) and the cepstral distance on the output vectors
-        const bool big_vad = !d.signal_out && (o.vad_cri_mode == "energy" || (o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "fea"));
-        if (o.do_vad() && !big_vad) return "VAD with an FFT size above 512 (the energy criterion and -vad_cepdist_mode fea excepted)";
+        // the VAD on 1024 .. 4096-point frames: the energy of the vector the NR left (wave1k_kernel / bigfft_kernel store it per frame),
+        // the cepstral distance on the output vectors, and the Burg-cepstral criterion on the spectra bigfft_kernel exports
+        // (bigburg_kernel.h).  Every criterion unsupported_reason lets through above is one of the three.
         if (d.B > 64) return "more than 64 bands with an FFT size above 512";
     }
     else if (d.wfft != 512 && d.wfft != 256) return "FFT size below 32";
@@ -787,7 +786,9 @@ void build_tables(ctu_engine *e) {
     e->big = d.wfft >= 1024;
     if (e->big) {
         // (-remove_dc1 at 1024 points takes bigfft_kernel<4>, which reads the frames' offsets)
-        e->wave1k = d.wfft == 1024 && !d.o.remove_dc1 && !d.signal_out && !(getenv("CTU_WAVE1K") && atoi(getenv("CTU_WAVE1K")) == 0);  // (and speech output: the spectra's export is bigfft_kernel's)
+        // (and speech output and the Burg-cepstral VAD criterion: the spectra's export is bigfft_kernel's)
+        const bool burg = d.o.do_vad() && d.o.vad_cri_mode == "cepdist" && d.o.vad_cepdist_mode == "lpc";
+        e->wave1k = d.wfft == 1024 && !d.o.remove_dc1 && !d.signal_out && !burg && !(getenv("CTU_WAVE1K") && atoi(getenv("CTU_WAVE1K")) == 0);
         build_big_tables(e);
         return;
     }
@@ -1176,6 +1177,11 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
             VadParams &vp = e->vp;
             std::memset(&vp, 0, sizeof vp);
             vp.K = d.K; vp.wfft = d.wfft; vp.window = d.window;
+            vp.krow = d.K; vp.kstride = e->kstride;
+            if (e->kstride > 1) {  // an FFT size below 256 on the 256-point mode: the detector's inverse transform keeps the configuration's size
+                vp.K = e->user_K;
+                vp.wfft = e->user_wfft;
+            }
             vp.cri = o.vad_cri_mode == "energy" ? 0 : (o.vad_cepdist_mode == "lpc" ? 1 : 2);
             vp.ncoef = vp.cri == 1 ? o.vad_lpc_coefs : d.nfea;
             vp.thr = o.vad_thr_mode == "absolute" ? 0 : o.vad_thr_mode == "perc" ? 1 : o.vad_thr_mode == "adapt" ? 2 : 3;
@@ -1640,7 +1646,9 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             bp.nr_exten = kp.nr_exten; bp.nr_p = kp.nr_p; bp.nr_a = kp.nr_a;
             bp.vad_en = (e->do_vad && e->vp.cri == 0) ? pl->pnr.p : nullptr;
             bp.dc1 = kp.remove_dc1 ? pl->dc1.p : nullptr; bp.dc1_J = kp.dc1_J;
-            bp.xri = signal ? pl->xri.p : nullptr; bp.pnr = signal ? pl->pnr.p : nullptr;
+            const bool burg = e->do_vad && e->vp.cri == 1;  // bigburg_kernel reads the spectra; the rows are projected as well
+            bp.xri = (signal || burg) ? pl->xri.p : nullptr; bp.pnr = (signal || burg) ? pl->pnr.p : nullptr;
+            bp.xri_only = signal ? 1 : 0;
             bp.chain_first = pl->wg_first.p; bp.n_chains = (int)pl->wg_first.n;
             const size_t shm = (size_t)d.wfft * 8 + (size_t)((d.K + 3) & ~3) * 4 + 64 * 4 + 4 * 8 + (size_t)d.wfft / 2 * 8 +
                                (size_t)((d.window + 3) & ~3) * 4 + (size_t)((e->big_fb_total + 3) & ~3) * 4 +
@@ -1810,7 +1818,22 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             HIP_TRY(hipGetLastError());
         }
         if (e->do_vad) {
-            if (e->vp.cri == 1 && !e->vf) {
+            if (e->vp.cri == 1 && e->big && pl->total_frames > 0) {
+                // 1024 .. 4096 points: a workgroup per frame; LDS: bigsynth_kernel's two buffers and twiddles, and the lattice's exchange area
+                const size_t bshm = ((size_t)(d.wfft / 2) * 3 + 4) * sizeof(float2) + BIGBURG_XCH * sizeof(double);
+                const dim3 g((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * std::min<size_t>(8, (160 * 1024) / bshm)));
+#define BIGBURG(NIT_)                                                                                                                       \
+    do {                                                                                                                                    \
+        if (e->vp.ncoef <= 16) hipLaunchKernelGGL((bigburg_kernel<NIT_, 16>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp, \
+                                                  (int64_t)pl->total_frames, e->big_tw.p);                                                  \
+        else hipLaunchKernelGGL((bigburg_kernel<NIT_, 32>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp,                   \
+                                (int64_t)pl->total_frames, e->big_tw.p);                                                                    \
+    } while (0)
+                if (d.wfft == 1024) BIGBURG(4);
+                else if (d.wfft == 2048) BIGBURG(8);
+                else BIGBURG(16);
+#undef BIGBURG
+            } else if (e->vp.cri == 1 && !e->vf && !e->big) {
                 const dim3 g((unsigned)std::min<int64_t>((pl->total_frames + 3) / 4, (int64_t)e->n_cu * 4));
                 const size_t bshm = (512 + (size_t)4 * 2 * (d.wfft / 2 + 4)) * 2 * sizeof(vreal);
 #define BURG_LAUNCH(Q, NC) hipLaunchKernelGGL((vad_burg_kernel<Q, NC>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp, pl->total_frames)

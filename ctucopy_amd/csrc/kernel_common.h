@@ -32,6 +32,8 @@ enum FeatMode { FEAT_BANDS = 0, FEAT_DCTC = 2, FEAT_LP = 3, FEAT_LPD = 4 };  // 
 // VAD module parameters (src/vad/vad.cc, src/vad/vad.h; used by vad_kernels.h and by the fused path of the front end)
 struct VadParams {
     int K, wfft, window, ncoef;  // ncoef = vad_lpc_coefs (cepdist lpc) or feature vector length (cepdist fea)
+    int krow, kstride;           // cepdist lpc: the exported spectra's row length and the step from one of the K bins to the next (K, 1
+                                 // unless an FFT size below 256 rides on the 256-point mode: then K and wfft are the configuration's own)
     int cri;                     // 0 energy, 1 cepdist-lpc, 2 cepdist-fea
     int thr;                     // 0 absolute, 1 perc, 2 adapt, 3 dyn
     int energy_db, cep_init, filter_order;

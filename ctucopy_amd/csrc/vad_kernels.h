@@ -37,6 +37,49 @@ __device__ __forceinline__ T wave_sum_fast(T x) {
 struct vreal2 { vreal x, y; };
 __device__ __forceinline__ vreal2 vcmul(vreal2 a, vreal2 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
+// Entry k of the halfcomplex vector the detector transforms back (src/vad/vad.cc:227-230): Xa cos(phi), Xa sin(phi) with the
+// magnitude xa the NR left and the direction of the spectrum value x.  Shared with bigburg_kernel.h.
+template <class T>
+__device__ __forceinline__ void burg_hc_bin(const float2 x, const T xa, const int k, const int K, T &re, T &im) {
+    T c = 1.0, s_ = 0.0;  // Xph[0] = 0 (src/io/in.cc:398)
+    if (k > 0) {
+        // direction of a float spectrum value: float arithmetic (v_rsq + one Newton step) is as exact as its input
+        const float mag2 = x.x * x.x + x.y * x.y;
+        if (mag2 > 0.f) {
+            float inv = __builtin_amdgcn_rsqf(mag2);
+            inv = inv * (1.5f - 0.5f * mag2 * inv * inv);
+            c = (T)(x.x * inv);
+            s_ = (T)(x.y * inv);
+        } else {  // c_ph(0, 0) = -pi/2 (src/io/in.cc:191-193); the last bin is 0 or pi by the sign of re (:399)
+            c = (k == K - 1) ? 1.0 : 0.0;
+            s_ = (k == K - 1) ? 0.0 : -1.0;
+        }
+        if (k == K - 1) s_ = 0.0;
+    }
+    re = xa * c;
+    im = (k == 0 || k == K - 1) ? (T)0.0 : xa * s_;  // FFTW's halfcomplex format has no imaginary DC / Nyquist
+}
+
+// Burg2Cepstrum (src/vdet/Burg.h:141-152) in registers, the same in every lane of a wave whose lane i holds a[i]; returns c[lane]
+// (lanes beyond NCMAX: c[0]).  Shared with bigburg_kernel.h.
+template <class T, int NCMAX>
+__device__ __forceinline__ T burg_a2c(const T acoef, const T alpha, const int lane) {
+    T av[NCMAX], cc[NCMAX];
+#pragma unroll
+    for (int i = 0; i < NCMAX; i++) av[i] = lane_read(acoef, i);
+    cc[0] = (T)log((double)alpha);
+    T mine = cc[0];
+#pragma unroll
+    for (int m = 1; m < NCMAX; m++) {
+        T sum = 0.0;
+#pragma unroll
+        for (int k = 1; k < m; k++) sum += (T)(m - k) * cc[m - k] * av[k];
+        cc[m] = -av[m] - sum * (T)(1.0 / m);
+        mine = lane == m ? cc[m] : mine;
+    }
+    return mine;
+}
+
 template <int Q, int NCMAX>  // samples per lane: window <= 64*Q; cepstral coefficients: ncoef <= NCMAX
 __global__ __launch_bounds__(256) void vad_burg_kernel(const float2 *__restrict__ xri, const float *__restrict__ pnr,
                                                        double *__restrict__ ci_out, VadParams vp, int64_t total_frames) {
@@ -59,24 +102,11 @@ __global__ __launch_bounds__(256) void vad_burg_kernel(const float2 *__restrict_
     };
     for (int64_t fr = (int64_t)blockIdx.x * 4 + wave; fr < total_frames; fr += (int64_t)gridDim.x * 4) {
     for (int k = lane; k < K; k += 64) {  // halfcomplex input: Xa cos(phi), Xa sin(phi)   (src/vad/vad.cc:227-230)
-        const float2 x = xri[fr * K + k];
-        const vreal xa = pnr[fr * K + k];
-        vreal c = 1.0, s_ = 0.0;  // Xph[0] = 0 (src/io/in.cc:398)
-        if (k > 0) {
-            // direction of a float spectrum value: float arithmetic (v_rsq + one Newton step) is as exact as its input
-            const float mag2 = x.x * x.x + x.y * x.y;
-            if (mag2 > 0.f) {
-                float inv = __builtin_amdgcn_rsqf(mag2);
-                inv = inv * (1.5f - 0.5f * mag2 * inv * inv);
-                c = (vreal)(x.x * inv);
-                s_ = (vreal)(x.y * inv);
-            } else {  // c_ph(0, 0) = -pi/2 (src/io/in.cc:191-193); the last bin is 0 or pi by the sign of re (:399)
-                c = (k == K - 1) ? 1.0 : 0.0;
-                s_ = (k == K - 1) ? 0.0 : -1.0;
-            }
-            if (k == K - 1) s_ = 0.0;
-        }
-        A[k] = {xa * c, (k == 0 || k == K - 1) ? (vreal)0.0 : xa * s_};  // FFTW's halfcomplex format has no imaginary DC / Nyquist
+        // (FFT sizes below 256 ride on the 256-point mode: bin k of the frame's own transform is bin k * kstride of the exported row)
+        const int64_t at = fr * vp.krow + k * vp.kstride;
+        vreal2 h;
+        burg_hc_bin<vreal>(xri[at], (vreal)pnr[at], k, K, h.x, h.y);
+        A[k] = h;
     }
     wave_sync();
     // FFTW_HC2R, unnormalised: x_j = sum over the Hermitian extension of X_k e^{+2 pi i jk/n}.  Packed half-size form:
@@ -175,21 +205,8 @@ __global__ __launch_bounds__(256) void vad_burg_kernel(const float2 *__restrict_
         const vreal other = __shfl(acoef, (ik - lane) & 63, 64);
         acoef = (lane >= 1 && lane < ik) ? acoef + rc * other : (lane == ik ? rc : acoef);
     }
-    // Burg2Cepstrum (src/vdet/Burg.h:141-152) in registers, the same in every lane; lane m keeps c[m] for the store
-    {
-        vreal av[NCMAX], cc[NCMAX];
-#pragma unroll
-        for (int i = 0; i < NCMAX; i++) av[i] = lane_read(acoef, i);
-        cc[0] = (vreal)log((double)alpha);
-        vreal mine = cc[0];
-#pragma unroll
-        for (int m = 1; m < NCMAX; m++) {
-            vreal sum = 0.0;
-#pragma unroll
-            for (int k = 1; k < m; k++) sum += (vreal)(m - k) * cc[m - k] * av[k];
-            cc[m] = -av[m] - sum * (vreal)(1.0 / m);
-            mine = lane == m ? cc[m] : mine;
-        }
+    {   // a -> c in registers, the same in every lane; lane m keeps c[m] for the store
+        const vreal mine = burg_a2c<vreal, NCMAX>(acoef, alpha, lane);
         if (lane < nc) ci_out[fr * nc + lane] = (double)mine;
     }
     }  // frames

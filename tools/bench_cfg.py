@@ -17,6 +17,9 @@ CFGS = {"C2": C2, "C3": C3, "C4": C4, "C4_novad": C4_NOVAD, "C5": C5, "C2_d_a": 
         "fft1024": C2 + ["-w", "40", "-s", "10"], "fft1024_exten": C2 + ["-w", "40", "-s", "10", "-nr_mode", "exten"],
         "C2_fwss16_E_d_a": C2 + "-vad burg -nr_mode fwss -fea_E on -fea_delta d_a".split(), "fft128": "-fs 8000 -format_in raw -format_out htk -preset mfcc -preem 0.97 -w 16 -s 8".split(),
         "lp_noinld": C2 + "-fb_inld off -fea_kind lpc -fea_lporder 12 -fea_ncepcoefs 12".split(), "C2_dc1": C2 + ["-remove_dc1", "on"],
+        # 44.1 kHz audio (1103 samples, 2048 points) with the VAD: the Burg-cepstral criterion (bigburg_kernel) and the energy criterion
+        "m44_vad_burg": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -vad burg -vad_out_mode vad -vad_cri_mode cepdist -vad_cepdist_mode lpc -vad_thr_mode adapt".split(),
+        "m44_vad_energy": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -vad_out_mode vad -vad_cri_mode energy -vad_thr_mode adapt".split(),
         "C2_d_a_cmvn": C2 + ["-fea_delta", "d_a", "-stat_cmvn", "x.stat", "-apply_cmvn", "x.stat"]}
 ap = argparse.ArgumentParser()
 ap.add_argument("--cfg", default="C3")
