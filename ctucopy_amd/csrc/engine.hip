@@ -111,6 +111,8 @@ struct ctu_engine {
     DevBuf<double> big_coef_d;
     int lift_off = 0, tab_floats = 0, ck_off = 0, cf_off = 0, cfd_off = 0, am_off = 0, NS = 0, CW = 4, ncoef_out = 0;
     bool md = false;        // DCT tail on the matrix cores (frontend_kernel<..., MD>): tables are laid out for its lane map
+    int walk = -1;          // compiled walk signature (phase2_walks.h) that this engine's bank and frame shape match, -1: none (or CTU_PHASE2_GENERIC)
+    int walk_launched = -1; // what the last front-end launch ran: the index of its straight-line walk, -1: the generic walk (ctu_engine_phase2_walk)
     bool half_window = false;  // the headline instantiation (DUAL): the window table is scaled by 1/2, which is the 1/4 of its power spectrum
     bool vf = false;        // Burg-cepstral VAD criterion fused into the front end (frontend_kernel<..., VF>)
     bool sy = false;        // speech-enhancement output with the inverse transform inside the front end (frontend_kernel<..., SY>)
@@ -619,6 +621,23 @@ double check_phase2(const ctu::Design &d, const Phase2Tables &t) {
     return worst;
 }
 
+// The compiled walk signature (phase2_walks.h) that this bank matches, or -1: the chunk counts per slot must be the entry's and the
+// frames the shape the entries are compiled for.  The one place that compares banks; launch_walk uses the match where the
+// instantiation it is about to launch is the one the entry was compiled with, every other instantiation walks generically.  A
+// straight-line walk is correct for every bank with these counts (first bins and band indices stay per-lane records).
+int match_walk(const ctu::Design &d, const std::vector<int> &slot_chunk) {
+    if (d.wfft != WALK_WFFT || (d.window + 31) / 32 != WALK_NZ) return -1;
+    int found = -1;
+    for_each_walk([&](auto w) {
+        typedef decltype(w) W;
+        if (found >= 0 || (int)slot_chunk.size() != W::NS + 1) return;
+        for (int s = 0; s <= W::NS; s++)
+            if (slot_chunk[s] != W::first(s)) return;
+        found = W::index;
+    });
+    return found;
+}
+
 #ifndef CTU_TRAP_BF16
 #define CTU_TRAP_BF16 1  // 0: TRAP-DCT on the fp32 matrix pipe only (trapdct_mfma_kernel)
 #endif
@@ -857,6 +876,10 @@ void build_tables(ctu_engine *e) {
     e->NS = t.NS;
     e->CW = t.CW;
     e->lift_off = t.lift_off;
+    {   // CTU_PHASE2_GENERIC=1: the generic walk for every bank (A/B and identity checks inside one build)
+        const char *g = getenv("CTU_PHASE2_GENERIC");
+        e->walk = (g && atoi(g) != 0) ? -1 : match_walk(d, t.slot_chunk);
+    }
     e->ftab.upload(t.ft);
     e->itab.upload(t.it);
     e->lds_bytes = ((size_t)TILE * PSTRIDE + e->tab_floats + LTW_FLOATS + (d.o.nr_when_afterFB ? NWAVE * 128 : 0) +
@@ -917,11 +940,32 @@ void launch_fe(ctu_engine *e, K kern, dim3 grid, hipStream_t s, const KParams &k
     hipLaunchKernelGGL(kern, grid, dim3(WG), e->lds_bytes, s, kp);
 }
 
+// A front-end launch of an instantiation that phase2_walks.h may list: with the straight-line walk when the engine's bank matched
+// the entry compiled for exactly these parameters, with the generic walk otherwise.
+template <int NZ, int FEAT, int MODE, bool VX, int GEN, int LPO, bool MD>
+void launch_walk(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
+    bool done = false;
+    if constexpr (NZ == WALK_NZ && MODE == 0 && !VX) {
+        for_each_walk([&](auto w) {
+            typedef decltype(w) W;
+            if constexpr (W::FEAT == FEAT && W::GEN == GEN && W::LPO == LPO && W::MD == MD) {
+                if (!done && e->walk == W::index) {
+                    if (kp.NS != W::NS) throw std::runtime_error("internal: walk signature of another bank");
+                    launch_fe(e, &frontend_kernel<NZ, FEAT, MODE, false, 16, GEN, LPO, MD, false, false, false, W>, grid, s, kp);
+                    e->walk_launched = W::index;
+                    done = true;
+                }
+            }
+        });
+    }
+    if (!done) launch_fe(e, &frontend_kernel<NZ, FEAT, MODE, VX, 16, GEN, LPO, MD>, grid, s, kp);
+}
+
 template <int NZ, int MODE, bool VX, int GEN>
 void launch_nz(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
     const bool wide = kp.CW != 16;  // coefficient rows of MAXC entries (more than 16 cepstra / LP lags)
     const int feat = e->feat;
-    if (feat == FEAT_BANDS) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, VX, 16, GEN>, grid, s, kp);
+    if (feat == FEAT_BANDS) launch_walk<NZ, FEAT_BANDS, MODE, VX, GEN, 0, false>(e, grid, s, kp);
     else if (feat == FEAT_DCTC && !wide) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, VX, 16, GEN>, grid, s, kp);
     else if (feat == FEAT_DCTC) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, VX, MAXC, GEN>, grid, s, kp);
     else if (feat == FEAT_LPD) {
@@ -942,6 +986,7 @@ void launch_vx(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
     // with the VAD export, reads its flags at run time.
     const bool vx = kp.vad_export != 0;
     const int feat = e->feat;
+    e->walk_launched = -1;  // launch_walk sets it where it launches a straight-line walk
     const bool base = !vx && kp.e_mode == 0 && kp.fb_power && kp.remove_dc && !kp.remove_dc1 && !kp.dbg && !kp.skip_phase2 && !kp.nr_after_fb;
     const bool narrow = kp.CW == 16;
     {   // the window table of this engine is scaled for exactly one instantiation (ctu_engine::half_window)
@@ -1009,13 +1054,13 @@ void launch_vx(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
     }
     else if (e->md && feat == FEAT_LP) {  // the compressed-band LP chain: lags by the MFMA tail, the recursions in lp_tail_kernel
         if (!(base && kp.fb_inld && !kp.nr_exten && narrow)) throw std::runtime_error("internal: MD tables without the MD instantiation");
-        if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_INLD, 12, true>, grid, s, kp);
+        if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) launch_walk<NZ, FEAT_LP, MODE, false, GEN_INLD, 12, true>(e, grid, s, kp);
         else launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_INLD, 0, true>, grid, s, kp);
     }
     else if (e->md) {
         if (!(base && !kp.fb_inld && feat == FEAT_DCTC && narrow)) throw std::runtime_error("internal: MD tables without the MD instantiation");
         if (kp.nr_exten) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_EXTEN, 0, true>, grid, s, kp);
-        else launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_PLAIN, 0, true>, grid, s, kp);
+        else launch_walk<NZ, FEAT_DCTC, MODE, false, GEN_PLAIN, 0, true>(e, grid, s, kp);
     }
     else if (vx) launch_nz<NZ, MODE, true, GEN_FULL>(e, grid, s, kp);
     else if (base && !kp.fb_inld && !kp.nr_exten && feat != FEAT_LPD) launch_nz<NZ, MODE, false, GEN_PLAIN>(e, grid, s, kp);
@@ -1085,6 +1130,12 @@ int64_t ctu_config_table(int argc, const char *const *argv, const char *name, do
             Phase2Tables t;
             build_phase2(d, t);
             v = {check_phase2(d, t), (double)t.slot_chunk.back(), (double)t.NS};
+        }
+        else if (n == "phase2_walk") {  // chunks per slot, then the index of the compiled walk signature (phase2_walks.h) or -1
+            Phase2Tables t;
+            build_phase2(d, t);
+            for (int sl = 0; sl < t.NS; sl++) v.push_back(t.slot_chunk[sl + 1] - t.slot_chunk[sl]);
+            v.push_back((double)match_walk(d, t.slot_chunk));
         }
         else {
             g_create_error = "unknown table name";
@@ -2406,6 +2457,8 @@ const char *ctu_engine_kernel_name(const ctu_engine *e) {
     }
     return e->kname.c_str();
 }
+
+int ctu_engine_phase2_walk(const ctu_engine *e) { return e ? e->walk_launched : -1; }
 
 float ctu_engine_last_kernel_ms(ctu_engine *e) {
     if (!e || !e->timed) return -1.f;

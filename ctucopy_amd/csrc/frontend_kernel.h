@@ -2,6 +2,8 @@
 // Included by engine.hip (one translation unit: the kernels and their host launchers share types).
 #pragma once
 
+#include "phase2_walks.h"
+
 namespace {
 
 // NZ = number of 32-sample rows that can hold non-zero input (ceil(window/32)); rows >= NZ are
@@ -78,6 +80,9 @@ namespace {
 // SY:     speech-enhancement output (row N3, sigOUT src/io/out.cc:405-434): the step's spectra after NR go back to the time
 //         domain in registers (the inverse of vad_fused.h with the synthesis conventions) and the frames are written for
 //         the overlap-add kernel; no spectra through HBM, no phase 2.
+// WALK:   walk_generic, or a compile-time walk signature of phase 2's filter bank (phase2_walks.h: the preset banks): the slot loop
+//         and every slot's chunk run are straight-line, with the chunk counts and table addresses as immediates.  Same tables, same
+//         lane mapping, same order of additions: the rows are those of the generic walk bit for bit.
 // The fused detector paths of the 512-point mode (VF / SS with MODE 0) keep both passes' transform outputs and a 25-sample
 // lattice per lane alive: 256 VGPRs, one workgroup per CU (their staging area takes the LDS of the second one anyway).
 #ifndef CTU_SY_LB
@@ -90,7 +95,17 @@ constexpr int fe_waves_per_simd(int mode, bool vf, bool ss, bool sy = false) {
     return ((vf || ss) && mode == 0) ? 2 : (sy ? CTU_SY_LB : ((vf || ss) ? CTU_VF1_LB : CTU_LB));
 }
 
-template <int NZ, int FEAT, int MODE, bool VX, int NC, int GEN, int LPO = 0, bool MD = false, bool VF = false, bool SS = false, bool SY = false>
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
+template <class F, int... S>
+__device__ __forceinline__ void static_for_seq(F &&f, std::integer_sequence<int, S...>) {
+    (f(std::integral_constant<int, S>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
+template <int NZ, int FEAT, int MODE, bool VX, int NC, int GEN, int LPO = 0, bool MD = false, bool VF = false, bool SS = false, bool SY = false, class WALK = walk_generic>
 #if CTU_CAP_WAVES
 // also the MOST waves per SIMD the register file is laid out for: a workgroup is eight waves and the grid is at most two workgroups per
 // CU (engine.hip: max_wg), i.e. four per SIMD when they are dealt evenly.  An instantiation that needs 96 registers or fewer would be
@@ -1140,71 +1155,51 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
             uint32_t wbasea = (uint32_t)(size_t)(lvoid_t *)(ltab + g * 4);
             uint32_t ama = (uint32_t)(size_t)(lvoid_t *)(ltab + p.am_off + lane);
             asm volatile("" : "+v"(cella), "+v"(prowa), "+v"(wbasea), "+v"(ama));
-            li4_t *cellp = (li4_t *)(size_t)cella;
             lf_t *amp = (lf_t *)(size_t)ama;
-            int32x4 nxt = cellp[0];
-            for (int sl = 0; sl < p.NS; sl++) {
-                const int32x4 cur = nxt;
-                cellp += 8;
-                nxt = cellp[0];  // the table ends on a slot of idle cells
-                float a0 = 0.f, a1 = 0.f;
-                if constexpr (MD && !LPD) {
-                    a0 = amp[0];
-                    a1 = amp[64];
-                    amp += 128;
-                }
-                const int kstart = cur.x, bidx = cur.y;
-                const int nch = __builtin_amdgcn_readfirstlane(cur.w);
-                lf4_t *pq = (lf4_t *)(size_t)(prowa + 4u * (uint32_t)kstart);  // kstart is a multiple of 4
-                lf4_t *wq = (lf4_t *)(size_t)(wbasea + 128u * (uint32_t)cur.z);
-                float acc = 0.f, accb = 0.f;
-                int ch = 0;
-                for (; ch + 4 <= nch; ch += 4) {  // 4 chunks per group: 8 LDS reads in flight, then 16 FMAs
-                    f32x4 w4[4], p4[4];
+            // The chunk arithmetic, stated once for both walks.  Four chunks (8 LDS reads in flight, then 16 FMAs): chunk u adds its four
+            // products into acc for even u and into accb for odd u; the two- and one-chunk remainders alternate acc / accb per component.
+            auto fb_quad = [](lf4_t *pq, lf4_t *wq, float &acc, float &accb) {
+                f32x4 w4[4], p4[4];
 #pragma unroll
-                    for (int u = 0; u < 4; u++) w4[u] = wq[u * 8];
+                for (int u = 0; u < 4; u++) w4[u] = wq[u * 8];
 #pragma unroll
-                    for (int u = 0; u < 4; u++) p4[u] = pq[u];
+                for (int u = 0; u < 4; u++) p4[u] = pq[u];
 #pragma unroll
-                    for (int u = 0; u < 4; u += 2) {
-                        acc += w4[u].x * p4[u].x;
-                        accb += w4[u + 1].x * p4[u + 1].x;
-                        acc += w4[u].y * p4[u].y;
-                        accb += w4[u + 1].y * p4[u + 1].y;
-                        acc += w4[u].z * p4[u].z;
-                        accb += w4[u + 1].z * p4[u + 1].z;
-                        acc += w4[u].w * p4[u].w;
-                        accb += w4[u + 1].w * p4[u + 1].w;
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // DS reads
-                    __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);  // VALU
-                    pq += 4;
-                    wq += 32;
+                for (int u = 0; u < 4; u += 2) {
+                    acc += w4[u].x * p4[u].x;
+                    accb += w4[u + 1].x * p4[u + 1].x;
+                    acc += w4[u].y * p4[u].y;
+                    accb += w4[u + 1].y * p4[u + 1].y;
+                    acc += w4[u].z * p4[u].z;
+                    accb += w4[u + 1].z * p4[u + 1].z;
+                    acc += w4[u].w * p4[u].w;
+                    accb += w4[u + 1].w * p4[u + 1].w;
                 }
-                if (nch & 2) {
-                    const f32x4 wa = wq[0], wb = wq[8];
-                    const f32x4 pa = pq[0], pb = pq[1];
-                    acc += wa.x * pa.x;
-                    accb += wa.y * pa.y;
-                    acc += wa.z * pa.z;
-                    accb += wa.w * pa.w;
-                    acc += wb.x * pb.x;
-                    accb += wb.y * pb.y;
-                    acc += wb.z * pb.z;
-                    accb += wb.w * pb.w;
-                    pq += 2;
-                    wq += 16;
-                }
-                if (nch & 1) {
-                    const f32x4 w4 = wq[0];
-                    const f32x4 p4 = pq[0];
-                    acc += w4.x * p4.x;
-                    accb += w4.y * p4.y;
-                    acc += w4.z * p4.z;
-                    accb += w4.w * p4.w;
-                }
-                acc += accb;
-                float y = acc;
+                __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // DS reads
+                __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);  // VALU
+            };
+            auto fb_pair = [](lf4_t *pq, lf4_t *wq, float &acc, float &accb) {
+                const f32x4 wa = wq[0], wb = wq[8];
+                const f32x4 pa = pq[0], pb = pq[1];
+                acc += wa.x * pa.x;
+                accb += wa.y * pa.y;
+                acc += wa.z * pa.z;
+                accb += wa.w * pa.w;
+                acc += wb.x * pb.x;
+                accb += wb.y * pb.y;
+                acc += wb.z * pb.z;
+                accb += wb.w * pb.w;
+            };
+            auto fb_single = [](lf4_t *pq, lf4_t *wq, float &acc, float &accb) {
+                const f32x4 w4 = wq[0];
+                const f32x4 p4 = pq[0];
+                acc += w4.x * p4.x;
+                accb += w4.y * p4.y;
+                acc += w4.z * p4.z;
+                accb += w4.w * p4.w;
+            };
+            // What follows a slot's band energy y: compression, afterFB exten, energy column, logarithm, band store or DCT / LP accumulation
+            auto slot_tail = [&](const int sl, const int bidx, const float a0, const float a1, float y) {
                 if (o_fb_inld) y = __builtin_amdgcn_exp2f(0.33f * __builtin_amdgcn_logf(y));  // pow(Y, 0.33), src/fea/fb.cc:81-83
                 if (FULL && o_after_fb && o_nr_exten) {
                     // exten on the band energies (src/io/batch.cc:207-210; nr.cc:95-140 on fb->_Y): sequential over the step's
@@ -1269,6 +1264,64 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                             cell_accumulate<NC>(c, cf, y);
                         }
                     }
+                }
+            };
+            if constexpr (WALK::NS > 0) {
+                // Straight-line walk of a preset bank: per lane only {first bin, band}, one 8-byte read per slot (the compiler pairs the
+                // reads of two slots where it has the registers); chunk counts, weight and DCT operand addresses are immediates on
+                // wbasea / ama
+                typedef const __attribute__((address_space(3))) int32x2 li2_t;
+                li2_t *cell2 = (li2_t *)(size_t)cella;
+                static_for<WALK::NS>([&](auto SL) {
+                    constexpr int sl = decltype(SL)::value, nch = WALK::nch(sl), first = WALK::first(sl);
+                    const int32x2 kb = cell2[16 * sl];
+                    float a0 = 0.f, a1 = 0.f;
+                    if constexpr (MD && !LPD) {
+                        a0 = amp[128 * sl];
+                        a1 = amp[128 * sl + 64];
+                    }
+                    lf4_t *pq = (lf4_t *)(size_t)(prowa + 4u * (uint32_t)kb.x);  // kstart is a multiple of 4
+                    lf4_t *wq = (lf4_t *)(size_t)wbasea + 8 * first;
+                    float acc = 0.f, accb = 0.f;
+#pragma unroll
+                    for (int ch = 0; ch + 4 <= nch; ch += 4) fb_quad(pq + ch, wq + 8 * ch, acc, accb);
+                    if constexpr ((nch & 2) != 0) fb_pair(pq + (nch & ~3), wq + 8 * (nch & ~3), acc, accb);
+                    if constexpr ((nch & 1) != 0) fb_single(pq + (nch & ~1), wq + 8 * (nch & ~1), acc, accb);
+                    acc += accb;
+                    slot_tail(sl, kb.y, a0, a1, acc);
+                });
+            } else {
+                li4_t *cellp = (li4_t *)(size_t)cella;
+                int32x4 nxt = cellp[0];
+                for (int sl = 0; sl < p.NS; sl++) {
+                    const int32x4 cur = nxt;
+                    cellp += 8;
+                    nxt = cellp[0];  // the table ends on a slot of idle cells
+                    float a0 = 0.f, a1 = 0.f;
+                    if constexpr (MD && !LPD) {
+                        a0 = amp[0];
+                        a1 = amp[64];
+                        amp += 128;
+                    }
+                    const int kstart = cur.x, bidx = cur.y;
+                    const int nch = __builtin_amdgcn_readfirstlane(cur.w);
+                    lf4_t *pq = (lf4_t *)(size_t)(prowa + 4u * (uint32_t)kstart);  // kstart is a multiple of 4
+                    lf4_t *wq = (lf4_t *)(size_t)(wbasea + 128u * (uint32_t)cur.z);
+                    float acc = 0.f, accb = 0.f;
+                    int ch = 0;
+                    for (; ch + 4 <= nch; ch += 4) {
+                        fb_quad(pq, wq, acc, accb);
+                        pq += 4;
+                        wq += 32;
+                    }
+                    if (nch & 2) {
+                        fb_pair(pq, wq, acc, accb);
+                        pq += 2;
+                        wq += 16;
+                    }
+                    if (nch & 1) fb_single(pq, wq, acc, accb);
+                    acc += accb;
+                    slot_tail(sl, bidx, a0, a1, acc);
                 }
             }
             STAMP(8);  // filter bank + per-band accumulation

@@ -108,6 +108,7 @@ struct KParams {
 #endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));  // MFMA accumulator
 typedef int int32x4 __attribute__((ext_vector_type(4)));
+typedef int int32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 // A pointer that is the same in every lane, pinned to SGPRs: stores through it take the scalar-base + 32-bit lane-offset form, so the

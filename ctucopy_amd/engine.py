@@ -32,7 +32,7 @@ class Dims(ctypes.Structure):
 EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_last_error", "ctu_engine_dims",
            "ctu_config_dims", "ctu_config_table", "ctu_num_frames", "ctu_plan_create", "ctu_plan_destroy", "ctu_plan_sample_offsets",
            "ctu_plan_row_offsets", "ctu_arena_layout", "ctu_plan_total_samples", "ctu_plan_total_frames", "ctu_engine_run",
-           "ctu_engine_run_host", "ctu_host_alloc", "ctu_host_free", "ctu_engine_reset_chain", "ctu_engine_set_vad_stream", "ctu_vad_ring_step", "ctu_plan_set_vad_ring", "ctu_vad_ring_rows", "ctu_decode_g711", "ctu_engine_last_kernel_ms", "ctu_engine_kernel_name", "ctu_cmvn_cols", "ctu_cmvn_accumulate", "ctu_cmvn_apply",
+           "ctu_engine_run_host", "ctu_host_alloc", "ctu_host_free", "ctu_engine_reset_chain", "ctu_engine_set_vad_stream", "ctu_vad_ring_step", "ctu_plan_set_vad_ring", "ctu_vad_ring_rows", "ctu_decode_g711", "ctu_engine_last_kernel_ms", "ctu_engine_kernel_name", "ctu_engine_phase2_walk", "ctu_cmvn_cols", "ctu_cmvn_accumulate", "ctu_cmvn_apply",
            "ctu_cmvn_accumulate_host", "ctu_cmvn_apply_host", "ctu_plan_out_samples", "ctu_engine_run_signal",
            "ctu_engine_run_signal_host"]
 
@@ -91,6 +91,8 @@ def load_library():
     L.ctu_engine_last_kernel_ms.argtypes = [vp]
     L.ctu_engine_kernel_name.restype = ctypes.c_char_p
     L.ctu_engine_kernel_name.argtypes = [vp]
+    if hasattr(L, "ctu_engine_phase2_walk"):  # absent from older builds loaded through CTU_ENGINE_LIB for an A/B
+        L.ctu_engine_phase2_walk.argtypes = [vp]
     L.ctu_cmvn_cols.argtypes = [vp]
     L.ctu_cmvn_accumulate.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
     L.ctu_cmvn_apply.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
@@ -326,6 +328,10 @@ class Engine:
 
     def kernel_name(self):
         return load_library().ctu_engine_kernel_name(self._h).decode()
+
+    def phase2_walk(self):
+        """Index of the straight-line filter-bank walk that the last run's front end was launched with, or -1 (generic walk)."""
+        return int(load_library().ctu_engine_phase2_walk(self._h))
 
     def vad_ring_of_list(self, nsamples, order):
         """historyIdx each file of a list starts with when the list is one process's (ctu_vad_ring_step from 0, 0)."""

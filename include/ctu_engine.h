@@ -75,7 +75,10 @@ int ctu_config_dims(int argc, const char *const *argv, ctu_dims *out);
 
 /* Host-designed tables in double precision (no device needed), for inspection and tests:
  * name = "hamming" [window] | "fbank" [nbands*nbins] | "fb_first" | "fb_last" [nbands] |
- *        "dct" [(ncep+1)*nbands] | "idft" [(p+1)*nbands] | "trap" [ndct*traplen] | "lifter" [ncep].
+ *        "dct" [(ncep+1)*nbands] | "idft" [(p+1)*nbands] | "trap" [ndct*traplen] | "lifter" [ncep] |
+ *        "phase2_check" [3: table error, chunks, slots] | "phase2_walk" [slots + 1: the filter-bank walk's chunks per slot, then the
+ *        index of the compiled walk signature that this configuration's bank and frame shape match, or -1; whether a run uses it
+ *        depends on the instantiation too: ctu_engine_phase2_walk].
  * Returns the number of values (written up to cap), or a negative error code. */
 int64_t ctu_config_table(int argc, const char *const *argv, const char *name, double *out, int64_t cap);
 
@@ -157,6 +160,10 @@ float ctu_engine_last_kernel_ms(ctu_engine *);
 /* Name of that kernel: the instantiation this engine's configuration runs its front end on (profiles and the bench's roofline
  * line are keyed by it).  Valid for the life of the engine. */
 const char *ctu_engine_kernel_name(const ctu_engine *);
+/* What the front-end launch of the last run walked the filter bank with: the index of the compiled walk signature whose
+ * straight-line kernel was launched, or -1 for the generic walk (no run yet, no signature matches the bank and frame shape, the
+ * configuration's instantiation has no straight-line form, or CTU_PHASE2_GENERIC=1 was set at create). */
+int ctu_engine_phase2_walk(const ctu_engine *);
 
 /* ---- per-speaker CMVN over rows that are resident on the device -----------------------------------------------
  * Replaces cmvn_POST::sum_fea / stat_cm / sum_cv / stat_cv / process_frame (src/fea/post_impl.cc:51-118) and the
