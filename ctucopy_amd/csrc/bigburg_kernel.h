@@ -13,7 +13,8 @@
 //   * the prediction coefficients one per lane, redundantly in each wave; a -> c (burg_a2c); wave 0 stores vad_ci.
 // The sums run over 1103 or 3072 samples and the decisions downstream are states, so the lattice is double throughout: the kernel
 // is bound by its chain of (at most 31) reduction-and-barrier steps, not by arithmetic.
-// Resources (gfx950, -O3, the code object's metadata): VGPRs <4,16> 97, <8,16> 109, <16,16> 168, <4,32> 161, <8,32> 169, <16,32> 186
+// Resources (gfx950, -O3, the code object's metadata): VGPRs <4,16> 97, <8,16> 109, <16,16> 157, <4,32> 162, <8,32> 170, <16,32> 187;
+// the *ss modes' detector bigssdet_kernel (below) <8,16> 117, <8,32> 178, <16,16> 175, <16,32> 195
 // (one wave per SIMD and workgroup: up to 512 are free), 106 SGPRs, no scratch; LDS 3 wfft / 2 float2 + 32 + 384 bytes: 12.4 KiB at
 // 1024 points, 24.4 KiB at 2048, 48.4 KiB at 4096 - under 64 KiB, three workgroups a CU at the largest size.
 // Included by engine.hip after vad_kernels.h and bigfft_kernel.h.
@@ -23,11 +24,15 @@ namespace {
 
 constexpr int BIGBURG_XCH = 3 * 4 * 4;  // doubles: [order parity | energy][wave][num, den, ef, eb[i - 1]]
 
-template <int NIT, int NCMAX>  // NIT = wfft / 256 samples per thread; cepstral coefficients: ncoef <= NCMAX
-__global__ __launch_bounds__(256) void bigburg_kernel(const float2 *__restrict__ xri, const float *__restrict__ pnr, double *__restrict__ ci_out,
-                                                      const VadParams vp, const int64_t total_frames, const float2 *__restrict__ tw) {
+// SSDET: the detector of hwss / fwss / 2fwss (src/nr/nr.cc:278-295, src/vdet/CepstralDet.h:133-146) instead of the VAD's criterion: the
+// magnitudes are X^a of the exported vector (X itself in 2fwss) and the first `window` samples take the detector's Hann window
+// (han[window], doubles) ahead of the lattice.  The cepstra's recurrences are ss_decide_kernel's (bigss_kernel.h).
+template <int NIT, int NCMAX, bool SSDET>  // NIT = wfft / 256 samples per thread; cepstral coefficients: ncoef <= NCMAX
+__device__ __forceinline__ void bigburg_frames(const float2 *__restrict__ xri, const float *__restrict__ pnr, double *__restrict__ ci_out, const int wfft,
+                                               const int W, const int nc, const int64_t total_frames, const float2 *__restrict__ tw,
+                                               const double *__restrict__ han, const float ss_a, const int ss_two) {
     extern __shared__ __align__(16) float smem[];
-    const int Nc = vp.wfft >> 1, K = Nc + 1, W = vp.window, nc = vp.ncoef;
+    const int Nc = wfft >> 1, K = Nc + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float2 *A = reinterpret_cast<float2 *>(smem);       // [Nc + 1]
     float2 *Bf = A + Nc + 4;                            // [Nc]
@@ -38,7 +43,9 @@ __global__ __launch_bounds__(256) void bigburg_kernel(const float2 *__restrict__
     for (int64_t fr = blockIdx.x; fr < total_frames; fr += gridDim.x) {
         for (int k = tid; k <= Nc; k += 256) {
             float2 h;
-            burg_hc_bin<float>(xri[fr * K + k], pnr[fr * K + k], k, K, h.x, h.y);
+            float xa = pnr[fr * K + k];
+            if constexpr (SSDET) xa = ss_two ? xa : ss_pow(xa, ss_a);
+            burg_hc_bin<float>(xri[fr * K + k], xa, k, K, h.x, h.y);
             A[k] = h;
         }
         const float2 *z = big_hc2r_lds(A, Bf, ltw, Nc, tid);
@@ -49,6 +56,7 @@ __global__ __launch_bounds__(256) void bigburg_kernel(const float2 *__restrict__
             const int j = tid * NIT + q;  // < wfft
             const float2 v = z[j >> 1];
             ef[q] = j < W ? (double)((j & 1) ? v.y : v.x) : 0.0;  // only the first `window` samples go to Burg (src/vad/vad.cc:233)
+            if constexpr (SSDET) ef[q] = j < W ? han[j] * ef[q] : 0.0;
             eb[q] = ef[q];
             part = fma(ef[q], ef[q], part);
         }
@@ -56,6 +64,7 @@ __global__ __launch_bounds__(256) void bigburg_kernel(const float2 *__restrict__
         if (wave > 0 && tid * NIT - 1 < W) {
             const float2 v = z[(tid * NIT - 1) >> 1];
             edge = (double)v.y;  // an odd index
+            if constexpr (SSDET) edge *= han[tid * NIT - 1];
         }
         // (the transform's buffers are rewritten by the next frame: the barriers below come first)
         part = wave_sum_fast(part);
@@ -114,6 +123,19 @@ __global__ __launch_bounds__(256) void bigburg_kernel(const float2 *__restrict__
         const double c_lane = burg_a2c<double, NCMAX>(acoef, alpha, lane);
         if (wave == 0 && lane < nc) ci_out[fr * nc + lane] = c_lane;
     }
+}
+
+template <int NIT, int NCMAX>
+__global__ __launch_bounds__(256) void bigburg_kernel(const float2 *__restrict__ xri, const float *__restrict__ pnr, double *__restrict__ ci_out,
+                                                      const VadParams vp, const int64_t total_frames, const float2 *__restrict__ tw) {
+    bigburg_frames<NIT, NCMAX, false>(xri, pnr, ci_out, vp.wfft, vp.window, vp.ncoef, total_frames, tw, nullptr, 1.f, 0);
+}
+
+template <int NIT, int NCMAX>
+__global__ __launch_bounds__(256) void bigssdet_kernel(const float2 *__restrict__ xri, const float *__restrict__ pnr, double *__restrict__ ci_out,
+                                                       const int wfft, const int window, const int nc, const int64_t total_frames,
+                                                       const float2 *__restrict__ tw, const double *__restrict__ han, const float ss_a, const int ss_two) {
+    bigburg_frames<NIT, NCMAX, true>(xri, pnr, ci_out, wfft, window, nc, total_frames, tw, han, ss_a, ss_two);
 }
 
 }  // namespace

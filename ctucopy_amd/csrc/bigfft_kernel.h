@@ -2,8 +2,10 @@
 // src/io/opts.cc:277-280 allows any power of two).  The 16-lane register transforms of frontend_kernel.h are built for 512
 // and 256 points and for P rows of 260 floats; these sizes take the plain road: one workgroup per frame, the packed real
 // FFT as a Stockham radix-2 autosort through two LDS buffers, the power spectrum in LDS, four lanes per band for the
-// filter bank, one lane per output coefficient.  The plain chain only (no noise reduction, no VAD): pre-emphasis,
-// window, mean removal, |.|^2 or |.|, any filter bank, ^0.33, log, DCT / band outputs / LP analysis, the energy column.
+// filter bank, one lane per output coefficient.  The plain chain: pre-emphasis, window, mean removal, |.|^2 or |.|, any
+// filter bank, ^0.33, log, DCT / band outputs / LP analysis, the energy column (big_project); exten along chains of whole
+// utterances (EXTEN); the export of the spectra for the speech output, the Burg-cepstral VAD criterion (bigburg_kernel.h)
+// and hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h, which subtracts and calls big_project itself).
 // Every barrier here hands over LDS data only (lds_barrier, trap_kernel.h): __syncthreads() would also drain the vector-memory
 // counter, i.e. wait for the samples fetched a frame ahead and for the previous frame's row stores at every pass.
 // Included by engine.hip.
@@ -40,6 +42,15 @@ struct BigParams {
     const float *dc1;        // -remove_dc1 (bigfft_kernel): the frames' offsets (decode_kernels.h), or NULL; dc1_J = floor(window / wshift) <= 8
     int dc1_J;
     float *vad_en;           // wave1k_kernel: the VAD's energy criterion per frame (sum of squares of the vector the NR left, src/vad/vad.cc:96-107), or NULL
+    // hwss / fwss / 2fwss on 2048 / 4096-point frames (bigss_kernel.h): bigfft_kernel exports the spectra once (xri_only; with
+    // -fea_rawenergy it also leaves the energy column), bigss_kernel walks the chains once per pass of the seed iteration
+    int ss_mode, ss_init;    // 1 / 2 / 3 = hwss / fwss / 2fwss; -nr_initsegs
+    double ss_a, ss_b, ss_p; // -nr_a, -nr_b, -nr_p
+    const float *ss_seed;    // [n_utt][K] what every utterance's noise estimate starts from
+    float *ss_last;          // [n_utt][K] the vector every utterance leaves behind
+    const unsigned char *ss_dirty, *ss_vbits;  // [n_utt] utterances this pass recomputes; [total_frames] the detector's decisions
+    const int *tile_utt;     // utterance of every tile
+    float *pss;              // speech output: the subtracted magnitudes [total_frames][K] for bigsynth_kernel (pnr stays as exported), or NULL
 };
 
 __device__ __forceinline__ double block_sum(double v, double *red) {  // 256 threads; red: 4 doubles of LDS
@@ -48,6 +59,130 @@ __device__ __forceinline__ double block_sum(double v, double *red) {  // 256 thr
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     lds_barrier();
     return red[0] + red[1] + red[2] + red[3];
+}
+
+// The projection of a frame's spectrum vector P[K] (LDS, synchronised) onto its output row: the VAD's energy criterion, the energy
+// column, the filter bank (four lanes per band), ^0.33 / log, then DCT rows / band outputs / LP analysis in double.  Shared by
+// bigfft_kernel and bigss_kernel (bigss_kernel.h), which hands it the vector the spectral subtraction left.  The caller places the
+// barrier behind it (P and Y are rewritten by the next frame).
+__device__ __forceinline__ void big_project(const BigParams &p, const float *P, float *Y, float *Ylog, double *red, const float *lfb, const float *lcoef,
+                                            const double *lcoef_d, const int *lrange, const int64_t row, const double e_raw, const int tid) {
+    const int K = p.K;
+    if (p.vad_en) {  // the VAD's energy criterion on the vector the NR left (frontend_kernel's vad_export == 2)
+        double s = 0.0;
+        for (int k = tid; k < K; k += 256) s += (double)(P[k] * P[k]);
+        const double tot = block_sum(s, red);
+        if (tid == 0) p.vad_en[row] = (float)tot;
+    }
+    double e_spec = 0.0;
+    if (p.e_mode == 1) {  // E = log(2 (X0^2/2 + sum X_i^2 + X_{K-1}^2/2)) (src/nr/nr.cc:36-45)
+        double s = 0.0;
+        for (int k = tid; k < K; k += 256) s += ((k == 0 || k == K - 1) ? 0.5 : 1.0) * (double)P[k] * (double)P[k];
+        e_spec = block_sum(s, red);
+    }
+    // ---- filter bank: lanes 4b..4b+3 share band b (src/fea/fb.cc:60-83)
+    {
+        const int b = tid >> 2, q = tid & 3;
+        float acc = 0.f;
+        if (b < p.B) {
+            const int k0 = lrange[3 * b], k1 = lrange[3 * b + 1];
+            const float *w = lfb + lrange[3 * b + 2] - k0;
+            // four independent partial sums: the reads of a step are in flight together
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+            int k = k0 + q;
+            for (; k + 12 <= k1; k += 16) {
+                a0 += w[k] * P[k];
+                a1 += w[k + 4] * P[k + 4];
+                a2 += w[k + 8] * P[k + 8];
+                a3 += w[k + 12] * P[k + 12];
+            }
+            for (; k <= k1; k += 4) a0 += w[k] * P[k];
+            acc = (a0 + a1) + (a2 + a3);
+        }
+        acc += __shfl_xor(acc, 1);
+        acc += __shfl_xor(acc, 2);
+        if (p.fb_inld) acc = __builtin_amdgcn_exp2f(0.33f * __builtin_amdgcn_logf(acc));
+        if (q == 0 && b < 64) {
+            Y[b] = b < p.B ? acc : 0.f;
+            Ylog[b] = b < p.B ? __builtin_amdgcn_logf(acc) * 0.69314718056f : 0.f;
+        }
+    }
+    lds_barrier();
+    double e_band = 0.0;
+    if (p.e_mode == 3 && tid == 0) {  // band energy of the FB output (src/fea/fea_impl.cc:44-50,68-74)
+        for (int b = 0; b < p.B; b++) e_band += ((b == 0 || b == p.B - 1) ? 0.5 : 1.0) * (double)Y[b] * (double)Y[b];
+    }
+    if (p.feat == FEAT_BANDS) {
+        float *dst_ = p.band_to_scratch ? p.logmel : p.rows;
+        const int out_w = p.band_to_scratch ? p.B : p.D;
+        if (tid < p.B) dst_[row * out_w + tid] = p.band_log ? Ylog[tid] : Y[tid];
+    } else if (p.feat == FEAT_DCTC) {
+        // 16 lanes per coefficient (ncoef_out <= 16 here or the remaining rows take a second round): lane j sums bands
+        // j, j+16, ..., then four shuffle steps
+        for (int r0_ = 0; r0_ < p.ncoef_out; r0_ += 16) {
+            const int r = r0_ + (tid >> 4), j = tid & 15;
+            float acc = 0.f;
+            if (r < p.ncoef_out) {
+                const float *c = lcoef + r * p.B;
+                for (int b = j; b < p.B; b += 16) acc += c[b] * Ylog[b];
+            }
+            acc += __shfl_xor(acc, 1);
+            acc += __shfl_xor(acc, 2);
+            acc += __shfl_xor(acc, 4);
+            acc += __shfl_xor(acc, 8);
+            if (j == 0 && r < p.ncoef_out && p.row_slot[r] >= 0) p.rows[row * p.D + r] = acc;
+        }
+    } else if (tid == 0) {
+        // LP analysis in double by one lane (src/fea/fea_impl.cc:163-222, 251-284): R by cosine iDFT, Levinson-Durbin, a -> c
+        double R[MAX_LP + 1], a[MAX_LP + 1], aa[MAX_LP + 1], cc[MAX_LP + 1];
+        const int P_ = p.lporder;
+        for (int k = 0; k <= P_; k++) {
+            double r = 0.0;
+            for (int b = 0; b < p.B; b++) {
+                const double y = p.fb_inld ? (double)Y[b] : (double)Y[b] * (double)Y[b];
+                r += lcoef_d[k * p.B + b] * y;
+            }
+            R[k] = r;
+        }
+        float *orow = p.rows + row * p.D;
+        if (p.e_mode == 2) orow[p.e_slot] = (float)log(R[0]);
+        double rc = -R[1] / R[0], err = R[0] * (1 - rc * rc);
+        a[0] = aa[0] = 1;
+        a[1] = aa[1] = rc;
+        for (int ik = 2; ik <= P_; ik++) {
+            double dm = R[ik];
+            for (int n = 1; n < ik; n++) dm += aa[n] * R[ik - n];
+            rc = -dm / err;
+            a[ik] = rc;
+            for (int n = 1; n < ik; n++) a[n] = aa[n] + rc * aa[ik - n];
+            for (int n = 1; n <= ik; n++) aa[n] = a[n];
+            err *= (1 - rc * rc);
+        }
+        if (p.lp_is_lpa) {
+            for (int i = 1; i <= P_; i++) orow[i - 1] = (float)a[i];
+        } else {
+            cc[0] = log(err);
+            for (int n = 1; n <= p.ncep; n++) {
+                double sum = 0;
+                for (int k = 1; k < n; k++)
+                    if (k <= P_) sum += (double)(n - k) * cc[n - k] * a[k];
+                cc[n] = (n <= P_ ? -a[n] : 0.0) - sum / (double)n;
+            }
+            for (int n = 0; n <= p.ncep; n++) {
+                double val = cc[n];
+                if (n >= 1 && p.lifter_on) val *= (double)p.lifter[n - 1];
+                const int slot = p.row_slot[n];
+                if (slot >= 0) orow[slot] = (float)val;
+            }
+        }
+    }
+    if (p.e_mode && p.e_mode != 2 && tid == 0 && !(p.feat == FEAT_BANDS && p.band_to_scratch)) {
+        double e = 0.0;
+        if (p.e_mode == 1) e = log(2.0 * e_spec);
+        else if (p.e_mode == 3) e = log(2.0 * e_band);
+        else if (p.e_mode == 4) e = log(e_raw);
+        p.rows[row * p.D + p.e_slot] = (float)e;
+    }
 }
 
 // EXTEN: -nr_mode exten (src/nr/nr.cc:86-140) - the recurrence runs along an utterance, so a WORKGROUP walks one of the plan's chains of
@@ -229,126 +364,13 @@ __global__ __launch_bounds__(256) void bigfft_kernel(const BigParams p) {
                           // projected) or for the Burg-cepstral VAD criterion (bigburg_kernel; the rows are computed as well)
                 for (int k = tid; k < K; k += 256) p.pnr[(rec.rbase + f) * K + k] = P[k];
                 if (p.xri_only) {
+                    // (the *ss modes' export pass on the feature path: the raw energy is known here, bigss_kernel leaves the column alone)
+                    if (p.e_mode == 4 && p.rows && tid == 0) p.rows[(rec.rbase + f) * p.D + p.e_slot] = (float)log(e_raw);
                     lds_barrier();  // P and the FFT buffers are rewritten by the next frame
                     continue;
                 }
             }
-            if (p.vad_en) {  // the VAD's energy criterion on the vector the NR left (frontend_kernel's vad_export == 2)
-                double s = 0.0;
-                for (int k = tid; k < K; k += 256) s += (double)(P[k] * P[k]);
-                const double tot = block_sum(s, red);
-                if (tid == 0) p.vad_en[rec.rbase + f] = (float)tot;
-            }
-            double e_spec = 0.0;
-            if (p.e_mode == 1) {  // E = log(2 (X0^2/2 + sum X_i^2 + X_{K-1}^2/2)) (src/nr/nr.cc:36-45)
-                double s = 0.0;
-                for (int k = tid; k < K; k += 256) s += ((k == 0 || k == K - 1) ? 0.5 : 1.0) * (double)P[k] * (double)P[k];
-                e_spec = block_sum(s, red);
-            }
-            // ---- filter bank: lanes 4b..4b+3 share band b (src/fea/fb.cc:60-83)
-            {
-                const int b = tid >> 2, q = tid & 3;
-                float acc = 0.f;
-                if (b < p.B) {
-                    const int k0 = lrange[3 * b], k1 = lrange[3 * b + 1];
-                    const float *w = lfb + lrange[3 * b + 2] - k0;
-                    // four independent partial sums: the reads of a step are in flight together
-                    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-                    int k = k0 + q;
-                    for (; k + 12 <= k1; k += 16) {
-                        a0 += w[k] * P[k];
-                        a1 += w[k + 4] * P[k + 4];
-                        a2 += w[k + 8] * P[k + 8];
-                        a3 += w[k + 12] * P[k + 12];
-                    }
-                    for (; k <= k1; k += 4) a0 += w[k] * P[k];
-                    acc = (a0 + a1) + (a2 + a3);
-                }
-                acc += __shfl_xor(acc, 1);
-                acc += __shfl_xor(acc, 2);
-                if (p.fb_inld) acc = __builtin_amdgcn_exp2f(0.33f * __builtin_amdgcn_logf(acc));
-                if (q == 0 && b < 64) {
-                    Y[b] = b < p.B ? acc : 0.f;
-                    Ylog[b] = b < p.B ? __builtin_amdgcn_logf(acc) * 0.69314718056f : 0.f;
-                }
-            }
-            lds_barrier();
-            const int64_t row = rec.rbase + f;
-            double e_band = 0.0;
-            if (p.e_mode == 3 && tid == 0) {  // band energy of the FB output (src/fea/fea_impl.cc:44-50,68-74)
-                for (int b = 0; b < p.B; b++) e_band += ((b == 0 || b == p.B - 1) ? 0.5 : 1.0) * (double)Y[b] * (double)Y[b];
-            }
-            if (p.feat == FEAT_BANDS) {
-                float *dst_ = p.band_to_scratch ? p.logmel : p.rows;
-                const int out_w = p.band_to_scratch ? p.B : p.D;
-                if (tid < p.B) dst_[row * out_w + tid] = p.band_log ? Ylog[tid] : Y[tid];
-            } else if (p.feat == FEAT_DCTC) {
-                // 16 lanes per coefficient (ncoef_out <= 16 here or the remaining rows take a second round): lane j sums bands
-                // j, j+16, ..., then four shuffle steps
-                for (int r0_ = 0; r0_ < p.ncoef_out; r0_ += 16) {
-                    const int r = r0_ + (tid >> 4), j = tid & 15;
-                    float acc = 0.f;
-                    if (r < p.ncoef_out) {
-                        const float *c = lcoef + r * p.B;
-                        for (int b = j; b < p.B; b += 16) acc += c[b] * Ylog[b];
-                    }
-                    acc += __shfl_xor(acc, 1);
-                    acc += __shfl_xor(acc, 2);
-                    acc += __shfl_xor(acc, 4);
-                    acc += __shfl_xor(acc, 8);
-                    if (j == 0 && r < p.ncoef_out && p.row_slot[r] >= 0) p.rows[row * p.D + r] = acc;
-                }
-            } else if (tid == 0) {
-                // LP analysis in double by one lane (src/fea/fea_impl.cc:163-222, 251-284): R by cosine iDFT, Levinson-Durbin, a -> c
-                double R[MAX_LP + 1], a[MAX_LP + 1], aa[MAX_LP + 1], cc[MAX_LP + 1];
-                const int P_ = p.lporder;
-                for (int k = 0; k <= P_; k++) {
-                    double r = 0.0;
-                    for (int b = 0; b < p.B; b++) {
-                        const double y = p.fb_inld ? (double)Y[b] : (double)Y[b] * (double)Y[b];
-                        r += lcoef_d[k * p.B + b] * y;
-                    }
-                    R[k] = r;
-                }
-                float *orow = p.rows + row * p.D;
-                if (p.e_mode == 2) orow[p.e_slot] = (float)log(R[0]);
-                double rc = -R[1] / R[0], err = R[0] * (1 - rc * rc);
-                a[0] = aa[0] = 1;
-                a[1] = aa[1] = rc;
-                for (int ik = 2; ik <= P_; ik++) {
-                    double dm = R[ik];
-                    for (int n = 1; n < ik; n++) dm += aa[n] * R[ik - n];
-                    rc = -dm / err;
-                    a[ik] = rc;
-                    for (int n = 1; n < ik; n++) a[n] = aa[n] + rc * aa[ik - n];
-                    for (int n = 1; n <= ik; n++) aa[n] = a[n];
-                    err *= (1 - rc * rc);
-                }
-                if (p.lp_is_lpa) {
-                    for (int i = 1; i <= P_; i++) orow[i - 1] = (float)a[i];
-                } else {
-                    cc[0] = log(err);
-                    for (int n = 1; n <= p.ncep; n++) {
-                        double sum = 0;
-                        for (int k = 1; k < n; k++)
-                            if (k <= P_) sum += (double)(n - k) * cc[n - k] * a[k];
-                        cc[n] = (n <= P_ ? -a[n] : 0.0) - sum / (double)n;
-                    }
-                    for (int n = 0; n <= p.ncep; n++) {
-                        double val = cc[n];
-                        if (n >= 1 && p.lifter_on) val *= (double)p.lifter[n - 1];
-                        const int slot = p.row_slot[n];
-                        if (slot >= 0) orow[slot] = (float)val;
-                    }
-                }
-            }
-            if (p.e_mode && p.e_mode != 2 && tid == 0 && !(p.feat == FEAT_BANDS && p.band_to_scratch)) {
-                double e = 0.0;
-                if (p.e_mode == 1) e = log(2.0 * e_spec);
-                else if (p.e_mode == 3) e = log(2.0 * e_band);
-                else if (p.e_mode == 4) e = log(e_raw);
-                p.rows[row * p.D + p.e_slot] = (float)e;
-            }
+            big_project(p, P, Y, Ylog, red, lfb, lcoef, lcoef_d, lrange, rec.rbase + f, e_raw, tid);
             lds_barrier();  // P, Y and the FFT buffers are rewritten by the next frame
         }
     }

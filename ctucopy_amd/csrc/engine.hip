@@ -10,6 +10,8 @@
 //   trap_kernel.h      TRAP-DCT as fp32 MFMA Toeplitz contraction
 //   post_kernels.h     delta chain / stacking, CMS, per-speaker CMVN over resident rows
 //   signal_kernels.h   speech-enhancement output: inverse transform, overlap-add
+//   bigfft_kernel.h    1024 .. 4096-point frames, a workgroup per frame; bigburg_kernel.h the Burg-cepstral criterion / detector there;
+//   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
 //
 // Data layout in HBM
 //   pcm   : one packed int16 arena; utterance i starts at sample_off[i] (multiple of 8 samples)
@@ -22,6 +24,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -44,6 +47,7 @@
 #include "lp_tail_kernel.h"
 #include "wave1k_kernel.h"
 #include "bigburg_kernel.h"
+#include "bigss_kernel.h"
 
 namespace {
 
@@ -109,6 +113,7 @@ struct ctu_engine {
     DevBuf<float2> big_tw;
     DevBuf<int> big_range, big_slot, big_seg;
     DevBuf<double> big_coef_d;
+    DevBuf<double> big_han;     // hwss / fwss / 2fwss at 2048 / 4096 points: the detector's Hann window [window] (bigssdet_kernel)
     int lift_off = 0, tab_floats = 0, ck_off = 0, cf_off = 0, cfd_off = 0, am_off = 0, NS = 0, CW = 4, ncoef_out = 0;
     bool md = false;        // DCT tail on the matrix cores (frontend_kernel<..., MD>): tables are laid out for its lane map
     int walk = -1;          // compiled walk signature (phase2_walks.h) that this engine's bank and frame shape match, -1: none (or CTU_PHASE2_GENERIC)
@@ -116,7 +121,7 @@ struct ctu_engine {
     bool half_window = false;  // the headline instantiation (DUAL): the window table is scaled by 1/2, which is the 1/4 of its power spectrum
     bool vf = false;        // Burg-cepstral VAD criterion fused into the front end (frontend_kernel<..., VF>)
     bool sy = false;        // speech-enhancement output with the inverse transform inside the front end (frontend_kernel<..., SY>)
-    int ss = 0;             // hwss / fwss / 2fwss (1 / 2 / 3) on frontend_kernel<..., SS>
+    int ss = 0;             // hwss / fwss / 2fwss (1 / 2 / 3) on frontend_kernel<..., SS>, or with `big` on bigss_kernel (bigss_kernel.h)
     std::vector<float> ss_stale;  // the spectrum vector the last file of the previous run left behind (zeros at first)
     // -vad file=<f>: ONE byte stream for all files of the process, a byte per frame, never rewound (nr.cc:205-209, 273, 297-302)
     bool ss_file = false;
@@ -174,6 +179,7 @@ struct ctu_plan {
     DevBuf<unsigned char> ss_vbits;  // SS: the detector's decision of every frame (first pass), reused by the later passes
     DevBuf<float2> xri;         // VAD scratch
     DevBuf<float> pnr;
+    DevBuf<float> pss;          // hwss / fwss / 2fwss with speech output at 2048 / 4096 points: the subtracted magnitudes (pnr stays as exported)
     DevBuf<double> vad_ci;
     DevBuf<float> vad_cf;      // fused Burg-cepstral VAD: cepstra of every frame [total_frames][VFC_STRIDE] ahead of vad_lanes_kernel
     DevBuf<int> vf_order;      // utterances with at least one frame, longest first (a wave of vad_lanes_kernel takes 16 in a row)
@@ -200,6 +206,7 @@ namespace {
 void set_error(ctu_engine *e, const std::string &m) { e->err = m; }
 
 bool ss_eligible(const ctu::Design &d);
+bool ss_big_eligible(const ctu::Design &d);
 int ss_mode_of(const ctu::Opts &o);
 
 // reasons a valid ctucopy configuration is outside the accelerated path
@@ -213,15 +220,16 @@ std::string unsupported_reason(const ctu::Design &d) {
             if (d.window / d.wshift > 8) return "-remove_dc1 with more than 8 frames over a sample (window / shift above 8)";
             if (o.fea_E && o.fea_rawenergy) return "-remove_dc1 together with -fea_rawenergy";
         }
-        if (o.nr_mode != "none" && o.nr_mode != "exten" && !ss_eligible(d))
-            return "hwss / fwss / 2fwss with signal output outside the fused detector path (windows of 129 .. 208 samples on 256 points or 257 .. 400 on 512, -vad burg with 2 to 16 cepstral coefficients or -vad file=..., DC removal on)";
+        if (o.nr_mode != "none" && o.nr_mode != "exten" && !ss_eligible(d) && !ss_big_eligible(d))
+            return "hwss / fwss / 2fwss with signal output outside the detector paths (windows of 129 .. 208 samples on 256 points or 257 .. 400 on 512 with -vad burg and 2 to 16 cepstral coefficients, 2048 / 4096 points with 2 to 32, or -vad file=...; DC removal on, no -remove_dc1; 1024 points not yet)";
         if (o.rasta) return "-nr_rasta";
         // BATCH only constructs its VAD on the feature paths (init_out, src/io/batch.cc:70-76); with signal output save_frame() calls
         // through the never-assigned pointer (batch.cc:230-241): the reference crashes, there is nothing to reproduce
         if (o.do_vad()) return "VAD together with signal output (the reference dereferences a VAD it never constructs there, src/io/batch.cc:62-66,230-241)";
         if (d.wfft > 4096) return "FFT size above 4096";
-        if (d.wfft >= 1024) {  // bigfft_kernel exports the spectra, bigsynth_kernel transforms back: the plain chain and exten
-            if (o.nr_mode != "none" && o.nr_mode != "exten") return "hwss / fwss / 2fwss with signal output at an FFT size above 512";
+        if (d.wfft >= 1024) {  // bigfft_kernel exports the spectra, bigsynth_kernel transforms back: the plain chain, exten, and at
+                               // 2048 / 4096 points hwss / fwss / 2fwss (bigss_kernel between the two)
+            if (o.nr_mode != "none" && o.nr_mode != "exten" && !ss_big_eligible(d)) return "hwss / fwss / 2fwss with signal output at 1024 points (2048 and 4096 run)";
         }
         else if (d.wfft != 512 && d.wfft != 256) return "signal output at an FFT size below 256";
         if (d.window % 2 && d.wfft < 1024) return "odd window length with signal output at an FFT size below 1024";
@@ -241,7 +249,7 @@ std::string unsupported_reason(const ctu::Design &d) {
         // out by then and the next get_frame() rewrites the vector, so on every other chain the mode changes nothing - but these
         // modes seed the next file's noise estimate from that very vector (src/nr/nr.cc:212-221)
         if (o.vad_apply_mode == "silence") return "-vad_apply_mode silence together with hwss / fwss / 2fwss (it zeroes the vector the next file's noise estimate starts from)";
-        if (!ss_eligible(d)) return "hwss / fwss / 2fwss outside the fused detector path (windows of 129 .. 208 samples on 256 points or 257 .. 400 on 512, -vad burg with 2 to 16 cepstral coefficients or -vad file=..., DC removal on, at most 16 cepstral / LP coefficients, no trapdct, no -nr_when afterFB, no CMVN, no VAD module beside it)";
+        if (!ss_eligible(d) && !ss_big_eligible(d)) return "hwss / fwss / 2fwss outside the detector paths (windows of 129 .. 208 samples on 256 points or 257 .. 400 on 512 with -vad burg, 2 to 16 cepstral coefficients and at most 16 cepstral / LP coefficients; 2048 / 4096 points with 2 to 32 detector coefficients and at most 64 bands; or -vad file=...; DC removal on, no -remove_dc1, no trapdct, no -nr_when afterFB, no CMVN, no VAD module beside it; 1024 points not yet)";
     }
     if (o.nr_when_afterFB) {
         if (d.signal_out) return "-nr_when afterFB together with signal output";
@@ -293,7 +301,9 @@ std::string unsupported_reason(const ctu::Design &d) {
         // exten on the spectrum at 1024 points: wave1k_kernel carries the recurrence along per-wave chains of utterances
         // exten on the spectrum at 1024 .. 4096 points: wave1k_kernel / bigfft_kernel carry the recurrence along chains of whole utterances
         const bool big_exten = o.nr_mode == "exten" && !o.nr_when_afterFB && !d.signal_out;
-        if ((o.nr_mode != "none" || o.nr_when_afterFB) && !big_exten) return "noise reduction with an FFT size above 512 (exten on the spectrum excepted)";
+        // hwss / fwss / 2fwss at 2048 / 4096 points: bigss_kernel (bigss_kernel.h) on the spectra bigfft_kernel exports
+        if ((o.nr_mode != "none" || o.nr_when_afterFB) && !big_exten && !ss_big_eligible(d))
+            return "noise reduction with an FFT size above 512 (exten on the spectrum at 1024 .. 4096 points and hwss / fwss / 2fwss at 2048 / 4096 excepted)";
         // the VAD on 1024 .. 4096-point frames: the energy of the vector the NR left (wave1k_kernel / bigfft_kernel store it per frame),
         // the cepstral distance on the output vectors, and the Burg-cepstral criterion on the spectra bigfft_kernel exports
         // (bigburg_kernel.h).  Every criterion unsupported_reason lets through above is one of the three.
@@ -393,6 +403,20 @@ bool ss_eligible(const ctu::Design &d) {
     // left behind, and no oracle restates that - refused rather than guessed
     return CTU_MD && ss_mode_of(o) && det_ok && !o.nr_when_afterFB && ss_frame_shape(d) && kind_ok && o.remove_dc && !o.remove_dc1 && !o.do_vad() && !d.signal_out && !o.rasta &&
            !o.stat_cmvn && !o.apply_cmvn;
+}
+
+// the same modes on 2048- and 4096-point frames (bigss_kernel.h): spectra exported once, a workgroup per frame for the detector's cepstra
+// (2 to 32 coefficients: bigburg_kernel's two instantiations), a workgroup per chain of utterances for the subtraction.  What
+// ss_eligible excludes for reasons that do not depend on the size stays excluded; 1024 points (wave1k_kernel's size) stay refused whole.
+bool ss_big_eligible(const ctu::Design &d) {
+    const ctu::Opts &o = d.o;
+    if (!ss_mode_of(o) || (d.wfft != 2048 && d.wfft != 4096) || d.window <= d.wfft / 2) return false;
+    const bool det_ok = (o.vadmode == "burg" && o.fea_ncepcoefs >= 2 && o.fea_ncepcoefs <= 32) || o.vadmode == "file";
+    if (!det_ok || !o.remove_dc || o.remove_dc1 || o.rasta || o.do_vad()) return false;
+    if (d.signal_out) return true;
+    const bool kind_ok = d.kind == ctu::FeaKind::Dctc || d.kind == ctu::FeaKind::Lpc || d.kind == ctu::FeaKind::Lpa || d.kind == ctu::FeaKind::Spec ||
+                         d.kind == ctu::FeaKind::LogSpec;
+    return kind_ok && !o.nr_when_afterFB && !o.stat_cmvn && !o.apply_cmvn && d.B <= 64;
 }
 
 void build_phase2(const ctu::Design &d, Phase2Tables &t) {
@@ -809,6 +833,15 @@ void build_tables(ctu_engine *e) {
         const bool burg = d.o.do_vad() && d.o.vad_cri_mode == "cepdist" && d.o.vad_cepdist_mode == "lpc";
         e->wave1k = d.wfft == 1024 && !d.o.remove_dc1 && !d.signal_out && !burg && !(getenv("CTU_WAVE1K") && atoi(getenv("CTU_WAVE1K")) == 0);
         build_big_tables(e);
+        e->ss = ss_big_eligible(d) ? ss_mode_of(d.o) : 0;
+        e->ss_file = e->ss && d.o.vadmode == "file";
+        if (e->ss && !e->ss_file) {
+            // Hann window of the detector, han[i] = 0.5 (1 - cos(2 * 3.141592653 / window * i)) (src/vdet/CepstralDet.h:133-136)
+            std::vector<double> han((size_t)d.window);
+            const double m = 2 * 3.141592653 / d.window;
+            for (int i = 0; i < d.window; i++) han[(size_t)i] = 0.5 * (1 - std::cos(m * i));
+            e->big_han.upload(han);
+        }
         return;
     }
     // ---- per-lane constant records (see LC_* above)
@@ -1416,6 +1449,15 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
             pl->ss_last.alloc((size_t)std::max(n_utt, 1) * d.K);
             pl->ss_dirty.alloc((size_t)std::max(n_utt, 1));
             pl->ss_vbits.alloc((size_t)std::max<int64_t>(ro, 1));
+            if (e->big) {  // bigss_kernel.h: the exported spectra, the detector's cepstra, on the speech path the subtracted magnitudes
+                pl->xri.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+                pl->pnr.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+                if (d.signal_out) pl->pss.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+                if (!e->ss_file) {
+                    pl->vad_ci.alloc((size_t)std::max<int64_t>(ro, 1) * d.o.fea_ncepcoefs);
+                    pl->d_row_off.upload(pl->row_off);
+                }
+            }
         }
         if (e->do_vad) {
             pl->d_row_off.upload(pl->row_off);
@@ -1438,7 +1480,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
             } else if (e->vp.cri == 0) pl->pnr.alloc((size_t)ro);
         }
         if (d.signal_out) {
-            if (!e->sy) {
+            if (!e->sy && !(e->big && e->ss)) {
                 pl->xri.alloc((size_t)ro * d.K);
                 pl->pnr.alloc((size_t)ro * d.K);
             }
@@ -1681,8 +1723,9 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
                 default: e->mode ? launch_vx<16, 1>(e, dim3(grid), s, kp) : launch_vx<16, 0>(e, dim3(grid), s, kp); break;
             }
         };
+        std::function<void()> ss_launch = launch;  // one pass of the *ss modes' seed iteration (below)
+        BigParams bp;
         if (e->big) {
-            BigParams bp;
             std::memset(&bp, 0, sizeof bp);
             bp.pcm = d_pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = pl->n_tiles;
             bp.win = e->big_win.p; bp.tw = e->big_tw.p; bp.fbw = e->big_fbw.p; bp.fb_range = e->big_range.p;
@@ -1714,7 +1757,56 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             }
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / shm));
             const int g = std::max(1, std::min(pl->n_tiles, e->n_cu * per_cu));
-            if (e->wave1k) {
+            if (e->ss) {
+                // hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h): the spectra once, the detector's cepstra and decisions once,
+                // then bigss_kernel per pass of the seed iteration below
+                if (d.wfft != 2048 && d.wfft != 4096) throw std::runtime_error("internal: SS engine without an SS instantiation");
+                bp.xri = pl->xri.p; bp.pnr = pl->pnr.p; bp.xri_only = 1;
+                if (d.wfft == 2048) hipLaunchKernelGGL((bigfft_kernel<8>), dim3(g), dim3(256), shm, s, bp);
+                else hipLaunchKernelGGL((bigfft_kernel<16>), dim3(g), dim3(256), shm, s, bp);
+                HIP_TRY(hipGetLastError());
+                if (!e->ss_file) {
+                    const size_t bshm = ((size_t)(d.wfft / 2) * 3 + 4) * sizeof(float2) + BIGBURG_XCH * sizeof(double);
+                    const dim3 bg((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * std::min<size_t>(8, (160 * 1024) / bshm)));
+                    const int nc = d.o.fea_ncepcoefs, two = e->ss == 3;
+#define BIGSSDET(NIT_, NC_) hipLaunchKernelGGL((bigssdet_kernel<NIT_, NC_>), bg, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, d.wfft, d.window, nc, \
+                                               (int64_t)pl->total_frames, e->big_tw.p, e->big_han.p, (float)d.o.nr_a, two)
+                    if (d.wfft == 2048) {
+                        if (nc <= 16) BIGSSDET(8, 16);
+                        else BIGSSDET(8, 32);
+                    } else {
+                        if (nc <= 16) BIGSSDET(16, 16);
+                        else BIGSSDET(16, 32);
+                    }
+#undef BIGSSDET
+                    HIP_TRY(hipGetLastError());
+                    hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->n_utt, nc, d.o.nr_initsegs,
+                                       (double)d.o.nr_p, (double)d.o.nr_q, pl->ss_vbits.p);
+                    HIP_TRY(hipGetLastError());
+                }
+                bp.xri_only = signal ? 1 : 0;
+                bp.pss = signal ? pl->pss.p : nullptr;
+                bp.ss_mode = e->ss; bp.ss_init = d.o.nr_initsegs; bp.ss_a = d.o.nr_a; bp.ss_b = d.o.nr_b; bp.ss_p = d.o.nr_p;
+                bp.ss_seed = pl->ss_seed.p; bp.ss_last = pl->ss_last.p; bp.ss_dirty = pl->ss_dirty.p; bp.ss_vbits = pl->ss_vbits.p;
+                bp.tile_utt = pl->tile_utt.p;
+                // LDS: the spectrum vector, the bands and their logarithms, and the projection's tables (none on the speech path)
+                const size_t sshm = (size_t)((d.K + 3) & ~3) * 4 + 64 * 4 + 4 * 8 + 64 * 4 +
+                                    (signal ? 0 : (size_t)((e->big_fb_total + 3) & ~3) * 4 + (size_t)(e->feat == FEAT_LP ? (d.o.fea_lporder + 1) * d.B : 0) * 8 +
+                                                      (size_t)(((e->feat == FEAT_DCTC ? e->ncoef_out * d.B : 0) + 3) & ~3) * 4 + (size_t)((3 * d.B + 3) & ~3) * 4);
+                if (sshm > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
+                if (!e->per_wave) throw std::runtime_error("internal: hwss / fwss / 2fwss without chains");
+                const dim3 gx((unsigned)std::max(1, bp.n_chains));
+                ss_launch = [&bp, e, d_wfft = d.wfft, sshm, gx, s] {
+                    if (d_wfft == 2048) {
+                        if (sshm > 64 * 1024) allow_big_lds(e, &bigss_kernel<8>);
+                        hipLaunchKernelGGL((bigss_kernel<8>), gx, dim3(256), sshm, s, bp);
+                    } else {
+                        if (sshm > 64 * 1024) allow_big_lds(e, &bigss_kernel<16>);
+                        hipLaunchKernelGGL((bigss_kernel<16>), gx, dim3(256), sshm, s, bp);
+                    }
+                };
+            }
+            else if (e->wave1k) {
                 // 1024 points: one wave per frame, the transform in registers (wave1k_kernel.h); tiles are dealt to waves
                 const size_t wshm = ((size_t)W1K_WAVES * W1K_WAVE_FLOATS + 1024 + W1K_TW_FLOATS + (size_t)((e->big_fb_total + 3) & ~3) + 2) * 4 +
                                     (size_t)(e->feat == FEAT_LP ? (d.o.fea_lporder + 1) * d.B : 0) * 8 +
@@ -1745,7 +1837,7 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             else hipLaunchKernelGGL((bigfft_kernel<16>), dim3(g), dim3(256), shm, s, bp);
         }
         else if (!e->ss) launch();
-        else {
+        if (e->ss) {
             // hwss / fwss / 2fwss: a file's noise estimate starts from the vector the previous file of the list left
             // behind (src/nr/nr.cc:212-221), which chains the whole list.  Everything but that seed is independent per
             // file, so the list is run with the seeds known so far until they stop changing: pass j fixes the seeds of
@@ -1804,7 +1896,7 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
                 kp.ss_cached = e->ss_file ? 1 : (iter > 0 ? CTU_SS_CACHE : 0);
                 HIP_TRY(hipMemcpyAsync(pl->ss_seed.p, seed.data(), nk * sizeof(float), hipMemcpyHostToDevice, s));
                 HIP_TRY(hipMemcpyAsync(pl->ss_dirty.p, dirty.data(), dirty.size(), hipMemcpyHostToDevice, s));
-                launch();
+                ss_launch();
                 HIP_TRY(hipMemcpyAsync(last.data(), pl->ss_last.p, nk * sizeof(float), hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
                 propagate(next);
@@ -2320,7 +2412,7 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
 #define BIGSYNTH(NIT_)                                                                                                              \
     do {                                                                                                                            \
         if (shm > 64 * 1024) allow_big_lds(e, &bigsynth_kernel<NIT_>);                                                              \
-        hipLaunchKernelGGL((bigsynth_kernel<NIT_>), dim3(g), dim3(256), shm, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)pl->total_frames, \
+        hipLaunchKernelGGL((bigsynth_kernel<NIT_>), dim3(g), dim3(256), shm, s, pl->xri.p, e->ss ? pl->pss.p : pl->pnr.p, pl->ybuf.p, (long long)pl->total_frames, \
                            d.wfft, d.window, sp.inv_n, e->big_tw.p);                                                                \
     } while (0)
             if (d.wfft == 1024) BIGSYNTH(4);
@@ -2443,6 +2535,7 @@ const char *ctu_engine_kernel_name(const ctu_engine *e) {
         const ctu::Opts &o = d.o;
         std::string n;
         if (e->wave1k) n = "wave1k_kernel";
+        else if (e->big && e->ss) n = "bigss_kernel<" + std::to_string(d.wfft / 256) + ">";
         else if (e->big) n = "bigfft_kernel<" + std::to_string(d.wfft / 256) + ">";
         else {
             const char *feat = e->feat == FEAT_DCTC ? "DCTC" : e->feat == FEAT_BANDS ? "BANDS" : e->feat == FEAT_LP ? "LP" : "LPD";

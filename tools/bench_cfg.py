@@ -20,6 +20,8 @@ CFGS = {"C2": C2, "C3": C3, "C4": C4, "C4_novad": C4_NOVAD, "C5": C5, "C2_d_a": 
         # 44.1 kHz audio (1103 samples, 2048 points) with the VAD: the Burg-cepstral criterion (bigburg_kernel) and the energy criterion
         "m44_vad_burg": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -vad burg -vad_out_mode vad -vad_cri_mode cepdist -vad_cepdist_mode lpc -vad_thr_mode adapt".split(),
         "m44_vad_energy": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -vad_out_mode vad -vad_cri_mode energy -vad_thr_mode adapt".split(),
+        # the same audio through -nr_mode fwss with the Burg cepstral detector (bigss_kernel.h): export, detector, decisions, seed passes
+        "m44_fwss": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -nr_mode fwss -vad burg".split(),
         "C2_d_a_cmvn": C2 + ["-fea_delta", "d_a", "-stat_cmvn", "x.stat", "-apply_cmvn", "x.stat"]}
 ap = argparse.ArgumentParser()
 ap.add_argument("--cfg", default="C3")
