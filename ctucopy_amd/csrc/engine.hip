@@ -86,6 +86,17 @@ struct DevBuf {
     ~DevBuf() { release(); }
 };
 
+// The front-end instantiation an engine runs on: frontend_kernel's template arguments as values (walk: the entry of phase2_walks.h, -1 =
+// the generic walk).  fe_select decides it once, at create; fe_compiled says which exist; launch_frontend turns it into the launch.
+// All zero (walk -1) for the large-FFT kernels, whose choice is the FFT size alone.
+struct FeSel {
+    int nz = 0, feat = 0, mode = 0;
+    bool vx = false;
+    int nc = 0, gen = 0, lpo = 0;
+    bool md = false, vf = false, ss = false, sy = false;
+    int walk = -1;
+};
+
 }  // namespace
 
 #include "post_kernels.h"
@@ -98,8 +109,8 @@ struct ctu_engine {
     int user_wfft = 0, user_K = 0;
     int kstride = 1;            // > 1: an FFT size below 256 carried by the 256-point mode (ctu_engine_create)
     std::string err, kname;
+    FeSel sel;     // the front-end instantiation (build_tables); feat / mode / md / vf / sy / ss below are assigned with it
     int feat = FEAT_DCTC;
-    int nz = 16;
     int mode = 0;  // 0: 512-point FFT, 1: 256-point FFT (two frames per complex transform)
     DevBuf<float> lanec, ftab, trapG;
     DevBuf<uint4> trapG16;   // TRAP on the bf16 matrix pipe: A fragments [8 phases][4 k-steps][3 terms][64 lanes] (trap_kernel.h)
@@ -116,9 +127,7 @@ struct ctu_engine {
     DevBuf<double> big_han;     // hwss / fwss / 2fwss at 2048 / 4096 points: the detector's Hann window [window] (bigssdet_kernel)
     int lift_off = 0, tab_floats = 0, ck_off = 0, cf_off = 0, cfd_off = 0, am_off = 0, NS = 0, CW = 4, ncoef_out = 0;
     bool md = false;        // DCT tail on the matrix cores (frontend_kernel<..., MD>): tables are laid out for its lane map
-    int walk = -1;          // compiled walk signature (phase2_walks.h) that this engine's bank and frame shape match, -1: none (or CTU_PHASE2_GENERIC)
-    int walk_launched = -1; // what the last front-end launch ran: the index of its straight-line walk, -1: the generic walk (ctu_engine_phase2_walk)
-    bool half_window = false;  // the headline instantiation (DUAL): the window table is scaled by 1/2, which is the 1/4 of its power spectrum
+    int walk_launched = -1; // what the last front-end launch ran: sel.walk, -1 before the first run (ctu_engine_phase2_walk)
     bool vf = false;        // Burg-cepstral VAD criterion fused into the front end (frontend_kernel<..., VF>)
     bool sy = false;        // speech-enhancement output with the inverse transform inside the front end (frontend_kernel<..., SY>)
     int ss = 0;             // hwss / fwss / 2fwss (1 / 2 / 3) on frontend_kernel<..., SS>, or with `big` on bigss_kernel (bigss_kernel.h)
@@ -332,7 +341,7 @@ struct Phase2Tables {
     bool md = false;  // lane map of the MFMA tail: lane = frame + 8 h + 16 kk, group = kk + 4 h
 };
 
-// The DCT tail runs on the matrix cores for the plain cepstral chains (what launch_vx instantiates with MD).
+// The DCT tail runs on the matrix cores for the plain cepstral chains (what fe_select instantiates with MD).
 #ifndef CTU_MD
 #define CTU_MD 1
 #endif
@@ -646,8 +655,8 @@ double check_phase2(const ctu::Design &d, const Phase2Tables &t) {
 }
 
 // The compiled walk signature (phase2_walks.h) that this bank matches, or -1: the chunk counts per slot must be the entry's and the
-// frames the shape the entries are compiled for.  The one place that compares banks; launch_walk uses the match where the
-// instantiation it is about to launch is the one the entry was compiled with, every other instantiation walks generically.  A
+// frames the shape the entries are compiled for.  The one place that compares banks; fe_select uses the match where the
+// instantiation it chose is the one the entry was compiled with, every other instantiation walks generically.  A
 // straight-line walk is correct for every bank with these counts (first bins and band indices stay per-lane records).
 int match_walk(const ctu::Design &d, const std::vector<int> &slot_chunk) {
     if (d.wfft != WALK_WFFT || (d.window + 31) / 32 != WALK_NZ) return -1;
@@ -805,7 +814,6 @@ void build_big_tables(ctu_engine *e) {
     e->big_lifter.upload(lif);
     e->lds_bytes = 0;
     e->mode = 0;
-    e->nz = 16;
     // the tables of the 512 / 256-point kernels stay empty
     e->ftab.upload(std::vector<float>(4, 0.f));
     e->itab.upload(std::vector<int>(4, 0));
@@ -821,6 +829,113 @@ void build_big_tables(ctu_engine *e) {
         case ctu::FeaKind::Lpa: e->feat = FEAT_LP; break;
         default: e->feat = FEAT_BANDS; break;
     }
+}
+
+// Which combinations of frontend_kernel's template arguments are compiled (launch_frontend instantiates exactly these).
+constexpr bool fe_compiled(const FeSel &k) {
+    const bool bands = k.feat == FEAT_BANDS, lpo_ok = k.lpo == 0 || k.lpo == 12;
+    if ((k.nz != 13 && k.nz != 16) || (k.mode != 0 && k.mode != 1)) return false;
+    if (!bands && k.feat != FEAT_DCTC && k.feat != FEAT_LP && k.feat != FEAT_LPD) return false;
+    if (k.nc != 16 && !(k.nc == MAXC && !bands)) return false;  // MAXC: coefficient rows of more than 16 cepstra / LP lags
+    if (k.gen == GEN_DC1 && k.nz != 16) return false;          // -remove_dc1: the generic row count only
+    if ((k.vf || k.ss) && k.nz != 13) return false;            // the detector paths: the 25 ms frame shapes (13 rows cover every shorter window)
+    if (k.vx) return k.gen == GEN_FULL && !k.lpo && !k.md && !k.vf && !k.ss && !k.sy;  // the export costs registers: run-time flags only
+    if (k.sy) return bands && !k.lpo && !k.md && !k.vf && (k.gen == GEN_FULL || (k.gen == GEN_DC1 && !k.ss));
+    if (k.vf) return k.feat == FEAT_DCTC && k.md && k.nc == 16 && !k.lpo && !k.ss && (k.gen == GEN_PLAIN || k.gen == GEN_EXTEN);
+    if (k.ss)  // the plain chain with the detector's lattice unrolled for the presets' 12 coefficients (LPO = 12) or for up to 16, or run-time flags
+        return k.nc == 16 && ((k.gen == GEN_FULL && !k.lpo && !k.md) || (k.gen == GEN_PLAIN && lpo_ok && (bands ? !k.md : (k.feat == FEAT_DCTC && k.md))));
+    if (k.md) return k.nc == 16 && ((k.feat == FEAT_DCTC && !k.lpo && (k.gen == GEN_PLAIN || k.gen == GEN_EXTEN)) || (k.feat == FEAT_LP && k.gen == GEN_INLD && lpo_ok));
+    switch (k.gen) {
+        case GEN_PLAIN: return !k.lpo && k.feat != FEAT_LPD;  // (the double LP tail has run-time flags only)
+        case GEN_INLD: return k.feat == FEAT_LP && k.nc == 16 && lpo_ok;
+        case GEN_EXTEN: return bands && !k.lpo;
+        default: return (k.gen == GEN_FULL || k.gen == GEN_DC1) && !k.lpo;
+    }
+}
+// Is W the walk entry compiled for exactly this instantiation?
+template <class W>
+constexpr bool walk_serves(const FeSel &k) {
+    return k.nz == WALK_NZ && k.mode == 0 && !k.vx && k.nc == 16 && k.feat == W::FEAT && k.gen == W::GEN && k.lpo == W::LPO && k.md == W::MD && !k.vf && !k.ss && !k.sy;
+}
+// The name that keys the profiles: the walk, the export and the row width are not shown.
+std::string fe_name(const FeSel &k) {
+    const char *feat = k.feat == FEAT_DCTC ? "DCTC" : k.feat == FEAT_BANDS ? "BANDS" : k.feat == FEAT_LP ? "LP" : "LPD";
+    const char *gen = k.gen == GEN_PLAIN ? "plain" : k.gen == GEN_INLD ? "inld" : k.gen == GEN_EXTEN ? "exten" : "full";
+    return "frontend_kernel<" + std::to_string(k.nz) + ", " + feat + ", MODE " + std::to_string(k.mode) + ", " + gen + (k.md ? ", MD" : "") + (k.vf ? ", VF" : "") +
+           (k.ss ? ", SS" : "") + (k.sy ? ", SY" : "") + ">";
+}
+
+// The instantiation a configuration runs on, from the design (after ctu_engine_create has spread an FFT size below 256 onto the 256-point
+// mode) and its phase-2 tables (`t`; none with speech output).  Needs no device.  Specialised instantiations (see GEN in
+// frontend_kernel.h): the plain chain, plain + intensity-loudness law for the 16-coefficient LP path (PLP), plain + exten for
+// 16-coefficient DCT / band outputs; the cepstral ones of these run their DCT tail on the matrix cores (MD, tables laid out for it by
+// build_phase2).  Everything else, and every run with the VAD export, reads its flags at run time.
+FeSel fe_select(const ctu::Design &d, const Phase2Tables *t) {
+    const ctu::Opts &o = d.o;
+    FeSel k;
+    if (d.wfft >= 1024) return k;
+    const bool signal = d.signal_out, exten = o.nr_mode == "exten";
+    // ---- what the configuration and its tables fix
+    k.mode = d.wfft == 256;
+    k.sy = signal && CTU_SY;
+    k.ss = ss_eligible(d);
+    k.vf = !signal && vf_eligible(d);
+    k.md = t && t->md;             // the tables are laid out for the MFMA tail's lane map
+    k.nc = t ? t->CW : 16;         // rows of MAXC entries: more than 16 cepstra / LP lags
+    if (signal || (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc && d.kind != ctu::FeaKind::Lpa)) k.feat = FEAT_BANDS;
+    else k.feat = d.kind == ctu::FeaKind::Dctc ? FEAT_DCTC : o.fb_inld ? FEAT_LP : FEAT_LPD;
+    // rows of samples per lane that can be non-zero.  The 13-row instantiations serve the 25 ms windows (the *ss modes: every window of
+    // at most 13 rows - the window table is zero beyond the window); every other window, and -remove_dc1, takes the generic row count
+    const int rows = k.mode ? (d.window + 15) / 16 : (d.window + 31) / 32;
+    k.nz = (!o.remove_dc1 && (rows == 13 || (k.ss && rows < 13))) ? 13 : 16;
+    // the spectra leave the kernel for the VAD kernels (Burg-cepstral and energy criteria) or, in builds without SY, for synth_kernel
+    k.vx = (signal && !k.sy) || (o.do_vad() && !k.vf && !signal && (o.vad_cri_mode == "energy" || o.vad_cepdist_mode == "lpc"));
+    bool diag = false;
+#ifdef CTU_DIAG  // phase ablation (ctu_engine_run: kp.dbg) is a run-time flag
+    diag = getenv("CTU_DEBUG_MODE") && atoi(getenv("CTU_DEBUG_MODE")) != 0;
+#endif
+    // the plain chain: every flag a specialised GEN turns into a constant has its default
+    const bool base = !k.vx && !o.fea_E && o.fb_power && o.remove_dc && !o.remove_dc1 && !diag && !signal && !o.nr_when_afterFB;
+    const bool lp12 = o.fea_lporder == 12 && o.fea_ncepcoefs == 12 && d.kind != ctu::FeaKind::Lpa;  // the PLP preset exactly: order and number of cepstra fixed at compile time (LPO)
+    // ---- GEN and LPO, top to bottom
+    k.gen = GEN_FULL;
+    if (o.remove_dc1) k.gen = GEN_DC1;  // no spectrum export
+    else if (k.sy) {}                   // speech output: no phase 2, the flags at run time
+    else if (k.ss) {
+        // the straight-line lattices name the window's last sample: the presets' windows, cepstra on the matrix cores or plain band outputs.
+        // Energy columns, -fb_inld, -fb_power off, the LP kinds, other windows: the flags at run time
+        const bool preset_win = d.window == (k.mode ? VF_WINDOW : VF0_WINDOW);
+        if (preset_win && ((k.md && k.feat == FEAT_DCTC) || (k.feat == FEAT_BANDS && base && !o.fb_inld))) {
+            k.gen = GEN_PLAIN;
+            k.lpo = o.fea_ncepcoefs == 12 ? 12 : 0;  // the detector's order is -fea_ncepcoefs
+        }
+    }
+    else if (k.vf) k.gen = exten ? GEN_EXTEN : GEN_PLAIN;
+    else if (k.md && k.feat == FEAT_LP) {  // the compressed-band LP chain: lags by the MFMA tail, the recursions in lp_tail_kernel
+        k.gen = GEN_INLD;
+        k.lpo = lp12 ? 12 : 0;
+    }
+    else if (k.md) k.gen = exten ? GEN_EXTEN : GEN_PLAIN;
+    else if (k.vx) {}
+    else if (base && !o.fb_inld && !exten && k.feat != FEAT_LPD) k.gen = GEN_PLAIN;
+    else if (base && o.fb_inld && !exten && k.nc == 16 && k.feat == FEAT_LP) {
+        k.gen = GEN_INLD;
+        k.lpo = lp12 ? 12 : 0;
+    }
+    else if (base && !o.fb_inld && exten && k.feat == FEAT_BANDS) k.gen = GEN_EXTEN;
+    // ---- the straight-line filter-bank walk, where the bank matches the entry compiled for exactly this instantiation
+    if (t) {  // CTU_PHASE2_GENERIC=1: the generic walk for every bank (A/B and identity checks inside one build)
+        const char *g = getenv("CTU_PHASE2_GENERIC");
+        const int m = (g && atoi(g) != 0) ? -1 : match_walk(d, t->slot_chunk);
+        for_each_walk([&](auto w) {
+            if (m == w.index && walk_serves<decltype(w)>(k)) k.walk = m;
+        });
+    }
+    // what the eligibility rules (md_eligible, vf_eligible, ss_eligible) promise the tree above: the instantiation exists, and a specialised
+    // GEN's constants are the configuration's flags
+    const bool flags_ok = k.gen == GEN_FULL || k.gen == GEN_DC1 || (base && o.fb_inld == (k.gen == GEN_INLD) && exten == (k.gen == GEN_EXTEN));
+    if (!fe_compiled(k) || !flags_ok) throw std::runtime_error("internal: no front-end instantiation for this configuration (" + fe_name(k) + ")");
+    return k;
 }
 
 void build_tables(ctu_engine *e) {
@@ -844,9 +959,26 @@ void build_tables(ctu_engine *e) {
         }
         return;
     }
+    // ---- the 512 / 256-point front end: the phase-2 tables (none with speech output), then the instantiation, then what follows from it
+    Phase2Tables t;
+    if (!d.signal_out) {
+        build_phase2(d, t);
+        if (check_phase2(d, t) != 0.0) throw std::runtime_error("internal: phase-2 chunk tables do not reproduce the filter bank");
+    }
+    const FeSel k = e->sel = fe_select(d, d.signal_out ? nullptr : &t);
+    e->mode = k.mode;
+    e->feat = k.feat;
+    e->md = k.md;
+    e->vf = k.vf;
+    e->sy = k.sy;
+    e->ss = k.ss ? ss_mode_of(d.o) : 0;
+    e->ss_file = e->ss && d.o.vadmode == "file";
+    // The DUAL instantiations (frontend_kernel.h: the plain chain, with or without the intensity-loudness law) take their window scaled by 1/2: the packed transform's untangle owes the
+    // power spectrum a factor 1/4, and a power of two on the window goes through every rounding of the chain unchanged - the rows are
+    // bit for bit those of 0.25f * (re^2 + im^2), two multiplications per bin pair cheaper.
+    const float wscale = fe_dual(k.nz, k.mode, k.vx, k.gen, k.vf, k.ss, k.sy) ? 0.5f : 1.f;
     // ---- per-lane constant records (see LC_* above)
-    const bool mode1 = d.wfft == 256;
-    e->mode = mode1 ? 1 : 0;
+    const bool mode1 = k.mode == 1;
     std::vector<float> lc(16 * LANEC, 0.f);
     for (int l = 0; l < 16; l++) {
         float *r = lc.data() + l * LANEC;
@@ -854,7 +986,7 @@ void build_tables(ctu_engine *e) {
             for (int h = 0; h < 2; h++) {
                 // MODE 0: lane l holds samples 32j+2l, +1 of row j; MODE 1: sample 16j+l (second slot unused)
                 const int i = mode1 ? (h ? d.window : 16 * j + l) : 32 * j + 2 * l + h;
-                r[LC_WIN + 2 * j + h] = i < d.window ? (float)d.hamming[i] : 0.f;
+                r[LC_WIN + 2 * j + h] = i < d.window ? (float)d.hamming[i] * wscale : 0.f;
                 r[LC_MASK + 2 * j + h] = i < d.window ? 1.f : 0.f;
             }
         for (int k1 = 1; k1 < 16; k1++) {
@@ -873,12 +1005,6 @@ void build_tables(ctu_engine *e) {
         e->ncoef_out = 0; e->ck_off = 0; e->cf_off = 0; e->tab_floats = 0; e->NS = 0; e->CW = 16; e->lift_off = 0;
         e->ftab.upload(std::vector<float>(4, 0.f));
         e->itab.upload(std::vector<int>(4, 0));
-        e->lds_bytes = ((size_t)TILE * PSTRIDE + LTW_FLOATS) * sizeof(float);
-        e->feat = FEAT_BANDS;
-        e->nz = e->mode ? (d.window + 15) / 16 : (d.window + 31) / 32;
-        e->sy = CTU_SY;
-        e->ss = ss_eligible(d) ? ss_mode_of(d.o) : 0;
-        e->ss_file = e->ss && d.o.vadmode == "file";
         if (e->ss) {  // the detector's Hann window is the only table (as build_phase2 lays it out for the feature path)
             std::vector<float> ft;
             const double m = 2 * 3.141592653 / d.window;
@@ -888,73 +1014,29 @@ void build_tables(ctu_engine *e) {
             ft.push_back(0.f);  // (where the lifter sits on the feature path)
             e->lift_off = e->tab_floats;
             e->ftab.upload(ft);
-            e->lds_bytes = ((size_t)TILE * PSTRIDE + e->tab_floats + LTW_FLOATS + (!e->mode ? NWAVE * VF0_STAGE : 0)) * sizeof(float);
         }
-        return;
+    } else {
+        e->ncoef_out = t.ncoef_out;
+        e->ck_off = t.ck_off;
+        e->cf_off = t.cf_off;
+        e->cfd_off = t.cfd_off;
+        e->am_off = t.am_off;
+        e->han_off = t.han_off;
+        e->tab_floats = t.tab_floats;
+        e->NS = t.NS;
+        e->CW = t.CW;
+        e->lift_off = t.lift_off;
+        e->ftab.upload(t.ft);
+        e->itab.upload(t.it);
+        if (d.kind == ctu::FeaKind::TrapDct) {
+            std::vector<float> g(d.trap.begin(), d.trap.end());
+            e->trapG.upload(g);
+            build_trap_bf16(e);
+        }
     }
-    Phase2Tables t;
-    build_phase2(d, t);
-    if (check_phase2(d, t) != 0.0) throw std::runtime_error("internal: phase-2 chunk tables do not reproduce the filter bank");
-    e->ncoef_out = t.ncoef_out;
-    e->ck_off = t.ck_off;
-    e->cf_off = t.cf_off;
-    e->cfd_off = t.cfd_off;
-    e->am_off = t.am_off;
-    e->md = t.md;
-    e->vf = vf_eligible(d);
-    e->ss = ss_eligible(d) ? ss_mode_of(d.o) : 0;
-    e->ss_file = e->ss && d.o.vadmode == "file";
-    e->han_off = t.han_off;
-    e->tab_floats = t.tab_floats;
-    e->NS = t.NS;
-    e->CW = t.CW;
-    e->lift_off = t.lift_off;
-    {   // CTU_PHASE2_GENERIC=1: the generic walk for every bank (A/B and identity checks inside one build)
-        const char *g = getenv("CTU_PHASE2_GENERIC");
-        e->walk = (g && atoi(g) != 0) ? -1 : match_walk(d, t.slot_chunk);
-    }
-    e->ftab.upload(t.ft);
-    e->itab.upload(t.it);
     e->lds_bytes = ((size_t)TILE * PSTRIDE + e->tab_floats + LTW_FLOATS + (d.o.nr_when_afterFB ? NWAVE * 128 : 0) +
-                    ((e->vf || e->ss) && !e->mode ? NWAVE * VF0_STAGE : 0)) * sizeof(float);  // 512-point detector paths: staged frames per wave
+                    ((k.vf || k.ss) && !k.mode ? NWAVE * VF0_STAGE : 0)) * sizeof(float);  // 512-point detector paths: staged frames per wave
     if (e->lds_bytes > 160 * 1024) throw std::runtime_error("configuration needs more than 160 KiB of LDS");
-    if (d.kind == ctu::FeaKind::TrapDct) {
-        std::vector<float> g(d.trap.begin(), d.trap.end());
-        e->trapG.upload(g);
-        build_trap_bf16(e);
-    }
-    switch (d.kind) {
-        case ctu::FeaKind::Spec:
-        case ctu::FeaKind::LogSpec:
-        case ctu::FeaKind::TrapDct: e->feat = FEAT_BANDS; break;
-        case ctu::FeaKind::Dctc: e->feat = FEAT_DCTC; break;
-        case ctu::FeaKind::Lpc:
-        case ctu::FeaKind::Lpa: e->feat = d.o.fb_inld ? FEAT_LP : FEAT_LPD; break;
-        case ctu::FeaKind::None: e->feat = FEAT_BANDS; break;  // not reached: the signal path returns above
-    }
-    e->nz = e->mode ? (d.window + 15) / 16 : (d.window + 31) / 32;  // rows of samples per lane that can be non-zero
-    // The DUAL instantiations (frontend_kernel.h: the plain chain, with or without the intensity-loudness law) take their window scaled by 1/2: the packed transform's untangle owes the
-    // power spectrum a factor 1/4, and a power of two on the window goes through every rounding of the chain unchanged - the rows are
-    // bit for bit those of 0.25f * (re^2 + im^2), two multiplications per bin pair cheaper.  launch_vx checks that the instantiation
-    // it launches is the one the table was scaled for.
-    {   // the same decision tree as launch_vx, from the options
-        const ctu::Opts &o = d.o;
-        const bool vx = o.do_vad() && !e->vf && (o.vad_cri_mode == "energy" || (o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "lpc"));
-        const bool base = !vx && !o.fea_E && o.fb_power && o.remove_dc && !o.remove_dc1 && !o.nr_when_afterFB;
-        const bool exten = o.nr_mode == "exten", narrow = e->CW == 16;
-        bool dual = false;
-        if (e->md && e->feat == FEAT_LP) dual = true;
-        else if (e->md) dual = !exten;
-        else if (vx) dual = false;
-        else if (base && !o.fb_inld && !exten && e->feat != FEAT_LPD) dual = true;
-        else if (base && o.fb_inld && !exten && narrow && e->feat == FEAT_LP) dual = true;
-        e->half_window = CTU_DUAL && dual && !e->vf && !e->ss && !e->sy && !o.remove_dc1 && e->mode == 0 && e->nz == 13;
-    }
-    if (e->half_window) {
-        for (int l = 0; l < 16; l++)
-            for (int j = 0; j < 32; j++) lc[(size_t)l * LANEC + LC_WIN + j] *= 0.5f;
-        e->lanec.upload(lc);
-    }
 }
 
 // Kernels whose dynamic LDS may pass the 64 KiB default: the 160 KiB attribute is set once per engine (= per device) and instantiation.
@@ -973,142 +1055,67 @@ void launch_fe(ctu_engine *e, K kern, dim3 grid, hipStream_t s, const KParams &k
     hipLaunchKernelGGL(kern, grid, dim3(WG), e->lds_bytes, s, kp);
 }
 
-// A front-end launch of an instantiation that phase2_walks.h may list: with the straight-line walk when the engine's bank matched
-// the entry compiled for exactly these parameters, with the generic walk otherwise.
-template <int NZ, int FEAT, int MODE, bool VX, int GEN, int LPO, bool MD>
-void launch_walk(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
-    bool done = false;
-    if constexpr (NZ == WALK_NZ && MODE == 0 && !VX) {
-        for_each_walk([&](auto w) {
-            typedef decltype(w) W;
-            if constexpr (W::FEAT == FEAT && W::GEN == GEN && W::LPO == LPO && W::MD == MD) {
-                if (!done && e->walk == W::index) {
-                    if (kp.NS != W::NS) throw std::runtime_error("internal: walk signature of another bank");
-                    launch_fe(e, &frontend_kernel<NZ, FEAT, MODE, false, 16, GEN, LPO, MD, false, false, false, W>, grid, s, kp);
-                    e->walk_launched = W::index;
-                    done = true;
+// f(integral_constant<int, C>) for the C that v equals
+template <int... C, class F>
+void lift(int v, F &&f) {
+    (void)((v == C && (f(std::integral_constant<int, C>{}), true)) || ...);
+}
+// The front-end launch of an engine: its FeSel lifted to template arguments, one at a time; fe_compiled decides which leaves exist.
+void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
+    const FeSel &k = e->sel;
+#define V(x) decltype(x)::value
+    lift<13, 16>(k.nz, [&](auto NZ) {
+    lift<FEAT_BANDS, FEAT_DCTC, FEAT_LP, FEAT_LPD>(k.feat, [&](auto FEAT) {
+    lift<0, 1>(k.mode, [&](auto MODE) {
+    lift<0, 1>(k.vx, [&](auto VX) {
+    lift<16, MAXC>(k.nc, [&](auto NC) {
+    lift<GEN_PLAIN, GEN_INLD, GEN_EXTEN, GEN_FULL, GEN_DC1>(k.gen, [&](auto GEN) {
+    lift<0, 12>(k.lpo, [&](auto LPO) {
+    lift<0, 1>(k.md, [&](auto MD) {
+    lift<0, 1>(k.vf, [&](auto VF) {
+    lift<0, 1>(k.ss, [&](auto SS) {
+    lift<0, 1>(k.sy, [&](auto SY) {
+        constexpr FeSel K{V(NZ), V(FEAT), V(MODE), V(VX) != 0, V(NC), V(GEN), V(LPO), V(MD) != 0, V(VF) != 0, V(SS) != 0, V(SY) != 0, -1};
+        if constexpr (fe_compiled(K)) {
+            bool walked = false;
+            for_each_walk([&](auto w) {
+                typedef decltype(w) W;
+                if constexpr (walk_serves<W>(K)) {
+                    if (k.walk == W::index) {
+                        launch_fe(e, &frontend_kernel<K.nz, K.feat, K.mode, K.vx, K.nc, K.gen, K.lpo, K.md, K.vf, K.ss, K.sy, W>, grid, s, kp);
+                        walked = true;
+                    }
                 }
-            }
-        });
-    }
-    if (!done) launch_fe(e, &frontend_kernel<NZ, FEAT, MODE, VX, 16, GEN, LPO, MD>, grid, s, kp);
-}
-
-template <int NZ, int MODE, bool VX, int GEN>
-void launch_nz(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
-    const bool wide = kp.CW != 16;  // coefficient rows of MAXC entries (more than 16 cepstra / LP lags)
-    const int feat = e->feat;
-    if (feat == FEAT_BANDS) launch_walk<NZ, FEAT_BANDS, MODE, VX, GEN, 0, false>(e, grid, s, kp);
-    else if (feat == FEAT_DCTC && !wide) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, VX, 16, GEN>, grid, s, kp);
-    else if (feat == FEAT_DCTC) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, VX, MAXC, GEN>, grid, s, kp);
-    else if (feat == FEAT_LPD) {
-        if constexpr (GEN == GEN_FULL || GEN == GEN_DC1) {
-            if (!wide) launch_fe(e, &frontend_kernel<NZ, FEAT_LPD, MODE, VX, 16, GEN>, grid, s, kp);
-            else launch_fe(e, &frontend_kernel<NZ, FEAT_LPD, MODE, VX, MAXC, GEN>, grid, s, kp);
-        } else throw std::runtime_error("internal: the double LP tail has run-time flags only");
-    }
-    else if (!wide) launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, VX, 16, GEN>, grid, s, kp);
-    else launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, VX, MAXC, GEN>, grid, s, kp);
-}
-
-template <int NZ, int MODE>
-void launch_vx(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
-    // Specialised instantiations (see GEN in frontend_kernel.h): the plain chain, plain + intensity-loudness law for the
-    // 16-coefficient LP path (PLP), plain + exten for 16-coefficient DCT / band outputs; the cepstral ones of these run
-    // their DCT tail on the matrix cores (MD, tables laid out for it by build_phase2).  Everything else, and every run
-    // with the VAD export, reads its flags at run time.
-    const bool vx = kp.vad_export != 0;
-    const int feat = e->feat;
-    e->walk_launched = -1;  // launch_walk sets it where it launches a straight-line walk
-    const bool base = !vx && kp.e_mode == 0 && kp.fb_power && kp.remove_dc && !kp.remove_dc1 && !kp.dbg && !kp.skip_phase2 && !kp.nr_after_fb;
-    const bool narrow = kp.CW == 16;
-    {   // the window table of this engine is scaled for exactly one instantiation (ctu_engine::half_window)
-        constexpr bool dual_shape = CTU_DUAL && MODE == 0 && NZ < 16;
-        bool dual = false;  // does the tree below end on a DUAL instantiation (GEN_PLAIN or GEN_INLD without export / detector / synthesis)?
-        if (dual_shape && !(e->sy && kp.skip_phase2) && !kp.remove_dc1 && !e->ss && !e->vf) {
-            if (e->md && feat == FEAT_LP) dual = true;
-            else if (e->md) dual = !kp.nr_exten;
-            else if (vx) dual = false;
-            else if (base && !kp.fb_inld && !kp.nr_exten && feat != FEAT_LPD) dual = true;
-            else if (base && kp.fb_inld && !kp.nr_exten && narrow && feat == FEAT_LP) dual = true;
+            });
+            if (!walked) launch_fe(e, &frontend_kernel<K.nz, K.feat, K.mode, K.vx, K.nc, K.gen, K.lpo, K.md, K.vf, K.ss, K.sy>, grid, s, kp);
         }
-        if (dual != e->half_window) throw std::runtime_error("internal: window table scaled for another instantiation");
-    }
-    if (e->sy && kp.skip_phase2) {
-        if (kp.remove_dc1) {
-            if constexpr (NZ == 16) launch_fe(e, &frontend_kernel<16, FEAT_BANDS, MODE, false, 16, GEN_DC1, 0, false, false, false, true>, grid, s, kp);
-        }
-        else if (e->ss) {
-            if constexpr (MODE == 1 || NZ == 13) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_FULL, 0, false, false, true, true>, grid, s, kp);
-            else throw std::runtime_error("internal: SS engine without an SS instantiation");
-        }
-        else launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_FULL, 0, false, false, false, true>, grid, s, kp);
-    }
-    else if (kp.remove_dc1) {  // the generic row count only (ctu_engine_run picks NZ = 16), no spectrum export
-        if constexpr (NZ == 16) launch_nz<16, MODE, false, GEN_DC1>(e, grid, s, kp);
-    }
-    else if (e->ss) {
-        if constexpr (MODE == 1 || NZ == 13) {
-            // the plain chain: the detector's lattice unrolled for the presets' 12 coefficients (LPO = 12) or for up to 16
-            const bool preset_win = kp.window == (MODE == 1 ? VF_WINDOW : VF0_WINDOW);  // the straight-line lattices name the window's last sample
-            if (!preset_win) {
-                if constexpr (NZ == 13) {
-                    if (!narrow) throw std::runtime_error("internal: SS engine without an SS instantiation");
-                    if (feat == FEAT_BANDS) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                    else if (feat == FEAT_DCTC) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                    else if (feat == FEAT_LP) launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                    else launch_fe(e, &frontend_kernel<NZ, FEAT_LPD, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                } else throw std::runtime_error("internal: SS engine without an SS instantiation");
-            }
-            else if (e->md && feat == FEAT_DCTC && kp.ss_nc == 12) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_PLAIN, 12, true, false, true>, grid, s, kp);
-            else if (e->md && feat == FEAT_DCTC) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_PLAIN, 0, true, false, true>, grid, s, kp);
-            else if (feat == FEAT_BANDS && base && !kp.fb_inld && kp.ss_nc == 12) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_PLAIN, 12, false, false, true>, grid, s, kp);
-            else if (feat == FEAT_BANDS && base && !kp.fb_inld) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_PLAIN, 0, false, false, true>, grid, s, kp);
-            else if (!narrow) throw std::runtime_error("internal: SS engine without an SS instantiation");
-            // energy columns, -fb_inld, -fb_power off, the LP kinds: the flags at run time (the 25 ms frame shapes only: NZ = 13)
-            else if constexpr (NZ == 13) {
-                if (feat == FEAT_BANDS) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                else if (feat == FEAT_DCTC) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                else if (feat == FEAT_LP) launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                else if (feat == FEAT_LPD) launch_fe(e, &frontend_kernel<NZ, FEAT_LPD, MODE, false, 16, GEN_FULL, 0, false, false, true>, grid, s, kp);
-                else throw std::runtime_error("internal: SS engine without an SS instantiation");
-            }
-            else throw std::runtime_error("internal: SS engine without an SS instantiation");
-        }
-        else throw std::runtime_error("internal: SS engine without an SS instantiation");
-    }
-    else if (e->vf) {
-        if (!(kp.e_mode == 0 && kp.fb_power && kp.remove_dc && !kp.fb_inld && feat == FEAT_DCTC && narrow && (MODE == 1 || NZ == 13) && e->md))
-            throw std::runtime_error("internal: VF engine without the VF instantiation");
-        if constexpr (MODE == 1 || NZ == 13) {
-            if (kp.nr_exten) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_EXTEN, 0, true, true>, grid, s, kp);
-            else launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_PLAIN, 0, true, true>, grid, s, kp);
-        }
-    }
-    else if (e->md && feat == FEAT_LP) {  // the compressed-band LP chain: lags by the MFMA tail, the recursions in lp_tail_kernel
-        if (!(base && kp.fb_inld && !kp.nr_exten && narrow)) throw std::runtime_error("internal: MD tables without the MD instantiation");
-        if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) launch_walk<NZ, FEAT_LP, MODE, false, GEN_INLD, 12, true>(e, grid, s, kp);
-        else launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_INLD, 0, true>, grid, s, kp);
-    }
-    else if (e->md) {
-        if (!(base && !kp.fb_inld && feat == FEAT_DCTC && narrow)) throw std::runtime_error("internal: MD tables without the MD instantiation");
-        if (kp.nr_exten) launch_fe(e, &frontend_kernel<NZ, FEAT_DCTC, MODE, false, 16, GEN_EXTEN, 0, true>, grid, s, kp);
-        else launch_walk<NZ, FEAT_DCTC, MODE, false, GEN_PLAIN, 0, true>(e, grid, s, kp);
-    }
-    else if (vx) launch_nz<NZ, MODE, true, GEN_FULL>(e, grid, s, kp);
-    else if (base && !kp.fb_inld && !kp.nr_exten && feat != FEAT_LPD) launch_nz<NZ, MODE, false, GEN_PLAIN>(e, grid, s, kp);
-    else if (base && kp.fb_inld && !kp.nr_exten && narrow && feat == FEAT_LP && kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa)
-        // the PLP preset exactly: order and number of cepstra fixed at compile time (LPO)
-        launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_INLD, 12>, grid, s, kp);
-    else if (base && kp.fb_inld && !kp.nr_exten && narrow && feat == FEAT_LP) launch_fe(e, &frontend_kernel<NZ, FEAT_LP, MODE, false, 16, GEN_INLD>, grid, s, kp);
-    else if (base && !kp.fb_inld && kp.nr_exten && narrow && feat == FEAT_BANDS) launch_fe(e, &frontend_kernel<NZ, FEAT_BANDS, MODE, false, 16, GEN_EXTEN>, grid, s, kp);
-    else launch_nz<NZ, MODE, false, GEN_FULL>(e, grid, s, kp);
+    }); }); }); }); }); }); }); }); }); }); });
+#undef V
+    e->walk_launched = k.walk;
 }
 
 std::vector<std::string> to_args(int argc, const char *const *argv) {
     std::vector<std::string> a;
     for (int i = 0; i < argc; i++) a.emplace_back(argv[i] ? argv[i] : "");
     return a;
+}
+
+// FFT sizes below 256 (windows up to 128 samples): the N-point spectrum of a frame is every (256/N)-th bin of its
+// 256-point spectrum, because the frame is zero beyond the window either way.  The engine runs the 256-point mode
+// with the filter bank spread onto those bins (zero weight in between); sums over bins step by the stride returned.
+int spread_small_fft(ctu::Design &d) {
+    if (!(d.wfft < 256 && d.wfft >= 32 && !d.signal_out)) return 1;
+    const int S = 256 / d.wfft;
+    for (auto &row : d.fb) {
+        std::vector<double> wide(129, 0.0);
+        for (int k = 0; k < d.K; k++) wide[(size_t)k * S] = row[k];
+        row.swap(wide);
+    }
+    for (int &f : d.fb_first) f *= S;
+    for (int &l : d.fb_last) l *= S;
+    d.K = 129;
+    d.wfft = 256;
+    return S;
 }
 
 void fill_dims(const ctu::Design &d, ctu_dims *out) {
@@ -1170,6 +1177,14 @@ int64_t ctu_config_table(int argc, const char *const *argv, const char *name, do
             for (int sl = 0; sl < t.NS; sl++) v.push_back(t.slot_chunk[sl + 1] - t.slot_chunk[sl]);
             v.push_back((double)match_walk(d, t.slot_chunk));
         }
+        else if (n == "frontend") {  // the instantiation ctu_engine_create selects: frontend_kernel's template arguments, the walk's index last
+            spread_small_fft(d);
+            Phase2Tables t;
+            if (!d.signal_out && d.wfft < 1024) build_phase2(d, t);
+            const FeSel k = fe_select(d, d.signal_out ? nullptr : &t);
+            v = {(double)k.nz, (double)k.feat, (double)k.mode, (double)k.vx, (double)k.nc, (double)k.gen, (double)k.lpo, (double)k.md, (double)k.vf,
+                 (double)k.ss, (double)k.sy, (double)k.walk};
+        }
         else {
             g_create_error = "unknown table name";
             return CTU_ERR_INPUT;
@@ -1189,25 +1204,10 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
     try {
         ctu::Opts o = ctu::Opts::from_args(to_args(argc, argv));
         e->design.reset(new ctu::Design(o));
-        // FFT sizes below 256 (windows up to 128 samples): the N-point spectrum of a frame is every (256/N)-th bin of its
-        // 256-point spectrum, because the frame is zero beyond the window either way.  The engine runs the 256-point mode
-        // with the filter bank spread onto those bins (zero weight in between); sums over bins step by kstride.
         ctu::Design &d = *e->design;
         e->user_wfft = d.wfft;  // what ctu_engine_dims reports: the configuration's own FFT size and bin count (= ctu_config_dims)
         e->user_K = d.K;
-        if (d.wfft < 256 && d.wfft >= 32 && !d.signal_out) {
-            const int S = 256 / d.wfft;
-            e->kstride = S;
-            for (auto &row : d.fb) {
-                std::vector<double> wide(129, 0.0);
-                for (int k = 0; k < d.K; k++) wide[(size_t)k * S] = row[k];
-                row.swap(wide);
-            }
-            for (int &f : d.fb_first) f *= S;
-            for (int &l : d.fb_last) l *= S;
-            d.K = 129;
-            d.wfft = 256;
-        }
+        e->kstride = spread_small_fft(d);
     } catch (const std::exception &ex) {
         g_create_error = ex.what();
         return CTU_ERR_OPTS;
@@ -1398,10 +1398,10 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
     // Each workgroup walks a chain of tiles.  Stateless chains stride over the tile list; with a
     // per-utterance recurrence (exten) a workgroup takes whole utterances, tile after tile.
     std::vector<int> wg_first;
-    // workgroups that fit a CU at once: two when the instantiation keeps to 128 VGPRs and 80 KB of LDS; the synthesis and the
-    // 512-point detector instantiations take 256 VGPRs (fe_waves_per_simd)
-    const bool wide_regs = (e->sy && CTU_SY_LB < 4) || ((e->vf || e->ss) && (!e->mode || CTU_VF1_LB < 4));
-    const int max_wg = e->n_cu * ((CTU_LB >= 4 && e->lds_bytes <= (size_t)LDS_2WG && !wide_regs) ? 2 : 1);
+    // workgroups that fit a CU at once: two when the instantiation keeps to 128 VGPRs (four waves per SIMD) and 80 KB of LDS; the synthesis
+    // and the 512-point detector instantiations take 256 VGPRs
+    const FeSel &k = e->sel;
+    const int max_wg = e->n_cu * ((fe_waves_per_simd(k.mode, k.vf, k.ss, k.sy) >= 4 && e->lds_bytes <= (size_t)LDS_2WG) ? 2 : 1);
     if (e->per_wave) {
         // chains per wave: whole utterances, longest first onto the least loaded chain (LPT), tile after tile
         std::vector<int> live;  // utterances that have at least one frame
@@ -1715,14 +1715,7 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             hipLaunchKernelGGL(dc1_offsets_kernel, dim3((pl->n_utt + 63) / 64), dim3(64), 0, s, pl->dc1m.p, pl->utt_info.p, pl->dc1.p, pl->n_utt, d.window, d.wshift);
         }
         HIP_TRY(hipEventRecord(e->ev0, s));
-        auto launch = [&] {
-            // (the 13-row instantiations serve every window of at most 13 rows - the window table is zero beyond the window - and the *ss
-            // modes are instantiated for 13 rows only)
-            switch (kp.remove_dc1 ? 16 : (e->ss && e->nz <= 13) ? 13 : e->nz) {
-                case 13: e->mode ? launch_vx<13, 1>(e, dim3(grid), s, kp) : launch_vx<13, 0>(e, dim3(grid), s, kp); break;
-                default: e->mode ? launch_vx<16, 1>(e, dim3(grid), s, kp) : launch_vx<16, 0>(e, dim3(grid), s, kp); break;
-            }
-        };
+        auto launch = [&] { launch_frontend(e, dim3(grid), s, kp); };
         std::function<void()> ss_launch = launch;  // one pass of the *ss modes' seed iteration (below)
         BigParams bp;
         if (e->big) {
@@ -1751,10 +1744,7 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             if (shm > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
             const void *kfn = kp.nr_exten ? (d.wfft == 1024 ? (const void *)bigfft_kernel<4, true> : d.wfft == 2048 ? (const void *)bigfft_kernel<8, true> : (const void *)bigfft_kernel<16, true>)
                                           : (d.wfft == 1024 ? (const void *)bigfft_kernel<4> : d.wfft == 2048 ? (const void *)bigfft_kernel<8> : (const void *)bigfft_kernel<16>);
-            if (shm > 64 * 1024 && !e->attr_done.count(kfn)) {
-                HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                e->attr_done.insert(kfn);
-            }
+            if (shm > 64 * 1024) allow_big_lds(e, kfn);
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / shm));
             const int g = std::max(1, std::min(pl->n_tiles, e->n_cu * per_cu));
             if (e->ss) {
@@ -1813,10 +1803,7 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
                                     (size_t)(((e->feat == FEAT_DCTC ? e->ncoef_out * d.B : 0) + 3) & ~3) * 4 + (size_t)((3 * d.B + 3) & ~3) * 4 + (size_t)(256 + 2 * d.B) * 4 + 64;
                 if (wshm > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the 1024-point kernel");
                 const void *wfn = bp.nr_exten ? (const void *)wave1k_kernel<true> : (const void *)wave1k_kernel<false>;
-                if (wshm > 64 * 1024 && !e->attr_done.count(wfn)) {
-                    HIP_TRY(hipFuncSetAttribute(wfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    e->attr_done.insert(wfn);
-                }
+                if (wshm > 64 * 1024) allow_big_lds(e, wfn);
                 const int wper_cu = (int)std::max<size_t>(1, std::min<size_t>(CTU_W1K_LB * 4 / W1K_WAVES, (160 * 1024) / wshm));
                 if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without per-wave chains");
                 // exten: one wave per chain of utterances, every chain gets its wave whatever fits the chip at once
@@ -2532,20 +2519,11 @@ const char *ctu_engine_kernel_name(const ctu_engine *e) {
     if (!e) return "";
     if (e->kname.empty()) {
         const ctu::Design &d = *e->design;
-        const ctu::Opts &o = d.o;
         std::string n;
         if (e->wave1k) n = "wave1k_kernel";
         else if (e->big && e->ss) n = "bigss_kernel<" + std::to_string(d.wfft / 256) + ">";
         else if (e->big) n = "bigfft_kernel<" + std::to_string(d.wfft / 256) + ">";
-        else {
-            const char *feat = e->feat == FEAT_DCTC ? "DCTC" : e->feat == FEAT_BANDS ? "BANDS" : e->feat == FEAT_LP ? "LP" : "LPD";
-            const bool exten = o.nr_mode == "exten" && !o.nr_when_afterFB;
-            const bool plain = plain_cepstral(d) || (!o.fea_E && o.fb_power && o.remove_dc && !o.remove_dc1 && !o.nr_when_afterFB && !d.signal_out);
-            n = "frontend_kernel<" + std::to_string(o.remove_dc1 ? 16 : e->nz) + ", " + feat + ", MODE " + std::to_string(e->mode) + ", " +
-                (e->sy ? "full" : !plain ? "full" : (e->ss && (!fused_frame_shape(d) || (!(e->md && e->feat == FEAT_DCTC) && !(e->feat == FEAT_BANDS && !o.fb_inld)))) ? "full" :  // launch_vx's *ss branch
-                 exten ? "exten" : o.fb_inld ? "inld" : "plain") + (e->md ? ", MD" : "") + (e->vf ? ", VF" : "") +
-                (e->ss ? ", SS" : "") + (e->sy ? ", SY" : "") + ">";
-        }
+        else n = fe_name(e->sel);
         const_cast<ctu_engine *>(e)->kname = n;
     }
     return e->kname.c_str();

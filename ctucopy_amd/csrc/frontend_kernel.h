@@ -94,6 +94,10 @@ namespace {
 constexpr int fe_waves_per_simd(int mode, bool vf, bool ss, bool sy = false) {
     return ((vf || ss) && mode == 0) ? 2 : (sy ? CTU_SY_LB : ((vf || ss) ? CTU_VF1_LB : CTU_LB));
 }
+// The DUAL instantiations (phase 1 below).  They take their window table scaled by 1/2 (engine.hip: build_tables asks this same function).
+constexpr bool fe_dual(int nz, int mode, bool vx, int gen, bool vf, bool ss, bool sy) {
+    return CTU_DUAL && mode == 0 && (gen == GEN_PLAIN || gen == GEN_INLD) && !vx && nz < 16 && !vf && !ss && !sy;
+}
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
 template <class F, int... S>
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         // is bound by dependent latency (LDS round trips, transcendental-free but long FMA chains) at four waves per SIMD,
         // not by issue.  Every instantiation of the plain chain and of the plain chain + intensity-loudness law (round 4; rounds 2-3: the
         // headline instantiation only): phase 1 does not depend on the feature tail.
-        constexpr bool DUAL = CTU_DUAL && MODE == 0 && (GEN == GEN_PLAIN || GEN == GEN_INLD) && !VX && NZ < 16 && !VF && !SS && !SY;
+        constexpr bool DUAL = fe_dual(NZ, MODE, VX, GEN, VF, SS, SY);
         if constexpr (DUAL && CTU_PK) {
             // The two passes as the two halves of packed registers: every add / multiply / FMA of phase 1 is a v_pk_*_f32 that
             // serves slots 0-3 and 4-7 together (kernel_common.h: cx2).  Same statements as the scalar DUAL block below.

@@ -78,7 +78,10 @@ int ctu_config_dims(int argc, const char *const *argv, ctu_dims *out);
  *        "dct" [(ncep+1)*nbands] | "idft" [(p+1)*nbands] | "trap" [ndct*traplen] | "lifter" [ncep] |
  *        "phase2_check" [3: table error, chunks, slots] | "phase2_walk" [slots + 1: the filter-bank walk's chunks per slot, then the
  *        index of the compiled walk signature that this configuration's bank and frame shape match, or -1; whether a run uses it
- *        depends on the instantiation too: ctu_engine_phase2_walk].
+ *        depends on the instantiation too: ctu_engine_phase2_walk] |
+ *        "frontend" [12: the frontend_kernel instantiation ctu_engine_create selects for the configuration, as its template arguments
+ *        NZ, FEAT, MODE, VX, NC, GEN, LPO, MD, VF, SS, SY and last the index of its straight-line walk or -1 (CTU_PHASE2_GENERIC is
+ *        honoured); eleven zeros and -1 for the large-FFT kernels (1024 points and above), which the FFT size alone selects].
  * Returns the number of values (written up to cap), or a negative error code. */
 int64_t ctu_config_table(int argc, const char *const *argv, const char *name, double *out, int64_t cap);
 
