@@ -23,6 +23,8 @@
 namespace {
 
 constexpr int BIGBURG_XCH = 3 * 4 * 4;  // doubles: [order parity | energy][wave][num, den, ef, eb[i - 1]]
+// Host side, bigburg_frames' carve-up (bigburg_kernel and bigssdet_kernel): bigsynth_kernel's two buffers and twiddles, and the lattice's exchange area
+LdsFit bigburg_lds(int wfft) { return lds_fit(((size_t)(wfft / 2) * 3 + 4) * sizeof(float2) + BIGBURG_XCH * sizeof(double), 8); }
 
 // SSDET: the detector of hwss / fwss / 2fwss (src/nr/nr.cc:278-295, src/vdet/CepstralDet.h:133-146) instead of the VAD's criterion: the
 // magnitudes are X^a of the exported vector (X itself in 2fwss) and the first `window` samples take the detector's Hann window

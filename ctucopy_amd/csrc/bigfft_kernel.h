@@ -185,6 +185,19 @@ __device__ __forceinline__ void big_project(const BigParams &p, const float *P, 
     }
 }
 
+// Host side.  LDS of the projection's tables as big_project's callers stage them: the bank's runs, the LP kinds' cosine iDFT rows in double
+// or the DCT rows, the bands' ranges [B][3] (bigfft_kernel, bigss_kernel, wave1k_kernel)
+size_t big_proj_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
+    return (size_t)((fb_total + 3) & ~3) * 4 + (size_t)(feat == FEAT_LP ? (d.o.fea_lporder + 1) * d.B : 0) * 8 +
+           (size_t)(((feat == FEAT_DCTC ? ncoef_out * d.B : 0) + 3) & ~3) * 4 + (size_t)((3 * d.B + 3) & ~3) * 4;
+}
+// bigfft_kernel's carve-up below: A, Bf | P | Y | red | ltw | lwin | the projection's tables | Ylog
+LdsFit bigfft_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
+    return lds_fit((size_t)d.wfft * 8 + (size_t)((d.K + 3) & ~3) * 4 + 64 * 4 + 4 * 8 + (size_t)d.wfft / 2 * 8 + (size_t)((d.window + 3) & ~3) * 4 +
+                       big_proj_lds(d, feat, ncoef_out, fb_total) + 64 * 4,
+                   8);
+}
+
 // EXTEN: -nr_mode exten (src/nr/nr.cc:86-140) - the recurrence runs along an utterance, so a WORKGROUP walks one of the plan's chains of
 // whole utterances (chain_first / TileRec::next, as wave1k_kernel's waves do) with Navg / Yavg of its bins k = tid + 256 i in registers.
 template <int NIT, bool EXTEN = false>  // NIT = wfft / 256: 4, 8 or 16 samples per lane
@@ -418,6 +431,8 @@ __device__ __forceinline__ const float2 *big_hc2r_lds(float2 *A, float2 *Bf, con
 //   Z[k] = (X[k] + X*[M-k]) + i e^{+2 pi i k / N} (X[k] - X*[M-k]),  z = IDFT_M(Z),  y[2n] = Re z[n], y[2n+1] = Im z[n]
 // (bigfft_kernel's Stockham radix-2 passes with the conjugate twiddles); the first `window` samples go to the frame's scratch row,
 // which ola_kernel overlaps and adds.
+// Host side, the carve-up below: two buffers of wfft / 2 (+ 4) complex values and the twiddles; the grid is capped at eight workgroups a CU
+LdsFit bigsynth_lds(int wfft) { return {((size_t)(wfft / 2) * 3 + 8) * sizeof(float2), 8}; }
 template <int NIT>
 __global__ __launch_bounds__(256) void bigsynth_kernel(const float2 *__restrict__ xri, const float *__restrict__ pnr, float *__restrict__ ybuf,
                                                        long long total_frames, int wfft, int window, float inv_n, const float2 *__restrict__ tw) {

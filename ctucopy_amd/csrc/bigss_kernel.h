@@ -26,6 +26,12 @@
 
 namespace {
 
+// Host side, the carve-up below: the spectrum vector, the bands and their logarithms, and the projection's tables (none on the speech
+// path).  The grid is the plan's chains, whose number ctu_plan_create caps at eight a CU.
+LdsFit bigss_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
+    return lds_fit((size_t)((d.K + 3) & ~3) * 4 + 64 * 4 + 4 * 8 + 64 * 4 + (d.signal_out ? 0 : big_proj_lds(d, feat, ncoef_out, fb_total)), 8);
+}
+
 template <int NIT>  // NIT = wfft / 256: 8 or 16; K = 128 NIT + 1 bins, NIT / 2 + 1 of them per thread
 __global__ __launch_bounds__(256) void bigss_kernel(const BigParams p) {
     extern __shared__ __align__(16) float smem[];

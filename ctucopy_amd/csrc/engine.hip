@@ -96,6 +96,9 @@ struct FeSel {
     bool md = false, vf = false, ss = false, sy = false;
     int walk = -1;
 };
+// The front end of FFT sizes of 1024 to 4096 points (build_tables decides it once; the run dispatches on it, ctu_engine_kernel_name names it):
+// wave1k_kernel, bigfft_kernel's export ahead of bigss_kernel (hwss / fwss / 2fwss), or bigfft_kernel alone
+enum BigPath { BIG_NONE, BIG_WAVE1K, BIG_SS, BIG_FFT };
 
 }  // namespace
 
@@ -118,7 +121,7 @@ struct ctu_engine {
     DevBuf<int> itab;
     // FFT sizes of 1024 to 4096 points (bigfft_kernel.h)
     bool big = false;
-    bool wave1k = false;        // 1024-point frames on wave1k_kernel (one wave per frame); CTU_WAVE1K=0 keeps them on bigfft_kernel
+    BigPath path = BIG_NONE;    // BIG_WAVE1K: 1024-point frames on wave1k_kernel (one wave per frame); CTU_WAVE1K=0 keeps them on bigfft_kernel
     int big_fb_total = 0;
     DevBuf<float> big_win, big_fbw, big_coef, big_lifter;
     DevBuf<float2> big_tw;
@@ -152,6 +155,8 @@ struct ctu_engine {
     std::set<const void *> attr_done;  // kernels whose dynamic-LDS limit has been raised on this engine's device
     bool do_vad = false;
     VadParams vp;
+    KParams kp0;    // the kernels' parameter blocks as far as design and tables fix them (ctu_engine_create); a run adds its buffers
+    BigParams bp0;  // (`big` only)
 };
 
 struct ctu_plan {
@@ -946,10 +951,11 @@ void build_tables(ctu_engine *e) {
         // (-remove_dc1 at 1024 points takes bigfft_kernel<4>, which reads the frames' offsets)
         // (and speech output and the Burg-cepstral VAD criterion: the spectra's export is bigfft_kernel's)
         const bool burg = d.o.do_vad() && d.o.vad_cri_mode == "cepdist" && d.o.vad_cepdist_mode == "lpc";
-        e->wave1k = d.wfft == 1024 && !d.o.remove_dc1 && !d.signal_out && !burg && !(getenv("CTU_WAVE1K") && atoi(getenv("CTU_WAVE1K")) == 0);
+        const bool wave1k = d.wfft == 1024 && !d.o.remove_dc1 && !d.signal_out && !burg && !(getenv("CTU_WAVE1K") && atoi(getenv("CTU_WAVE1K")) == 0);
         build_big_tables(e);
         e->ss = ss_big_eligible(d) ? ss_mode_of(d.o) : 0;
         e->ss_file = e->ss && d.o.vadmode == "file";
+        e->path = wave1k ? BIG_WAVE1K : e->ss ? BIG_SS : BIG_FFT;
         if (e->ss && !e->ss_file) {
             // Hann window of the detector, han[i] = 0.5 (1 - cos(2 * 3.141592653 / window * i)) (src/vdet/CepstralDet.h:133-136)
             std::vector<double> han((size_t)d.window);
@@ -1093,6 +1099,437 @@ void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp)
 #undef V
     e->walk_launched = k.walk;
 }
+// A launch with dynamic LDS: past the 64 KiB default the instantiation's limit is raised first.
+template <class K, class... A>
+void launch_lds(ctu_engine *e, K kern, dim3 grid, dim3 block, size_t shm, hipStream_t s, const A &...args) {
+    if (shm > 64 * 1024) allow_big_lds(e, kern);
+    hipLaunchKernelGGL(kern, grid, block, shm, s, args...);
+}
+
+// ---- what ctu_plan_create allocates for and the runs launch by, one name each
+// The LP kinds' recursions run in lp_tail_kernel, on the lags the front end or wave1k_kernel left (bigfft_kernel and bigss_kernel finish the LP
+// analysis themselves; nothing is projected with speech output)
+bool lp_tail_runs(const ctu_engine *e) { return (e->feat == FEAT_LP || e->feat == FEAT_LPD) && (!e->big || e->path == BIG_WAVE1K) && !e->design->signal_out; }
+// its lags are double: LP analysis on uncompressed band energies, and wave1k_kernel's lags
+bool lags_double(const ctu_engine *e) { return e->feat == FEAT_LPD || e->big; }
+// hwss / fwss / 2fwss with speech output at 2048 / 4096 points: the synthesis reads the subtracted magnitudes (pss), pnr stays as exported
+bool synth_reads_pss(const ctu_engine *e) { return e->big && e->ss && e->design->signal_out; }
+// NIT of the large-FFT kernels (samples per thread of a workgroup's 256): 4, 8 or 16
+int big_nit(const ctu_engine *e) { return e->design->wfft / 256; }
+
+// The parameter block of the 256 / 512-point front end as far as design and tables fix it (after build_tables and e->vp).
+KParams engine_kparams(const ctu_engine *e) {
+    const ctu::Design &d = *e->design;
+    const bool signal = d.signal_out;
+    KParams kp;
+    std::memset(&kp, 0, sizeof kp);
+    kp.band_log = d.kind != ctu::FeaKind::Spec;
+    kp.band_to_scratch = d.kind == ctu::FeaKind::TrapDct;
+    kp.lp_is_lpa = d.kind == ctu::FeaKind::Lpa;
+    kp.syn_scale = 1.0f / (float)d.wfft;
+    kp.vad_export = (signal && !e->sy) ? 1 : ((!e->do_vad || e->vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0)));
+    kp.vad_nc = e->vp.ncoef;
+    kp.ss_mode = e->ss; kp.ss_init = d.o.nr_initsegs; kp.ss_nc = d.o.fea_ncepcoefs; kp.han_off = e->han_off;
+    kp.nr_b = (float)d.o.nr_b; kp.ss_q = d.o.nr_q;
+    kp.skip_phase2 = signal ? 1 : 0;
+    kp.lanec = e->lanec.p; kp.ftab = e->ftab.p; kp.itab = e->itab.p;
+    kp.tab_floats = e->tab_floats; kp.ck_off = e->ck_off; kp.cf_off = e->cf_off; kp.cfd_off = e->cfd_off; kp.am_off = e->am_off;
+    kp.NS = e->NS; kp.CW = e->CW; kp.ncoef_out = e->ncoef_out; kp.lift_off = e->lift_off;
+    kp.K = d.K; kp.window = d.window; kp.wshift = d.wshift; kp.B = d.B; kp.nfea = d.nfea; kp.D = d.Dbase;
+    kp.e_slot = d.e_slot;
+    if (d.o.fea_E && !signal) {  // energy routing of src/io/batch.cc:98-119
+        if (d.o.fea_rawenergy) kp.e_mode = 4;
+        else if (d.kind == ctu::FeaKind::Dctc) kp.e_mode = d.o.nr_when_afterFB ? 5 : 1;
+        else if (d.kind == ctu::FeaKind::Lpc || d.kind == ctu::FeaKind::Lpa) kp.e_mode = 2;
+        else kp.e_mode = 3;
+    }
+    kp.ncep = d.o.fea_ncepcoefs; kp.lporder = d.o.fea_lporder; kp.lp_stride = d.o.fea_lporder + 1;
+    kp.preem = d.o.preem; kp.inv_window = 1.0f / (float)d.window; kp.inv_window_d = 1.0 / (double)d.window;
+    kp.remove_dc = d.o.remove_dc; kp.kstride = e->kstride;
+    kp.remove_dc1 = d.o.remove_dc1 ? 1 : 0; kp.dc1_J = d.window / d.wshift;
+    kp.fb_power = d.o.fb_power; kp.fb_inld = d.o.fb_inld; kp.lifter_on = d.o.fea_lifter > 1;
+    kp.nr_exten = d.o.nr_mode == "exten"; kp.nr_after_fb = d.o.nr_when_afterFB ? 1 : 0;
+    kp.nr_p = (float)d.o.nr_p; kp.nr_p_d = d.o.nr_p; kp.nr_a = (float)d.o.nr_a;
+    kp.per_wave = e->per_wave ? 1 : 0;
+    return kp;
+}
+// ... and of the large-FFT kernels, from the block above
+BigParams engine_bigparams(const ctu_engine *e) {
+    const ctu::Design &d = *e->design;
+    const KParams &kp = e->kp0;
+    BigParams bp;
+    std::memset(&bp, 0, sizeof bp);
+    bp.win = e->big_win.p; bp.tw = e->big_tw.p; bp.fbw = e->big_fbw.p; bp.fb_range = e->big_range.p;
+    bp.coef = e->big_coef.p; bp.coef_d = e->big_coef_d.p; bp.lifter = e->big_lifter.p; bp.row_slot = e->big_slot.p;
+    bp.wfft = d.wfft; bp.K = d.K; bp.window = d.window; bp.wshift = d.wshift; bp.B = d.B; bp.D = kp.D;
+    bp.ncoef_out = e->ncoef_out; bp.feat = e->feat; bp.e_mode = kp.e_mode; bp.e_slot = kp.e_slot;
+    bp.remove_dc = kp.remove_dc; bp.fb_power = kp.fb_power; bp.fb_inld = kp.fb_inld; bp.band_log = kp.band_log;
+    bp.band_to_scratch = kp.band_to_scratch; bp.lp_is_lpa = kp.lp_is_lpa; bp.lporder = kp.lporder; bp.ncep = kp.ncep;
+    bp.lifter_on = kp.lifter_on; bp.preem = kp.preem;
+    bp.fb_total = e->big_fb_total;
+    bp.seg = e->big_seg.p;
+    bp.nr_exten = kp.nr_exten; bp.nr_p = kp.nr_p; bp.nr_a = kp.nr_a;
+    bp.dc1_J = kp.dc1_J;
+    bp.xri_only = d.signal_out ? 1 : 0;
+    if (e->ss) {
+        bp.ss_mode = e->ss; bp.ss_init = d.o.nr_initsegs; bp.ss_a = d.o.nr_a; bp.ss_b = d.o.nr_b; bp.ss_p = d.o.nr_p;
+    }
+    return bp;
+}
+// A run's blocks: the engine's, with the caller's buffers and the plan's scratch.
+KParams run_kparams(const ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    KParams kp = e->kp0;
+    kp.pcm = d_pcm;
+    kp.rows = (d.post_order > 0 || d.cms) ? pl->base_rows.p : d_rows;
+    kp.logmel = pl->logmel.p; kp.xri = pl->xri.p; kp.pnr = pl->pnr.p; kp.ybuf = pl->ybuf.p;
+    kp.vad_ci = pl->vad_ci.p; kp.vad_cf = pl->vad_cf.p; kp.lp_r = pl->lp_r.p; kp.dc1 = pl->dc1.p;
+    kp.tiles = pl->tiles.p; kp.wg_first = pl->wg_first.p; kp.tile_utt = pl->tile_utt.p;
+    kp.ss_seed = pl->ss_seed.p; kp.ss_last = pl->ss_last.p; kp.ss_dirty = pl->ss_dirty.p; kp.ss_vbits = pl->ss_vbits.p;
+#ifdef CTU_DIAG  // phase ablation (1 = phase 1 only, 2 = phase 2 only): diagnostic builds only
+    kp.dbg = getenv("CTU_DEBUG_MODE") ? atoi(getenv("CTU_DEBUG_MODE")) : 0;
+#endif
+    return kp;
+}
+BigParams run_bigparams(const ctu_engine *e, const ctu_plan *pl, const KParams &kp) {
+    BigParams bp = e->bp0;
+    bp.pcm = kp.pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = pl->n_tiles;
+    bp.chain_first = pl->wg_first.p; bp.n_chains = (int)pl->wg_first.n;
+    bp.vad_en = (e->do_vad && e->vp.cri == 0) ? pl->pnr.p : nullptr;
+    bp.dc1 = pl->dc1.p;
+    // the spectra leave bigfft_kernel for bigsynth_kernel, bigburg_kernel (which reads them; the rows are projected as well) or bigss_kernel
+    const bool exported = e->design->signal_out || (e->do_vad && e->vp.cri == 1) || e->ss;
+    bp.xri = exported ? pl->xri.p : nullptr; bp.pnr = exported ? pl->pnr.p : nullptr;
+    bp.pss = pl->pss.p;
+    bp.ss_seed = pl->ss_seed.p; bp.ss_last = pl->ss_last.p; bp.ss_dirty = pl->ss_dirty.p; bp.ss_vbits = pl->ss_vbits.p; bp.tile_utt = pl->tile_utt.p;
+    return bp;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the stages of a run, in ctu_engine_run's order
+// ------------------------------------------------------------------------------------------------
+// -remove_dc1: the frames' means, then the offsets the frames subtract (decode_kernels.h)
+void stage_dc1(const ctu_engine *e, const ctu_plan *pl, hipStream_t s, const int16_t *d_pcm) {
+    const ctu::Design &d = *e->design;
+    const int gx = std::max(1, std::min((pl->max_frames + 3) / 4, 64));
+    hipLaunchKernelGGL(dc1_means_kernel, dim3(gx, pl->n_utt), dim3(256), 0, s, d_pcm, pl->utt_info.p, pl->d_sample_off.p, pl->dc1m.p, pl->n_utt, d.window, d.wshift);
+    hipLaunchKernelGGL(dc1_offsets_kernel, dim3((pl->n_utt + 63) / 64), dim3(64), 0, s, pl->dc1m.p, pl->utt_info.p, pl->dc1.p, pl->n_utt, d.window, d.wshift);
+}
+
+// bigfft_kernel: a workgroup per frame over the tile list, as many as fit the chip at once; with exten one workgroup per chain of utterances
+void launch_bigfft(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigParams &bp) {
+    const LdsFit fit = bigfft_lds(*e->design, e->feat, e->ncoef_out, e->big_fb_total);
+    if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
+    if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without chains");
+    const dim3 g((unsigned)std::max(1, bp.nr_exten ? bp.n_chains : std::min(pl->n_tiles, e->n_cu * fit.per_cu)));
+    lift<4, 8, 16>(big_nit(e), [&](auto nit) {
+        constexpr int NIT = decltype(nit)::value;
+        if (bp.nr_exten) launch_lds(e, &bigfft_kernel<NIT, true>, g, dim3(256), fit.bytes, s, bp);
+        else launch_lds(e, &bigfft_kernel<NIT>, g, dim3(256), fit.bytes, s, bp);
+    });
+}
+// 1024 points: one wave per frame, the transform in registers (wave1k_kernel.h); tiles are dealt to waves
+void stage_wave1k(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigParams &bp) {
+    const ctu::Design &d = *e->design;
+    const LdsFit fit = wave1k_lds(d, e->feat, e->ncoef_out, e->big_fb_total);
+    if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the 1024-point kernel");
+    if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without per-wave chains");
+    // exten: one wave per chain of utterances, every chain gets its wave whatever fits the chip at once
+    const int wg = bp.nr_exten ? std::max(1, (bp.n_chains + W1K_WAVES - 1) / W1K_WAVES)
+                               : std::max(1, std::min((pl->n_tiles + W1K_WAVES - 1) / W1K_WAVES, e->n_cu * fit.per_cu));
+    lift<0, 1>(bp.nr_exten, [&](auto ex) {
+        launch_lds(e, &wave1k_kernel<decltype(ex)::value != 0>, dim3(wg), dim3(64 * W1K_WAVES), fit.bytes, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
+    });
+}
+// hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h): the spectra once (bigfft_kernel with the export on and the projection off),
+// the detector's cepstra and decisions once; returns the launch of bigss_kernel, one pass of the seed iteration (run_ss_chain)
+std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigParams &bp) {
+    const ctu::Design &d = *e->design;
+    if (d.wfft != 2048 && d.wfft != 4096) throw std::runtime_error("internal: SS engine without an SS instantiation");
+    BigParams xp = bp;
+    xp.xri_only = 1;
+    launch_bigfft(e, pl, s, xp);
+    HIP_TRY(hipGetLastError());
+    if (!e->ss_file) {
+        const LdsFit fit = bigburg_lds(d.wfft);
+        const dim3 bg((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * fit.per_cu));
+        const int nc = d.o.fea_ncepcoefs, two = e->ss == 3;
+        lift<8, 16>(big_nit(e), [&](auto nit) {
+            lift<16, 32>(nc <= 16 ? 16 : 32, [&](auto cap) {
+                launch_lds(e, &bigssdet_kernel<decltype(nit)::value, decltype(cap)::value>, bg, dim3(256), fit.bytes, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, d.wfft,
+                           d.window, nc, (int64_t)pl->total_frames, e->big_tw.p, e->big_han.p, (float)d.o.nr_a, two);
+            });
+        });
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->n_utt, nc, d.o.nr_initsegs,
+                           (double)d.o.nr_p, (double)d.o.nr_q, pl->ss_vbits.p);
+        HIP_TRY(hipGetLastError());
+    }
+    const LdsFit fit = bigss_lds(d, e->feat, e->ncoef_out, e->big_fb_total);
+    if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
+    if (!e->per_wave) throw std::runtime_error("internal: hwss / fwss / 2fwss without chains");
+    return [e, s, &bp, shm = fit.bytes] {
+        lift<8, 16>(big_nit(e), [&](auto nit) {
+            launch_lds(e, &bigss_kernel<decltype(nit)::value>, dim3((unsigned)std::max(1, bp.n_chains)), dim3(256), shm, s, bp);
+        });
+    };
+}
+
+// hwss / fwss / 2fwss: a file's noise estimate starts from the vector the previous file of the list left
+// behind (src/nr/nr.cc:212-221), which chains the whole list.  Everything but that seed is independent per
+// file, so the list is run with the seeds known so far until they stop changing: pass j fixes the seeds of
+// the first j files for good, and a seed's influence dies out as p^(noise updates), so real lists settle in
+// two or three passes.  Synchronous: each pass reads the vectors back.  `pass` launches one pass (the front end on kp, or bigss_kernel).
+// CTU_ERR_INPUT, with vad_pos and ss_stale untouched, when the -vad file= stream ends inside the run.
+template <class Pass>
+int run_ss_chain(ctu_engine *e, const ctu_plan *pl, hipStream_t s, KParams &kp, Pass &&pass) {
+    const ctu::Design &d = *e->design;
+    const size_t nk = (size_t)pl->n_utt * d.K;
+    std::vector<float> seed(nk, 0.f), last(nk, 0.f), next(nk, 0.f);
+    if (e->ss_stale.size() != (size_t)d.K) e->ss_stale.assign(d.K, 0.f);
+    // new_file() seeds the estimate from the vector and then scales the vector by 0.1 (nr.cc:217-220, 402-407); a
+    // file with a frame overwrites it in its first get_frame(), a file without one (window - wshift <= N < window)
+    // leaves it scaled.  So file i starts from what the last file with a frame ahead of it left - or, ahead of the
+    // first such file, what the previous run left (the reference keeps the vector for the life of the process,
+    // base/types.h:35-38) - times 0.1 for every frameless file in between.
+    auto scaled = [&](float *dst, const float *src, int skipped) {
+        double f = 1.0;
+        for (int z = 0; z < skipped; z++) f *= 0.1;
+        for (int k = 0; k < d.K; k++) dst[k] = (float)((double)src[k] * f);
+    };
+    auto propagate = [&](std::vector<float> &dst) {  // seeds of every file from `last` (files with frames) and e->ss_stale
+        int prev = -1, skipped = 0;
+        for (int i = 0; i < pl->n_utt; i++) {
+            scaled(&dst[(size_t)i * d.K], prev >= 0 ? &last[(size_t)prev * d.K] : e->ss_stale.data(), skipped);
+            if (pl->frames[i] > 0) {
+                prev = i;
+                skipped = 0;
+            } else
+                skipped++;
+        }
+        return std::make_pair(prev, skipped);
+    };
+    propagate(seed);  // `last` is still zero: only the seeds ahead of the first file with a frame are final
+    // An utterance's rows and last vector depend on its samples and its seed only: a pass recomputes just the utterances
+    // whose seed changed since the pass before (all of them in the first one).
+    std::vector<unsigned char> dirty(std::max(pl->n_utt, 1), 1);
+    if (e->ss_file) {
+        // -vad file=<f>: `char vad = fgetc(fvad); if (vad != EOF) return bool(vad); else throw` (nr.cc:297-302), one byte per frame in
+        // list order, the stream running on from file to file and from run to run.  Every byte but NUL is speech; a byte 0xFF
+        // compares equal to EOF in the reference's (signed) char and ends the run like the end of the file does.
+        const int64_t nf = pl->total_frames;
+        std::vector<unsigned char> vb((size_t)std::max<int64_t>(nf, 1), 0);
+        for (int64_t i = 0; i < nf; i++) {
+            if (e->vad_pos + i >= (int64_t)e->vad_stream.size() || e->vad_stream[(size_t)(e->vad_pos + i)] == 0xFF) {
+                set_error(e, "NR: Unexpected end of VAD file!");
+                return CTU_ERR_INPUT;
+            }
+            vb[(size_t)i] = e->vad_stream[(size_t)(e->vad_pos + i)] != 0;
+        }
+        HIP_TRY(hipMemcpyAsync(pl->ss_vbits.p, vb.data(), (size_t)nf, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));  // vb leaves scope
+        e->vad_pos += nf;
+    }
+    for (int iter = 0;; iter++) {
+        // the detector never sees a subtracted spectrum (nr.cc:278-295): its decisions are those of the first pass
+        kp.ss_cached = e->ss_file ? 1 : (iter > 0 ? CTU_SS_CACHE : 0);
+        HIP_TRY(hipMemcpyAsync(pl->ss_seed.p, seed.data(), nk * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(pl->ss_dirty.p, dirty.data(), dirty.size(), hipMemcpyHostToDevice, s));
+        pass();
+        HIP_TRY(hipMemcpyAsync(last.data(), pl->ss_last.p, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        propagate(next);
+        bool any = false;
+        for (int i = 0; i < pl->n_utt; i++) {
+            dirty[i] = std::memcmp(&next[(size_t)i * d.K], &seed[(size_t)i * d.K], d.K * sizeof(float)) != 0;
+            any = any || dirty[i];
+        }
+        if (!any) break;
+        if (iter > pl->n_utt) throw std::runtime_error("internal: noise seeds of the *ss chain did not settle");
+        seed = next;
+    }
+    // what this run leaves for the next one
+    const auto tail = propagate(next);
+    std::vector<float> keep(d.K);
+    scaled(keep.data(), tail.first >= 0 ? &last[(size_t)tail.first * d.K] : e->ss_stale.data(), tail.second);
+    e->ss_stale = keep;
+    return CTU_OK;
+}
+
+// Levinson-Durbin and a -> c on the lags the front end or wave1k_kernel left, one frame per lane (lp_tail_kernel.h)
+void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KParams &kp) {
+    LpTailParams tp;
+    tp.lags = pl->lp_r.p; tp.rows = kp.rows; tp.total_frames = pl->total_frames;
+    tp.lifter = e->big ? e->big_lifter.p : e->ftab.p + e->lift_off;
+    tp.row_slot = e->big ? e->big_slot.p : e->itab.p + e->NS + 1;
+    tp.stride = kp.lp_stride; tp.D = kp.D; tp.lporder = kp.lporder; tp.ncep = kp.ncep; tp.is_lpa = kp.lp_is_lpa;
+    tp.lifter_on = kp.lifter_on; tp.e_mode = kp.e_mode; tp.e_slot = kp.e_slot;
+    tp.inv_stride = (unsigned)((1ull << 32) / (unsigned)tp.stride) + 1u;
+    tp.inv_D = (unsigned)((1ull << 32) / (unsigned)tp.D) + 1u;
+    const LdsFit fit = lp_tail_lds(tp.stride, tp.D, lags_double(e));
+    const dim3 tg((unsigned)std::max<int64_t>(1, std::min<int64_t>((pl->total_frames + 255) / 256, (int64_t)e->n_cu * fit.per_cu)));
+    if (lags_double(e)) launch_lds(e, &lp_tail_kernel<double, 0>, tg, dim3(256), fit.bytes, s, tp);
+    else if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) launch_lds(e, &lp_tail_kernel<float, 12>, tg, dim3(256), fit.bytes, s, tp);
+    else launch_lds(e, &lp_tail_kernel<float, 0>, tg, dim3(256), fit.bytes, s, tp);
+    HIP_TRY(hipGetLastError());
+}
+
+// The VAD's Burg-cepstral criterion outside the fused path, on the spectra the front end exported: bigburg_kernel at 1024 .. 4096 points
+// (a workgroup per frame), vad_burg_kernel below (a wave per frame; Q samples per lane: windows of up to 256 samples, or longer)
+void stage_burg_vad(ctu_engine *e, const ctu_plan *pl, hipStream_t s) {
+    const ctu::Design &d = *e->design;
+    const int cap = e->vp.ncoef <= 16 ? 16 : 32;
+    if (e->vp.cri == 1 && e->big && pl->total_frames > 0) {
+        const LdsFit fit = bigburg_lds(d.wfft);
+        const dim3 g((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * fit.per_cu));
+        lift<4, 8, 16>(big_nit(e), [&](auto nit) {
+            lift<16, 32>(cap, [&](auto nc) {
+                launch_lds(e, &bigburg_kernel<decltype(nit)::value, decltype(nc)::value>, g, dim3(256), fit.bytes, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp,
+                           (int64_t)pl->total_frames, e->big_tw.p);
+            });
+        });
+    } else if (e->vp.cri == 1 && !e->vf && !e->big) {
+        const dim3 g((unsigned)std::min<int64_t>((pl->total_frames + 3) / 4, (int64_t)e->n_cu * 4));
+        const size_t bshm = (512 + (size_t)4 * 2 * (d.wfft / 2 + 4)) * 2 * sizeof(vreal);
+        lift<4, 8>(d.window <= 256 ? 4 : 8, [&](auto q) {
+            lift<16, 32>(cap, [&](auto nc) {
+                hipLaunchKernelGGL((vad_burg_kernel<decltype(q)::value, decltype(nc)::value>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp,
+                                   pl->total_frames);
+            });
+        });
+    }
+    HIP_TRY(hipGetLastError());
+}
+
+// TRAP-DCT over the log-mel rows (trap_kernel.h): the 16-bit matrix pipe where the tables fit it, else fp32 MFMA
+void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    const int tl = d.o.fea_trapdct_traplen, nd = d.o.fea_trapdct_ndct;
+    const int ns = (tl + 3) / 4;
+    if (e->trap_bf16) {
+        constexpr int NT16 = CTU_TRAP_F16 ? 2 : 3;
+        const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16;
+        hipLaunchKernelGGL((trapdct_split16_kernel<CTU_TRAP_F16 != 0>), dim3(std::max(pl->n_trap_chunks128, 1)), dim3(512), shm16, s,
+                           pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->n_trap_chunks128, d.B, nd, d.D);
+    } else {
+        const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float);
+        lift<1, 2>(nd <= 16 ? 1 : 2, [&](auto nrb) {
+            lift<26, 64>(ns <= 26 ? 26 : 64, [&](auto nsm) {
+                hipLaunchKernelGGL((trapdct_mfma_kernel<decltype(nrb)::value, decltype(nsm)::value>), dim3(pl->n_trap_chunks), dim3(256), shm, s, pl->logmel.p, d_rows,
+                                   e->trapG.p, pl->utt_info.p, pl->trap_chunks.p, d.B, tl, nd, d.D);
+            });
+        });
+    }
+    HIP_TRY(hipGetLastError());
+}
+
+// Delta chain / stacking from the base rows into the caller's rows (post_kernels.h)
+void stage_post(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    PostParams pp;
+    std::memset(&pp, 0, sizeof pp);
+    pp.fea_c = d.o.fea_ncepcoefs + 1; pp.Dbase = d.Dbase; pp.D = d.D;
+    pp.order = d.post_order; pp.stack = d.post_stack ? 1 : 0; pp.has_e = d.o.fea_E ? 1 : 0;
+    int H = 0;
+    for (int j = 0; j < d.post_order; j++) {
+        pp.w[j] = d.post_w[j];
+        int den = 0;
+        for (int i = 1; i <= d.post_w[j]; i++) den += i * i;
+        pp.inv_den[j] = (float)(1.0 / (2.0 * den));
+        H += d.post_w[j];
+    }
+    const int R = 64 + 2 * H;
+    const size_t shm = ((size_t)R * d.Dbase + (size_t)(d.post_stack ? 0 : d.post_order) * R * pp.fea_c) * sizeof(float);
+    if ((size_t)R * d.Dbase > 256 * 12) throw std::runtime_error("delta tile larger than the prefetch registers");
+    const int pgrid = std::min(pl->n_trap_chunks, e->n_cu * 8);
+    const bool std39 = !d.post_stack && d.post_order == 2 && pp.fea_c == 13 && d.Dbase == 13 && d.D == 39 && pp.w[0] == 2 && pp.w[1] == 2;
+    lift<0, 1>(std39, [&](auto v) {
+        hipLaunchKernelGGL(post_kernel<decltype(v)::value != 0>, dim3(pgrid), dim3(256), shm, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->trap_chunks.p, pl->n_trap_chunks, pp);
+    });
+    HIP_TRY(hipGetLastError());
+}
+
+// CMS, exponential or over a block window (post_kernels.h)
+void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    CmsParams cp;
+    std::memset(&cp, 0, sizeof cp);
+    cp.ncols = d.cms_cols; cp.Dbase = d.Dbase; cp.D = d.D; cp.copy_rest = d.post_order > 0 ? 0 : 1;
+    cp.L = d.o.length_b; cp.z = d.o.fea_Z_exp; cp.omz = 1 - d.o.fea_Z_exp;
+    if (d.cms == 1) hipLaunchKernelGGL(cms_exp_kernel, dim3((pl->n_utt + 1) / 2), dim3(64), 0, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->n_utt, cp);
+    else
+        hipLaunchKernelGGL(cms_block_kernel, dim3(pl->n_trap_chunks), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, pl->base_rows.p, d_rows,
+                           pl->utt_info.p, pl->trap_chunks.p, cp);
+    HIP_TRY(hipGetLastError());
+}
+
+// The fused path left the lattice's output of every frame behind: the coefficient recursion and a -> c one frame per lane,
+// then the detector's recurrences, sixteen utterances per wave
+void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, hipStream_t s, uint8_t *d_vad) {
+    if (CTU_VF_A2C)
+        hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((pl->total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)pl->total_frames);
+    lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
+        hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((pl->n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->n_live,
+                           pl->d_row_off.p, d_vad, e->vp);
+    });
+    HIP_TRY(hipGetLastError());
+}
+
+// After the post passes: the `fea` criterion reads the vector the writer sees (CMS applied), and the energy
+// column is shifted in the finished rows.
+void stage_vad_decide(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows, uint8_t *d_vad) {
+    hipLaunchKernelGGL(vad_decide_kernel, dim3(pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->pnr.p, d_rows, pl->d_row_off.p, pl->n_utt, d_vad, e->vp);
+    HIP_TRY(hipGetLastError());
+}
+
+// A file with no more frames than the majority filter delays never gets the filter `ready` (src/vad/vad.h:126-136), so
+// BATCH::flush_vad's loop does not start (src/vad/vad.cc:742-745, src/io/batch.cc:243-249): the reference writes neither a
+// row nor a decision for it.  Its decision bytes become NUL ("nothing written"); ctu_engine_run_host reports 0 rows.
+void stage_short_files(ctu_engine *e, const ctu_plan *pl, hipStream_t s, uint8_t *d_vad) {
+    hipLaunchKernelGGL(vad_short_files_kernel, dim3((unsigned)((pl->n_utt + 255) / 256)), dim3(256), 0, s, d_vad, pl->d_row_off.p, pl->n_utt,
+                       (e->design->o.vad_filter_order - 1) / 2);
+    HIP_TRY(hipGetLastError());
+}
+
+// The list behaviour of the reference's majority filter (ctu_plan_set_vad_ring): every column but the energy (which does not
+// go through the ring, src/io/batch.cc:101-120) of row k := the vector of frame ring_src[k], or zeros
+void stage_ring_gather(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    const size_t n = (size_t)pl->total_frames * d.D;
+    HIP_TRY(hipMemcpyAsync(pl->ring_tmp.p, d_rows, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(vad_ring_gather_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535u * 16)), dim3(256), 0, s, pl->ring_tmp.p, d_rows,
+                       pl->ring_src.p, (int64_t)pl->total_frames, d.D, d.o.fea_E ? (d.post_order > 0 ? d.D - 1 : d.e_slot) : -1);
+    HIP_TRY(hipGetLastError());
+}
+
+// Speech output at 1024 .. 4096 points (ctu_engine_run_signal): a workgroup per frame
+void launch_bigsynth(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float inv_n) {
+    const ctu::Design &d = *e->design;
+    const LdsFit fit = bigsynth_lds(d.wfft);
+    const int g = (int)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * fit.per_cu);
+    lift<4, 8, 16>(big_nit(e), [&](auto nit) {
+        launch_lds(e, &bigsynth_kernel<decltype(nit)::value>, dim3(g), dim3(256), fit.bytes, s, pl->xri.p, synth_reads_pss(e) ? pl->pss.p : pl->pnr.p, pl->ybuf.p,
+                   (long long)pl->total_frames, d.wfft, d.window, inv_n, e->big_tw.p);
+    });
+    HIP_TRY(hipGetLastError());
+}
+
+#if CTU_STAMP
+void dump_stamps(ctu_engine *e, int grid, hipStream_t s, const char *sf) {
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<unsigned long long> h(e->stamps.n);
+    HIP_TRY(hipMemcpy(h.data(), e->stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
+    double sum[16] = {0};
+    for (size_t w = 0; w < (size_t)grid * NWAVE; w++)
+        for (int i = 0; i < 16; i++) sum[i] += (double)h[w * 16 + i];
+    if (FILE *f = fopen(sf, "w")) {
+        double tot = 0;
+        for (int i = 0; i < 16; i++) tot += sum[i];
+        for (int i = 0; i < 16; i++) fprintf(f, "seg %2d  mean cycles per wave %12.0f  share %.3f\n", i, sum[i] / (grid * NWAVE), sum[i] / tot);
+        fclose(f);
+    }
+}
+#endif
 
 std::vector<std::string> to_args(int argc, const char *const *argv) {
     std::vector<std::string> a;
@@ -1281,6 +1718,8 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
             vp.e_slot = o.fea_E ? (d.post_order > 0 ? d.D - 1 : d.e_slot) : -1;
             vp.e_delay = (o.vad_filter_order - 1) / 2;
         }
+        e->kp0 = engine_kparams(e.get());
+        if (e->big) e->bp0 = engine_bigparams(e.get());
         HIP_TRY(hipEventCreate(&e->ev0));
         HIP_TRY(hipEventCreate(&e->ev1));
     } catch (const std::exception &ex) {
@@ -1409,7 +1848,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
             if (uts[i + 1] > uts[i]) live.push_back(i);
         std::stable_sort(live.begin(), live.end(), [&](int a, int b) { return pl->frames[a] > pl->frames[b]; });
         // (bigfft_kernel walks a chain with a whole workgroup of 256 threads: eight of them fit a CU at once)
-        const int slots = (e->big && !e->wave1k) ? e->n_cu * 8 : max_wg * NWAVE;
+        const int slots = (e->big && e->path != BIG_WAVE1K) ? e->n_cu * 8 : max_wg * NWAVE;
         const int C = std::max(1, std::min<int>((int)live.size(), slots));
         const int G = (C + NWAVE - 1) / NWAVE;
         wg_first.assign((size_t)G * NWAVE, -1);
@@ -1452,7 +1891,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
             if (e->big) {  // bigss_kernel.h: the exported spectra, the detector's cepstra, on the speech path the subtracted magnitudes
                 pl->xri.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
                 pl->pnr.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-                if (d.signal_out) pl->pss.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+                if (synth_reads_pss(e)) pl->pss.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
                 if (!e->ss_file) {
                     pl->vad_ci.alloc((size_t)std::max<int64_t>(ro, 1) * d.o.fea_ncepcoefs);
                     pl->d_row_off.upload(pl->row_off);
@@ -1480,7 +1919,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
             } else if (e->vp.cri == 0) pl->pnr.alloc((size_t)ro);
         }
         if (d.signal_out) {
-            if (!e->sy && !(e->big && e->ss)) {
+            if (!e->sy && !synth_reads_pss(e)) {  // (with pss the *ss block above has allocated the exported spectra)
                 pl->xri.alloc((size_t)ro * d.K);
                 pl->pnr.alloc((size_t)ro * d.K);
             }
@@ -1514,8 +1953,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
             pl->trap_chunks128.upload(c128);
         }
         if (d.kind == ctu::FeaKind::TrapDct) pl->logmel.alloc((size_t)ro * d.B);
-        if ((d.kind == ctu::FeaKind::Lpc || d.kind == ctu::FeaKind::Lpa) && (!e->big || e->wave1k))
-            pl->lp_r.alloc(((size_t)std::max<int64_t>(ro, 1) * (d.o.fea_lporder + 1) * ((e->feat == FEAT_LPD || e->big) ? 8 : 4) + 7) / 8);
+        if (lp_tail_runs(e)) pl->lp_r.alloc(((size_t)std::max<int64_t>(ro, 1) * (d.o.fea_lporder + 1) * (lags_double(e) ? 8 : 4) + 7) / 8);
         if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
     } catch (const std::exception &ex) {
         set_error(e, std::string("ENGINE: ") + ex.what());
@@ -1624,468 +2062,44 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
     hipStream_t s = (hipStream_t)stream;
     try {
         HIP_TRY(hipSetDevice(e->device));
-        KParams kp;
-        std::memset(&kp, 0, sizeof kp);
-        kp.pcm = d_pcm;
-        kp.rows = (d.post_order > 0 || d.cms) ? pl->base_rows.p : d_rows;
-        kp.logmel = pl->logmel.p;
-        kp.xri = pl->xri.p;
-        kp.pnr = pl->pnr.p;
-        kp.band_log = d.kind != ctu::FeaKind::Spec;
-        kp.band_to_scratch = d.kind == ctu::FeaKind::TrapDct;
-        kp.lp_is_lpa = d.kind == ctu::FeaKind::Lpa;
-        kp.ybuf = pl->ybuf.p;
-        kp.syn_scale = 1.0f / (float)d.wfft;
-        kp.vad_export = (signal && !e->sy) ? 1 : ((!e->do_vad || e->vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0)));
-        kp.vad_ci = pl->vad_ci.p;
-        kp.vad_nc = e->vp.ncoef;
-        kp.ss_mode = e->ss;
-        kp.ss_init = d.o.nr_initsegs;
-        kp.ss_nc = d.o.fea_ncepcoefs;
-        kp.han_off = e->han_off;
-        kp.nr_b = (float)d.o.nr_b;
-        kp.ss_q = d.o.nr_q;
-        kp.ss_seed = pl->ss_seed.p;
-        kp.ss_last = pl->ss_last.p;
-        kp.tile_utt = pl->tile_utt.p;
-        kp.vad_cf = pl->vad_cf.p;
-        kp.skip_phase2 = signal ? 1 : 0;
-        kp.tiles = pl->tiles.p;
-        kp.wg_first = pl->wg_first.p;
-        kp.lanec = e->lanec.p;
-        kp.ftab = e->ftab.p;
-        kp.itab = e->itab.p;
-        kp.tab_floats = e->tab_floats;
-        kp.ck_off = e->ck_off;
-        kp.cf_off = e->cf_off;
-        kp.cfd_off = e->cfd_off;
-        kp.NS = e->NS;
-        kp.CW = e->CW;
-        kp.ncoef_out = e->ncoef_out;
-        kp.K = d.K;
-        kp.window = d.window;
-        kp.e_slot = d.e_slot;
-        kp.e_mode = 0;
-        if (d.o.fea_E) {  // energy routing of src/io/batch.cc:98-119
-            if (d.o.fea_rawenergy) kp.e_mode = 4;
-            else if (d.kind == ctu::FeaKind::Dctc) kp.e_mode = d.o.nr_when_afterFB ? 5 : 1;
-            else if (d.kind == ctu::FeaKind::Lpc || d.kind == ctu::FeaKind::Lpa) kp.e_mode = 2;
-            else kp.e_mode = 3;
-        }
-        if (signal) kp.e_mode = 0;
-        kp.wshift = d.wshift;
-        kp.B = d.B;
-        kp.nfea = d.nfea;
-        kp.D = d.Dbase;
-        kp.ncep = d.o.fea_ncepcoefs;
-        kp.lporder = d.o.fea_lporder;
-        kp.lp_r = pl->lp_r.p;
-        kp.lp_stride = d.o.fea_lporder + 1;
-        kp.lift_off = e->lift_off;
-        kp.preem = d.o.preem;
-        kp.inv_window = 1.0f / (float)d.window;
-        kp.inv_window_d = 1.0 / (double)d.window;
-        kp.remove_dc = d.o.remove_dc;
-        kp.kstride = e->kstride;
-        kp.remove_dc1 = d.o.remove_dc1 ? 1 : 0;
-        kp.dc1_J = d.window / d.wshift;
-        kp.dc1 = pl->dc1.p;
-        kp.fb_power = d.o.fb_power;
-        kp.fb_inld = d.o.fb_inld;
-        kp.lifter_on = d.o.fea_lifter > 1;
-        kp.nr_exten = d.o.nr_mode == "exten";
-        kp.nr_after_fb = d.o.nr_when_afterFB ? 1 : 0;
-        kp.nr_p = (float)d.o.nr_p;
-        kp.nr_p_d = d.o.nr_p;
-        kp.nr_a = (float)d.o.nr_a;
-        kp.per_wave = e->per_wave ? 1 : 0;
-        kp.am_off = e->am_off;
-#ifdef CTU_DIAG  // phase ablation (1 = phase 1 only, 2 = phase 2 only): diagnostic builds only
-        kp.dbg = getenv("CTU_DEBUG_MODE") ? atoi(getenv("CTU_DEBUG_MODE")) : 0;
-#endif
+        KParams kp = run_kparams(e, pl, d_pcm, d_rows);
+        const BigParams bp = e->big ? run_bigparams(e, pl, kp) : BigParams{};
         const int grid = pl->grid;
 #if CTU_STAMP
         if (e->stamps.n < (size_t)grid * NWAVE * 16) e->stamps.alloc((size_t)grid * NWAVE * 16);
         HIP_TRY(hipMemsetAsync(e->stamps.p, 0, e->stamps.n * 8, s));
         kp.stamps = e->stamps.p;
 #endif
-        if (d.o.remove_dc1) {
-            const int gx = std::max(1, std::min((pl->max_frames + 3) / 4, 64));
-            hipLaunchKernelGGL(dc1_means_kernel, dim3(gx, pl->n_utt), dim3(256), 0, s, d_pcm, pl->utt_info.p, pl->d_sample_off.p, pl->dc1m.p, pl->n_utt, d.window, d.wshift);
-            hipLaunchKernelGGL(dc1_offsets_kernel, dim3((pl->n_utt + 63) / 64), dim3(64), 0, s, pl->dc1m.p, pl->utt_info.p, pl->dc1.p, pl->n_utt, d.window, d.wshift);
-        }
+        if (d.o.remove_dc1) stage_dc1(e, pl, s, d_pcm);
         HIP_TRY(hipEventRecord(e->ev0, s));
-        auto launch = [&] { launch_frontend(e, dim3(grid), s, kp); };
-        std::function<void()> ss_launch = launch;  // one pass of the *ss modes' seed iteration (below)
-        BigParams bp;
-        if (e->big) {
-            std::memset(&bp, 0, sizeof bp);
-            bp.pcm = d_pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = pl->n_tiles;
-            bp.win = e->big_win.p; bp.tw = e->big_tw.p; bp.fbw = e->big_fbw.p; bp.fb_range = e->big_range.p;
-            bp.coef = e->big_coef.p; bp.coef_d = e->big_coef_d.p; bp.lifter = e->big_lifter.p; bp.row_slot = e->big_slot.p;
-            bp.wfft = d.wfft; bp.K = d.K; bp.window = d.window; bp.wshift = d.wshift; bp.B = d.B; bp.D = kp.D;
-            bp.ncoef_out = e->ncoef_out; bp.feat = e->feat; bp.e_mode = kp.e_mode; bp.e_slot = kp.e_slot;
-            bp.remove_dc = kp.remove_dc; bp.fb_power = kp.fb_power; bp.fb_inld = kp.fb_inld; bp.band_log = kp.band_log;
-            bp.band_to_scratch = kp.band_to_scratch; bp.lp_is_lpa = kp.lp_is_lpa; bp.lporder = kp.lporder; bp.ncep = kp.ncep;
-            bp.lifter_on = kp.lifter_on; bp.preem = kp.preem;
-            bp.fb_total = e->big_fb_total;
-            bp.seg = e->big_seg.p;
-            bp.nr_exten = kp.nr_exten; bp.nr_p = kp.nr_p; bp.nr_a = kp.nr_a;
-            bp.vad_en = (e->do_vad && e->vp.cri == 0) ? pl->pnr.p : nullptr;
-            bp.dc1 = kp.remove_dc1 ? pl->dc1.p : nullptr; bp.dc1_J = kp.dc1_J;
-            const bool burg = e->do_vad && e->vp.cri == 1;  // bigburg_kernel reads the spectra; the rows are projected as well
-            bp.xri = (signal || burg) ? pl->xri.p : nullptr; bp.pnr = (signal || burg) ? pl->pnr.p : nullptr;
-            bp.xri_only = signal ? 1 : 0;
-            bp.chain_first = pl->wg_first.p; bp.n_chains = (int)pl->wg_first.n;
-            const size_t shm = (size_t)d.wfft * 8 + (size_t)((d.K + 3) & ~3) * 4 + 64 * 4 + 4 * 8 + (size_t)d.wfft / 2 * 8 +
-                               (size_t)((d.window + 3) & ~3) * 4 + (size_t)((e->big_fb_total + 3) & ~3) * 4 +
-                               (size_t)(e->feat == FEAT_LP ? (d.o.fea_lporder + 1) * d.B : 0) * 8 +
-                               (size_t)(((e->feat == FEAT_DCTC ? e->ncoef_out * d.B : 0) + 3) & ~3) * 4 + (size_t)((3 * d.B + 3) & ~3) * 4 + 64 * 4;
-            if (shm > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
-            const void *kfn = kp.nr_exten ? (d.wfft == 1024 ? (const void *)bigfft_kernel<4, true> : d.wfft == 2048 ? (const void *)bigfft_kernel<8, true> : (const void *)bigfft_kernel<16, true>)
-                                          : (d.wfft == 1024 ? (const void *)bigfft_kernel<4> : d.wfft == 2048 ? (const void *)bigfft_kernel<8> : (const void *)bigfft_kernel<16>);
-            if (shm > 64 * 1024) allow_big_lds(e, kfn);
-            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / shm));
-            const int g = std::max(1, std::min(pl->n_tiles, e->n_cu * per_cu));
-            if (e->ss) {
-                // hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h): the spectra once, the detector's cepstra and decisions once,
-                // then bigss_kernel per pass of the seed iteration below
-                if (d.wfft != 2048 && d.wfft != 4096) throw std::runtime_error("internal: SS engine without an SS instantiation");
-                bp.xri = pl->xri.p; bp.pnr = pl->pnr.p; bp.xri_only = 1;
-                if (d.wfft == 2048) hipLaunchKernelGGL((bigfft_kernel<8>), dim3(g), dim3(256), shm, s, bp);
-                else hipLaunchKernelGGL((bigfft_kernel<16>), dim3(g), dim3(256), shm, s, bp);
-                HIP_TRY(hipGetLastError());
-                if (!e->ss_file) {
-                    const size_t bshm = ((size_t)(d.wfft / 2) * 3 + 4) * sizeof(float2) + BIGBURG_XCH * sizeof(double);
-                    const dim3 bg((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * std::min<size_t>(8, (160 * 1024) / bshm)));
-                    const int nc = d.o.fea_ncepcoefs, two = e->ss == 3;
-#define BIGSSDET(NIT_, NC_) hipLaunchKernelGGL((bigssdet_kernel<NIT_, NC_>), bg, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, d.wfft, d.window, nc, \
-                                               (int64_t)pl->total_frames, e->big_tw.p, e->big_han.p, (float)d.o.nr_a, two)
-                    if (d.wfft == 2048) {
-                        if (nc <= 16) BIGSSDET(8, 16);
-                        else BIGSSDET(8, 32);
-                    } else {
-                        if (nc <= 16) BIGSSDET(16, 16);
-                        else BIGSSDET(16, 32);
-                    }
-#undef BIGSSDET
-                    HIP_TRY(hipGetLastError());
-                    hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->n_utt, nc, d.o.nr_initsegs,
-                                       (double)d.o.nr_p, (double)d.o.nr_q, pl->ss_vbits.p);
-                    HIP_TRY(hipGetLastError());
-                }
-                bp.xri_only = signal ? 1 : 0;
-                bp.pss = signal ? pl->pss.p : nullptr;
-                bp.ss_mode = e->ss; bp.ss_init = d.o.nr_initsegs; bp.ss_a = d.o.nr_a; bp.ss_b = d.o.nr_b; bp.ss_p = d.o.nr_p;
-                bp.ss_seed = pl->ss_seed.p; bp.ss_last = pl->ss_last.p; bp.ss_dirty = pl->ss_dirty.p; bp.ss_vbits = pl->ss_vbits.p;
-                bp.tile_utt = pl->tile_utt.p;
-                // LDS: the spectrum vector, the bands and their logarithms, and the projection's tables (none on the speech path)
-                const size_t sshm = (size_t)((d.K + 3) & ~3) * 4 + 64 * 4 + 4 * 8 + 64 * 4 +
-                                    (signal ? 0 : (size_t)((e->big_fb_total + 3) & ~3) * 4 + (size_t)(e->feat == FEAT_LP ? (d.o.fea_lporder + 1) * d.B : 0) * 8 +
-                                                      (size_t)(((e->feat == FEAT_DCTC ? e->ncoef_out * d.B : 0) + 3) & ~3) * 4 + (size_t)((3 * d.B + 3) & ~3) * 4);
-                if (sshm > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
-                if (!e->per_wave) throw std::runtime_error("internal: hwss / fwss / 2fwss without chains");
-                const dim3 gx((unsigned)std::max(1, bp.n_chains));
-                ss_launch = [&bp, e, d_wfft = d.wfft, sshm, gx, s] {
-                    if (d_wfft == 2048) {
-                        if (sshm > 64 * 1024) allow_big_lds(e, &bigss_kernel<8>);
-                        hipLaunchKernelGGL((bigss_kernel<8>), gx, dim3(256), sshm, s, bp);
-                    } else {
-                        if (sshm > 64 * 1024) allow_big_lds(e, &bigss_kernel<16>);
-                        hipLaunchKernelGGL((bigss_kernel<16>), gx, dim3(256), sshm, s, bp);
-                    }
-                };
-            }
-            else if (e->wave1k) {
-                // 1024 points: one wave per frame, the transform in registers (wave1k_kernel.h); tiles are dealt to waves
-                const size_t wshm = ((size_t)W1K_WAVES * W1K_WAVE_FLOATS + 1024 + W1K_TW_FLOATS + (size_t)((e->big_fb_total + 3) & ~3) + 2) * 4 +
-                                    (size_t)(e->feat == FEAT_LP ? (d.o.fea_lporder + 1) * d.B : 0) * 8 +
-                                    (size_t)(((e->feat == FEAT_DCTC ? e->ncoef_out * d.B : 0) + 3) & ~3) * 4 + (size_t)((3 * d.B + 3) & ~3) * 4 + (size_t)(256 + 2 * d.B) * 4 + 64;
-                if (wshm > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the 1024-point kernel");
-                const void *wfn = bp.nr_exten ? (const void *)wave1k_kernel<true> : (const void *)wave1k_kernel<false>;
-                if (wshm > 64 * 1024) allow_big_lds(e, wfn);
-                const int wper_cu = (int)std::max<size_t>(1, std::min<size_t>(CTU_W1K_LB * 4 / W1K_WAVES, (160 * 1024) / wshm));
-                if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without per-wave chains");
-                // exten: one wave per chain of utterances, every chain gets its wave whatever fits the chip at once
-                const int wg = bp.nr_exten ? std::max(1, (bp.n_chains + W1K_WAVES - 1) / W1K_WAVES)
-                                           : std::max(1, std::min((pl->n_tiles + W1K_WAVES - 1) / W1K_WAVES, e->n_cu * wper_cu));
-                if (bp.nr_exten) hipLaunchKernelGGL(wave1k_kernel<true>, dim3(wg), dim3(64 * W1K_WAVES), wshm, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
-                else hipLaunchKernelGGL(wave1k_kernel<false>, dim3(wg), dim3(64 * W1K_WAVES), wshm, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
-            }
-            else if (bp.nr_exten) {  // one workgroup per chain of utterances
-                if (!e->per_wave) throw std::runtime_error("internal: exten without chains");
-                const dim3 gx((unsigned)std::max(1, bp.n_chains));
-                if (d.wfft == 1024) hipLaunchKernelGGL((bigfft_kernel<4, true>), gx, dim3(256), shm, s, bp);
-                else if (d.wfft == 2048) hipLaunchKernelGGL((bigfft_kernel<8, true>), gx, dim3(256), shm, s, bp);
-                else hipLaunchKernelGGL((bigfft_kernel<16, true>), gx, dim3(256), shm, s, bp);
-            }
-            else if (d.wfft == 1024) hipLaunchKernelGGL((bigfft_kernel<4>), dim3(g), dim3(256), shm, s, bp);
-            else if (d.wfft == 2048) hipLaunchKernelGGL((bigfft_kernel<8>), dim3(g), dim3(256), shm, s, bp);
-            else hipLaunchKernelGGL((bigfft_kernel<16>), dim3(g), dim3(256), shm, s, bp);
+        // the front end; with hwss / fwss / 2fwss `pass` is one pass of the seed iteration, which launches it
+        std::function<void()> pass = [&] { launch_frontend(e, dim3(grid), s, kp); };
+        switch (e->path) {
+            case BIG_NONE: if (!e->ss) pass(); break;
+            case BIG_WAVE1K: stage_wave1k(e, pl, s, bp); break;
+            case BIG_SS: pass = stage_bigss_front(e, pl, s, bp); break;
+            case BIG_FFT: launch_bigfft(e, pl, s, bp); break;
         }
-        else if (!e->ss) launch();
         if (e->ss) {
-            // hwss / fwss / 2fwss: a file's noise estimate starts from the vector the previous file of the list left
-            // behind (src/nr/nr.cc:212-221), which chains the whole list.  Everything but that seed is independent per
-            // file, so the list is run with the seeds known so far until they stop changing: pass j fixes the seeds of
-            // the first j files for good, and a seed's influence dies out as p^(noise updates), so real lists settle in
-            // two or three passes.  Synchronous: each pass reads the vectors back.
-            const size_t nk = (size_t)pl->n_utt * d.K;
-            std::vector<float> seed(nk, 0.f), last(nk, 0.f), next(nk, 0.f);
-            if (e->ss_stale.size() != (size_t)d.K) e->ss_stale.assign(d.K, 0.f);
-            // new_file() seeds the estimate from the vector and then scales the vector by 0.1 (nr.cc:217-220, 402-407); a
-            // file with a frame overwrites it in its first get_frame(), a file without one (window - wshift <= N < window)
-            // leaves it scaled.  So file i starts from what the last file with a frame ahead of it left - or, ahead of the
-            // first such file, what the previous run left (the reference keeps the vector for the life of the process,
-            // base/types.h:35-38) - times 0.1 for every frameless file in between.
-            auto scaled = [&](float *dst, const float *src, int skipped) {
-                double f = 1.0;
-                for (int z = 0; z < skipped; z++) f *= 0.1;
-                for (int k = 0; k < d.K; k++) dst[k] = (float)((double)src[k] * f);
-            };
-            auto propagate = [&](std::vector<float> &dst) {  // seeds of every file from `last` (files with frames) and e->ss_stale
-                int prev = -1, skipped = 0;
-                for (int i = 0; i < pl->n_utt; i++) {
-                    scaled(&dst[(size_t)i * d.K], prev >= 0 ? &last[(size_t)prev * d.K] : e->ss_stale.data(), skipped);
-                    if (pl->frames[i] > 0) {
-                        prev = i;
-                        skipped = 0;
-                    } else
-                        skipped++;
-                }
-                return std::make_pair(prev, skipped);
-            };
-            propagate(seed);  // `last` is still zero: only the seeds ahead of the first file with a frame are final
-            // An utterance's rows and last vector depend on its samples and its seed only: a pass recomputes just the utterances
-            // whose seed changed since the pass before (all of them in the first one).
-            std::vector<unsigned char> dirty(std::max(pl->n_utt, 1), 1);
-            kp.ss_dirty = pl->ss_dirty.p;
-            kp.ss_vbits = pl->ss_vbits.p;
-            if (e->ss_file) {
-                // -vad file=<f>: `char vad = fgetc(fvad); if (vad != EOF) return bool(vad); else throw` (nr.cc:297-302), one byte per frame in
-                // list order, the stream running on from file to file and from run to run.  Every byte but NUL is speech; a byte 0xFF
-                // compares equal to EOF in the reference's (signed) char and ends the run like the end of the file does.
-                const int64_t nf = pl->total_frames;
-                std::vector<unsigned char> vb((size_t)std::max<int64_t>(nf, 1), 0);
-                for (int64_t i = 0; i < nf; i++) {
-                    if (e->vad_pos + i >= (int64_t)e->vad_stream.size() || e->vad_stream[(size_t)(e->vad_pos + i)] == 0xFF) {
-                        set_error(e, "NR: Unexpected end of VAD file!");
-                        return CTU_ERR_INPUT;
-                    }
-                    vb[(size_t)i] = e->vad_stream[(size_t)(e->vad_pos + i)] != 0;
-                }
-                HIP_TRY(hipMemcpyAsync(pl->ss_vbits.p, vb.data(), (size_t)nf, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipStreamSynchronize(s));  // vb leaves scope
-                e->vad_pos += nf;
-            }
-            for (int iter = 0;; iter++) {
-                // the detector never sees a subtracted spectrum (nr.cc:278-295): its decisions are those of the first pass
-                kp.ss_cached = e->ss_file ? 1 : (iter > 0 ? CTU_SS_CACHE : 0);
-                HIP_TRY(hipMemcpyAsync(pl->ss_seed.p, seed.data(), nk * sizeof(float), hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(pl->ss_dirty.p, dirty.data(), dirty.size(), hipMemcpyHostToDevice, s));
-                ss_launch();
-                HIP_TRY(hipMemcpyAsync(last.data(), pl->ss_last.p, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                propagate(next);
-                bool any = false;
-                for (int i = 0; i < pl->n_utt; i++) {
-                    dirty[i] = std::memcmp(&next[(size_t)i * d.K], &seed[(size_t)i * d.K], d.K * sizeof(float)) != 0;
-                    any = any || dirty[i];
-                }
-                if (!any) break;
-                if (iter > pl->n_utt) throw std::runtime_error("internal: noise seeds of the *ss chain did not settle");
-                seed = next;
-            }
-            {   // what this run leaves for the next one
-                const auto tail = propagate(next);
-                std::vector<float> keep(d.K);
-                scaled(keep.data(), tail.first >= 0 ? &last[(size_t)tail.first * d.K] : e->ss_stale.data(), tail.second);
-                e->ss_stale = keep;
-            }
+            const int rc = run_ss_chain(e, pl, s, kp, pass);
+            if (rc != CTU_OK) return rc;
         }
         HIP_TRY(hipEventRecord(e->ev1, s));
         e->timed = true;
         e->host_timed = false;
         HIP_TRY(hipGetLastError());
 #if CTU_STAMP
-        if (const char *sf = getenv("CTU_STAMP_FILE")) {
-            HIP_TRY(hipStreamSynchronize(s));
-            std::vector<unsigned long long> h(e->stamps.n);
-            HIP_TRY(hipMemcpy(h.data(), e->stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
-            double sum[16] = {0};
-            for (size_t w = 0; w < (size_t)grid * NWAVE; w++)
-                for (int i = 0; i < 16; i++) sum[i] += (double)h[w * 16 + i];
-            if (FILE *f = fopen(sf, "w")) {
-                double tot = 0;
-                for (int i = 0; i < 16; i++) tot += sum[i];
-                for (int i = 0; i < 16; i++) fprintf(f, "seg %2d  mean cycles per wave %12.0f  share %.3f\n", i, sum[i] / (grid * NWAVE), sum[i] / tot);
-                fclose(f);
-            }
-        }
+        if (const char *sf = getenv("CTU_STAMP_FILE")) dump_stamps(e, grid, s, sf);
 #endif
-        if ((e->feat == FEAT_LP || e->feat == FEAT_LPD) && (!e->big || e->wave1k) && !signal) {
-            LpTailParams tp;
-            tp.lags = pl->lp_r.p;
-            tp.rows = kp.rows;
-            tp.lifter = e->big ? e->big_lifter.p : e->ftab.p + e->lift_off;
-            tp.row_slot = e->big ? e->big_slot.p : e->itab.p + e->NS + 1;
-            tp.total_frames = pl->total_frames;
-            tp.stride = kp.lp_stride; tp.D = kp.D; tp.lporder = kp.lporder; tp.ncep = kp.ncep; tp.is_lpa = kp.lp_is_lpa;
-            tp.lifter_on = kp.lifter_on; tp.e_mode = kp.e_mode; tp.e_slot = kp.e_slot;
-            tp.inv_stride = (unsigned)((1ull << 32) / (unsigned)tp.stride) + 1u;
-            tp.inv_D = (unsigned)((1ull << 32) / (unsigned)tp.D) + 1u;
-            const dim3 tg((unsigned)std::max<int64_t>(1, std::min<int64_t>((pl->total_frames + 255) / 256, (int64_t)e->n_cu * 8)));
-            const size_t tshm = (size_t)256 * ((tp.stride | 1) * ((e->feat == FEAT_LPD || e->big) ? 8 : 4) + (tp.D | 1) * 4);
-            // double lags at orders 20..23 pass 64 KiB (order 23 with -fea_E: 75 KiB)
-            if (e->feat == FEAT_LPD || e->big) {
-                if (tshm > 64 * 1024) allow_big_lds(e, &lp_tail_kernel<double, 0>);
-                hipLaunchKernelGGL((lp_tail_kernel<double, 0>), tg, dim3(256), tshm, s, tp);
-            } else if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) hipLaunchKernelGGL((lp_tail_kernel<float, 12>), tg, dim3(256), tshm, s, tp);
-            else {
-                if (tshm > 64 * 1024) allow_big_lds(e, &lp_tail_kernel<float, 0>);
-                hipLaunchKernelGGL((lp_tail_kernel<float, 0>), tg, dim3(256), tshm, s, tp);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        if (e->do_vad) {
-            if (e->vp.cri == 1 && e->big && pl->total_frames > 0) {
-                // 1024 .. 4096 points: a workgroup per frame; LDS: bigsynth_kernel's two buffers and twiddles, and the lattice's exchange area
-                const size_t bshm = ((size_t)(d.wfft / 2) * 3 + 4) * sizeof(float2) + BIGBURG_XCH * sizeof(double);
-                const dim3 g((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * std::min<size_t>(8, (160 * 1024) / bshm)));
-#define BIGBURG(NIT_)                                                                                                                       \
-    do {                                                                                                                                    \
-        if (e->vp.ncoef <= 16) hipLaunchKernelGGL((bigburg_kernel<NIT_, 16>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp, \
-                                                  (int64_t)pl->total_frames, e->big_tw.p);                                                  \
-        else hipLaunchKernelGGL((bigburg_kernel<NIT_, 32>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp,                   \
-                                (int64_t)pl->total_frames, e->big_tw.p);                                                                    \
-    } while (0)
-                if (d.wfft == 1024) BIGBURG(4);
-                else if (d.wfft == 2048) BIGBURG(8);
-                else BIGBURG(16);
-#undef BIGBURG
-            } else if (e->vp.cri == 1 && !e->vf && !e->big) {
-                const dim3 g((unsigned)std::min<int64_t>((pl->total_frames + 3) / 4, (int64_t)e->n_cu * 4));
-                const size_t bshm = (512 + (size_t)4 * 2 * (d.wfft / 2 + 4)) * 2 * sizeof(vreal);
-#define BURG_LAUNCH(Q, NC) hipLaunchKernelGGL((vad_burg_kernel<Q, NC>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp, pl->total_frames)
-                if (d.window <= 256) {
-                    if (e->vp.ncoef <= 16) BURG_LAUNCH(4, 16);
-                    else BURG_LAUNCH(4, 32);
-                } else {
-                    if (e->vp.ncoef <= 16) BURG_LAUNCH(8, 16);
-                    else BURG_LAUNCH(8, 32);
-                }
-#undef BURG_LAUNCH
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        if (d.kind == ctu::FeaKind::TrapDct) {
-            const int tl = d.o.fea_trapdct_traplen, nd = d.o.fea_trapdct_ndct;
-            const int ns = (tl + 3) / 4;
-            const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float);
-#define TRAP_LAUNCH(NRB, NSM)                                                                                          \
-    hipLaunchKernelGGL((trapdct_mfma_kernel<NRB, NSM>), dim3(pl->n_trap_chunks), dim3(256), shm, s, pl->logmel.p, d_rows, \
-                       e->trapG.p, pl->utt_info.p, pl->trap_chunks.p, d.B, tl, nd, d.D)
-            if (e->trap_bf16) {
-                constexpr int NT16 = CTU_TRAP_F16 ? 2 : 3;
-                const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16;
-                hipLaunchKernelGGL((trapdct_split16_kernel<CTU_TRAP_F16 != 0>), dim3(std::max(pl->n_trap_chunks128, 1)), dim3(512), shm16, s,
-                                   pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->n_trap_chunks128, d.B, nd, d.D);
-            }
-            else if (nd <= 16 && ns <= 26) TRAP_LAUNCH(1, 26);
-            else if (nd <= 16) TRAP_LAUNCH(1, 64);
-            else if (ns <= 26) TRAP_LAUNCH(2, 26);
-            else TRAP_LAUNCH(2, 64);
-#undef TRAP_LAUNCH
-            HIP_TRY(hipGetLastError());
-        }
-        if (d.post_order > 0) {
-            PostParams pp;
-            std::memset(&pp, 0, sizeof pp);
-            pp.fea_c = d.o.fea_ncepcoefs + 1;
-            pp.Dbase = d.Dbase;
-            pp.D = d.D;
-            pp.order = d.post_order;
-            pp.stack = d.post_stack ? 1 : 0;
-            pp.has_e = d.o.fea_E ? 1 : 0;
-            int H = 0;
-            for (int j = 0; j < d.post_order; j++) {
-                pp.w[j] = d.post_w[j];
-                int den = 0;
-                for (int i = 1; i <= d.post_w[j]; i++) den += i * i;
-                pp.inv_den[j] = (float)(1.0 / (2.0 * den));
-                H += d.post_w[j];
-            }
-            const int R = 64 + 2 * H;
-            const size_t shm = ((size_t)R * d.Dbase + (size_t)(d.post_stack ? 0 : d.post_order) * R * pp.fea_c) * sizeof(float);
-            if ((size_t)R * d.Dbase > 256 * 12) throw std::runtime_error("delta tile larger than the prefetch registers");
-            const int pgrid = std::min(pl->n_trap_chunks, e->n_cu * 8);
-            const bool std39 = !d.post_stack && d.post_order == 2 && pp.fea_c == 13 && d.Dbase == 13 && d.D == 39 && pp.w[0] == 2 && pp.w[1] == 2;
-            if (std39)
-                hipLaunchKernelGGL(post_kernel<true>, dim3(pgrid), dim3(256), shm, s, pl->base_rows.p, d_rows,
-                                   pl->utt_info.p, pl->trap_chunks.p, pl->n_trap_chunks, pp);
-            else
-                hipLaunchKernelGGL(post_kernel<false>, dim3(pgrid), dim3(256), shm, s, pl->base_rows.p, d_rows,
-                                   pl->utt_info.p, pl->trap_chunks.p, pl->n_trap_chunks, pp);
-            HIP_TRY(hipGetLastError());
-        }
-        if (d.cms) {
-            CmsParams cp;
-            std::memset(&cp, 0, sizeof cp);
-            cp.ncols = d.cms_cols;
-            cp.Dbase = d.Dbase;
-            cp.D = d.D;
-            cp.copy_rest = d.post_order > 0 ? 0 : 1;
-            cp.L = d.o.length_b;
-            cp.z = d.o.fea_Z_exp;
-            cp.omz = 1 - d.o.fea_Z_exp;
-            if (d.cms == 1)
-                hipLaunchKernelGGL(cms_exp_kernel, dim3((pl->n_utt + 1) / 2), dim3(64), 0, s, pl->base_rows.p, d_rows,
-                                   pl->utt_info.p, pl->n_utt, cp);
-            else
-                hipLaunchKernelGGL(cms_block_kernel, dim3(pl->n_trap_chunks), dim3(256),
-                                   (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, pl->base_rows.p, d_rows,
-                                   pl->utt_info.p, pl->trap_chunks.p, cp);
-            HIP_TRY(hipGetLastError());
-        }
-        if (e->do_vad && e->vf && pl->n_live > 0) {
-            // the fused path left the lattice's output of every frame behind: the coefficient recursion and a -> c one frame per lane,
-            // then the detector's recurrences, sixteen utterances per wave
-            if (CTU_VF_A2C)
-                hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((pl->total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)pl->total_frames);
-#define LANES_LAUNCH(THR) hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, THR>), dim3((pl->n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->n_live, pl->d_row_off.p, d_vad, e->vp)
-            switch (e->vp.thr) {
-                case 0: LANES_LAUNCH(0); break;
-                case 1: LANES_LAUNCH(1); break;
-                case 2: LANES_LAUNCH(2); break;
-                default: LANES_LAUNCH(3); break;
-            }
-#undef LANES_LAUNCH
-            HIP_TRY(hipGetLastError());
-        }
-        if (e->do_vad && !e->vf) {
-            // After the post passes: the `fea` criterion reads the vector the writer sees (CMS applied), and the energy
-            // column is shifted in the finished rows.
-            hipLaunchKernelGGL(vad_decide_kernel, dim3(pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->pnr.p, d_rows,
-                               pl->d_row_off.p, pl->n_utt, d_vad, e->vp);
-            HIP_TRY(hipGetLastError());
-        }
-        if (e->do_vad && d.o.vad_filter_order > 1) {
-            // A file with no more frames than the majority filter delays never gets the filter `ready` (src/vad/vad.h:126-136), so
-            // BATCH::flush_vad's loop does not start (src/vad/vad.cc:742-745, src/io/batch.cc:243-249): the reference writes neither a
-            // row nor a decision for it.  Its decision bytes become NUL ("nothing written"); ctu_engine_run_host reports 0 rows.
-            hipLaunchKernelGGL(vad_short_files_kernel, dim3((unsigned)((pl->n_utt + 255) / 256)), dim3(256), 0, s, d_vad, pl->d_row_off.p, pl->n_utt,
-                               (d.o.vad_filter_order - 1) / 2);
-            HIP_TRY(hipGetLastError());
-        }
-        if (e->do_vad && !pl->ring_hidx.empty() && pl->total_frames > 0) {
-            // the list behaviour of the reference's majority filter (ctu_plan_set_vad_ring): every column but the energy (which does not
-            // go through the ring, src/io/batch.cc:101-120) of row k := the vector of frame ring_src[k], or zeros
-            const size_t n = (size_t)pl->total_frames * d.D;
-            HIP_TRY(hipMemcpyAsync(pl->ring_tmp.p, d_rows, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(vad_ring_gather_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535u * 16)), dim3(256), 0, s, pl->ring_tmp.p, d_rows,
-                               pl->ring_src.p, (int64_t)pl->total_frames, d.D, d.o.fea_E ? (d.post_order > 0 ? d.D - 1 : d.e_slot) : -1);
-            HIP_TRY(hipGetLastError());
-        }
+        if (lp_tail_runs(e)) stage_lp_tail(e, pl, s, kp);
+        if (e->do_vad) stage_burg_vad(e, pl, s);
+        if (d.kind == ctu::FeaKind::TrapDct) stage_trap(e, pl, s, d_rows);
+        if (d.post_order > 0) stage_post(e, pl, s, d_rows);
+        if (d.cms) stage_cms(e, pl, s, d_rows);
+        if (e->do_vad && e->vf && pl->n_live > 0) stage_fused_vad(e, pl, s, d_vad);
+        if (e->do_vad && !e->vf) stage_vad_decide(e, pl, s, d_rows, d_vad);
+        if (e->do_vad && d.o.vad_filter_order > 1) stage_short_files(e, pl, s, d_vad);
+        if (e->do_vad && !pl->ring_hidx.empty() && pl->total_frames > 0) stage_ring_gather(e, pl, s, d_rows);
     } catch (const std::exception &ex) {
         set_error(e, std::string("ENGINE: ") + ex.what());
         return CTU_ERR_DEVICE;
@@ -2392,22 +2406,7 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
         sp.K = d.K; sp.wfft = d.wfft; sp.window = d.window; sp.wshift = d.wshift;
         sp.inv_n = 1.0f / (float)d.wfft;
         sp.corr = d.ola_corr;
-        if (pl->total_frames > 0 && e->big) {
-            // 1024 .. 4096 points: a workgroup per frame, LDS: two buffers of wfft / 2 (+ 4) complex values and the twiddles
-            const size_t shm = ((size_t)(d.wfft / 2) * 3 + 8) * sizeof(float2);
-            const int g = (int)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * 8);
-#define BIGSYNTH(NIT_)                                                                                                              \
-    do {                                                                                                                            \
-        if (shm > 64 * 1024) allow_big_lds(e, &bigsynth_kernel<NIT_>);                                                              \
-        hipLaunchKernelGGL((bigsynth_kernel<NIT_>), dim3(g), dim3(256), shm, s, pl->xri.p, e->ss ? pl->pss.p : pl->pnr.p, pl->ybuf.p, (long long)pl->total_frames, \
-                           d.wfft, d.window, sp.inv_n, e->big_tw.p);                                                                \
-    } while (0)
-            if (d.wfft == 1024) BIGSYNTH(4);
-            else if (d.wfft == 2048) BIGSYNTH(8);
-            else BIGSYNTH(16);
-#undef BIGSYNTH
-            HIP_TRY(hipGetLastError());
-        }
+        if (pl->total_frames > 0 && e->big) launch_bigsynth(e, pl, s, sp.inv_n);
         else if (pl->total_frames > 0 && !e->sy) {
             const int g = (int)std::min<int64_t>((pl->total_frames + 7) / 8, (int64_t)e->n_cu * 8);
             hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)pl->total_frames, sp);
@@ -2518,12 +2517,13 @@ int ctu_engine_set_vad_stream(ctu_engine *e, const unsigned char *bytes, int64_t
 const char *ctu_engine_kernel_name(const ctu_engine *e) {
     if (!e) return "";
     if (e->kname.empty()) {
-        const ctu::Design &d = *e->design;
         std::string n;
-        if (e->wave1k) n = "wave1k_kernel";
-        else if (e->big && e->ss) n = "bigss_kernel<" + std::to_string(d.wfft / 256) + ">";
-        else if (e->big) n = "bigfft_kernel<" + std::to_string(d.wfft / 256) + ">";
-        else n = fe_name(e->sel);
+        switch (e->path) {
+            case BIG_WAVE1K: n = "wave1k_kernel"; break;
+            case BIG_SS: n = "bigss_kernel<" + std::to_string(big_nit(e)) + ">"; break;
+            case BIG_FFT: n = "bigfft_kernel<" + std::to_string(big_nit(e)) + ">"; break;
+            case BIG_NONE: n = fe_name(e->sel); break;
+        }
         const_cast<ctu_engine *>(e)->kname = n;
     }
     return e->kname.c_str();

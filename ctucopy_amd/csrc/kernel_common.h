@@ -16,6 +16,14 @@ constexpr int PCM_ALIGN = 8;   // utterance starts are multiples of this many sa
 constexpr int PCM_HEAD = 8;    // samples of padding before the first utterance (x[-2..-1] of frame 0 is loaded)
 constexpr int PCM_TAIL = 512;  // padding after the last one: the generic instantiation loads 16 rows of 32 samples whatever the window
 
+// Host side: the dynamic LDS of a launch and the workgroups of it that share a CU's 160 KiB (at most `cap`).  Each kernel's header has the
+// function that sizes it, beside the carve-up it must match.
+struct LdsFit {
+    size_t bytes;
+    int per_cu;
+};
+LdsFit lds_fit(size_t bytes, size_t cap) { return {bytes, (int)std::max<size_t>(1, std::min<size_t>(cap, (160 * 1024) / bytes))}; }
+
 // Per-lane constant record, one per l16 = lane & 15, streamed from L1 every pass instead of pinning
 // 70+ VGPRs:  [0,32) Hamming pairs (w[32j+2l], w[32j+2l+1]) j=0..15 | [32,64) 1/0 "sample is inside the
 // window" pairs for DC removal | [64,96) inter-stage twiddles W256^(l*k1), k1=1..15 (+pad) |

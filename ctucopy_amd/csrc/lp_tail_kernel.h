@@ -22,6 +22,10 @@ struct LpTailParams {
     unsigned inv_stride, inv_D;  // floor(2^32 / n) + 1: e / n = __umulhi(e, inv) for the e < 2^13 of a 256-frame block
 };
 
+// Host side, the carve-up below: 256 lag records and 256 rows, each padded to an odd stride; the grid is capped at eight workgroups a CU.
+// Double lags at orders 20..23 pass 64 KiB (order 23 with -fea_E: 75 KiB).
+LdsFit lp_tail_lds(int stride, int D, bool dbl) { return {(size_t)256 * ((stride | 1) * (dbl ? 8 : 4) + (D | 1) * 4), 8}; }
+
 template <class T, int LPO>  // LPO: order = number of cepstra fixed at compile time (12: the PLP preset), 0 = run-time up to MAX_LP
 __global__ __launch_bounds__(256) void lp_tail_kernel(const LpTailParams p) {
     constexpr bool DBL = sizeof(T) == 8;

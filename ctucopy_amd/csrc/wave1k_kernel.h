@@ -61,6 +61,12 @@ constexpr int W1K_TW_FLOATS = 2 * (512 + 64 + 512);        // W1024^m for m < 51
 #define CTU_W1K_LB 5     // 8 x 3 (80 VGPRs, 35 spilled) 3.09 ms, 4 x 4 (120 VGPRs, none spilled) 3.05 ms; round 3's first version (163 VGPRs, 3 per SIMD) 4.10 ms
 #endif
 constexpr int W1K_WAVES = CTU_W1K_WAVES;         // waves per workgroup
+// Host side, the carve-up below: the waves' areas | window pairs | twiddles | the projection's tables (two floats of slack ahead of the doubles)
+// | the bank's segment table [64][4] + [B][2] | 64 bytes of slack; workgroups a CU as the launch bounds have it
+LdsFit wave1k_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
+    return lds_fit(((size_t)W1K_WAVES * W1K_WAVE_FLOATS + 1024 + W1K_TW_FLOATS + 2) * 4 + big_proj_lds(d, feat, ncoef_out, fb_total) + (size_t)(256 + 2 * d.B) * 4 + 64,
+                   CTU_W1K_LB * 4 / W1K_WAVES);
+}
 
 // A frame is one wave's serial chain of ~40 LDS round trips: what hides them is other waves, so the kernel is built for five
 // per SIMD - twiddles come from one shared W1024 table instead of 48 registers per lane, samples are not fetched a frame ahead.
