@@ -124,6 +124,33 @@ Design::Design(const Opts &opts) : o(opts) {
         period = (unsigned)std::floor(.5 + 10000000. * wshift / (double)o.fs);
         return;
     }
+    if (o.format_in == "htk") {
+        // Feature files in (src/io/batch.cc:57-60): BATCH builds neither FB nor FEA; htkIN's vector has -nfeacoefs entries
+        // (src/io/in.cc:623-627) and goes to the delta chain, POST and OUT where fea->_fvec would.  The writers copy the first
+        // fea_size entries of the last vector in order (src/io/out.cc:177-179,723-725) - no c0 rotation - with fea_size from
+        // get_fea_size (out.cc:95-113), the header's kind and period from the options as ever (out.cc:146-159).
+        rows_in = true;
+        const std::string &fk = o.fea_kind;
+        kind = fk == "spec" ? FeaKind::Spec : fk == "logspec" ? FeaKind::LogSpec : fk == "dctc" ? FeaKind::Dctc : fk == "lpa" ? FeaKind::Lpa :
+               fk == "lpc" ? FeaKind::Lpc : fk == "trapdct" ? FeaKind::TrapDct : FeaKind::None;
+        if (o.nfeacoefs < 1) throw DesignError("IN: -nfeacoefs must be positive");
+        if ((kind == FeaKind::Lpa || kind == FeaKind::Spec || kind == FeaKind::LogSpec) && o.fea_c0) o.fea_c0 = false;
+        B = 0;
+        nfea = o.nfeacoefs;
+        row_slot.resize(nfea);
+        for (int i = 0; i < nfea; i++) row_slot[i] = i;
+        int size = nfea;
+        if (kind == FeaKind::Lpa || ((kind == FeaKind::Lpc || kind == FeaKind::Dctc) && !o.fea_c0)) size--;
+        if (o.fea_E) size++;
+        output_geometry(size);
+        Dbase = nfea;
+        // BATCH::process_frame reaches post->process_frame() only through cmvn_stat() (src/io/batch.cc:198-199), and with feature input
+        // that is called from fea_delta() or for CMVN (:217-220): without a delta chain or stacking the cms_POST object is built and
+        // cleaned per file but never applied, and the rows are written unchanged (:223-226)
+        if (cms && post_order == 0) cms = 0;
+        if (cms) cms_cols = o.fea_ncepcoefs + 1;  // cms_POST walks fea_ncepcoefs+1 entries (src/fea/post_impl.cc:208,217)
+        return;
+    }
     // ---- filter bank
     const bool plp = (o.fb_shape == "trapez");
     if (plp) {  // src/fea/fb.cc:44-54
@@ -314,6 +341,11 @@ Design::Design(const Opts &opts) : o(opts) {
         if (o.fea_E) e_slot = (o.fea_c0 && kind != FeaKind::Lpa) ? nfea : ncep;
     }
     if (o.fea_E) size++;
+    output_geometry(size);
+}
+
+void Design::output_geometry(int size) {
+    const int ncep = o.fea_ncepcoefs;
     Dbase = D = size;
     if (o.fea_delta || o.fea_trap) {
         // BATCH::init_delta (src/io/batch.cc:122-130): n_order chained deltaFEA stages, each sized on

@@ -10,6 +10,7 @@
 //   TRAP Hamming / REDFT10    src/fea/fea_trap.cc:20-107
 //   output geometry           src/io/out.cc:95-113,145-171
 //   delta / stacking chain    src/io/batch.cc:122-130, src/fea/fea_delta.cc:20-60 (geometry only)
+//   HTK feature input         src/io/in.cc:623-709, src/io/batch.cc:57-60 (geometry only: no tables)
 #pragma once
 
 #include <string>
@@ -36,6 +37,7 @@ struct Design {
     bool post_stack = false;   // -fea_trap: the single stage stacks 2*d_win+1 frames instead of differentiating
     int post_w[3] = {0, 0, 0}; // window half-width of each stage (d_win, a_win, t_win)
     bool signal_out = false;   // -format_out raw|wave: IN -> NR -> sigOUT, no FB / FEA (src/io/batch.cc:62-65)
+    bool rows_in = false;      // -format_in htk: htkIN -> delta chain / CMS / CMVN -> OUT, no FB / FEA (src/io/batch.cc:57-60); nfea = Dbase = -nfeacoefs
     double ola_corr = 1.0;     // largest sum of overlapping Hamming windows (src/io/out.cc:355-377)
     int cms = 0;               // cepstral mean subtraction after the chain: 0 off, 1 exponential, 2 block (src/fea/post_impl.cc:159-240)
     int cms_cols = 0;          // leading row columns it touches (c1..cN and, with -fea_c0, c0)
@@ -54,6 +56,9 @@ struct Design {
     int e_slot = -1;
 
     explicit Design(const Opts &opts);
+
+private:
+    void output_geometry(int size);  // delta / stacking widths, CMS, HTK header fields from the width of the plain row
 };
 
 }  // namespace ctu

@@ -9,6 +9,7 @@
 //   wave1k_kernel.h    1024-point frames, one wave per frame
 //   trap_kernel.h      TRAP-DCT as fp32 MFMA Toeplitz contraction
 //   post_kernels.h     delta chain / stacking, CMS, per-speaker CMVN over resident rows
+//   rows_in_kernels.h  HTK feature input: byte order and slot of every word of the files' rows
 //   signal_kernels.h   speech-enhancement output: inverse transform, overlap-add
 //   bigfft_kernel.h    1024 .. 4096-point frames, a workgroup per frame; bigburg_kernel.h the Burg-cepstral criterion / detector there;
 //   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
@@ -43,6 +44,7 @@
 #include "frontend_kernel.h"
 #include "trap_kernel.h"
 #include "decode_kernels.h"
+#include "rows_in_kernels.h"
 #include "bigfft_kernel.h"
 #include "lp_tail_kernel.h"
 #include "wave1k_kernel.h"
@@ -147,6 +149,7 @@ struct ctu_engine {
     bool host_timed = false;    // the last run was a host run cut into ranges: host_kernel_ms = sum over the ranges' front-end launches
     float host_kernel_ms = 0.f;
     bool in_signal_call = false;
+    bool rows_in = false;   // -format_in htk: runs start from rows (ctu_engine_run_rows), no front end, no tables
     // CMVN (row N2): statistic slot <-> row column maps, and per-call scratch
     std::vector<int> col_of_slot, slot_of_col;
     DevBuf<int> d_col_of_slot, d_slot_of_col, d_spk;
@@ -170,6 +173,7 @@ struct ctu_plan {
     DevBuf<int> wg_first;
     // host-buffer runs: device copies of the arena / rows / VAD bytes, kept for the life of the plan
     DevBuf<int16_t> h_pcm;
+    DevBuf<uint32_t> h_words;   // (a plan over rows: the files' words)
     DevBuf<float> h_rows;
     DevBuf<uint8_t> h_vad;
     // host-buffer runs of large batches: consecutive utterance ranges as plans of their own, run on two streams so that
@@ -223,6 +227,67 @@ bool ss_eligible(const ctu::Design &d);
 bool ss_big_eligible(const ctu::Design &d);
 int ss_mode_of(const ctu::Opts &o);
 
+// the passes behind the front end - or behind the ingest of feature files: delta chain / stacking, CMVN, CMS
+std::string post_unsupported_reason(const ctu::Design &d) {
+    const ctu::Opts &o = d.o;
+    if (d.post_order > 0) {
+        if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "delta / stacking on non-cepstral kinds (the reference sizes the chain as fea_ncepcoefs+1, src/fea/fea_delta.cc:22-28)";
+        if (!o.fea_c0) return "delta / stacking without -fea_c0 (the reference's writers leave slots of the row unwritten, src/io/out.cc:190-201)";
+        int wsum = 0;
+        for (int j = 0; j < d.post_order; j++) {
+            if (d.post_w[j] > 16) return "delta / stacking window above 16 frames";
+            wsum += d.post_w[j];
+        }
+        if (wsum > 24) return "delta windows adding up to more than 24 frames (LDS tile of the chain)";
+    }
+    if (o.stat_cmvn || o.apply_cmvn) {
+        if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "CMVN on non-cepstral kinds";
+        if (!o.fea_c0) return "CMVN without -fea_c0 (c0 is part of the statistics but not of the written row)";
+        if (d.post_stack) return "CMVN on stacked vectors";
+        if (d.cms) return "CMVN together with CMS (the reference warns and lets CMVN win, src/io/opts.cc:262-264)";
+        // the statistics are taken over every frame and the VAD runs on the normalised vectors of the last pass (src/io/batch.cc:193-204,230-241):
+        // a criterion on those vectors would need the statistics first
+        if (o.do_vad() && o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "fea") return "the `fea` VAD criterion together with CMVN";
+    }
+    if (d.cms) {
+        if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "CMS on non-cepstral kinds (the reference walks fea_ncepcoefs+1 entries whatever the vector holds, src/fea/post_impl.cc:203-240)";
+        if (d.post_stack) return "CMS on stacked vectors";
+        if (d.cms == 2 && (o.length_b < 1 || o.length_b > 512)) return "block CMS window outside 1..512 frames";
+        if (d.cms_cols > 32) return "more than 32 CMS columns";
+        if (d.cms == 2 && (size_t)(64 + o.length_b - 1) * d.cms_cols * sizeof(float) > 64 * 1024) return "block CMS tile above 64 KiB of LDS";
+    }
+    return "";
+}
+
+// -format_in htk (src/io/batch.cc:57-60, src/io/in.cc:623-709): what DESIGN.md section 4.8 derives from the reference
+std::string rows_unsupported_reason(const ctu::Design &d) {
+    const ctu::Opts &o = d.o;
+    // no FEA object is built, so -fea_kind only picks the header's kind code and the writers' size rule (src/io/out.cc:95-113,148-153)
+    if (d.kind == ctu::FeaKind::TrapDct) return "trapdct on input features (HTK feature input builds no FEA, src/io/batch.cc:57-60)";
+    if (d.kind == ctu::FeaKind::None) return "fea_kind outside dctc | lpc | spec | logspec with HTK feature input";
+    if (d.kind == ctu::FeaKind::Lpa) return "fea_kind lpa with HTK feature input (the writers drop the vector's last entry as if it held a0, src/io/out.cc:108,178)";
+    if ((d.kind == ctu::FeaKind::Dctc || d.kind == ctu::FeaKind::Lpc) && !o.fea_c0)
+        return "HTK feature input without -fea_c0 (the writers drop the vector's last entry, whatever it holds, src/io/out.cc:109-110,178)";
+    // BATCH::init_out (src/io/batch.cc:98-119) picks the energy pointer OUT is built with: for dctc without -fea_rawenergy and with
+    // -nr_when beforeFB it is nr->E (:101-108) - a load through the NR object that feature input never builds (:43,57-60; NR::E is a
+    // member, src/nr/nr.h:59): the reference dies in its constructor.  The other branches pass in->E (:99,105,114) and are defined.
+    if (d.kind == ctu::FeaKind::Dctc && !o.fea_rawenergy && !o.nr_when_afterFB)
+        return "fea_kind dctc with HTK feature input needs -fea_rawenergy on or -nr_when afterFB (BATCH::init_out otherwise reads nr->E of the NR object it never "
+               "builds for feature input, src/io/batch.cc:101-108,57-60: the reference crashes at start)";
+    if ((o.stat_cmvn || o.apply_cmvn) && (o.fea_Z_exp > 0 || o.fea_Z_block > 0))
+        return "CMVN together with CMS (the reference warns and lets CMVN win, src/io/opts.cc:262-264)";
+    if (o.fea_E) return "-fea_E with HTK feature input (the writers read one entry past the vector, src/io/out.cc:111,178; in->E is never computed)";
+    // every VAD option: the criteria read in->_Xsabs, which htkIN never fills, or (-vad_cepdist_mode in | fea) index the vector as c0-first
+    if (o.do_vad()) return o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "in" ? "-vad_cepdist_mode in (HTK feature input)" : "VAD together with HTK feature input";
+    if (o.nr_mode != "none" || o.rasta) return "noise reduction with HTK feature input (no NR object is built, src/io/batch.cc:57-60,224)";
+    if ((d.post_order > 0 || o.stat_cmvn || o.apply_cmvn) && o.nfeacoefs != o.fea_ncepcoefs + 1)
+        return "delta / stacking / CMS / CMVN on feature files whose -nfeacoefs differs from fea_ncepcoefs+1 (the chain is sized on fea_ncepcoefs+1 whatever the "
+               "vector holds, src/fea/fea_delta.cc:22-28, src/fea/post_impl.cc:208)";
+    if (o.format_out == "pfile" && !d.post_stack && o.nfeacoefs != o.fea_ncepcoefs + 1 && (d.kind == ctu::FeaKind::Dctc || d.kind == ctu::FeaKind::Lpc))
+        return "pfile output of feature files whose -nfeacoefs differs from fea_ncepcoefs+1 (pfileOUT rotates fea_ncepcoefs+1 entries and leaves the rest unwritten, src/io/out.cc:292-300)";
+    return post_unsupported_reason(d);
+}
+
 // reasons a valid ctucopy configuration is outside the accelerated path
 std::string unsupported_reason(const ctu::Design &d) {
     const ctu::Opts &o = d.o;
@@ -250,7 +315,7 @@ std::string unsupported_reason(const ctu::Design &d) {
         if (d.window < 32) return "window shorter than 32 samples";
         return "";
     }
-    if (o.format_in == "htk") return "HTK feature input (-format_in htk) bypasses the spectral path";
+    if (d.rows_in) return rows_unsupported_reason(d);
     if (o.fea_kind == "td-iir-mfcc" || o.fea_kind == "none") return "fea_kind outside the spectral feature path";
     if (o.dither != 0.) return "-dither != 0 makes outputs depend on file order (src/io/in.cc:205,454)";
     if (o.remove_dc1) {
@@ -270,32 +335,7 @@ std::string unsupported_reason(const ctu::Design &d) {
         if (d.B > 64) return "-nr_when afterFB with more than 64 bands";
     }
     if (o.rasta) return "-nr_rasta";
-    if (d.post_order > 0) {
-        if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "delta / stacking on non-cepstral kinds (the reference sizes the chain as fea_ncepcoefs+1, src/fea/fea_delta.cc:22-28)";
-        if (!o.fea_c0) return "delta / stacking without -fea_c0 (the reference's writers leave slots of the row unwritten, src/io/out.cc:190-201)";
-        int wsum = 0;
-        for (int j = 0; j < d.post_order; j++) {
-            if (d.post_w[j] > 16) return "delta / stacking window above 16 frames";
-            wsum += d.post_w[j];
-        }
-        if (wsum > 24) return "delta windows adding up to more than 24 frames (LDS tile of the chain)";
-    }
-    if (o.stat_cmvn || o.apply_cmvn) {
-        if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "CMVN on non-cepstral kinds";
-        if (!o.fea_c0) return "CMVN without -fea_c0 (c0 is part of the statistics but not of the written row)";
-        if (d.post_stack) return "CMVN on stacked vectors";
-        if (d.cms) return "CMVN together with CMS (the reference warns and lets CMVN win, src/io/opts.cc:262-264)";
-        // the statistics are taken over every frame and the VAD runs on the normalised vectors of the last pass (src/io/batch.cc:193-204,230-241):
-        // a criterion on those vectors would need the statistics first
-        if (o.do_vad() && o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "fea") return "the `fea` VAD criterion together with CMVN";
-    }
-    if (d.cms) {
-        if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "CMS on non-cepstral kinds (the reference walks fea_ncepcoefs+1 entries whatever the vector holds, src/fea/post_impl.cc:203-240)";
-        if (d.post_stack) return "CMS on stacked vectors";
-        if (d.cms == 2 && (o.length_b < 1 || o.length_b > 512)) return "block CMS window outside 1..512 frames";
-        if (d.cms_cols > 32) return "more than 32 CMS columns";
-        if (d.cms == 2 && (size_t)(64 + o.length_b - 1) * d.cms_cols * sizeof(float) > 64 * 1024) return "block CMS tile above 64 KiB of LDS";
-    }
+    if (const std::string why = post_unsupported_reason(d); !why.empty()) return why;
     if (o.fea_E && d.kind == ctu::FeaKind::TrapDct) return "-fea_E with trapdct (the energy lags the features by 50 frames in the reference)";
     if (o.do_vad()) {
         // trapdct delays the writer by half a context (src/fea/fea_trap.cc:53-127): the detector runs when a vector comes out, on the
@@ -1569,6 +1609,9 @@ void fill_dims(const ctu::Design &d, ctu_dims *out) {
     out->swap_out = d.o.swap_out ? 1 : 0;
     out->pcm_align = PCM_ALIGN;
     out->signal_out = d.signal_out ? 1 : 0;
+    out->rows_in = d.rows_in ? 1 : 0;
+    out->row_floats_in = d.rows_in ? d.Dbase : 0;
+    out->swap_in = d.o.swap_in ? 1 : 0;
 }
 
 }  // namespace
@@ -1689,7 +1732,9 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         e->device = device;
         e->n_cu = prop.multiProcessorCount;
-        build_tables(e.get());
+        e->rows_in = e->design->rows_in;
+        if (e->rows_in) e->kname = "rows_ingest_kernel";  // no front end: no tables, no parameter blocks
+        else build_tables(e.get());
         {
             const ctu::Opts &o = e->design->o;
             const ctu::Design &d = *e->design;
@@ -1718,7 +1763,7 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
             vp.e_slot = o.fea_E ? (d.post_order > 0 ? d.D - 1 : d.e_slot) : -1;
             vp.e_delay = (o.vad_filter_order - 1) / 2;
         }
-        e->kp0 = engine_kparams(e.get());
+        if (!e->rows_in) e->kp0 = engine_kparams(e.get());
         if (e->big) e->bp0 = engine_bigparams(e.get());
         HIP_TRY(hipEventCreate(&e->ev0));
         HIP_TRY(hipEventCreate(&e->ev1));
@@ -1749,6 +1794,7 @@ int ctu_engine_dims(const ctu_engine *e, ctu_dims *out) {
 }
 
 int64_t ctu_num_frames(const ctu_engine *e, int64_t n) {
+    if (e->rows_in) return n < 0 ? -1 : n;  // the "samples" of a feature file are its rows
     const int pre = e->design->window - e->design->wshift;
     if (n < pre) return -1;
     return (n - pre) / e->design->wshift;
@@ -1766,9 +1812,91 @@ int64_t ctu_arena_layout(const int64_t *utt_nsamples, int32_t n_utt, int64_t *sa
     return so + PCM_TAIL;  // loads run to the end of the last 32-sample row of a frame
 }
 
+int64_t ctu_rows_arena_layout(const int64_t *utt_rows, int32_t n_utt, int32_t width, int64_t *word_off) {
+    if (n_utt < 0 || width < 1 || (n_utt && !utt_rows)) return CTU_ERR_INPUT;
+    int64_t wo = 0;
+    for (int i = 0; i < n_utt; i++) {
+        if (utt_rows[i] < 0) return CTU_ERR_INPUT;
+        if (word_off) word_off[i] = wo;
+        wo += (utt_rows[i] * width + ROWS_ALIGN - 1) / ROWS_ALIGN * ROWS_ALIGN;
+    }
+    if (word_off) word_off[n_utt] = wo;
+    return wo;  // rows_ingest_kernel reads an utterance's own words only: no padding around the arena
+}
+
+// The plan of an engine that starts from rows (-format_in htk): lengths are row counts, the arena is ctu_rows_arena_layout's, tiles
+// are what rows_ingest_kernel strides over (no chains), and what the delta / CMS / CMVN passes need is as in ctu_plan_create.
+static int plan_create_rows(ctu_engine *e, const int64_t *utt_rows, int32_t n_utt, ctu_plan **out) {
+    std::unique_ptr<ctu_plan> pl(new ctu_plan);
+    const ctu::Design &d = *e->design;
+    pl->eng = e;
+    pl->n_utt = n_utt;
+    pl->nsamples.assign(utt_rows, utt_rows + n_utt);
+    pl->sample_off.resize(n_utt + 1);
+    pl->row_off.resize(n_utt + 1);
+    pl->frames.resize(n_utt);
+    pl->total_samples = ctu_rows_arena_layout(utt_rows, n_utt, d.Dbase, pl->sample_off.data());
+    if (pl->total_samples < 0) {
+        set_error(e, "ENGINE: negative utterance length");
+        return CTU_ERR_INPUT;
+    }
+    std::vector<TileRec> tiles;
+    std::vector<int4> uinfo(n_utt);
+    std::vector<int> chunks;
+    int wmax = 0;
+    for (int j = 0; j < d.post_order; j++) wmax = std::max(wmax, d.post_w[j]);
+    int64_t ro = 0;
+    for (int i = 0; i < n_utt; i++) {
+        const int64_t T = utt_rows[i];
+        if (T > 0x7fffffff / 2) {
+            set_error(e, "ENGINE: feature file too long");
+            return CTU_ERR_INPUT;
+        }
+        if (d.post_order > 0 && T > 0 && T < wmax + 2) {  // as in ctu_plan_create
+            set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
+            return CTU_ERR_INPUT;
+        }
+        pl->row_off[i] = ro;
+        pl->frames[i] = T;
+        for (int64_t t0 = 0; t0 < T; t0 += TILE) {
+            TileRec r;
+            r.sbase = pl->sample_off[i] + t0 * d.Dbase;
+            r.rbase = ro + t0;
+            r.nvalid = (int)std::min<int64_t>(TILE, T - t0);
+            r.t0 = (int)t0;
+            r.next = -1;
+            r.T = (int)T;
+            tiles.push_back(r);
+            chunks.push_back(i);
+            chunks.push_back((int)t0);
+        }
+        uinfo[i] = make_int4((int)(ro & 0xffffffff), (int)(ro >> 32), (int)T, 0);
+        pl->max_frames = std::max<int>(pl->max_frames, (int)T);
+        ro += T;
+    }
+    pl->row_off[n_utt] = ro;
+    pl->total_frames = ro;
+    pl->n_tiles = (int)tiles.size();
+    pl->grid = std::max(1, std::min((pl->n_tiles + 3) / 4, e->n_cu * ROWS_WG_PER_CU));  // four waves = four tiles per workgroup pass
+    try {
+        HIP_TRY(hipSetDevice(e->device));
+        pl->tiles.upload(tiles);
+        pl->utt_info.upload(uinfo);
+        pl->trap_chunks.upload(chunks);
+        pl->n_trap_chunks = (int)chunks.size() / 2;
+        if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
+    } catch (const std::exception &ex) {
+        set_error(e, std::string("ENGINE: ") + ex.what());
+        return CTU_ERR_DEVICE;
+    }
+    *out = pl.release();
+    return CTU_OK;
+}
+
 int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, ctu_plan **out) {
     if (!e || !out || n_utt < 0 || (n_utt && !utt_nsamples)) return CTU_ERR_INPUT;
     *out = nullptr;
+    if (e->rows_in) return plan_create_rows(e, utt_nsamples, n_utt, out);
     std::unique_ptr<ctu_plan> pl(new ctu_plan);
     pl->eng = e;
     pl->n_utt = n_utt;
@@ -2048,6 +2176,10 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
 
 int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
+    if (e->rows_in) {
+        set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows");
+        return CTU_ERR_INPUT;
+    }
     if (pl->n_tiles == 0) return CTU_OK;
     const ctu::Design &d = *e->design;
     const bool signal = d.signal_out;
@@ -2125,6 +2257,38 @@ bool is_pinned(const void *p) {
     }
     return a.type == hipMemoryTypeHost;
 }
+// The utterance ranges of a host-buffer run (ctu_engine_run_host, ctu_engine_run_rows_host): `nparts` consecutive ranges of about equal
+// input as plans of their own, and the two streams they alternate on.  Keyed on the count asked for: fewer ranges may come out (a long
+// utterance spans several).  A part's arena is the slice of the caller's arena that starts where its first utterance does - PCM_HEAD
+// samples ahead of it for PCM: both layout rules are translation invariant.  A failure leaves the plan without ranges.
+int split_host_parts(ctu_engine *e, ctu_plan *pl, int nparts) {
+    if (nparts <= 1 || pl->parts_for == nparts) return CTU_OK;
+    pl->parts.clear();
+    pl->parts_for = 0;
+    pl->part_first.assign(1, 0);
+    const int64_t per = (pl->sample_off[pl->n_utt] - pl->sample_off[0] + nparts - 1) / nparts;
+    for (int k = 1; k < nparts; k++) {
+        int u = pl->part_first.back();
+        const int64_t goal = pl->sample_off[0] + per * k;
+        while (u < pl->n_utt && pl->sample_off[u] < goal) u++;
+        if (u > pl->part_first.back() && u < pl->n_utt) pl->part_first.push_back(u);
+    }
+    pl->part_first.push_back(pl->n_utt);
+    for (size_t k = 0; k + 1 < pl->part_first.size(); k++) {
+        ctu_plan *sub = nullptr;
+        const int u0 = pl->part_first[k], u1 = pl->part_first[k + 1];
+        const int rc = ctu_plan_create(e, pl->nsamples.data() + u0, u1 - u0, &sub);
+        if (rc != CTU_OK) {
+            pl->parts.clear();
+            return rc;
+        }
+        pl->parts.emplace_back(sub);
+    }
+    for (hipStream_t &st : pl->part_stream)
+        if (!st) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    pl->parts_for = nparts;
+    return CTU_OK;
+}
 }  // namespace
 
 // How many utterance ranges a host-buffer run is cut into: CTU_HOST_CHUNKS if set (1 = one range), else 8 for batches of
@@ -2140,6 +2304,10 @@ static int host_chunks(const ctu_engine *e, const ctu_plan *pl, bool pinned) {
 int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm, float *h_rows, uint8_t *h_vad,
                         int64_t *rows_per_utt) {
     if (!e || !pl_ || pl_->eng != e) return CTU_ERR_INPUT;
+    if (e->rows_in) {
+        set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows_host");
+        return CTU_ERR_INPUT;
+    }
     ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
     const ctu::Design &d = *e->design;
     if (rows_per_utt)
@@ -2151,30 +2319,7 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
         // DMA-ed asynchronously at the link rate; pageable memory goes through the runtime's own staging (hipMemcpy).
         const bool pin_in = is_pinned(h_pcm), pin_out = is_pinned(h_rows);
         const int nparts = host_chunks(e, pl, pin_in && pin_out);
-        if (nparts > 1 && pl->parts_for != nparts) {  // keyed on the count asked for: fewer ranges may come out (a long utterance spans several)
-            pl->parts_for = nparts;
-            // ranges of about equal PCM; a part's arena is the slice of the caller's arena that starts PCM_HEAD samples
-            // ahead of its first utterance (the layout rule of ctu_plan_create is translation invariant)
-            pl->parts.clear();
-            pl->part_first.assign(1, 0);
-            const int64_t per = (pl->sample_off[pl->n_utt] - pl->sample_off[0] + nparts - 1) / nparts;
-            for (int k = 1; k < nparts; k++) {
-                int u = pl->part_first.back();
-                const int64_t goal = pl->sample_off[0] + per * k;
-                while (u < pl->n_utt && pl->sample_off[u] < goal) u++;
-                if (u > pl->part_first.back() && u < pl->n_utt) pl->part_first.push_back(u);
-            }
-            pl->part_first.push_back(pl->n_utt);
-            for (size_t k = 0; k + 1 < pl->part_first.size(); k++) {
-                ctu_plan *sub = nullptr;
-                const int u0 = pl->part_first[k], u1 = pl->part_first[k + 1];
-                const int rc = ctu_plan_create(e, pl->nsamples.data() + u0, u1 - u0, &sub);
-                if (rc != CTU_OK) return rc;
-                pl->parts.emplace_back(sub);
-            }
-            for (hipStream_t &st : pl->part_stream)
-                if (!st) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        }
+        if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
         std::vector<uint8_t> v(e->do_vad ? (size_t)pl->total_frames : 0);
         if (nparts > 1 && pl->parts.size() > 1) {
             const int np = (int)pl->parts.size();
@@ -2284,6 +2429,145 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
     return CTU_OK;
 }
 
+// ---- runs that start from rows (-format_in htk) ------------------------------------------------------------------------------
+// Stages: ingest (rows_in_kernels.h) -> 7 delta chain / stacking -> 8 CMS; CMVN is the caller's, over the resulting rows.
+int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in, float *d_rows, void *stream) {
+    if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
+    if (!e->rows_in) {
+        set_error(e, "ENGINE: this configuration starts from samples: use ctu_engine_run (ctu_engine_run_rows needs -format_in htk)");
+        return CTU_ERR_INPUT;
+    }
+    if (pl->n_tiles == 0) return CTU_OK;
+    if (!d_rows_in || !d_rows) {
+        set_error(e, "ENGINE: null device buffer");
+        return CTU_ERR_INPUT;
+    }
+    const ctu::Design &d = *e->design;
+    hipStream_t s = (hipStream_t)stream;
+    try {
+        HIP_TRY(hipSetDevice(e->device));
+        const bool staged = d.post_order > 0 || d.cms;  // the passes behind read the plan's base rows, else the ingest writes the caller's
+        uint32_t *dst = reinterpret_cast<uint32_t *>(staged ? pl->base_rows.p : d_rows);
+        HIP_TRY(hipEventRecord(e->ev0, s));
+        lift<0, 1>(d.o.swap_in, [&](auto sw) {
+            lift<0, 1>(d.post_stack, [&](auto rot) {
+                hipLaunchKernelGGL((rows_ingest_kernel<decltype(sw)::value != 0, decltype(rot)::value != 0>), dim3(pl->grid), dim3(256), 0, s,
+                                   static_cast<const uint32_t *>(d_rows_in), dst, pl->tiles.p, pl->n_tiles, d.Dbase);
+            });
+        });
+        HIP_TRY(hipEventRecord(e->ev1, s));
+        e->timed = true;
+        e->host_timed = false;
+        HIP_TRY(hipGetLastError());
+        if (d.post_order > 0) stage_post(e, pl, s, d_rows);
+        if (d.cms) stage_cms(e, pl, s, d_rows);
+    } catch (const std::exception &ex) {
+        set_error(e, std::string("ENGINE: ") + ex.what());
+        return CTU_ERR_DEVICE;
+    }
+    return CTU_OK;
+}
+
+int ctu_engine_run_rows_host(ctu_engine *e, const ctu_plan *pl_, const void *h_rows_in, float *h_rows) {
+    if (!e || !pl_ || pl_->eng != e) return CTU_ERR_INPUT;
+    if (!e->rows_in) {
+        set_error(e, "ENGINE: this configuration starts from samples: use ctu_engine_run_host (ctu_engine_run_rows_host needs -format_in htk)");
+        return CTU_ERR_INPUT;
+    }
+    ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
+    const ctu::Design &d = *e->design;
+    if (pl->total_frames == 0) return CTU_OK;
+    if (!h_rows_in || !h_rows) {
+        set_error(e, "ENGINE: null host buffer");
+        return CTU_ERR_INPUT;
+    }
+    const uint32_t *h_in = static_cast<const uint32_t *>(h_rows_in);
+    try {
+        HIP_TRY(hipSetDevice(e->device));
+        const bool pin_in = is_pinned(h_rows_in), pin_out = is_pinned(h_rows);
+        // ranges as in ctu_engine_run_host: eight for at least 16 utterances and 32 MiB of input in page-locked buffers, CTU_HOST_CHUNKS overrides
+        int nparts = (pin_in && pin_out && pl->n_utt >= 16 && pl->total_samples >= (int64_t)8 << 20) ? 8 : 1;
+        if (const char *v = getenv("CTU_HOST_CHUNKS")) nparts = std::max(1, atoi(v));
+        nparts = std::min(nparts, std::max(1, pl->n_utt));
+        if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
+        if (nparts > 1 && pl->parts.size() > 1) {
+            const int np = (int)pl->parts.size();
+            std::vector<std::pair<hipEvent_t, hipEvent_t>> part_events;  // (start, stop) of every range's ingest launch
+            auto drain = [&] {
+                (void)hipStreamSynchronize(pl->part_stream[0]);
+                (void)hipStreamSynchronize(pl->part_stream[1]);
+            };
+            auto download = [&](int k) {
+                ctu_plan *sp = pl->parts[k].get();
+                if (sp->total_frames == 0) return;
+                hipStream_t st = pl->part_stream[k & 1];
+                float *dst = h_rows + pl->row_off[pl->part_first[k]] * d.D;
+                if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->total_frames * d.D * 4, hipMemcpyDeviceToHost, st));
+                else {
+                    HIP_TRY(hipStreamSynchronize(st));
+                    HIP_TRY(hipMemcpy(dst, sp->h_rows.p, (size_t)sp->total_frames * d.D * 4, hipMemcpyDeviceToHost));
+                }
+            };
+            for (int k = 0; k < np; k++) {
+                ctu_plan *sp = pl->parts[k].get();
+                hipStream_t st = pl->part_stream[k & 1];
+                if (sp->total_frames) {
+                    if (sp->h_words.n < (size_t)sp->total_samples) sp->h_words.alloc((size_t)sp->total_samples);
+                    if (sp->h_rows.n < (size_t)sp->total_frames * d.D) sp->h_rows.alloc((size_t)sp->total_frames * d.D);
+                    const uint32_t *src = h_in + pl->sample_off[pl->part_first[k]];
+                    if (pin_in) HIP_TRY(hipMemcpyAsync(sp->h_words.p, src, (size_t)sp->total_samples * 4, hipMemcpyHostToDevice, st));
+                    else HIP_TRY(hipMemcpy(sp->h_words.p, src, (size_t)sp->total_samples * 4, hipMemcpyHostToDevice));
+                    const int rc = ctu_engine_run_rows(e, sp, sp->h_words.p, sp->h_rows.p, st);
+                    if (rc != CTU_OK) {  // earlier ranges are still in flight: drain them before the caller reuses its buffers
+                        drain();
+                        for (auto &pe : part_events) {
+                            (void)hipEventDestroy(pe.first);
+                            (void)hipEventDestroy(pe.second);
+                        }
+                        return rc;
+                    }
+                    part_events.emplace_back();
+                    HIP_TRY(hipEventCreate(&part_events.back().first));
+                    HIP_TRY(hipEventCreate(&part_events.back().second));
+                    std::swap(part_events.back().first, e->ev0);
+                    std::swap(part_events.back().second, e->ev1);
+                }
+                if (k > 0) download(k - 1);
+            }
+            download(np - 1);
+            HIP_TRY(hipStreamSynchronize(pl->part_stream[0]));
+            HIP_TRY(hipStreamSynchronize(pl->part_stream[1]));
+            e->host_kernel_ms = 0.f;
+            for (auto &pe : part_events) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, pe.first, pe.second) == hipSuccess) e->host_kernel_ms += ms;
+                (void)hipEventDestroy(pe.first);
+                (void)hipEventDestroy(pe.second);
+            }
+            e->host_timed = true;
+        } else {
+            if (pl->h_words.n < (size_t)pl->total_samples) pl->h_words.alloc((size_t)pl->total_samples);
+            if (pl->h_rows.n < (size_t)pl->total_frames * d.D) pl->h_rows.alloc((size_t)pl->total_frames * d.D);
+            hipStream_t s = nullptr;
+            if (pin_in) HIP_TRY(hipMemcpyAsync(pl->h_words.p, h_in, (size_t)pl->total_samples * 4, hipMemcpyHostToDevice, s));
+            else HIP_TRY(hipMemcpy(pl->h_words.p, h_in, (size_t)pl->total_samples * 4, hipMemcpyHostToDevice));
+            const int rc = ctu_engine_run_rows(e, pl, pl->h_words.p, pl->h_rows.p, s);
+            if (rc != CTU_OK) return rc;
+            if (pin_out) {
+                HIP_TRY(hipMemcpyAsync(h_rows, pl->h_rows.p, (size_t)pl->total_frames * d.D * 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            } else {
+                HIP_TRY(hipStreamSynchronize(s));
+                HIP_TRY(hipMemcpy(h_rows, pl->h_rows.p, (size_t)pl->total_frames * d.D * 4, hipMemcpyDeviceToHost));
+            }
+        }
+    } catch (const std::exception &ex) {
+        set_error(e, std::string("ENGINE: ") + ex.what());
+        return CTU_ERR_DEVICE;
+    }
+    return CTU_OK;
+}
+
 static void cmvn_maps(ctu_engine *e) {
     if (!e->col_of_slot.empty()) return;
     const ctu::Design &d = *e->design;
@@ -2291,6 +2575,11 @@ static void cmvn_maps(ctu_engine *e) {
     e->col_of_slot.assign(X, 0);
     e->slot_of_col.assign(d.D, -1);
     for (int k = 0; k < X; k++) {
+        if (e->rows_in) {  // feature files: slot k is vector entry k, written to column k (src/fea/post_impl.cc:55-57, src/io/out.cc:177-179)
+            e->col_of_slot[k] = k;
+            e->slot_of_col[k] = k;
+            continue;
+        }
         const int i = (k + 1) % X;               // internal vector entry held by slot k (post_impl.cc:56-62)
         const int j = i / fc, ii = i % fc;       // block, entry within the block (0 = c0)
         const int col = fc * j + (ii == 0 ? fc - 1 : ii - 1);  // writer order: c1..cN, c0 (out.cc:188-201)

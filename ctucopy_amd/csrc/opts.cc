@@ -362,7 +362,7 @@ Opts Opts::from_args(const std::vector<std::string> &args) {
 std::string Opts::usage() const {
     return "ctucopy (MI355X engine) -- CtuCopy-compatible speech feature extraction\n"
            "usage: ctucopy -C <config> | <options>  -S <list>   (batch)   or   -i <in> -o <out>\n"
-           "  I/O:      -format_in raw|alaw|mulaw|wave  -format_out htk|pfile=<f>|ark=<f>  -fs <Hz>\n"
+           "  I/O:      -format_in raw|alaw|mulaw|wave|htk  -format_out htk|pfile=<f>|ark=<f>  -fs <Hz>\n"
            "            -endian_in|-endian_out big|little  -preem <0..1)  -remove_dc on|off\n"
            "  framing:  -w <ms>  -s <ms>\n"
            "  bank:     -fb_scale mel|bark|lin|expolog  -fb_shape triang|rect|trapez  -fb_norm|-fb_power|\n"

@@ -25,7 +25,8 @@ class Dims(ctypes.Structure):
                 ("wfft", ctypes.c_int32), ("nbins", ctypes.c_int32), ("nbands", ctypes.c_int32),
                 ("row_floats", ctypes.c_int32), ("htk_kind", ctypes.c_int32), ("htk_period", ctypes.c_uint32),
                 ("has_vad", ctypes.c_int32), ("swap_out", ctypes.c_int32), ("pcm_align", ctypes.c_int32),
-                ("signal_out", ctypes.c_int32)]
+                ("signal_out", ctypes.c_int32), ("rows_in", ctypes.c_int32), ("row_floats_in", ctypes.c_int32),
+                ("swap_in", ctypes.c_int32)]
 
 
 # every symbol include/ctu_engine.h declares (checked by tests/test_abi.py)
@@ -34,7 +35,7 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_plan_row_offsets", "ctu_arena_layout", "ctu_plan_total_samples", "ctu_plan_total_frames", "ctu_engine_run",
            "ctu_engine_run_host", "ctu_host_alloc", "ctu_host_free", "ctu_engine_reset_chain", "ctu_engine_set_vad_stream", "ctu_vad_ring_step", "ctu_plan_set_vad_ring", "ctu_vad_ring_rows", "ctu_decode_g711", "ctu_engine_last_kernel_ms", "ctu_engine_kernel_name", "ctu_engine_phase2_walk", "ctu_cmvn_cols", "ctu_cmvn_accumulate", "ctu_cmvn_apply",
            "ctu_cmvn_accumulate_host", "ctu_cmvn_apply_host", "ctu_plan_out_samples", "ctu_engine_run_signal",
-           "ctu_engine_run_signal_host"]
+           "ctu_engine_run_signal_host", "ctu_rows_arena_layout", "ctu_engine_run_rows", "ctu_engine_run_rows_host"]
 
 _lib = None
 
@@ -102,6 +103,10 @@ def load_library():
     L.ctu_engine_run_signal.argtypes = [vp, vp, vp, vp, vp]
     L.ctu_engine_run_signal_host.argtypes = [vp, vp, vp, vp]
     L.ctu_cmvn_apply_host.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    L.ctu_rows_arena_layout.restype = i64
+    L.ctu_rows_arena_layout.argtypes = [ctypes.POINTER(i64), i32, i32, ctypes.POINTER(i64)]
+    L.ctu_engine_run_rows.argtypes = [vp, vp, vp, vp, vp]
+    L.ctu_engine_run_rows_host.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -275,6 +280,39 @@ class Engine:
             out = torch.zeros(plan.total_samples, dtype=torch.int16, device=pcm.device)
         s = stream if stream is not None else torch.cuda.current_stream(pcm.device)
         self._check(load_library().ctu_engine_run_signal(self._h, plan._h, pcm.data_ptr(), out.data_ptr(), s.cuda_stream))
+        return out
+
+    # ---- feature files in (-format_in htk)
+    def run_rows_device(self, plan, words, rows=None, stream=None):
+        """words: torch int32 CUDA tensor [plan.total_samples] (the files' payloads at plan.sample_off); returns the rows tensor (async)."""
+        import torch
+        assert words.is_cuda and words.dtype == torch.int32 and words.numel() >= plan.total_samples
+        if rows is None:
+            rows = torch.empty((plan.total_frames, self.dims.row_floats), dtype=torch.float32, device=words.device)
+        s = stream if stream is not None else torch.cuda.current_stream(words.device)
+        self._check(load_library().ctu_engine_run_rows(self._h, plan._h, words.data_ptr(), rows.data_ptr(), s.cuda_stream))
+        return rows
+
+    def run_rows_host(self, plan, arena, rows_out=None):
+        """numpy uint32 arena (the files' payloads as they stand, at plan.sample_off) in, numpy float32 rows out."""
+        assert arena.dtype == np.uint32 and arena.flags.c_contiguous and arena.size >= plan.total_samples
+        rows = rows_out if rows_out is not None else np.empty((plan.total_frames, self.dims.row_floats), dtype=np.float32)
+        self._check(load_library().ctu_engine_run_rows_host(self._h, plan._h, arena.ctypes.data, rows.ctypes.data))
+        return rows
+
+    def postprocess(self, features):
+        """list of [rows, -nfeacoefs] float32 arrays (the rows of HTK feature files, in file order) -> list of [rows, D] float32 arrays:
+        delta / stacking and CMS as the engine's command line says (an engine created with -format_in htk)."""
+        width = self.dims.row_floats_in
+        feats = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, width) for f in features]
+        plan = self.plan([f.shape[0] for f in feats])
+        arena = np.zeros(max(plan.total_samples, 1), dtype=np.uint32)
+        order = ">u4" if self.dims.swap_in else "<u4"   # the engine reads the words in the byte order -endian_in names
+        for f, off in zip(feats, plan.sample_off[:-1]):
+            arena[off:off + f.size] = f.reshape(-1).view(np.uint32).astype(order).view(np.uint32)
+        rows = self.run_rows_host(plan, arena)
+        out = [rows[plan.row_off[i]:plan.row_off[i + 1]] for i in range(plan.n_utt)]
+        plan.close()
         return out
 
     # ---- per-speaker CMVN over device-resident rows (include/ctu_engine.h; src/fea/post_impl.cc:51-118)

@@ -2,7 +2,7 @@
 //
 // Keeps the reference's command line (src/io/opts.cc:644-846), `-S` list format
 // (`fin fout [spk] [vadfile]`, src/io/batch.cc:349-356), input decoders (raw / a-law / mu-law / WAVE,
-// src/io/in.cc:434-619, src/io/amulaw.h:20-53) and feature writers (HTK src/io/out.cc:115-213, KALDI ark+scp
+// src/io/in.cc:434-619, src/io/amulaw.h:20-53; HTK feature files, in.cc:623-709, for delta / CMS / CMVN on existing features) and feature writers (HTK src/io/out.cc:115-213, KALDI ark+scp
 // :648-781, ICSI pfile src/io/pfile.cc:435-592), so that it is a drop-in for batch feature extraction.
 // The per-frame chain itself runs on the GPU(s) behind include/ctu_engine.h; this file only moves bytes.
 //
@@ -75,8 +75,38 @@ size_t wave_samples(const ctu::Opts &o, FILE *f, size_t file_bytes) {
     return std::min<size_t>(rd32(&b[40]) / 2, (file_bytes - 44) / 2);
 }
 
+// HTK feature file (htkIN::new_file / get_frame, src/io/in.cc:629-709): the 12-byte header in the byte order -endian_in names, its
+// sampSize / 4 the row width of this file; the frame count is what the file really holds - get_frame stops at the first row it
+// cannot read whole, the header's nSamples is never looked at.  htkIN's vector has -nfeacoefs entries for the life of the
+// process (in.cc:623-627) and get_frame writes sampSize / 4 of them: a wider file writes past it, a narrower one leaves entries
+// of the file before - neither is reproduced.
+int64_t probe_htk_rows(const ctu::Opts &o, const std::string &path) {
+    File f(std::fopen(path.c_str(), "rb"));
+    if (!f) throw Fatal("IN: Cannot open data file!");
+    uint8_t h[12];
+    if (std::fread(h, 1, 12, f.get()) != 12) throw Fatal("OUT: Error in stream writing!\n");  // (sic: the reader throws the writer's text, in.cc:644-647)
+    const int width = (o.swap_in ? (h[8] << 8 | h[9]) : rd16(&h[8])) / 4;
+    if (width != o.nfeacoefs)
+        throw Fatal("IN: " + path + " holds vectors of " + std::to_string(width) + " values, -nfeacoefs says " + std::to_string(o.nfeacoefs) +
+                    " (the reference keeps one vector of -nfeacoefs entries for every file, src/io/in.cc:623-627,694-701)");
+    // the rows are read in a second pass, at the offsets this one lays out: a stream that can be read only once (a FIFO) cannot be taken
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw Fatal("IN: " + path + " is not a regular file (feature input is sized first and read afterwards)");
+    const size_t bytes = (size_t)st.st_size - 12;  // (the 12 header bytes have just been read: the file has them)
+    return (int64_t)(bytes / (4 * (size_t)width));
+}
+
+// the payload of `n` rows as it stands in the file, into the words arena (the engine swaps and places the words)
+void read_htk_rows(const ctu::Opts &o, const std::string &path, uint32_t *dst, size_t n) {
+    File f(std::fopen(path.c_str(), "rb"));
+    if (!f) throw Fatal("IN: Cannot open data file!");
+    const size_t words = n * (size_t)o.nfeacoefs;
+    if (std::fseek(f.get(), 12, SEEK_SET) != 0 || std::fread(dst, 4, words, f.get()) != words) throw Fatal("IN: Cannot read data file!");
+}
+
 // number of samples `path` will decode to, without reading its data
 int64_t probe_samples(const ctu::Opts &o, const std::string &path) {
+    if (o.format_in == "htk") return probe_htk_rows(o, path);
     const bool wave = o.format_in == "wave";
     if (o.format_in != "raw" && o.format_in != "alaw" && o.format_in != "mulaw" && !wave) throw Fatal("IN: Unknown input file format!");
     struct stat st;
@@ -219,13 +249,20 @@ struct PfileWriter {
     std::vector<uint8_t> data;
     std::vector<uint32_t> sent_start{0};
     uint32_t nframes = 0;
+    // -format_in htk: pfileOUT::save_frame has no branch for feature input (src/io/out.cc:280-303, unlike htkOUT and arkOUT), so
+    // it moves entry 0 of every block of fea_ncepcoefs+1 behind the others although the file's c0 is already there: rot = that block size
+    int rot = 0;
     PfileWriter(const std::string &n, int nf) : name(n), nfea(nf) {}
     void add(const float *rows, int64_t n, int cols) {
         const uint32_t sid = (uint32_t)sent_start.size() - 1;
         for (int64_t t = 0; t < n; t++) {
             put32(data, sid, true);
             put32(data, (uint32_t)t, true);
-            for (int i = 0; i < nfea; i++) putf(data, i < cols ? rows[t * cols + i] : 0.f, true);
+            for (int i = 0; i < nfea; i++) {
+                int c = i;
+                if (rot && i < cols / rot * rot) c = i / rot * rot + (i % rot + 1) % rot;
+                putf(data, c < cols ? rows[t * cols + c] : 0.f, true);
+            }
         }
         nframes += (uint32_t)n;
         sent_start.push_back(nframes);
@@ -428,7 +465,7 @@ struct Batch {
 };
 
 // the engine's part of a shard: plan over its lengths, H2D + kernels + D2H from / to the page-locked buffers
-void run_shard(ctu_engine *eng, Shard &sh, PinPool &pool, bool signal_out, bool has_vad, int row_floats) {
+void run_shard(ctu_engine *eng, Shard &sh, PinPool &pool, bool signal_out, bool rows_in, bool has_vad, int row_floats) {
     ctu_plan *plan = nullptr;
     if (ctu_plan_create(eng, sh.ns.data(), (int)sh.ns.size(), &plan) != CTU_OK) throw Fatal(ctu_last_error(eng));
     struct PlanGuard {
@@ -438,7 +475,7 @@ void run_shard(ctu_engine *eng, Shard &sh, PinPool &pool, bool signal_out, bool 
     const size_t n = sh.ns.size();
     const int64_t *so = ctu_plan_sample_offsets(plan), *ro = ctu_plan_row_offsets(plan);
     if (ctu_plan_total_samples(plan) != sh.total_samples || !std::equal(sh.so.begin(), sh.so.end(), so))
-        throw Fatal("ENGINE: internal: the plan's arena layout differs from ctu_arena_layout");
+        throw Fatal("ENGINE: internal: the plan's arena layout differs from ctu_arena_layout / ctu_rows_arena_layout");
     if (!sh.hidx.empty() && ctu_plan_set_vad_ring(plan, sh.hidx.data()) != CTU_OK) throw Fatal(ctu_last_error(eng));
     sh.total_frames = ctu_plan_total_frames(plan);
     sh.ro.assign(ro, ro + n + 1);
@@ -454,6 +491,11 @@ void run_shard(ctu_engine *eng, Shard &sh, PinPool &pool, bool signal_out, bool 
     sh.rows = pool.get((size_t)sh.total_frames * row_floats * sizeof(float));
     sh.vad.assign(has_vad ? (size_t)sh.total_frames : 0, 0);
     // rows_per_utt < frames only with -vad_apply_mode drop (rows compacted in place by the library)
+    if (rows_in) {  // -format_in htk: every row of the file comes out (no VAD on this path)
+        for (size_t i = 0; i < n; i++) sh.kept[i] = ro[i + 1] - ro[i];
+        if (ctu_engine_run_rows_host(eng, plan, sh.arena.p, static_cast<float *>(sh.rows.p)) != CTU_OK) throw Fatal(ctu_last_error(eng));
+        return;
+    }
     if (ctu_engine_run_host(eng, plan, static_cast<const int16_t *>(sh.arena.p), static_cast<float *>(sh.rows.p), has_vad ? sh.vad.data() : nullptr,
                             sh.kept.data()) != CTU_OK)
         throw Fatal(ctu_last_error(eng));
@@ -589,6 +631,7 @@ int real_main(int argc, char **argv) {
         if ((o.fea_kind == "dctc" || o.fea_kind == "lpc") && !o.fea_c0) nfea_pf += 1;
         if (o.fea_kind == "lpa") nfea_pf += 1;
         pf.reset(new PfileWriter(o.pfilename, nfea_pf));
+        if (o.format_in == "htk" && !o.fea_trap && (o.fea_kind == "dctc" || o.fea_kind == "lpc")) pf->rot = o.fea_ncepcoefs + 1;
     }
 
     // ---- per-speaker CMVN (src/io/batch.cc:131-171,331-419).  -apply_cmvn <f>: the reference first tries to read <f>;
@@ -611,6 +654,7 @@ int real_main(int argc, char **argv) {
 
     // ---- the pipeline: reader -> engines (this thread) -> writer, one batch in each at a time
     const size_t batch_samples = (size_t)batch_mib << 19;  // samples of PCM per batch (default 1 GiB)
+    const size_t unit = d.rows_in ? 2 * (size_t)d.row_floats_in : 1;  // -format_in htk: a "sample" is a row of that many floats, batches stay sized in bytes
     PinPool pool;
     // CTU_HOST_TIMING=1: seconds each stage was busy (not waiting for its neighbours), on stderr at the end
     const bool timing = std::getenv("CTU_HOST_TIMING") != nullptr;
@@ -659,7 +703,7 @@ int real_main(int argc, char **argv) {
                             break;
                         }
                         ns.push_back(probed[end]);
-                        total += (size_t)probed[end];
+                        total += (size_t)probed[end] * unit;
                     }
                 }
                 const size_t n = b->n = end - pos;
@@ -697,15 +741,17 @@ int real_main(int argc, char **argv) {
                         b->where[sh.idx[k]] = {g, k};
                     }
                     sh.so.resize(sh.ns.size() + 1);
-                    sh.total_samples = ctu_arena_layout(sh.ns.data(), (int)sh.ns.size(), sh.so.data());
+                    sh.total_samples = d.rows_in ? ctu_rows_arena_layout(sh.ns.data(), (int)sh.ns.size(), d.row_floats_in, sh.so.data())
+                                                 : ctu_arena_layout(sh.ns.data(), (int)sh.ns.size(), sh.so.data());
                     if (sh.idx.empty()) continue;
                     // the bytes between utterances are read under zero weights and need no particular value (include/ctu_engine.h)
-                    sh.arena = pool.get((size_t)sh.total_samples * sizeof(int16_t));
+                    sh.arena = pool.get((size_t)sh.total_samples * (d.rows_in ? sizeof(uint32_t) : sizeof(int16_t)));
                 }
                 parallel_for(io_threads, n, [&](size_t i) {
                     Shard &sh = b->sh[b->where[i].first];
                     const size_t k = b->where[i].second;
-                    decode_into(o, items[pos + i].fin, static_cast<int16_t *>(sh.arena.p) + sh.so[k], (size_t)sh.ns[k]);
+                    if (d.rows_in) read_htk_rows(o, items[pos + i].fin, static_cast<uint32_t *>(sh.arena.p) + sh.so[k], (size_t)sh.ns[k]);
+                    else decode_into(o, items[pos + i].fin, static_cast<int16_t *>(sh.arena.p) + sh.so[k], (size_t)sh.ns[k]);
                 });
                 pos = end;
                 t_read += now() - t0;
@@ -783,9 +829,10 @@ int real_main(int argc, char **argv) {
                         }
                         if (per_file) {
                             // -fea_trap: the reference's writers overwrite fea_kind with "spec" when they save their first frame
-                            // (src/io/out.cc:182), so every header after the first file carries base kind 8 (out.cc:146-152).
+                            // (src/io/out.cc:182), so every header after the first file carries base kind 8 (out.cc:146-152).  Not with
+                            // feature files in: htkOUT::save_frame's branch for them does not touch fea_kind (out.cc:177-179).
                             ctu_dims dh = d;
-                            if (o.fea_trap && b->pos + i > 0) dh.htk_kind = (d.htk_kind & ~077) | 8;
+                            if (o.fea_trap && !d.rows_in && b->pos + i > 0) dh.htk_kind = (d.htk_kind & ~077) | 8;
                             int64_t nr;
                             const float *r = rows_of(i, nr);
                             write_htk(it.fout, r, nr, dh);
@@ -829,7 +876,7 @@ int real_main(int argc, char **argv) {
                 for (int g = 0; g < ngpu; g++)
                     th.emplace_back([&, g] {
                         try {
-                            if (!b->sh[g].idx.empty()) run_shard(gpus[g].eng, b->sh[g], pool, signal_out, d.has_vad != 0, d.row_floats);
+                            if (!b->sh[g].idx.empty()) run_shard(gpus[g].eng, b->sh[g], pool, signal_out, d.rows_in != 0, d.has_vad != 0, d.row_floats);
                         } catch (...) {
                             errs[g] = std::current_exception();
                         }

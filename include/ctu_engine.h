@@ -60,6 +60,9 @@ typedef struct {
     int32_t swap_out;   /* caller must byte-swap on write (-endian_out big), src/io/opts.cc:287 */
     int32_t pcm_align;  /* utterance starts inside the packed PCM arena are multiples of this many samples */
     int32_t signal_out; /* -format_out raw|wave: the engine writes enhanced speech (ctu_engine_run_signal), no rows */
+    int32_t rows_in;    /* -format_in htk: runs start from rows of row_floats_in floats (ctu_engine_run_rows), src/io/batch.cc:57-60 */
+    int32_t row_floats_in; /* -nfeacoefs, src/io/in.cc:623-627 (0 unless rows_in) */
+    int32_t swap_in;    /* the input's byte order is not the host's (-endian_in big), src/io/opts.cc:286 */
 } ctu_dims;
 
 /* argv = the ctucopy command line without argv[0] (flags of src/io/opts.cc:644-846, incl. -C <file>).
@@ -125,6 +128,27 @@ void ctu_host_free(void *);
  * row nor a decision; the utterance's bytes in h_vad / d_vad are NUL then, '0' / '1' otherwise). */
 int ctu_engine_run_host(ctu_engine *, const ctu_plan *, const int16_t *h_pcm, float *h_rows, uint8_t *h_vad,
                         int64_t *rows_per_utt);
+
+/* ---- feature files in (-format_in htk): delta / stacking, CMS and CMVN on rows that already exist ---------------
+ * Replaces htkIN::get_frame (src/io/in.cc:691-709) and, behind it, what BATCH wires to in->_fvec (src/io/batch.cc:57-60,
+ * 217-220): the delta chain, cms_POST and the writers' copy (src/io/out.cc:177-179).  An engine created with -format_in htk
+ * starts its runs from rows: ctu_engine_run[_host] refuse it, and ctu_engine_run_rows[_host] refuse every other engine.
+ * -nfeacoefs is the width of the files' rows (htkIN's vector, in.cc:623-627); reading the 12-byte headers, checking
+ * sampSize / 4 against it and counting the whole rows a file really holds stay with the caller (bin/ctucopy does).
+ *
+ * Such an engine's plan takes ROW counts where ctu_plan_create says samples (ctu_num_frames is the identity) and its
+ * ctu_plan_sample_offsets() / ctu_plan_total_samples() are in 32-bit words of the input arena.  The arena holds every file's
+ * payload as it stands in the file - rows of `width` words in the file's byte order, -endian_in tells the engine which -
+ * at the offsets this pure function computes (no engine, no device; word_off may be NULL): multiples of four words
+ * (16 bytes), no padding around the arena.  Returns the arena's size in words, or a negative error code. */
+int64_t ctu_rows_arena_layout(const int64_t *utt_rows, int32_t n_utt, int32_t width, int64_t *word_off);
+/* Device-resident run: d_rows_in = the arena, d_rows = total_frames*row_floats floats.  Asynchronous on `stream`.  The rows
+ * come out in file order - the reference's writers do not rotate c0 in this mode - and ctu_cmvn_* work on them as ever,
+ * with statistic slot k = column k (src/fea/post_impl.cc:55-57). */
+int ctu_engine_run_rows(ctu_engine *, const ctu_plan *, const void *d_rows_in, float *d_rows, void *stream);
+/* Host-buffer convenience, like ctu_engine_run_host: page-locked buffers of at least 16 utterances and 32 MiB go in eight
+ * ranges on two streams (CTU_HOST_CHUNKS overrides), pageable ones through the runtime's staging.  Synchronised on return. */
+int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_in, float *h_rows);
 
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53
  * (alaw2lin, called from src/io/in.cc:481-560) bit for bit.  The caller lays the codes of an utterance at the same offsets
