@@ -80,6 +80,9 @@ struct DevBuf {
         n = count;
         if (n) HIP_TRY(hipMalloc(&p, n * sizeof(T)));
     }
+    void reserve(size_t count) {  // grows, never shrinks: a buffer kept from call to call
+        if (n < count) alloc(count);
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -222,6 +225,18 @@ struct ctu_plan {
 namespace {
 
 void set_error(ctu_engine *e, const std::string &m) { e->err = m; }
+
+// The frame of every call that reaches the device: what `body` returns, or CTU_ERR_DEVICE with "ENGINE: <what>" as the engine's
+// last error when it throws (HIP_TRY, DevBuf).
+template <class F>
+int guarded(ctu_engine *e, F &&body) {
+    try {
+        return body();
+    } catch (const std::exception &ex) {
+        set_error(e, std::string("ENGINE: ") + ex.what());
+        return CTU_ERR_DEVICE;
+    }
+}
 
 bool ss_eligible(const ctu::Design &d);
 bool ss_big_eligible(const ctu::Design &d);
@@ -1824,43 +1839,70 @@ int64_t ctu_rows_arena_layout(const int64_t *utt_rows, int32_t n_utt, int32_t wi
     return wo;  // rows_ingest_kernel reads an utterance's own words only: no padding around the arena
 }
 
-// The plan of an engine that starts from rows (-format_in htk): lengths are row counts, the arena is ctu_rows_arena_layout's, tiles
-// are what rows_ingest_kernel strides over (no chains), and what the delta / CMS / CMVN passes need is as in ctu_plan_create.
-static int plan_create_rows(ctu_engine *e, const int64_t *utt_rows, int32_t n_utt, ctu_plan **out) {
-    std::unique_ptr<ctu_plan> pl(new ctu_plan);
+namespace {
+// The host side of a plan between the three steps of ctu_plan_create: plan_layout fills it, plan_chains links the tiles, plan_alloc uploads it.
+struct PlanHost {
+    std::vector<TileRec> tiles;
+    std::vector<int> uts;       // first tile of every utterance, n_tiles at the end
+    std::vector<int4> uinfo;    // (first row: low, high word; frames; 0) of every utterance
+    std::vector<int> chunks;    // (utterance, first frame) of every 64-frame chunk
+    std::vector<int> wg_first;  // first tile of every chain (plan_chains)
+};
+
+// Step 1, host only, for both kinds of plan: where every utterance sits in the arena and in the rows, the refusals, its tiles and
+// 64-frame chunks, the totals.  The two kinds differ in the arena's layout rule, in what a length counts (ctu_num_frames: samples
+// against the rows themselves, -format_in htk), in the arena elements between two frames, and in a refusal each.
+int plan_layout(ctu_engine *e, ctu_plan *pl, const int64_t *utt_n, int32_t n_utt, PlanHost &h) {
+    static_assert(TILE == 64, "the chunk list of the TRAP / delta / CMS / CMVN passes (64 frames per workgroup) is the tile list");
     const ctu::Design &d = *e->design;
+    const bool rows = e->rows_in;
     pl->eng = e;
     pl->n_utt = n_utt;
-    pl->nsamples.assign(utt_rows, utt_rows + n_utt);
+    pl->nsamples.assign(utt_n, utt_n + n_utt);
     pl->sample_off.resize(n_utt + 1);
     pl->row_off.resize(n_utt + 1);
     pl->frames.resize(n_utt);
-    pl->total_samples = ctu_rows_arena_layout(utt_rows, n_utt, d.Dbase, pl->sample_off.data());
+    pl->total_samples = rows ? ctu_rows_arena_layout(utt_n, n_utt, d.Dbase, pl->sample_off.data()) : ctu_arena_layout(utt_n, n_utt, pl->sample_off.data());
     if (pl->total_samples < 0) {
         set_error(e, "ENGINE: negative utterance length");
         return CTU_ERR_INPUT;
     }
-    std::vector<TileRec> tiles;
-    std::vector<int4> uinfo(n_utt);
-    std::vector<int> chunks;
+    const int64_t stride = rows ? d.Dbase : d.wshift;  // arena elements from one frame to the next
     int wmax = 0;
     for (int j = 0; j < d.post_order; j++) wmax = std::max(wmax, d.post_w[j]);
+    h.uts.assign(n_utt + 1, 0);
+    h.uinfo.resize(n_utt);
+    std::vector<TileRec> tiles;  // local, moved into `h` behind the loop: pushing through `h` measured 3 % on plan creation (profiles/host_pipeline_ab.txt)
+    std::vector<int> chunks;
     int64_t ro = 0;
     for (int i = 0; i < n_utt; i++) {
-        const int64_t T = utt_rows[i];
-        if (T > 0x7fffffff / 2) {
+        const int64_t T = ctu_num_frames(e, utt_n[i]);
+        if (T < 0) {
+            set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277
+            return CTU_ERR_INPUT;
+        }
+        if (rows && T > 0x7fffffff / 2) {
             set_error(e, "ENGINE: feature file too long");
             return CTU_ERR_INPUT;
         }
-        if (d.post_order > 0 && T > 0 && T < wmax + 2) {  // as in ctu_plan_create
+        // With exactly window+1 frames a stage never takes its steady-state branch, so its flush starts from ring
+        // slot 0 instead of the oldest slot and the emitted rows mix frames (src/fea/fea_delta.cc:118,183-186);
+        // with fewer it reads slots that were never written.  Neither is a feature worth reproducing.
+        if (d.post_order > 0 && T > 0 && T < wmax + 2) {
             set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
             return CTU_ERR_INPUT;
         }
+        if (!rows && d.kind == ctu::FeaKind::TrapDct && T > 0 && T < (d.o.fea_trapdct_traplen + 1) / 2) {
+            set_error(e, "ENGINE: trapdct on fewer than (traplen+1)/2 frames is undefined in the reference (src/fea/fea_trap.cc:64-70)");
+            return CTU_ERR_INPUT;
+        }
+        const int64_t so = pl->sample_off[i];
         pl->row_off[i] = ro;
         pl->frames[i] = T;
+        h.uts[i] = (int)tiles.size();
         for (int64_t t0 = 0; t0 < T; t0 += TILE) {
             TileRec r;
-            r.sbase = pl->sample_off[i] + t0 * d.Dbase;
+            r.sbase = so + t0 * stride;
             r.rbase = ro + t0;
             r.nvalid = (int)std::min<int64_t>(TILE, T - t0);
             r.t0 = (int)t0;
@@ -1870,101 +1912,28 @@ static int plan_create_rows(ctu_engine *e, const int64_t *utt_rows, int32_t n_ut
             chunks.push_back(i);
             chunks.push_back((int)t0);
         }
-        uinfo[i] = make_int4((int)(ro & 0xffffffff), (int)(ro >> 32), (int)T, 0);
+        h.uinfo[i] = make_int4((int)(ro & 0xffffffff), (int)(ro >> 32), (int)T, 0);
         pl->max_frames = std::max<int>(pl->max_frames, (int)T);
         ro += T;
     }
+    h.uts[n_utt] = (int)tiles.size();
     pl->row_off[n_utt] = ro;
     pl->total_frames = ro;
     pl->n_tiles = (int)tiles.size();
-    pl->grid = std::max(1, std::min((pl->n_tiles + 3) / 4, e->n_cu * ROWS_WG_PER_CU));  // four waves = four tiles per workgroup pass
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        pl->tiles.upload(tiles);
-        pl->utt_info.upload(uinfo);
-        pl->trap_chunks.upload(chunks);
-        pl->n_trap_chunks = (int)chunks.size() / 2;
-        if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    *out = pl.release();
+    h.tiles = std::move(tiles);
+    h.chunks = std::move(chunks);
     return CTU_OK;
 }
 
-int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, ctu_plan **out) {
-    if (!e || !out || n_utt < 0 || (n_utt && !utt_nsamples)) return CTU_ERR_INPUT;
-    *out = nullptr;
-    if (e->rows_in) return plan_create_rows(e, utt_nsamples, n_utt, out);
-    std::unique_ptr<ctu_plan> pl(new ctu_plan);
-    pl->eng = e;
-    pl->n_utt = n_utt;
-    pl->nsamples.assign(utt_nsamples, utt_nsamples + n_utt);
-    pl->sample_off.resize(n_utt + 1);
-    pl->row_off.resize(n_utt + 1);
-    pl->frames.resize(n_utt);
-    const ctu::Design &d = *e->design;
-    int64_t ro = 0;
-    pl->total_samples = ctu_arena_layout(utt_nsamples, n_utt, pl->sample_off.data());
-    if (pl->total_samples < 0) {
-        set_error(e, "ENGINE: negative utterance length");
-        return CTU_ERR_INPUT;
-    }
-    std::vector<TileRec> tiles;
-    std::vector<int> uts(n_utt + 1, 0);
-    std::vector<int4> uinfo(n_utt);
-    std::vector<int> chunks;
-    const int trap_chunk = 64;  // output frames per TRAP workgroup
-    for (int i = 0; i < n_utt; i++) {
-        const int64_t T = ctu_num_frames(e, utt_nsamples[i]);
-        if (T < 0) {
-            set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277
-            return CTU_ERR_INPUT;
-        }
-        if (d.post_order > 0 && T > 0) {
-            int wmax = 0;
-            for (int j = 0; j < d.post_order; j++) wmax = std::max(wmax, d.post_w[j]);
-            // With exactly window+1 frames a stage never takes its steady-state branch, so its flush starts from ring
-            // slot 0 instead of the oldest slot and the emitted rows mix frames (src/fea/fea_delta.cc:118,183-186);
-            // with fewer it reads slots that were never written.  Neither is a feature worth reproducing.
-            if (T < wmax + 2) {
-                set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
-                return CTU_ERR_INPUT;
-            }
-        }
-        if (d.kind == ctu::FeaKind::TrapDct && T > 0 && T < (d.o.fea_trapdct_traplen + 1) / 2) {
-            set_error(e, "ENGINE: trapdct on fewer than (traplen+1)/2 frames is undefined in the reference (src/fea/fea_trap.cc:64-70)");
-            return CTU_ERR_INPUT;
-        }
-        const int64_t so = pl->sample_off[i];
-        pl->row_off[i] = ro;
-        pl->frames[i] = T;
-        uts[i] = (int)tiles.size();
-        for (int64_t t0 = 0; t0 < T; t0 += TILE) {
-            TileRec r;
-            r.sbase = so + t0 * d.wshift;
-            r.rbase = ro + t0;
-            r.nvalid = (int)std::min<int64_t>(TILE, T - t0);
-            r.t0 = (int)t0;
-            r.next = -1;
-            r.T = (int)T;
-            tiles.push_back(r);
-        }
-        uinfo[i] = make_int4((int)(ro & 0xffffffff), (int)(ro >> 32), (int)T, 0);
-        for (int64_t tc = 0; tc < T; tc += trap_chunk) {
-            chunks.push_back(i);
-            chunks.push_back((int)tc);
-        }
-        ro += T;
-    }
-    uts[n_utt] = (int)tiles.size();
-    pl->row_off[n_utt] = ro;
-    pl->total_frames = ro;
-    pl->n_tiles = (int)tiles.size();
-    // Each workgroup walks a chain of tiles.  Stateless chains stride over the tile list; with a
-    // per-utterance recurrence (exten) a workgroup takes whole utterances, tile after tile.
-    std::vector<int> wg_first;
+// Step 2, host only, for plans over samples: the chains the front end walks and the grid they are built for.  (A plan over rows has
+// no chains: rows_ingest_kernel strides over the tile list.)
+// Each workgroup walks a chain of tiles.  Stateless chains stride over the tile list; with a
+// per-utterance recurrence (exten) a workgroup takes whole utterances, tile after tile.
+void plan_chains(const ctu_engine *e, ctu_plan *pl, PlanHost &h) {
+    std::vector<TileRec> &tiles = h.tiles;
+    const std::vector<int> &uts = h.uts;
+    std::vector<int> &wg_first = h.wg_first;
+    const int n_utt = pl->n_utt;
     // workgroups that fit a CU at once: two when the instantiation keeps to 128 VGPRs (four waves per SIMD) and 80 KB of LDS; the synthesis
     // and the 512-point detector instantiations take 256 VGPRs
     const FeSel &k = e->sel;
@@ -2003,90 +1972,107 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
         for (int g = 0; g < G && g < pl->n_tiles; g++) wg_first[g] = g;
         pl->grid = G;
     }
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        pl->tiles.upload(tiles);
-        pl->wg_first.upload(wg_first);
-        if (e->ss) {
-            std::vector<int> tu(tiles.size());
-            for (int i = 0; i < n_utt; i++)
-                for (int t = uts[i]; t < uts[i + 1]; t++) tu[t] = i;
-            pl->tile_utt.upload(tu);
-            pl->ss_seed.alloc((size_t)std::max(n_utt, 1) * d.K);
-            pl->ss_last.alloc((size_t)std::max(n_utt, 1) * d.K);
-            pl->ss_dirty.alloc((size_t)std::max(n_utt, 1));
-            pl->ss_vbits.alloc((size_t)std::max<int64_t>(ro, 1));
-            if (e->big) {  // bigss_kernel.h: the exported spectra, the detector's cepstra, on the speech path the subtracted magnitudes
-                pl->xri.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-                pl->pnr.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-                if (synth_reads_pss(e)) pl->pss.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-                if (!e->ss_file) {
-                    pl->vad_ci.alloc((size_t)std::max<int64_t>(ro, 1) * d.o.fea_ncepcoefs);
-                    pl->d_row_off.upload(pl->row_off);
-                }
-            }
+}
+
+// Step 3, the device side: the uploads and the scratch of every stage the engine's runs have.  Throws (ctu_plan_create's frame).
+void plan_alloc(ctu_engine *e, ctu_plan *pl, const PlanHost &h) {
+    const ctu::Design &d = *e->design;
+    const int n_utt = pl->n_utt;
+    const int64_t ro = pl->total_frames;
+    HIP_TRY(hipSetDevice(e->device));
+    pl->tiles.upload(h.tiles);
+    // the passes that run a workgroup per 64-frame chunk (TRAP, delta / stacking, CMS, CMVN); a plan over rows has the list in any case
+    const bool chunked = e->rows_in || d.kind == ctu::FeaKind::TrapDct || d.post_order > 0 || d.cms || d.o.stat_cmvn || d.o.apply_cmvn;
+    const bool per_utt = !e->rows_in && (d.signal_out || d.o.remove_dc1);  // the overlap-add and the -remove_dc1 recurrence go by utterance
+    if (chunked || per_utt) pl->utt_info.upload(h.uinfo);
+    if (chunked) {
+        pl->trap_chunks.upload(h.chunks);
+        pl->n_trap_chunks = (int)h.chunks.size() / 2;
+    }
+    if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
+    if (e->rows_in) return;  // what follows serves the front end and the stages that read its scratch
+    pl->wg_first.upload(h.wg_first);
+    if (per_utt) pl->d_sample_off.upload(std::vector<long long>(pl->sample_off.begin(), pl->sample_off.end()));
+    if (e->do_vad || (e->ss && e->big && !e->ss_file)) pl->d_row_off.upload(pl->row_off);
+    if (e->ss) {
+        std::vector<int> tu(h.tiles.size());
+        for (int i = 0; i < n_utt; i++)
+            for (int t = h.uts[i]; t < h.uts[i + 1]; t++) tu[t] = i;
+        pl->tile_utt.upload(tu);
+        pl->ss_seed.alloc((size_t)std::max(n_utt, 1) * d.K);
+        pl->ss_last.alloc((size_t)std::max(n_utt, 1) * d.K);
+        pl->ss_dirty.alloc((size_t)std::max(n_utt, 1));
+        pl->ss_vbits.alloc((size_t)std::max<int64_t>(ro, 1));
+        if (e->big) {  // bigss_kernel.h: the exported spectra, the detector's cepstra, on the speech path the subtracted magnitudes
+            pl->xri.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+            pl->pnr.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+            if (synth_reads_pss(e)) pl->pss.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
+            if (!e->ss_file) pl->vad_ci.alloc((size_t)std::max<int64_t>(ro, 1) * d.o.fea_ncepcoefs);
         }
-        if (e->do_vad) {
-            pl->d_row_off.upload(pl->row_off);
-            if (e->vp.cri == 1) {
-                if (!e->vf) {
-                    pl->xri.alloc((size_t)ro * d.K);
-                    pl->pnr.alloc((size_t)ro * d.K);
-                }
-                if (!e->vf) pl->vad_ci.alloc((size_t)ro * e->vp.ncoef);
-                else {
-                    pl->vad_cf.alloc((size_t)std::max<int64_t>(ro, 1) * VFC_STRIDE);
-                    std::vector<int> ord;
-                    for (int i = 0; i < n_utt; i++)
-                        if (pl->frames[i] > 0) ord.push_back(i);
-                    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return pl->frames[a] > pl->frames[b]; });
-                    pl->n_live = (int)ord.size();
-                    if (ord.empty()) ord.push_back(0);
-                    pl->vf_order.upload(ord);
-                }
-            } else if (e->vp.cri == 0) pl->pnr.alloc((size_t)ro);
-        }
-        if (d.signal_out) {
-            if (!e->sy && !synth_reads_pss(e)) {  // (with pss the *ss block above has allocated the exported spectra)
+    }
+    if (e->do_vad) {
+        if (e->vp.cri == 1) {
+            if (!e->vf) {
                 pl->xri.alloc((size_t)ro * d.K);
                 pl->pnr.alloc((size_t)ro * d.K);
             }
-            pl->utt_info.upload(uinfo);
-            std::vector<long long> so64(pl->sample_off.begin(), pl->sample_off.end());
-            pl->d_sample_off.upload(so64);
-            pl->out_samples.resize(n_utt);
-            for (int i = 0; i < n_utt; i++) pl->out_samples[i] = pl->frames[i] * d.wshift + (d.window - d.wshift);
-            pl->ybuf.alloc((size_t)ro * d.window);
-        }
-        for (int i = 0; i < n_utt; i++) pl->max_frames = std::max<int>(pl->max_frames, (int)pl->frames[i]);
-        if (d.o.remove_dc1) {
-            pl->utt_info.upload(uinfo);
-            std::vector<long long> so64(pl->sample_off.begin(), pl->sample_off.end());
-            pl->d_sample_off.upload(so64);
-            pl->dc1m.alloc((size_t)std::max<int64_t>(ro, 1));
-            pl->dc1.alloc((size_t)std::max<int64_t>(ro, 1));
-        }
-        if (d.kind == ctu::FeaKind::TrapDct || d.post_order > 0 || d.cms || d.o.stat_cmvn || d.o.apply_cmvn) {
-            pl->utt_info.upload(uinfo);
-            pl->trap_chunks.upload(chunks);
-            pl->n_trap_chunks = (int)chunks.size() / 2;
-            std::vector<int> c128;
-            for (size_t k = 0; k + 1 < chunks.size(); k += 2)
-                if (!(chunks[k + 1] & 64)) {
-                    c128.push_back(chunks[k]);
-                    c128.push_back(chunks[k + 1]);
-                }
-            pl->n_trap_chunks128 = (int)c128.size() / 2;
-            if (c128.empty()) c128.assign(2, 0);
-            pl->trap_chunks128.upload(c128);
-        }
-        if (d.kind == ctu::FeaKind::TrapDct) pl->logmel.alloc((size_t)ro * d.B);
-        if (lp_tail_runs(e)) pl->lp_r.alloc(((size_t)std::max<int64_t>(ro, 1) * (d.o.fea_lporder + 1) * (lags_double(e) ? 8 : 4) + 7) / 8);
-        if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
+            if (!e->vf) pl->vad_ci.alloc((size_t)ro * e->vp.ncoef);
+            else {
+                pl->vad_cf.alloc((size_t)std::max<int64_t>(ro, 1) * VFC_STRIDE);
+                std::vector<int> ord;
+                for (int i = 0; i < n_utt; i++)
+                    if (pl->frames[i] > 0) ord.push_back(i);
+                std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return pl->frames[a] > pl->frames[b]; });
+                pl->n_live = (int)ord.size();
+                if (ord.empty()) ord.push_back(0);
+                pl->vf_order.upload(ord);
+            }
+        } else if (e->vp.cri == 0) pl->pnr.alloc((size_t)ro);
     }
+    if (d.signal_out) {
+        if (!e->sy && !synth_reads_pss(e)) {  // (with pss the *ss block above has allocated the exported spectra)
+            pl->xri.alloc((size_t)ro * d.K);
+            pl->pnr.alloc((size_t)ro * d.K);
+        }
+        pl->out_samples.resize(n_utt);
+        for (int i = 0; i < n_utt; i++) pl->out_samples[i] = pl->frames[i] * d.wshift + (d.window - d.wshift);
+        pl->ybuf.alloc((size_t)ro * d.window);
+    }
+    if (d.o.remove_dc1) {
+        pl->dc1m.alloc((size_t)std::max<int64_t>(ro, 1));
+        pl->dc1.alloc((size_t)std::max<int64_t>(ro, 1));
+    }
+    if (chunked) {  // the 128-frame chunks (trapdct_split16_kernel): every other 64-frame one
+        std::vector<int> c128;
+        for (size_t k = 0; k + 1 < h.chunks.size(); k += 2)
+            if (!(h.chunks[k + 1] & 64)) {
+                c128.push_back(h.chunks[k]);
+                c128.push_back(h.chunks[k + 1]);
+            }
+        pl->n_trap_chunks128 = (int)c128.size() / 2;
+        if (c128.empty()) c128.assign(2, 0);
+        pl->trap_chunks128.upload(c128);
+    }
+    if (d.kind == ctu::FeaKind::TrapDct) pl->logmel.alloc((size_t)ro * d.B);
+    if (lp_tail_runs(e)) pl->lp_r.alloc(((size_t)std::max<int64_t>(ro, 1) * (d.o.fea_lporder + 1) * (lags_double(e) ? 8 : 4) + 7) / 8);
+}
+}  // namespace
+
+// The plan of an engine that starts from rows (-format_in htk) takes row counts as lengths and lays its arena out by
+// ctu_rows_arena_layout; its tiles are what rows_ingest_kernel strides over, four (one per wave) to a workgroup pass.
+int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, ctu_plan **out) {
+    if (!e || !out || n_utt < 0 || (n_utt && !utt_nsamples)) return CTU_ERR_INPUT;
+    *out = nullptr;
+    std::unique_ptr<ctu_plan> pl(new ctu_plan);
+    PlanHost h;
+    if (const int rc = plan_layout(e, pl.get(), utt_nsamples, n_utt, h); rc != CTU_OK) return rc;
+    if (e->rows_in) pl->grid = std::max(1, std::min((pl->n_tiles + 3) / 4, e->n_cu * ROWS_WG_PER_CU));
+    else plan_chains(e, pl.get(), h);
+    const int rc = guarded(e, [&]() -> int {
+        plan_alloc(e, pl.get(), h);
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) return rc;
     *out = pl.release();
     return CTU_OK;
 }
@@ -2152,7 +2138,7 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
     bool any = false;
     for (int i = 0; i < pl->n_utt; i++) any = any || (hidx[i] % order) != 0;
     if (!any) return CTU_OK;
-    try {
+    const int rc = guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         pl->ring_hidx.assign(hidx, hidx + pl->n_utt);
         std::vector<int> src((size_t)std::max<int64_t>(pl->total_frames, 1), -1);
@@ -2165,13 +2151,11 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
             for (int64_t k = 0; k < T; k++) src[(size_t)(r0 + k)] = rel[(size_t)k] < 0 ? -1 : (int)(r0 + rel[(size_t)k]);
         }
         pl->ring_src.upload(src);
-        if (pl->ring_tmp.n < (size_t)std::max<int64_t>(pl->total_frames, 1) * d.D) pl->ring_tmp.alloc((size_t)std::max<int64_t>(pl->total_frames, 1) * d.D);
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        pl->ring_hidx.clear();
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        pl->ring_tmp.reserve((size_t)std::max<int64_t>(pl->total_frames, 1) * d.D);
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) pl->ring_hidx.clear();  // a plan without its ring is in phase
+    return rc;
 }
 
 int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream) {
@@ -2192,13 +2176,13 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
         return CTU_ERR_INPUT;
     }
     hipStream_t s = (hipStream_t)stream;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         KParams kp = run_kparams(e, pl, d_pcm, d_rows);
         const BigParams bp = e->big ? run_bigparams(e, pl, kp) : BigParams{};
         const int grid = pl->grid;
 #if CTU_STAMP
-        if (e->stamps.n < (size_t)grid * NWAVE * 16) e->stamps.alloc((size_t)grid * NWAVE * 16);
+        e->stamps.reserve((size_t)grid * NWAVE * 16);
         HIP_TRY(hipMemsetAsync(e->stamps.p, 0, e->stamps.n * 8, s));
         kp.stamps = e->stamps.p;
 #endif
@@ -2232,11 +2216,8 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
         if (e->do_vad && !e->vf) stage_vad_decide(e, pl, s, d_rows, d_vad);
         if (e->do_vad && d.o.vad_filter_order > 1) stage_short_files(e, pl, s, d_vad);
         if (e->do_vad && !pl->ring_hidx.empty() && pl->total_frames > 0) stage_ring_gather(e, pl, s, d_rows);
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 void *ctu_host_alloc(size_t bytes) {
@@ -2289,17 +2270,118 @@ int split_host_parts(ctu_engine *e, ctu_plan *pl, int nparts) {
     pl->parts_for = nparts;
     return CTU_OK;
 }
-}  // namespace
-
-// How many utterance ranges a host-buffer run is cut into: CTU_HOST_CHUNKS if set (1 = one range), else 8 for batches of
-// at least 16 utterances and 32 MiB of PCM in page-locked buffers.  Modes whose state crosses utterances (the *ss noise seed) stay in one range.
-static int host_chunks(const ctu_engine *e, const ctu_plan *pl, bool pinned) {
+// How many utterance ranges a host-buffer run is cut into - the one home of the rule: CTU_HOST_CHUNKS if set (1 = one range), else 8
+// for batches of at least 16 utterances and 32 MiB of input (16 Mi samples, 8 Mi words of feature files) with both buffers page-locked.
+// Modes whose state crosses utterances (the *ss noise seed) stay in one range; an engine over rows (-format_in htk) refuses the NR
+// options, so e->ss is 0 there.
+int host_chunks(const ctu_engine *e, const ctu_plan *pl, int64_t input_bytes, bool pinned) {
     if (e->ss) return 1;
     // pageable buffers go through blocking staged copies: cutting those up only adds calls (measured 1.04e8 -> 0.96e8 frames/s)
-    int k = (pinned && pl->n_utt >= 16 && pl->total_samples >= (int64_t)16 << 20) ? 8 : 1;
+    int k = (pinned && pl->n_utt >= 16 && input_bytes >= (int64_t)32 << 20) ? 8 : 1;
     if (const char *v = getenv("CTU_HOST_CHUNKS")) k = std::max(1, atoi(v));
     return std::min(k, std::max(1, pl->n_utt));
 }
+
+// What a host-buffer run feeds run_host_ranges: the caller's arena and how a (sub)plan stages and runs its share of it.
+struct HostInput {
+    const void *base;   // the caller's arena
+    size_t elem;        // bytes per element of it: an int16 sample or a 32-bit word of a feature file
+    int64_t head;       // elements ahead of the first utterance that belong to a plan's arena (PCM_HEAD; a plan over rows has none)
+    std::function<void *(ctu_plan *)> stage;          // the device copy of a (sub)plan's arena, grown to hold it (with what else its run needs)
+    std::function<int(ctu_plan *, hipStream_t)> run;  // the device run of a (sub)plan from its staged arena into its h_rows
+    // with the VAD only (else empty): hands a range, which starts at utterance `first`, its share of the caller's majority-filter ring ...
+    std::function<int(ctu_plan *sub, int first)> ring;
+    std::function<void(const ctu_plan *, int64_t row0)> vad;  // ... and fetches a finished (sub)plan's bytes, which start at row `row0`
+};
+
+// (start, stop) of every range's front-end launch; destroyed on every way out of the run
+struct RangeEvents {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    ~RangeEvents() {
+        for (auto &pe : ev) {
+            if (pe.first) (void)hipEventDestroy(pe.first);
+            if (pe.second) (void)hipEventDestroy(pe.second);
+        }
+    }
+    void take(ctu_engine *e) {  // the engine's pair is re-recorded by every range: keep the recorded pair, leave a fresh one
+        ev.emplace_back(nullptr, nullptr);
+        HIP_TRY(hipEventCreate(&ev.back().first));
+        HIP_TRY(hipEventCreate(&ev.back().second));
+        std::swap(ev.back().first, e->ev0);
+        std::swap(ev.back().second, e->ev1);
+    }
+    float sum_ms() const {
+        float sum = 0.f, ms = 0.f;
+        for (auto &pe : ev)
+            if (hipEventElapsedTime(&ms, pe.first, pe.second) == hipSuccess) sum += ms;
+        return sum;
+    }
+};
+
+// The host-buffer run (ctu_engine_run_host, ctu_engine_run_rows_host): upload, device run, download; in ranges on two streams when
+// host_chunks says so, else the whole plan on the default stream - the same walk with one part.  Device buffers are allocated once
+// per plan (per part).  Transfers: a caller buffer from ctu_host_alloc (pinned) is DMA-ed asynchronously at the link rate; pageable
+// memory goes through the runtime's own staging (hipMemcpy).  Throws (the caller's frame); a refusal of `run` or `ring` is returned.
+int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_rows) {
+    const int D = e->design->D;
+    HIP_TRY(hipSetDevice(e->device));
+    const bool pin_in = is_pinned(in.base), pin_out = is_pinned(h_rows);
+    const int nparts = host_chunks(e, pl, pl->total_samples * (int64_t)in.elem, pin_in && pin_out);
+    if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
+    const bool ranges = nparts > 1 && pl->parts.size() > 1;
+    const int np = ranges ? (int)pl->parts.size() : 1;
+    auto part = [&](int k) { return ranges ? pl->parts[k].get() : pl; };
+    auto first = [&](int k) { return ranges ? pl->part_first[k] : 0; };
+    const hipStream_t st[2] = {ranges ? pl->part_stream[0] : nullptr, ranges ? pl->part_stream[1] : nullptr};
+    RangeEvents events;
+    auto download = [&](int k) {
+        ctu_plan *sp = part(k);
+        if (sp->total_frames == 0) return;
+        float *dst = h_rows + pl->row_off[first(k)] * D;
+        if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->total_frames * D * 4, hipMemcpyDeviceToHost, st[k & 1]));
+        else {
+            HIP_TRY(hipStreamSynchronize(st[k & 1]));
+            HIP_TRY(hipMemcpy(dst, sp->h_rows.p, (size_t)sp->total_frames * D * 4, hipMemcpyDeviceToHost));
+        }
+    };
+    for (int k = 0; k < np; k++) {
+        ctu_plan *sp = part(k);
+        if (ranges && in.ring) {  // a range is a plan of its own: it starts its utterances where the caller's plan does
+            const int rc = in.ring(sp, first(k));
+            if (rc != CTU_OK) return rc;
+        }
+        if (sp->total_frames) {
+            void *d_in = in.stage(sp);
+            sp->h_rows.reserve((size_t)sp->total_frames * D);
+            // a part's arena is the slice of the caller's that starts `head` elements ahead of its first utterance (split_host_parts)
+            const char *src = static_cast<const char *>(in.base) + (pl->sample_off[first(k)] - in.head) * (int64_t)in.elem;
+            if (pin_in) HIP_TRY(hipMemcpyAsync(d_in, src, (size_t)sp->total_samples * in.elem, hipMemcpyHostToDevice, st[k & 1]));
+            else HIP_TRY(hipMemcpy(d_in, src, (size_t)sp->total_samples * in.elem, hipMemcpyHostToDevice));
+            const int rc = in.run(sp, st[k & 1]);
+            if (rc != CTU_OK) {  // earlier ranges are still in flight on the two streams: drain them before the caller reuses its buffers
+                if (ranges) {
+                    (void)hipStreamSynchronize(st[0]);
+                    (void)hipStreamSynchronize(st[1]);
+                }
+                return rc;
+            }
+            if (ranges) events.take(e);  // (one range: the engine's own pair is the time of the run)
+        }
+        if (k > 0) download(k - 1);  // behind the launch of part k: the copy engines and the kernels overlap
+    }
+    download(np - 1);
+    if (ranges || pin_out) HIP_TRY(hipStreamSynchronize(st[0]));  // (one range into pageable rows has waited in download)
+    if (ranges) {
+        HIP_TRY(hipStreamSynchronize(st[1]));
+        e->host_kernel_ms = events.sum_ms();  // ctu_engine_last_kernel_ms after a host run in ranges
+        e->host_timed = true;
+    }
+    if (in.vad)
+        for (int k = 0; k < np; k++)
+            if (part(k)->total_frames) in.vad(part(k), pl->row_off[first(k)]);
+    return CTU_OK;
+}
+}  // namespace
 
 int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm, float *h_rows, uint8_t *h_vad,
                         int64_t *rows_per_utt) {
@@ -2313,94 +2395,24 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
     if (rows_per_utt)
         for (int i = 0; i < pl->n_utt; i++) rows_per_utt[i] = pl->frames[i];
     if (pl->total_frames == 0) return CTU_OK;
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        // Device buffers are allocated once per plan (per part).  Transfers: a caller buffer from ctu_host_alloc (pinned) is
-        // DMA-ed asynchronously at the link rate; pageable memory goes through the runtime's own staging (hipMemcpy).
-        const bool pin_in = is_pinned(h_pcm), pin_out = is_pinned(h_rows);
-        const int nparts = host_chunks(e, pl, pin_in && pin_out);
-        if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
+    if (!h_pcm || !h_rows) {
+        set_error(e, "ENGINE: null host buffer");
+        return CTU_ERR_INPUT;
+    }
+    return guarded(e, [&]() -> int {
         std::vector<uint8_t> v(e->do_vad ? (size_t)pl->total_frames : 0);
-        if (nparts > 1 && pl->parts.size() > 1) {
-            const int np = (int)pl->parts.size();
-            std::vector<std::pair<hipEvent_t, hipEvent_t>> part_events;  // (start, stop) of every range's front-end launch
-            auto download = [&](int k) {
-                ctu_plan *sp = pl->parts[k].get();
-                if (sp->total_frames == 0) return;
-                hipStream_t st = pl->part_stream[k & 1];
-                float *dst = h_rows + pl->row_off[pl->part_first[k]] * d.D;
-                if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->total_frames * d.D * 4, hipMemcpyDeviceToHost, st));
-                else {
-                    HIP_TRY(hipStreamSynchronize(st));
-                    HIP_TRY(hipMemcpy(dst, sp->h_rows.p, (size_t)sp->total_frames * d.D * 4, hipMemcpyDeviceToHost));
-                }
-            };
-            for (int k = 0; k < np; k++) {
-                ctu_plan *sp = pl->parts[k].get();
-                hipStream_t st = pl->part_stream[k & 1];
-                if (e->do_vad) {  // a range is a plan of its own: it starts its utterances where the caller's plan does
-                    const int rc = ctu_plan_set_vad_ring(sp, pl->ring_hidx.empty() ? nullptr : pl->ring_hidx.data() + pl->part_first[k]);
-                    if (rc != CTU_OK) return rc;
-                }
-                if (sp->total_frames) {
-                    if (sp->h_pcm.n < (size_t)sp->total_samples) sp->h_pcm.alloc((size_t)sp->total_samples);
-                    if (sp->h_rows.n < (size_t)sp->total_frames * d.D) sp->h_rows.alloc((size_t)sp->total_frames * d.D);
-                    if (e->do_vad && sp->h_vad.n < (size_t)sp->total_frames) sp->h_vad.alloc((size_t)sp->total_frames);
-                    const int16_t *src = h_pcm + (pl->sample_off[pl->part_first[k]] - PCM_HEAD);
-                    if (pin_in) HIP_TRY(hipMemcpyAsync(sp->h_pcm.p, src, (size_t)sp->total_samples * 2, hipMemcpyHostToDevice, st));
-                    else HIP_TRY(hipMemcpy(sp->h_pcm.p, src, (size_t)sp->total_samples * 2, hipMemcpyHostToDevice));
-                    const int rc = ctu_engine_run(e, sp, sp->h_pcm.p, sp->h_rows.p, sp->h_vad.p, st);
-                    if (rc != CTU_OK) {  // earlier ranges are still in flight on the two streams: drain them before the caller reuses its buffers
-                        (void)hipStreamSynchronize(pl->part_stream[0]);
-                        (void)hipStreamSynchronize(pl->part_stream[1]);
-                        for (auto &pe : part_events) {
-                            (void)hipEventDestroy(pe.first);
-                            (void)hipEventDestroy(pe.second);
-                        }
-                        return rc;
-                    }
-                    // the engine's event pair is re-recorded by every range: keep the sum (ctu_engine_last_kernel_ms after a host run)
-                    part_events.emplace_back();
-                    HIP_TRY(hipEventCreate(&part_events.back().first));
-                    HIP_TRY(hipEventCreate(&part_events.back().second));
-                    std::swap(part_events.back().first, e->ev0);
-                    std::swap(part_events.back().second, e->ev1);
-                }
-                if (k > 0) download(k - 1);  // behind the launch of part k: the copy engines and the kernels overlap
-            }
-            download(np - 1);
-            HIP_TRY(hipStreamSynchronize(pl->part_stream[0]));
-            HIP_TRY(hipStreamSynchronize(pl->part_stream[1]));
-            e->host_kernel_ms = 0.f;
-            for (auto &pe : part_events) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, pe.first, pe.second) == hipSuccess) e->host_kernel_ms += ms;
-                (void)hipEventDestroy(pe.first);
-                (void)hipEventDestroy(pe.second);
-            }
-            e->host_timed = true;
-            if (e->do_vad)
-                for (int k = 0; k < np; k++)
-                    if (pl->parts[k]->total_frames)
-                        HIP_TRY(hipMemcpy(v.data() + pl->row_off[pl->part_first[k]], pl->parts[k]->h_vad.p, (size_t)pl->parts[k]->total_frames, hipMemcpyDeviceToHost));
-        } else {
-            if (pl->h_pcm.n < (size_t)pl->total_samples) pl->h_pcm.alloc((size_t)pl->total_samples);
-            if (pl->h_rows.n < (size_t)pl->total_frames * d.D) pl->h_rows.alloc((size_t)pl->total_frames * d.D);
-            if (e->do_vad && pl->h_vad.n < (size_t)pl->total_frames) pl->h_vad.alloc((size_t)pl->total_frames);
-            hipStream_t s = nullptr;
-            if (pin_in) HIP_TRY(hipMemcpyAsync(pl->h_pcm.p, h_pcm, (size_t)pl->total_samples * 2, hipMemcpyHostToDevice, s));
-            else HIP_TRY(hipMemcpy(pl->h_pcm.p, h_pcm, (size_t)pl->total_samples * 2, hipMemcpyHostToDevice));
-            int rc = ctu_engine_run(e, pl, pl->h_pcm.p, pl->h_rows.p, pl->h_vad.p, s);
-            if (rc != CTU_OK) return rc;
-            if (pin_out) {
-                HIP_TRY(hipMemcpyAsync(h_rows, pl->h_rows.p, (size_t)pl->total_frames * d.D * 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            } else {
-                HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(hipMemcpy(h_rows, pl->h_rows.p, (size_t)pl->total_frames * d.D * 4, hipMemcpyDeviceToHost));
-            }
-            if (e->do_vad) HIP_TRY(hipMemcpy(v.data(), pl->h_vad.p, v.size(), hipMemcpyDeviceToHost));
+        HostInput in{h_pcm, sizeof(int16_t), PCM_HEAD};
+        in.stage = [&](ctu_plan *p) {
+            p->h_pcm.reserve((size_t)p->total_samples);
+            if (e->do_vad) p->h_vad.reserve((size_t)p->total_frames);
+            return p->h_pcm.p;
+        };
+        in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run(e, p, p->h_pcm.p, p->h_rows.p, p->h_vad.p, s); };
+        if (e->do_vad) {
+            in.ring = [&](ctu_plan *sub, int first) { return ctu_plan_set_vad_ring(sub, pl->ring_hidx.empty() ? nullptr : pl->ring_hidx.data() + first); };
+            in.vad = [&](const ctu_plan *p, int64_t row0) { HIP_TRY(hipMemcpy(v.data() + row0, p->h_vad.p, (size_t)p->total_frames, hipMemcpyDeviceToHost)); };
         }
+        if (const int rc = run_host_ranges(e, pl, in, h_rows); rc != CTU_OK) return rc;
         if (e->do_vad) {
             if (h_vad) std::memcpy(h_vad, v.data(), v.size());
             if (d.o.vad_apply_mode == "drop") {
@@ -2422,11 +2434,8 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
                     if (pl->frames[i] <= delay) rows_per_utt[i] = 0;
             }
         }
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 // ---- runs that start from rows (-format_in htk) ------------------------------------------------------------------------------
@@ -2444,7 +2453,7 @@ int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in
     }
     const ctu::Design &d = *e->design;
     hipStream_t s = (hipStream_t)stream;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         const bool staged = d.post_order > 0 || d.cms;  // the passes behind read the plan's base rows, else the ingest writes the caller's
         uint32_t *dst = reinterpret_cast<uint32_t *>(staged ? pl->base_rows.p : d_rows);
@@ -2461,11 +2470,8 @@ int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in
         HIP_TRY(hipGetLastError());
         if (d.post_order > 0) stage_post(e, pl, s, d_rows);
         if (d.cms) stage_cms(e, pl, s, d_rows);
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 int ctu_engine_run_rows_host(ctu_engine *e, const ctu_plan *pl_, const void *h_rows_in, float *h_rows) {
@@ -2475,97 +2481,20 @@ int ctu_engine_run_rows_host(ctu_engine *e, const ctu_plan *pl_, const void *h_r
         return CTU_ERR_INPUT;
     }
     ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
-    const ctu::Design &d = *e->design;
     if (pl->total_frames == 0) return CTU_OK;
     if (!h_rows_in || !h_rows) {
         set_error(e, "ENGINE: null host buffer");
         return CTU_ERR_INPUT;
     }
-    const uint32_t *h_in = static_cast<const uint32_t *>(h_rows_in);
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        const bool pin_in = is_pinned(h_rows_in), pin_out = is_pinned(h_rows);
-        // ranges as in ctu_engine_run_host: eight for at least 16 utterances and 32 MiB of input in page-locked buffers, CTU_HOST_CHUNKS overrides
-        int nparts = (pin_in && pin_out && pl->n_utt >= 16 && pl->total_samples >= (int64_t)8 << 20) ? 8 : 1;
-        if (const char *v = getenv("CTU_HOST_CHUNKS")) nparts = std::max(1, atoi(v));
-        nparts = std::min(nparts, std::max(1, pl->n_utt));
-        if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
-        if (nparts > 1 && pl->parts.size() > 1) {
-            const int np = (int)pl->parts.size();
-            std::vector<std::pair<hipEvent_t, hipEvent_t>> part_events;  // (start, stop) of every range's ingest launch
-            auto drain = [&] {
-                (void)hipStreamSynchronize(pl->part_stream[0]);
-                (void)hipStreamSynchronize(pl->part_stream[1]);
-            };
-            auto download = [&](int k) {
-                ctu_plan *sp = pl->parts[k].get();
-                if (sp->total_frames == 0) return;
-                hipStream_t st = pl->part_stream[k & 1];
-                float *dst = h_rows + pl->row_off[pl->part_first[k]] * d.D;
-                if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->total_frames * d.D * 4, hipMemcpyDeviceToHost, st));
-                else {
-                    HIP_TRY(hipStreamSynchronize(st));
-                    HIP_TRY(hipMemcpy(dst, sp->h_rows.p, (size_t)sp->total_frames * d.D * 4, hipMemcpyDeviceToHost));
-                }
-            };
-            for (int k = 0; k < np; k++) {
-                ctu_plan *sp = pl->parts[k].get();
-                hipStream_t st = pl->part_stream[k & 1];
-                if (sp->total_frames) {
-                    if (sp->h_words.n < (size_t)sp->total_samples) sp->h_words.alloc((size_t)sp->total_samples);
-                    if (sp->h_rows.n < (size_t)sp->total_frames * d.D) sp->h_rows.alloc((size_t)sp->total_frames * d.D);
-                    const uint32_t *src = h_in + pl->sample_off[pl->part_first[k]];
-                    if (pin_in) HIP_TRY(hipMemcpyAsync(sp->h_words.p, src, (size_t)sp->total_samples * 4, hipMemcpyHostToDevice, st));
-                    else HIP_TRY(hipMemcpy(sp->h_words.p, src, (size_t)sp->total_samples * 4, hipMemcpyHostToDevice));
-                    const int rc = ctu_engine_run_rows(e, sp, sp->h_words.p, sp->h_rows.p, st);
-                    if (rc != CTU_OK) {  // earlier ranges are still in flight: drain them before the caller reuses its buffers
-                        drain();
-                        for (auto &pe : part_events) {
-                            (void)hipEventDestroy(pe.first);
-                            (void)hipEventDestroy(pe.second);
-                        }
-                        return rc;
-                    }
-                    part_events.emplace_back();
-                    HIP_TRY(hipEventCreate(&part_events.back().first));
-                    HIP_TRY(hipEventCreate(&part_events.back().second));
-                    std::swap(part_events.back().first, e->ev0);
-                    std::swap(part_events.back().second, e->ev1);
-                }
-                if (k > 0) download(k - 1);
-            }
-            download(np - 1);
-            HIP_TRY(hipStreamSynchronize(pl->part_stream[0]));
-            HIP_TRY(hipStreamSynchronize(pl->part_stream[1]));
-            e->host_kernel_ms = 0.f;
-            for (auto &pe : part_events) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, pe.first, pe.second) == hipSuccess) e->host_kernel_ms += ms;
-                (void)hipEventDestroy(pe.first);
-                (void)hipEventDestroy(pe.second);
-            }
-            e->host_timed = true;
-        } else {
-            if (pl->h_words.n < (size_t)pl->total_samples) pl->h_words.alloc((size_t)pl->total_samples);
-            if (pl->h_rows.n < (size_t)pl->total_frames * d.D) pl->h_rows.alloc((size_t)pl->total_frames * d.D);
-            hipStream_t s = nullptr;
-            if (pin_in) HIP_TRY(hipMemcpyAsync(pl->h_words.p, h_in, (size_t)pl->total_samples * 4, hipMemcpyHostToDevice, s));
-            else HIP_TRY(hipMemcpy(pl->h_words.p, h_in, (size_t)pl->total_samples * 4, hipMemcpyHostToDevice));
-            const int rc = ctu_engine_run_rows(e, pl, pl->h_words.p, pl->h_rows.p, s);
-            if (rc != CTU_OK) return rc;
-            if (pin_out) {
-                HIP_TRY(hipMemcpyAsync(h_rows, pl->h_rows.p, (size_t)pl->total_frames * d.D * 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            } else {
-                HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(hipMemcpy(h_rows, pl->h_rows.p, (size_t)pl->total_frames * d.D * 4, hipMemcpyDeviceToHost));
-            }
-        }
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+    return guarded(e, [&]() -> int {
+        HostInput in{h_rows_in, sizeof(uint32_t), 0};
+        in.stage = [](ctu_plan *p) {
+            p->h_words.reserve((size_t)p->total_samples);
+            return p->h_words.p;
+        };
+        in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run_rows(e, p, p->h_words.p, p->h_rows.p, s); };
+        return run_host_ranges(e, pl, in, h_rows);
+    });
 }
 
 static void cmvn_maps(ctu_engine *e) {
@@ -2622,7 +2551,7 @@ int ctu_cmvn_accumulate(ctu_engine *e, const ctu_plan *pl, const float *d_rows, 
     if (!acc || (pl->total_frames && !d_rows)) return CTU_ERR_INPUT;
     if (pl->total_frames == 0) return CTU_OK;
     hipStream_t s = (hipStream_t)stream;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         cmvn_maps(e);
         const int cols = ctu_cmvn_cols(e);
@@ -2638,11 +2567,8 @@ int ctu_cmvn_accumulate(ctu_engine *e, const ctu_plan *pl, const float *d_rows, 
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipMemcpy(zero.data(), e->d_stat_a.p, zero.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < zero.size(); i++) acc[i] += zero[i];
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 int ctu_cmvn_apply(ctu_engine *e, const ctu_plan *pl, float *d_rows, const int32_t *spk_of_utt, int32_t n_spk,
@@ -2652,7 +2578,7 @@ int ctu_cmvn_apply(ctu_engine *e, const ctu_plan *pl, float *d_rows, const int32
     if (!mean || !var || (pl->total_frames && !d_rows)) return CTU_ERR_INPUT;
     if (pl->total_frames == 0) return CTU_OK;
     hipStream_t s = (hipStream_t)stream;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         cmvn_maps(e);
         const int cols = ctu_cmvn_cols(e);
@@ -2663,11 +2589,8 @@ int ctu_cmvn_apply(ctu_engine *e, const ctu_plan *pl, float *d_rows, const int32
         hipLaunchKernelGGL(cmvn_apply_kernel, dim3(pl->n_trap_chunks), dim3(256), 0, s, d_rows, pl->utt_info.p,
                            pl->trap_chunks.p, e->d_spk.p, e->d_slot_of_col.p, e->d_stat_a.p, e->d_stat_b.p, cols, e->design->D);
         HIP_TRY(hipGetLastError());
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 const int64_t *ctu_plan_out_samples(const ctu_plan *p) { return p->out_samples.empty() ? nullptr : p->out_samples.data(); }
@@ -2689,7 +2612,7 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
     const int rc = ctu_engine_run(e, pl, d_pcm, nullptr, nullptr, stream);  // spectra before / after NR into the plan's scratch
     e->in_signal_call = false;
     if (rc != CTU_OK) return rc;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         SynthParams sp;
         sp.K = d.K; sp.wfft = d.wfft; sp.window = d.window; sp.wshift = d.wshift;
@@ -2707,16 +2630,13 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
         hipLaunchKernelGGL(ola_kernel, dim3(gx, pl->n_utt), dim3(256), 0, s, pl->ybuf.p, d_out, pl->utt_info.p, pl->d_sample_off.p,
                            pl->n_utt, sp);
         HIP_TRY(hipGetLastError());
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 int ctu_engine_run_signal_host(ctu_engine *e, const ctu_plan *pl, const int16_t *h_pcm, int16_t *h_out) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         DevBuf<int16_t> pcm, out;
         pcm.alloc((size_t)pl->total_samples);
@@ -2728,33 +2648,27 @@ int ctu_engine_run_signal_host(ctu_engine *e, const ctu_plan *pl, const int16_t 
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(h_out, out.p, (size_t)pl->total_samples * 2, hipMemcpyDeviceToHost));
         return CTU_OK;
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
+    });
 }
 
 int ctu_cmvn_accumulate_host(ctu_engine *e, const ctu_plan *pl, const float *h_rows, const int32_t *spk_of_utt, int32_t n_spk,
                              const double *mean, double *acc) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
     if (pl->total_frames == 0) return CTU_OK;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         DevBuf<float> rows;
         rows.alloc((size_t)pl->total_frames * e->design->D);
         HIP_TRY(hipMemcpy(rows.p, h_rows, rows.n * sizeof(float), hipMemcpyHostToDevice));
         return ctu_cmvn_accumulate(e, pl, rows.p, spk_of_utt, n_spk, mean, acc, nullptr);
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
+    });
 }
 
 int ctu_cmvn_apply_host(ctu_engine *e, const ctu_plan *pl, float *h_rows, const int32_t *spk_of_utt, int32_t n_spk,
                         const double *mean, const double *var) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
     if (pl->total_frames == 0) return CTU_OK;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         DevBuf<float> rows;
         rows.alloc((size_t)pl->total_frames * e->design->D);
@@ -2764,25 +2678,19 @@ int ctu_cmvn_apply_host(ctu_engine *e, const ctu_plan *pl, float *h_rows, const 
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(h_rows, rows.p, rows.n * sizeof(float), hipMemcpyDeviceToHost));
         return CTU_OK;
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
+    });
 }
 
 int ctu_decode_g711(ctu_engine *e, const uint8_t *d_codes, int64_t n, int alaw, int16_t *d_pcm, void *stream) {
     if (!e || n < 0 || (n && (!d_codes || !d_pcm))) return CTU_ERR_INPUT;
     if (n == 0) return CTU_OK;
-    try {
+    return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         const int grid = (int)std::min<int64_t>((n / 8 + 255) / 256, (int64_t)e->n_cu * 8);
         hipLaunchKernelGGL(g711_kernel, dim3(std::max(grid, 1)), dim3(256), 0, (hipStream_t)stream, d_codes, d_pcm, n, alaw);
         HIP_TRY(hipGetLastError());
-    } catch (const std::exception &ex) {
-        set_error(e, std::string("ENGINE: ") + ex.what());
-        return CTU_ERR_DEVICE;
-    }
-    return CTU_OK;
+        return CTU_OK;
+    });
 }
 
 int ctu_engine_reset_chain(ctu_engine *e) {

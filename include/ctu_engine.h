@@ -119,10 +119,11 @@ int ctu_engine_run(ctu_engine *, const ctu_plan *, const int16_t *d_pcm, float *
 void *ctu_host_alloc(size_t bytes);
 void ctu_host_free(void *);
 
-/* Host-buffer convenience: H2D, run, D2H, synchronised on return.  The device copies are kept in the plan.  Batches of at
- * least 16 utterances and 32 MiB in page-locked buffers go in eight utterance ranges on two streams, so the upload of a
- * range overlaps the kernels and the download of the previous one (environment CTU_HOST_CHUNKS=<n> overrides, 1 = one
- * range; the hwss / fwss / 2fwss chain always runs in one).  rows_per_utt (optional, n_utt entries) receives the number
+/* Host-buffer convenience: H2D, run, D2H, synchronised on return.  The device copies are kept in the plan.  The 32 MiB rule:
+ * a batch of at least 16 utterances and 32 MiB of input (the arena's bytes), with input and output in page-locked buffers,
+ * goes in eight utterance ranges on two streams, so the upload of a range overlaps the kernels and the download of the
+ * previous one (environment CTU_HOST_CHUNKS=<n> overrides, 1 = one range; the hwss / fwss / 2fwss chain always runs in one).
+ * A null h_pcm or h_rows on a plan that has frames is CTU_ERR_INPUT.  rows_per_utt (optional, n_utt entries) receives the number
  * of rows actually produced per utterance: < frames with -vad_apply_mode drop, and 0 for an utterance with no more frames than the VAD's
  * majority filter delays ((vad_filter_order-1)/2: the filter never gets ready, src/vad/vad.h:126-136, and the reference writes neither a
  * row nor a decision; the utterance's bytes in h_vad / d_vad are NUL then, '0' / '1' otherwise). */
@@ -146,8 +147,8 @@ int64_t ctu_rows_arena_layout(const int64_t *utt_rows, int32_t n_utt, int32_t wi
  * come out in file order - the reference's writers do not rotate c0 in this mode - and ctu_cmvn_* work on them as ever,
  * with statistic slot k = column k (src/fea/post_impl.cc:55-57). */
 int ctu_engine_run_rows(ctu_engine *, const ctu_plan *, const void *d_rows_in, float *d_rows, void *stream);
-/* Host-buffer convenience, like ctu_engine_run_host: page-locked buffers of at least 16 utterances and 32 MiB go in eight
- * ranges on two streams (CTU_HOST_CHUNKS overrides), pageable ones through the runtime's staging.  Synchronised on return. */
+/* Host-buffer convenience, the same pipeline as ctu_engine_run_host: its 32 MiB rule decides on the ranges (the arena's bytes:
+ * four per word; CTU_HOST_CHUNKS overrides), pageable buffers go through the runtime's staging.  Synchronised on return. */
 int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_in, float *h_rows);
 
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53

@@ -1269,6 +1269,18 @@ def test_files_shorter_than_the_majority_filter_delay_write_nothing(Engine, orde
                 _assert_rows(g, ref, cfg)
 
 
+def _vad_list_utts(cfg, order):
+    fs = 8000 if "8000" in cfg else 16000
+    hop, pre = fs // 100, fs * 25 // 1000 - fs // 100
+    # 0: a file without a frame; 1: one the filter never gets ready on (not behind a delta chain, which wants window + 2 frames, nor at
+    # order 5, where it would leave historySize half drained: the corner the ABI does not reproduce)
+    frames = [17, 9, 31, 8, 1 if order == 3 and "-fea_delta" not in cfg else 12, 25, 0, 14, 40]
+    if "drop" in cfg:  # dropped rows need decisions of both kinds: the noisy set's miniatures
+        from ctucopy_amd import synth
+        return [synth.utterance_c(synth.SET_NOISY, k, True) for k in range(7)]
+    return [synth_utt(400 + i, pre + hop * T + (hop // 2 if T == 0 else 3 * i), fs=fs) for i, T in enumerate(frames)]
+
+
 @pytest.mark.parametrize("cfg,order", [(C4, 3),
                                        (C2 + "-vad_out_mode vad -vad_cri_mode energy -vad_thr_mode adapt".split(), 3),
                                        (C2 + "-fea_delta d_a -fea_E on -vad_out_mode vad -vad_cri_mode energy -vad_thr_mode dyn".split(), 3),
@@ -1280,15 +1292,7 @@ def test_the_list_behaviour_of_the_reference_vad_filter(Engine, cfg, order):
     # counts of the files in front of it.  The oracle's list mode is pinned against the reference's own class
     # (tests/test_oracle_median_ref.py); the engine reproduces it when the plan is told where each utterance's ring starts
     # (ctu_plan_set_vad_ring) and treats every utterance as the first of its process otherwise.
-    fs = 8000 if "8000" in cfg else 16000
-    hop, pre = fs // 100, fs * 25 // 1000 - fs // 100
-    # 0: a file without a frame; 1: one the filter never gets ready on (not behind a delta chain, which wants window + 2 frames, nor at
-    # order 5, where it would leave historySize half drained: the corner the ABI does not reproduce)
-    frames = [17, 9, 31, 8, 1 if order == 3 and "-fea_delta" not in cfg else 12, 25, 0, 14, 40]
-    utts = [synth_utt(400 + i, pre + hop * T + (hop // 2 if T == 0 else 3 * i), fs=fs) for i, T in enumerate(frames)]
-    if "drop" in cfg:  # dropped rows need decisions of both kinds: the noisy set's miniatures
-        from ctucopy_amd import synth
-        utts = [synth.utterance_c(synth.SET_NOISY, k, True) for k in range(7)]
+    utts = _vad_list_utts(cfg, order)
     eng, orc = Engine(cfg), Oracle(cfg)
     got, vads = eng.extract(utts, want_vad=True, as_list_of_one_process=order)
     ref = orc.process_list(utts, want_vad=True)
@@ -1303,6 +1307,21 @@ def test_the_list_behaviour_of_the_reference_vad_filter(Engine, cfg, order):
             differs += not np.array_equal(g, alone[i])
     assert differs >= (1 if "drop" in cfg else 2)                # the list does change the rows of the files behind the first
     assert np.array_equal(got[0], alone[0])                      # ... not those of the first
+
+
+@pytest.mark.parametrize("cfg", [C2 + "-vad_out_mode vad -vad_cri_mode energy -vad_thr_mode adapt".split(), C4 + ["-vad_apply_mode", "drop"]])
+def test_the_list_behaviour_holds_when_the_host_run_goes_in_ranges(Engine, monkeypatch, cfg):
+    # ctu_engine_run_host in utterance ranges hands every range the ring indices of its own utterances (the caller's, from the range's
+    # first utterance on): rows, VAD bytes and row counts of the list are those of the run in one range, bit for bit
+    utts = _vad_list_utts(cfg, 3)
+    monkeypatch.setenv("CTU_HOST_CHUNKS", "1")
+    one, vone = Engine(cfg).extract(utts, want_vad=True, as_list_of_one_process=3)
+    monkeypatch.setenv("CTU_HOST_CHUNKS", "3")
+    many, vmany = Engine(cfg).extract(utts, want_vad=True, as_list_of_one_process=3)
+    assert len(one) == len(many) == len(utts)
+    for a, b, va, vb in zip(one, many, vone, vmany):
+        assert a.shape == b.shape and np.array_equal(a, b)
+        assert np.array_equal(va, vb)
 
 
 @pytest.mark.parametrize("extra", [["-fea_delta", "d_a"], ["-fea_delta", "d_a_t", "-fea_E", "on"], ["-fea_trap", "3"], ["-fea_delta", "d_a", "-fea_Z_exp", "0.98"],

@@ -198,6 +198,11 @@ def test_wrong_entry_point_is_an_error_not_a_run():
         p.run_rows_host(pplan, np.zeros(pplan.total_samples, np.uint32))
     with pytest.raises(CtuError, match="-format_in htk"):
         p.run_rows_device(pplan, torch.zeros(pplan.total_samples, dtype=torch.int32, device="cuda"))
+    # a null arena on a plan that has frames is refused, as ctu_engine_run_rows_host refuses it
+    L = ceng.load_library()
+    out = np.empty((pplan.total_frames, p.dims.row_floats), np.float32)
+    assert L.ctu_engine_run_host(p._h, pplan._h, None, out.ctypes.data, None, None) == ceng.CTU_ERR_INPUT
+    assert L.ctu_last_error(p._h).decode() == "ENGINE: null host buffer"
 
 
 def test_postprocess_binding():
