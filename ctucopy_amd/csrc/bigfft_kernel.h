@@ -176,7 +176,7 @@ __device__ __forceinline__ void big_project(const BigParams &p, const float *P, 
             }
         }
     }
-    if (p.e_mode && p.e_mode != 2 && tid == 0 && !(p.feat == FEAT_BANDS && p.band_to_scratch)) {
+    if (p.e_mode && p.e_mode != 2 && tid == 0 && !(p.feat == FEAT_BANDS && p.band_to_scratch == 1)) {
         double e = 0.0;
         if (p.e_mode == 1) e = log(2.0 * e_spec);
         else if (p.e_mode == 3) e = log(2.0 * e_band);

@@ -8,6 +8,7 @@
 //   lp_tail_kernel.h   Levinson-Durbin and a -> c, one frame per lane
 //   wave1k_kernel.h    1024-point frames, one wave per frame
 //   trap_kernel.h      TRAP-DCT as fp32 MFMA Toeplitz contraction
+//   dctw_kernel.h      DCT-II tail of 25 to 64 values per frame (hi-res MFCC) over the band logarithms a front end left in scratch
 //   post_kernels.h     delta chain / stacking, CMS, per-speaker CMVN over resident rows
 //   rows_in_kernels.h  HTK feature input: byte order and slot of every word of the files' rows
 //   signal_kernels.h   speech-enhancement output: inverse transform, overlap-add
@@ -43,6 +44,7 @@
 #include "vad_fused.h"
 #include "frontend_kernel.h"
 #include "trap_kernel.h"
+#include "dctw_kernel.h"
 #include "decode_kernels.h"
 #include "rows_in_kernels.h"
 #include "bigfft_kernel.h"
@@ -123,6 +125,9 @@ struct ctu_engine {
     DevBuf<float> lanec, ftab, trapG;
     DevBuf<uint4> trapG16;   // TRAP on the bf16 matrix pipe: A fragments [8 phases][4 k-steps][3 terms][64 lanes] (trap_kernel.h)
     bool trap_bf16 = false;
+    bool dctw = false;       // dctc with more than MAXC values per frame: the front end runs band-valued into the plan's logmel, dct_wide_kernel follows
+    DevBuf<float> dctw_tab;  // its A operands (build_dctw)
+    int dctw_nout = 0, dctw_chunks = 0;
     DevBuf<int> itab;
     // FFT sizes of 1024 to 4096 points (bigfft_kernel.h)
     bool big = false;
@@ -238,6 +243,8 @@ int guarded(ctu_engine *e, F &&body) {
     }
 }
 
+// dctc with more values per frame (cepstra and c0) than phase 2 of the front ends accumulates: dct_wide_kernel behind a band-valued front end
+bool dct_wide(const ctu::Design &d) { return !d.rows_in && !d.signal_out && d.kind == ctu::FeaKind::Dctc && d.nfea > MAXC; }
 bool ss_eligible(const ctu::Design &d);
 bool ss_big_eligible(const ctu::Design &d);
 int ss_mode_of(const ctu::Opts &o);
@@ -254,6 +261,7 @@ std::string post_unsupported_reason(const ctu::Design &d) {
             wsum += d.post_w[j];
         }
         if (wsum > 24) return "delta windows adding up to more than 24 frames (LDS tile of the chain)";
+        if ((size_t)(64 + 2 * wsum) * d.Dbase > 256 * 12) return "delta / stacking tile (64 frames and both halos, times the base row's columns) above 3072 floats (post_kernel's prefetch registers)";
     }
     if (o.stat_cmvn || o.apply_cmvn) {
         if (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "CMVN on non-cepstral kinds";
@@ -269,6 +277,7 @@ std::string post_unsupported_reason(const ctu::Design &d) {
         if (d.post_stack) return "CMS on stacked vectors";
         if (d.cms == 2 && (o.length_b < 1 || o.length_b > 512)) return "block CMS window outside 1..512 frames";
         if (d.cms_cols > 32) return "more than 32 CMS columns";
+        if (d.cms == 1 && d.post_order == 0 && d.Dbase > 32) return "exponential CMS on rows of more than 32 columns (cms_exp_kernel has a lane per column of a 32-lane half wave)";
         if (d.cms == 2 && (size_t)(64 + o.length_b - 1) * d.cms_cols * sizeof(float) > 64 * 1024) return "block CMS tile above 64 KiB of LDS";
     }
     return "";
@@ -338,6 +347,13 @@ std::string unsupported_reason(const ctu::Design &d) {
         if (o.fea_E && o.fea_rawenergy) return "-remove_dc1 together with -fea_rawenergy";
         if (o.do_vad() && !(o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "fea")) return "-remove_dc1 together with a VAD criterion on the spectrum";
     }
+    if (dct_wide(d)) {  // what dct_wide_kernel's band-valued front end does not carry
+        if (d.nfea > DCTW_MAX) return "more than 64 cepstral values per frame (-fea_ncepcoefs above 63: dct_wide_kernel has four row blocks of 16)";
+        if (o.nr_mode != "none" && o.nr_mode != "exten")
+            return "hwss / fwss / 2fwss with more than 24 cepstral values per frame (the detector's order is -fea_ncepcoefs; its paths take 2 to 16 coefficients on 256 / 512 points and a dctc chain of at most 24 values on 2048 / 4096)";
+        if (o.do_vad()) return "the VAD module beside more than 24 cepstral values per frame (the detector's stages sit behind DCTC-valued front ends)";
+        if (o.nr_when_afterFB) return "-nr_when afterFB with more than 24 cepstral values per frame";
+    }
     if (o.nr_mode != "none" && o.nr_mode != "exten") {
         // -vad_apply_mode silence zeroes in->_Xsabs behind a non-speech frame (src/vad/vad.cc:727-736).  The features of the frame are
         // out by then and the next get_frame() rewrites the vector, so on every other chain the mode changes nothing - but these
@@ -384,7 +400,6 @@ std::string unsupported_reason(const ctu::Design &d) {
         if (o.fea_lporder >= d.B) return "LP order not below the number of bands: the normal equations are singular and the reference's output is rounding noise";
         if (o.fea_lporder > MAX_LP || o.fea_ncepcoefs > MAX_LP) return "LP order / cepstral order above 23 (the front end accumulates 24 lags per frame)";
     }
-    if (d.kind == ctu::FeaKind::Dctc && d.nfea > MAXC) return "more cepstral coefficients than the kernel accumulates";
     if (d.B > 512) return "more than 512 filter bank channels";
     if (d.kind == ctu::FeaKind::TrapDct && o.fea_trapdct_ndct > 32) return "more than 32 TRAP DCT coefficients";
     if (d.kind == ctu::FeaKind::TrapDct && o.fea_trapdct_traplen > 255) return "TRAP longer than 255 frames";
@@ -501,7 +516,8 @@ void build_phase2(const ctu::Design &d, Phase2Tables &t) {
     const int NS = (B + 7) / 8;
     int ncoef = 0;
     const std::vector<double> *coef_tab = nullptr;
-    if (d.kind == ctu::FeaKind::Dctc) { coef_tab = &d.dct; ncoef = d.nfea; }
+    const bool dctc = d.kind == ctu::FeaKind::Dctc && !dct_wide(d);  // (wide: a band-valued front end, no coefficient rows)
+    if (dctc) { coef_tab = &d.dct; ncoef = d.nfea; }
     else if (d.kind == ctu::FeaKind::Lpc || d.kind == ctu::FeaKind::Lpa) { coef_tab = &d.idft; ncoef = d.o.fea_lporder + 1; }
     if (ncoef > MAXC) throw std::runtime_error("more cepstral / LP coefficients than the kernel accumulates");
     const int CW = ncoef <= 16 ? 16 : MAXC;  // the kernel has straight-line code for these two widths
@@ -515,7 +531,7 @@ void build_phase2(const ctu::Design &d, Phase2Tables &t) {
     std::vector<double> cfd(lpd ? (size_t)NS * 8 * CW : 0, 0.0);
     // DCTC: coefficient row r of a cell is the value written to output slot r (c1..cN, then c0)
     std::vector<int> coef_of_slot;
-    if (d.kind == ctu::FeaKind::Dctc) {
+    if (dctc) {
         coef_of_slot.assign(d.nfea, -1);
         int nout = 0;
         for (int i = 0; i < d.nfea; i++)
@@ -597,7 +613,7 @@ void build_phase2(const ctu::Design &d, Phase2Tables &t) {
             cell[(sl * 8 + g) * 2] = kstart[g];
             cell[(sl * 8 + g) * 2 + 1] = b;
             for (int i = 0; i < ncoef; i++) {
-                const int src = (d.kind == ctu::FeaKind::Dctc) ? coef_of_slot[i] : i;
+                const int src = dctc ? coef_of_slot[i] : i;
                 if (src >= 0) cf[((size_t)sl * 8 + g) * CWS + i] = (float)(*coef_tab)[(size_t)src * B + b];
                 if (src >= 0 && lpd) cfd[((size_t)sl * 8 + g) * CW + i] = (*coef_tab)[(size_t)src * B + b];
             }
@@ -652,7 +668,7 @@ void build_phase2(const ctu::Design &d, Phase2Tables &t) {
                     const int m = lane & 15, g = (lane >> 4) + 4 * h;
                     const int b = cell[(sl * 8 + g) * 2 + 1];
                     float v = 0.f;
-                    if (d.kind == ctu::FeaKind::Dctc) {
+                    if (dctc) {
                         if (b >= 0 && m < t.ncoef_out && coef_of_slot[m] >= 0) v = (float)(*coef_tab)[(size_t)coef_of_slot[m] * B + b];
                     } else if (b >= 0 && m < ncoef) v = (float)(*coef_tab)[(size_t)m * B + b];  // LP: row m = lag m
                     ft.push_back(v);
@@ -844,7 +860,8 @@ void build_big_tables(ctu_engine *e) {
     std::vector<float> coef(4, 0.f);
     std::vector<double> coef_d(4, 0.0);
     std::vector<int> slot(4, -1);
-    if (d.kind == ctu::FeaKind::Dctc) {
+    const bool wide = dct_wide(d);  // a band-valued front end, no coefficient rows
+    if (d.kind == ctu::FeaKind::Dctc && !wide) {
         // row r of the table is the value written to output slot r (c1..cN, then c0): norm and lifter are in d.dct
         std::vector<int> coef_of_slot(d.nfea, -1);
         int nout = 0;
@@ -884,7 +901,7 @@ void build_big_tables(ctu_engine *e) {
         build_trap_bf16(e);
     }
     switch (d.kind) {
-        case ctu::FeaKind::Dctc: e->feat = FEAT_DCTC; break;
+        case ctu::FeaKind::Dctc: e->feat = wide ? FEAT_BANDS : FEAT_DCTC; break;
         case ctu::FeaKind::Lpc:
         case ctu::FeaKind::Lpa: e->feat = FEAT_LP; break;
         default: e->feat = FEAT_BANDS; break;
@@ -942,7 +959,7 @@ FeSel fe_select(const ctu::Design &d, const Phase2Tables *t) {
     k.vf = !signal && vf_eligible(d);
     k.md = t && t->md;             // the tables are laid out for the MFMA tail's lane map
     k.nc = t ? t->CW : 16;         // rows of MAXC entries: more than 16 cepstra / LP lags
-    if (signal || (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc && d.kind != ctu::FeaKind::Lpa)) k.feat = FEAT_BANDS;
+    if (signal || dct_wide(d) || (d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc && d.kind != ctu::FeaKind::Lpa)) k.feat = FEAT_BANDS;
     else k.feat = d.kind == ctu::FeaKind::Dctc ? FEAT_DCTC : o.fb_inld ? FEAT_LP : FEAT_LPD;
     // rows of samples per lane that can be non-zero.  The 13-row instantiations serve the 25 ms windows (the *ss modes: every window of
     // at most 13 rows - the window table is zero beyond the window); every other window, and -remove_dc1, takes the generic row count
@@ -998,10 +1015,39 @@ FeSel fe_select(const ctu::Design &d, const Phase2Tables *t) {
     return k;
 }
 
+// A operands of dct_wide_kernel (dctw_kernel.h): [chunk][row block][k-step][lane], lane m + 16 k holding row m of the block at band
+// 64 chunk + 4 step + k.  Row r of the table is the value written to row column r (c1..cN, then c0): norm and lifter are in d.dct.
+void build_dctw(ctu_engine *e) {
+    const ctu::Design &d = *e->design;
+    std::vector<int> coef_of_slot(d.nfea, -1);
+    int nout = 0;
+    for (int i = 0; i < d.nfea; i++)
+        if (d.row_slot[i] >= 0) {
+            coef_of_slot[d.row_slot[i]] = i;
+            nout = std::max(nout, d.row_slot[i] + 1);
+        }
+    if (nout <= 16 || nout > DCTW_MAX) throw std::runtime_error("internal: row width outside dct_wide_kernel's row blocks");
+    const int nrb = (nout + 15) / 16, chunks = (d.B + DCTW_KC - 1) / DCTW_KC, KS = DCTW_KC / 4;
+    std::vector<float> tab((size_t)chunks * nrb * KS * 64, 0.f);
+    for (int c = 0; c < chunks; c++)
+        for (int rb = 0; rb < nrb; rb++)
+            for (int s_ = 0; s_ < KS; s_++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int r = rb * 16 + (lane & 15), b = c * DCTW_KC + 4 * s_ + (lane >> 4);
+                    if (r < nout && b < d.B && coef_of_slot[r] >= 0)
+                        tab[(((size_t)c * nrb + rb) * KS + s_) * 64 + lane] = (float)d.dct[(size_t)coef_of_slot[r] * d.B + b];
+                }
+    e->dctw_tab.upload(tab);
+    e->dctw_nout = nout;
+    e->dctw_chunks = chunks;
+}
+
 void build_tables(ctu_engine *e) {
     const ctu::Design &d = *e->design;
     const double pi = 3.14159265358979323846;
     e->big = d.wfft >= 1024;
+    e->dctw = dct_wide(d);
+    if (e->dctw) build_dctw(e);
     if (e->big) {
         // (-remove_dc1 at 1024 points takes bigfft_kernel<4>, which reads the frames' offsets)
         // (and speech output and the Burg-cepstral VAD criterion: the spectra's export is bigfft_kernel's)
@@ -1179,7 +1225,7 @@ KParams engine_kparams(const ctu_engine *e) {
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
     kp.band_log = d.kind != ctu::FeaKind::Spec;
-    kp.band_to_scratch = d.kind == ctu::FeaKind::TrapDct;
+    kp.band_to_scratch = d.kind == ctu::FeaKind::TrapDct ? 1 : e->dctw ? 2 : 0;  // 2: the bands to the scratch, the energy column (-fea_E) to its slot of the row
     kp.lp_is_lpa = d.kind == ctu::FeaKind::Lpa;
     kp.syn_scale = 1.0f / (float)d.wfft;
     kp.vad_export = (signal && !e->sy) ? 1 : ((!e->do_vad || e->vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0)));
@@ -1475,6 +1521,17 @@ void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
             });
         });
     }
+    HIP_TRY(hipGetLastError());
+}
+
+// The wide DCT tail (dctw_kernel.h) over the band logarithms the front end left, into the rows the front end would have written
+void stage_dctw(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KParams &kp) {
+    DctwParams wp;
+    wp.logmel = pl->logmel.p; wp.rows = kp.rows; wp.atab = e->dctw_tab.p; wp.total_frames = pl->total_frames;
+    wp.B = kp.B; wp.D = kp.D; wp.nout = e->dctw_nout; wp.chunks = e->dctw_chunks;
+    wp.n_tiles = (int)((pl->total_frames + DCTW_TILE - 1) / DCTW_TILE);
+    const dim3 g((unsigned)std::max(1, std::min(wp.n_tiles, e->n_cu * 8)));
+    lift<2, 3, 4>((wp.nout + 15) / 16, [&](auto nrb) { hipLaunchKernelGGL(dct_wide_kernel<decltype(nrb)::value>, g, dim3(256), 0, s, wp); });
     HIP_TRY(hipGetLastError());
 }
 
@@ -2053,7 +2110,7 @@ void plan_alloc(ctu_engine *e, ctu_plan *pl, const PlanHost &h) {
         if (c128.empty()) c128.assign(2, 0);
         pl->trap_chunks128.upload(c128);
     }
-    if (d.kind == ctu::FeaKind::TrapDct) pl->logmel.alloc((size_t)ro * d.B);
+    if (d.kind == ctu::FeaKind::TrapDct || e->dctw) pl->logmel.alloc((size_t)ro * d.B);
     if (lp_tail_runs(e)) pl->lp_r.alloc(((size_t)std::max<int64_t>(ro, 1) * (d.o.fea_lporder + 1) * (lags_double(e) ? 8 : 4) + 7) / 8);
 }
 }  // namespace
@@ -2200,6 +2257,7 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
             const int rc = run_ss_chain(e, pl, s, kp, pass);
             if (rc != CTU_OK) return rc;
         }
+        if (e->dctw) stage_dctw(e, pl, s, kp);  // (inside the timed span: the tail finishes what the front end of a narrower chain does itself)
         HIP_TRY(hipEventRecord(e->ev1, s));
         e->timed = true;
         e->host_timed = false;
@@ -2721,6 +2779,7 @@ const char *ctu_engine_kernel_name(const ctu_engine *e) {
             case BIG_FFT: n = "bigfft_kernel<" + std::to_string(big_nit(e)) + ">"; break;
             case BIG_NONE: n = fe_name(e->sel); break;
         }
+        if (e->dctw) n = "dct_wide_kernel";  // the front end ahead of it is ctu_config_table(..., "frontend") / the FFT size
         const_cast<ctu_engine *>(e)->kname = n;
     }
     return e->kname.c_str();

@@ -1329,7 +1329,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                 }
             }
             STAMP(8);  // filter bank + per-band accumulation
-            if (o_e_mode && !(FEAT == FEAT_BANDS && p.band_to_scratch)) {
+            if (o_e_mode && !(FEAT == FEAT_BANDS && p.band_to_scratch == 1)) {  // (2: the bands to the scratch, the energy to its column)
                 float e = 0.f;
                 if (o_e_mode == 1 || o_e_mode == 3 || o_e_mode == 5) e = (float)log(2.0 * lanes8_allreduce_add(esum));
                 else if (o_e_mode == 4) e = (float)log(lanes8_allreduce_add(esum));

@@ -11,7 +11,8 @@ constexpr int PSTRIDE = 260;   // floats per P-tile row: 257 bins padded so rows
 constexpr int LDS_2WG = 80 * 1024;  // two workgroups per CU fit when a workgroup's LDS stays at or under this
 constexpr int MAX_LP = 23;     // LP order / cepstral order limit: the front end accumulates MAXC = 24 lags (R[0..23]) per frame, lp_tail_kernel keeps one frame's recursion in a lane's registers
 constexpr int GEN_PLAIN = 0, GEN_INLD = 1, GEN_EXTEN = 2, GEN_FULL = 3, GEN_DC1 = 4;  // front-end option specialisations (frontend_kernel.h)
-constexpr int MAXC = 24;       // most coefficients accumulated per frame in phase 2 (cepstra incl. c0, or LP lags)
+constexpr int MAXC = 24;       // most coefficients accumulated per frame in phase 2 (cepstra incl. c0, or LP lags): the in-kernel limit.  A dctc chain of
+                               // 25 to 64 values runs its front end band-valued and takes dct_wide_kernel (dctw_kernel.h) for the DCT
 constexpr int PCM_ALIGN = 8;   // utterance starts are multiples of this many samples
 constexpr int PCM_HEAD = 8;    // samples of padding before the first utterance (x[-2..-1] of frame 0 is loaded)
 constexpr int PCM_TAIL = 512;  // padding after the last one: the generic instantiation loads 16 rows of 32 samples whatever the window
@@ -33,7 +34,7 @@ constexpr int LC_WIN = 0, LC_MASK = 32, LC_TW = 64, LC_UT = 96, LANEC = 112;
 // ~1k cycles.  Row stride 116 floats makes the 16 lanes' ds_read_b128 conflict-free (116 mod 64 = 52).
 constexpr int LTW_STRIDE = 116, LTW_FLOATS = 16 * LTW_STRIDE;
 
-// Kernel variants by feature tail.  BANDS covers spec / logspec / the log-mel scratch of TRAP (runtime flags
+// Kernel variants by feature tail.  BANDS covers spec / logspec / the log-mel scratch of TRAP and of the wide DCT tail (runtime flags
 // band_log, band_to_scratch); LP covers lpc and lpa (runtime flag lp_is_lpa).
 enum FeatMode { FEAT_BANDS = 0, FEAT_DCTC = 2, FEAT_LP = 3, FEAT_LPD = 4 };  // LPD: LP analysis with the autocorrelation and the recursions in double
 
@@ -57,11 +58,12 @@ struct VadParams {
 struct KParams {
     const int16_t *pcm;
     float *rows;
-    float *logmel;              // [total_frames][B] scratch (TRAP only)
+    float *logmel;              // [total_frames][B] scratch (TRAP, dct_wide_kernel)
     float2 *xri;                // [total_frames][K] complex spectrum before NR (VAD cepdist-lpc only)
     float *pnr;                 // [total_frames][K] spectrum after NR (VAD cepdist-lpc) or [total_frames] energy (VAD energy)
     int vad_export;             // 0 none, 1 spectra for the Burg-cepstral criterion, 2 frame energy criterion
-    int band_log, band_to_scratch, lp_is_lpa;
+    int band_log, band_to_scratch, lp_is_lpa;  // band_to_scratch: 1 = the bands go to logmel and nothing to the rows (TRAP), 2 = the same but the
+                                               // energy column (-fea_E) is written at its slot of the row (ahead of dct_wide_kernel)
     const struct TileRec *tiles;
     const int *wg_first;        // [grid] first tile of each workgroup's chain (-1 = none)
     const float *lanec;         // [16][LANEC]

@@ -372,7 +372,7 @@ __global__ __launch_bounds__(64 * W1K_WAVES, EXTEN ? CTU_W1K_LB - 1 : CTU_W1K_LB
             }
             double e_raw = 0.0;
             if (p.e_mode == 4) e_raw = wave_sum_fast(raw);
-            if (p.e_mode && p.e_mode != 2 && lane == 0 && !(p.feat == FEAT_BANDS && p.band_to_scratch)) {
+            if (p.e_mode && p.e_mode != 2 && lane == 0 && !(p.feat == FEAT_BANDS && p.band_to_scratch == 1)) {
                 double e = 0.0;
                 if (p.e_mode == 1) e = log(2.0 * e_spec);
                 else if (p.e_mode == 3) e = log(2.0 * e_band);

@@ -22,6 +22,9 @@ CFGS = {"C2": C2, "C3": C3, "C4": C4, "C4_novad": C4_NOVAD, "C5": C5, "C2_d_a": 
         "m44_vad_energy": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -vad_out_mode vad -vad_cri_mode energy -vad_thr_mode adapt".split(),
         # the same audio through -nr_mode fwss with the Burg cepstral detector (bigss_kernel.h): export, detector, decisions, seed passes
         "m44_fwss": "-fs 44100 -format_in raw -format_out htk -preset mfcc -preem 0.97 -nr_mode fwss -vad burg".split(),
+        # hi-res MFCC (40 bands, 39 cepstra + c0: a band-valued front end, then dct_wide_kernel) and the same front end alone
+        "hires40": C2 + ["-fb_definition", "1-40/40filters", "-fea_ncepcoefs", "39"],
+        "logspec40": C2 + ["-fb_definition", "1-40/40filters", "-fea_kind", "logspec"],
         "C2_d_a_cmvn": C2 + ["-fea_delta", "d_a", "-stat_cmvn", "x.stat", "-apply_cmvn", "x.stat"]}
 ap = argparse.ArgumentParser()
 ap.add_argument("--cfg", default="C3")
