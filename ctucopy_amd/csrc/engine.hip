@@ -14,6 +14,7 @@
 //   signal_kernels.h   speech-enhancement output: inverse transform, overlap-add
 //   bigfft_kernel.h    1024 .. 4096-point frames, a workgroup per frame; bigburg_kernel.h the Burg-cepstral criterion / detector there;
 //   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
+//   stream_kernels.h   streaming input: carry | new samples into the slots of a push arena, the tile records of the push, the next carry
 //
 // Data layout in HBM
 //   pcm   : one packed int16 arena; utterance i starts at sample_off[i] (multiple of 8 samples)
@@ -52,6 +53,7 @@
 #include "wave1k_kernel.h"
 #include "bigburg_kernel.h"
 #include "bigss_kernel.h"
+#include "stream_kernels.h"
 
 namespace {
 
@@ -225,6 +227,41 @@ struct ctu_plan {
     DevBuf<int4> utt_info;
     DevBuf<int> trap_chunks, trap_chunks128;   // (utterance, first frame) of every 64- / 128-frame chunk
     int n_trap_chunks = 0, n_trap_chunks128 = 0;
+};
+
+// A stream set (ctu_streams_create): per-stream state in HBM, and what a push needs that does not change from push to push - a plan over
+// n_streams utterances of the longest stitched length, whose tile list, chain heads (workgroup g starts at tile g), arena size and scratch a
+// push uses the front of.  The tile records themselves are written by stream_stitch_kernel, push after push.
+struct ctu_streams {
+    ctu_engine *eng = nullptr;
+    int n_streams = 0, cstride = 0, max_wg = 1;
+    int64_t max_push = 0;
+    std::unique_ptr<ctu_plan> plan;
+    DevBuf<int16_t> arena, carry;
+    DevBuf<StreamState> state;
+    std::vector<int64_t> consumed;   // the host's mirror of StreamState::consumed: layout and row counts of a push need no copy back
+    std::vector<uint32_t> seen;      // the push a stream was last named in (a repeat inside one push is refused)
+    uint32_t push_no = 0;
+    // the descriptors of a push: two page-locked buffers and their device copies in turn, each guarded by the event behind its last reader
+    StreamPush *h_desc[2] = {nullptr, nullptr};
+    DevBuf<StreamPush> d_desc[2];
+    hipEvent_t desc_free[2] = {nullptr, nullptr};
+    int turn = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around stream_stitch_kernel and stream_carry_kernel of the last push
+    bool timed = false;
+    // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
+    int16_t *h_stage = nullptr;
+    DevBuf<int16_t> d_stage;
+    DevBuf<float> d_rows;
+    std::vector<int64_t> offs;
+    ~ctu_streams() {
+        for (StreamPush *h : h_desc) ctu_host_free(h);
+        ctu_host_free(h_stage);
+        for (hipEvent_t v : desc_free)
+            if (v) (void)hipEventDestroy(v);
+        for (hipEvent_t v : ev)
+            if (v) (void)hipEventDestroy(v);
+    }
 };
 
 namespace {
@@ -404,6 +441,23 @@ std::string unsupported_reason(const ctu::Design &d) {
     if (d.kind == ctu::FeaKind::TrapDct && o.fea_trapdct_ndct > 32) return "more than 32 TRAP DCT coefficients";
     if (d.kind == ctu::FeaKind::TrapDct && o.fea_trapdct_traplen > 255) return "TRAP longer than 255 frames";
     if (d.kind == ctu::FeaKind::TrapDct && (size_t)(64 + 256) * (d.B | 1) * 4 > 64 * 1024) return "too many bands for the TRAP tile";
+    return "";
+}
+
+// Streaming input (ctu_streams_create): what an accepted configuration carries from one frame of a file to the next beyond the samples
+// themselves.  A stream set keeps samples (stream_kernels.h), so every such chain is refused by the option that brings the state in.
+std::string streams_unsupported_reason(const ctu::Design &d) {
+    const ctu::Opts &o = d.o;
+    if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
+    if (d.signal_out) return "-format_out raw | wave (speech output: the overlap-add runs across a file's frames)";
+    if (o.nr_mode != "none") return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
+    if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
+    if (o.do_vad()) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";
+    if (d.kind == ctu::FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
+    if (d.post_order > 0) return d.post_stack ? "-fea_trap (stacking spans 2 * trap_win + 1 frames)" : "-fea_delta (the delta chain spans the frames of its windows)";
+    if (d.cms) return d.cms == 1 ? "-fea_Z_exp (CMS: the running mean runs along the file)" : "-fea_Z_block (CMS: the block mean spans its window of frames)";
+    if (o.stat_cmvn || o.apply_cmvn) return "-stat_cmvn / -apply_cmvn (CMVN: statistics over whole lists)";
+    if (d.wshift > d.window) return "-s above -w (frames that leave samples out)";
     return "";
 }
 
@@ -1982,6 +2036,13 @@ int plan_layout(ctu_engine *e, ctu_plan *pl, const int64_t *utt_n, int32_t n_utt
     return CTU_OK;
 }
 
+// Front-end workgroups the chip holds at once: two per CU when the instantiation keeps to 128 VGPRs (four waves per SIMD) and 80 KB of LDS; the
+// synthesis and the 512-point detector instantiations take 256 VGPRs.  What plan_chains and a stream set's pushes build their chains for.
+int fe_max_wg(const ctu_engine *e) {
+    const FeSel &k = e->sel;
+    return e->n_cu * ((fe_waves_per_simd(k.mode, k.vf, k.ss, k.sy) >= 4 && e->lds_bytes <= (size_t)LDS_2WG) ? 2 : 1);
+}
+
 // Step 2, host only, for plans over samples: the chains the front end walks and the grid they are built for.  (A plan over rows has
 // no chains: rows_ingest_kernel strides over the tile list.)
 // Each workgroup walks a chain of tiles.  Stateless chains stride over the tile list; with a
@@ -1991,10 +2052,7 @@ void plan_chains(const ctu_engine *e, ctu_plan *pl, PlanHost &h) {
     const std::vector<int> &uts = h.uts;
     std::vector<int> &wg_first = h.wg_first;
     const int n_utt = pl->n_utt;
-    // workgroups that fit a CU at once: two when the instantiation keeps to 128 VGPRs (four waves per SIMD) and 80 KB of LDS; the synthesis
-    // and the 512-point detector instantiations take 256 VGPRs
-    const FeSel &k = e->sel;
-    const int max_wg = e->n_cu * ((fe_waves_per_simd(k.mode, k.vf, k.ss, k.sy) >= 4 && e->lds_bytes <= (size_t)LDS_2WG) ? 2 : 1);
+    const int max_wg = fe_max_wg(e);
     if (e->per_wave) {
         // chains per wave: whole utterances, longest first onto the least loaded chain (LPT), tile after tile
         std::vector<int> live;  // utterances that have at least one frame
@@ -2794,6 +2852,277 @@ float ctu_engine_last_kernel_ms(ctu_engine *e) {
     if (hipEventSynchronize(e->ev1) != hipSuccess) return -1.f;
     if (hipEventElapsedTime(&ms, e->ev0, e->ev1) != hipSuccess) return -1.f;
     return ms;
+}
+
+
+// ---- streaming input ---------------------------------------------------------------------------------------------------------
+int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
+    auto say = [&](const std::string &m) {
+        g_create_error = m;
+        if (reason && cap > 0) {
+            std::strncpy(reason, m.c_str(), (size_t)cap - 1);
+            reason[cap - 1] = 0;
+        }
+    };
+    say("");
+    try {
+        ctu::Opts o = ctu::Opts::from_args(to_args(argc, argv));
+        ctu::Design d(o);
+        spread_small_fft(d);
+        if (const std::string why = unsupported_reason(d); !why.empty()) {
+            say("ENGINE: configuration not on the accelerated path: " + why);
+            return CTU_ERR_UNSUPPORTED;
+        }
+        if (const std::string why = streams_unsupported_reason(d); !why.empty()) {
+            say("ENGINE: configuration cannot be streamed: " + why);
+            return CTU_ERR_UNSUPPORTED;
+        }
+        return CTU_OK;
+    } catch (const std::exception &ex) {
+        say(ex.what());
+        return CTU_ERR_OPTS;
+    }
+}
+
+int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry) {
+    if (window < 1 || wshift < 1 || wshift > window || total < 0) return CTU_ERR_INPUT;
+    const int64_t F = stream_frames(total, window, wshift);
+    if (carry) *carry = total - F * wshift;
+    return F;
+}
+
+int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, ctu_streams **out) {
+    if (!e || !out) return CTU_ERR_INPUT;
+    *out = nullptr;
+    if (n_streams < 1 || max_push_samples < 1 || max_push_samples > (1 << 26)) {
+        set_error(e, "ENGINE: a stream set needs at least one stream and pushes of 1 .. 2^26 samples");
+        return CTU_ERR_INPUT;
+    }
+    const ctu::Design &d = *e->design;
+    if (const std::string why = streams_unsupported_reason(d); !why.empty()) {
+        set_error(e, "ENGINE: configuration cannot be streamed: " + why);
+        return CTU_ERR_UNSUPPORTED;
+    }
+    if (e->per_wave || e->do_vad || e->ss) {
+        set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
+        return CTU_ERR_UNSUPPORTED;
+    }
+    std::unique_ptr<ctu_streams> st(new ctu_streams);
+    st->eng = e;
+    st->n_streams = n_streams;
+    st->max_push = max_push_samples;
+    st->cstride = (d.window + 7) / 8 * 8;
+    st->max_wg = fe_max_wg(e);
+    st->consumed.assign((size_t)n_streams, 0);
+    st->seen.assign((size_t)n_streams, 0);
+    // the longest slot: the lead, a full carry, a full push
+    const std::vector<int64_t> longest((size_t)n_streams, (int64_t)STREAM_LEAD + d.window - 1 + max_push_samples);
+    ctu_plan *pl = nullptr;
+    if (const int rc = ctu_plan_create(e, longest.data(), n_streams, &pl); rc != CTU_OK) return rc;
+    st->plan.reset(pl);
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        st->arena.alloc((size_t)pl->total_samples);
+        st->carry.alloc((size_t)n_streams * st->cstride);
+        st->state.alloc((size_t)n_streams);
+        HIP_TRY(hipMemset(st->arena.p, 0, st->arena.n * sizeof(int16_t)));
+        HIP_TRY(hipMemset(st->carry.p, 0, st->carry.n * sizeof(int16_t)));
+        HIP_TRY(hipMemset(st->state.p, 0, st->state.n * sizeof(StreamState)));
+        for (int k = 0; k < 2; k++) {
+            st->h_desc[k] = static_cast<StreamPush *>(ctu_host_alloc((size_t)n_streams * sizeof(StreamPush)));
+            if (!st->h_desc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+            st->d_desc[k].alloc((size_t)n_streams);
+            HIP_TRY(hipEventCreateWithFlags(&st->desc_free[k], hipEventDisableTiming));
+        }
+        for (hipEvent_t &v : st->ev) HIP_TRY(hipEventCreate(&v));
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) return rc;
+    *out = st.release();
+    return CTU_OK;
+}
+
+void ctu_streams_destroy(ctu_streams *st) {
+    if (!st) return;
+    (void)hipSetDevice(st->eng->device);
+    (void)hipDeviceSynchronize();  // pushes may still be in flight on the caller's streams
+    delete st;
+}
+
+int64_t ctu_streams_frames(const ctu_streams *st, int32_t id) {
+    if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
+    const ctu::Design &d = *st->eng->design;
+    return stream_frames(st->consumed[(size_t)id], d.window, d.wshift);
+}
+
+int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
+                     float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
+    ctu_plan *pl = st->plan.get();
+    auto refuse = [&](const char *m) {
+        set_error(e, std::string("ENGINE: ") + m);
+        return CTU_ERR_INPUT;
+    };
+    // ---- everything that can be refused is refused here, ahead of the first launch and of any change to the set
+    if (n < 0 || n > st->n_streams || (n && (!ids || !n_samples))) return refuse("push: bad stream count or null argument");
+    if (n == 0) return CTU_OK;
+    if (++st->push_no == 0) {  // (the counter wrapped: forget the marks)
+        std::fill(st->seen.begin(), st->seen.end(), 0u);
+        st->push_no = 1;
+    }
+    int64_t rows = 0, fresh = 0;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= st->n_streams) return refuse("push: stream id out of range");
+        if (st->seen[(size_t)ids[i]] == st->push_no) return refuse("push: a stream id appears twice");
+        st->seen[(size_t)ids[i]] = st->push_no;
+        if (n_samples[i] < 0 || n_samples[i] > st->max_push) return refuse("push: more samples than the set's max_push_samples (or fewer than none)");
+        if (n_samples[i] && (!sample_off || sample_off[i] < 0)) return refuse("push: null or negative sample offsets");
+        const int64_t c = st->consumed[(size_t)ids[i]];
+        rows += stream_frames(c + n_samples[i], d.window, d.wshift) - stream_frames(c, d.window, d.wshift);
+        fresh += n_samples[i];
+    }
+    if (fresh && !d_pcm) return refuse("push: null sample buffer");
+    if (rows > rows_capacity || (rows && !d_rows)) return refuse("push: the rows of this push do not fit rows_capacity");
+    hipStream_t s = (hipStream_t)stream;
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const int k = st->turn;
+        st->turn ^= 1;
+        HIP_TRY(hipEventSynchronize(st->desc_free[k]));  // (the push before last has read them; immediate before the first record)
+        StreamPush *h = st->h_desc[k];
+        int64_t so = PCM_HEAD, ro = 0;
+        int tiles = 0, slices = 1;
+        for (int i = 0; i < n; i++) {
+            const int64_t c = st->consumed[(size_t)ids[i]];
+            const int64_t F = stream_frames(c, d.window, d.wshift), T = stream_frames(c + n_samples[i], d.window, d.wshift) - F;
+            const int64_t len = STREAM_LEAD + (c - F * d.wshift) + n_samples[i];  // the stitched utterance, laid out by ctu_arena_layout's rule
+            h[i].src = n_samples[i] ? sample_off[i] : 0;
+            h[i].slot = so;
+            h[i].row0 = ro;
+            h[i].id = ids[i];
+            h[i].n = (int)n_samples[i];
+            h[i].tile0 = tiles;
+            h[i].pad = 0;
+            so += (len + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN;
+            ro += T;
+            tiles += (int)((T + TILE - 1) / TILE);
+            slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
+            if (row_counts) row_counts[i] = T;
+            st->consumed[(size_t)ids[i]] = c + n_samples[i];
+        }
+        if (so + PCM_TAIL > pl->total_samples || tiles > (int)pl->tiles.n) throw std::runtime_error("internal: a push beyond the set's arena");
+        HIP_TRY(hipMemcpyAsync(st->d_desc[k].p, h, (size_t)n * sizeof(StreamPush), hipMemcpyHostToDevice, s));
+        StreamParams sp;
+        sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
+        sp.cstride = st->cstride; sp.window = d.window; sp.wshift = d.wshift;
+        sp.n_tiles = tiles; sp.grid = std::max(1, std::min(tiles, st->max_wg));
+        HIP_TRY(hipEventRecord(st->ev[0], s));
+        hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)slices), dim3(256), 0, s, sp);
+        HIP_TRY(hipEventRecord(st->ev[1], s));
+        HIP_TRY(hipGetLastError());
+        // the front end and its tails, as a run of the set's plan cut down to this push
+        pl->n_tiles = tiles;
+        pl->grid = sp.grid;
+        pl->total_frames = ro;
+        int rc = CTU_OK;
+        if (tiles) rc = ctu_engine_run(e, pl, st->arena.p, d_rows, nullptr, s);
+        HIP_TRY(hipEventRecord(st->ev[2], s));
+        hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
+        HIP_TRY(hipEventRecord(st->ev[3], s));
+        HIP_TRY(hipEventRecord(st->desc_free[k], s));
+        HIP_TRY(hipGetLastError());
+        st->timed = true;
+        return rc;
+    });
+}
+
+int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples, float *h_rows,
+                          int64_t rows_capacity, int64_t *row_counts) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const int D = e->design->D;
+    if (n < 0 || n > st->n_streams || (n && (!ids || !n_samples || !h_pcm))) {
+        set_error(e, "ENGINE: push: bad stream count or null argument");
+        return CTU_ERR_INPUT;
+    }
+    int64_t fresh = 0;
+    for (int i = 0; i < n; i++) {
+        if (n_samples[i] < 0 || n_samples[i] > st->max_push || (n_samples[i] && !h_pcm[i])) {
+            set_error(e, "ENGINE: push: more samples than the set's max_push_samples (or fewer than none), or a null sample buffer");
+            return CTU_ERR_INPUT;
+        }
+        fresh += n_samples[i];
+    }
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const size_t cap = (size_t)st->n_streams * (size_t)st->max_push;
+        if (!st->h_stage) {
+            st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
+            if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
+            st->d_stage.alloc(cap);
+            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->row_off[st->plan->n_utt], 1) * D);
+        }
+        st->offs.resize((size_t)n);
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            st->offs[(size_t)i] = at;
+            if (n_samples[i]) std::memcpy(st->h_stage + at, h_pcm[i], (size_t)n_samples[i] * sizeof(int16_t));
+            at += n_samples[i];
+        }
+        if (fresh) HIP_TRY(hipMemcpyAsync(st->d_stage.p, st->h_stage, (size_t)fresh * sizeof(int16_t), hipMemcpyHostToDevice, nullptr));
+        std::vector<int64_t> counts((size_t)std::max(n, 1));
+        // the device rows hold any push of the set; what the caller's buffer holds is the device form's check
+        const int rc = ctu_streams_push(st, n, ids, st->d_stage.p, st->offs.data(), n_samples, h_rows ? st->d_rows.p : nullptr, h_rows ? rows_capacity : 0,
+                                        counts.data(), nullptr);
+        if (rc != CTU_OK) return rc;
+        int64_t rows = 0;
+        for (int i = 0; i < n; i++) {
+            rows += counts[(size_t)i];
+            if (row_counts) row_counts[i] = counts[(size_t)i];
+        }
+        if (rows) {  // page-locked rows at the link rate, pageable ones through the runtime's staging (as run_host_ranges downloads)
+            if (is_pinned(h_rows)) HIP_TRY(hipMemcpyAsync(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost, nullptr));
+            else HIP_TRY(hipMemcpy(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost));
+        }
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return CTU_OK;
+    });
+}
+
+int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream) {
+    (void)d_rows;
+    (void)rows_capacity;
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    if (id < 0 || id >= st->n_streams) {
+        set_error(e, "ENGINE: finish: stream id out of range");
+        return CTU_ERR_INPUT;
+    }
+    if (row_count) *row_count = 0;  // fread() comes up short on a trailing partial window and the file ends there (src/io/in.cc:314,438)
+    const int64_t total = st->consumed[(size_t)id];
+    st->consumed[(size_t)id] = 0;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), (hipStream_t)stream));
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) return rc;
+    if (total > 0 && total < e->design->window - e->design->wshift) {
+        set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
+        return CTU_ERR_INPUT;
+    }
+    return CTU_OK;
+}
+
+int ctu_streams_last_push_ms(ctu_streams *st, float *ms3) {
+    if (!st || !ms3 || !st->timed) return CTU_ERR_INPUT;
+    if (hipEventSynchronize(st->ev[3]) != hipSuccess) return CTU_ERR_DEVICE;
+    if (hipEventElapsedTime(&ms3[0], st->ev[0], st->ev[1]) != hipSuccess) return CTU_ERR_DEVICE;
+    if (hipEventElapsedTime(&ms3[1], st->ev[1], st->ev[2]) != hipSuccess) return CTU_ERR_DEVICE;
+    if (hipEventElapsedTime(&ms3[2], st->ev[2], st->ev[3]) != hipSuccess) return CTU_ERR_DEVICE;
+    return CTU_OK;
 }
 
 }  // extern "C"

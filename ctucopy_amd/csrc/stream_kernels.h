@@ -1,0 +1,116 @@
+// Streaming input (include/ctu_engine.h: ctu_streams_*): the two kernels around the front end of a push.
+// Included by engine.hip.
+//
+// A stream is a file whose samples arrive in pushes.  Frame t of a file reads samples [t wshift - 1, t wshift + window): its window and,
+// with pre-emphasis, the sample ahead of it (src/io/in.cc:365,384: preemtmp; 0 ahead of frame 0).  DC removal (-remove_dc) takes the mean
+// of the frame's own window (in.cc:375-382) and needs nothing more.  So after `total` samples, of which F = stream_frames() frames have
+// come out, the next frame still needs the samples from F wshift - 1 on: the carry, at most `window` values
+//   carry[0]      the sample ahead of the next frame (anything while F = 0: the kernels put 0 there at a file's start, TileRec::t0)
+//   carry[1 + k]  sample F wshift + k of the file, k < total - F wshift <= window - 1
+// kept per stream in HBM beside the count of samples taken.
+//
+//   stream_stitch_kernel  writes lead | carry | new samples of every pushed stream into its slot of the push arena - the slot
+//                         ctu_arena_layout's rule gives an utterance of 8 + carry + new samples, the next frame's first sample 8 samples
+//                         into it - and the tile records of the frames the stream now completes: what an offline plan holds for an
+//                         utterance of that many frames, except that t0 counts from the file's start (only t0 + frame == 0 is ever
+//                         asked of it on the chains a stream set accepts: the first sample of a file has no history)
+//   stream_carry_kernel   behind it: the new carry out of the slot, the new count
+// Vector loads and stores only; sources are 2-byte aligned (as the front ends' pcm4 loads are), the slots and the carry rows 16-byte
+// aligned, so every store is a b128.  A workgroup of 256 lanes per stream and slice of 2048 slot samples; no atomics: a stream id
+// appears once in a push.
+//
+// gfx950, hipcc -O3: stream_stitch_kernel 14 VGPRs, 56 SGPRs; stream_carry_kernel 17 VGPRs, 45 SGPRs; no spills, no scratch, no LDS.
+#pragma once
+
+namespace {
+
+constexpr int STREAM_LEAD = 8;       // samples of a slot ahead of the next frame's first one (= PCM_ALIGN: the frame starts 16-byte aligned)
+constexpr int STREAM_SLICE = 2048;   // slot samples per workgroup of stream_stitch_kernel: 256 lanes x one b128 store
+
+// Frames a file of `total` samples has produced: floor((total - (window - wshift)) / wshift), none while it is shorter than the
+// window - wshift samples rawIN::new_file loads first (src/io/in.cc:277,314).  A trailing partial window never makes a frame.
+__host__ __device__ inline long long stream_frames(long long total, int window, int wshift) {
+    const long long pre = window - wshift;
+    return total < pre ? 0 : (total - pre) / wshift;
+}
+
+struct StreamState {
+    long long consumed;  // samples of the current file taken so far
+};
+
+// One stream of a push (host-built: the prefix sums over the push are the host's, which mirrors the counts)
+struct StreamPush {
+    long long src;    // where its new samples start in the caller's arena (samples)
+    long long slot;   // where its slot starts in the push arena (samples, a multiple of PCM_ALIGN)
+    long long row0;   // first row of the push it writes
+    int id, n;        // stream, new samples
+    int tile0, pad;   // first tile record it fills
+};
+
+struct StreamParams {
+    const StreamPush *push;
+    StreamState *state;
+    int16_t *carry;         // [n_streams][cstride]
+    int16_t *arena;         // the push arena
+    const int16_t *src;     // the caller's new samples
+    TileRec *tiles;
+    int cstride, window, wshift;
+    int n_tiles, grid;      // tiles of the whole push and the workgroups of the front-end launch: tile i is followed by tile i + grid
+};
+
+__device__ __forceinline__ unsigned pack2(const int16_t a, const int16_t b) { return (unsigned)(unsigned short)a | ((unsigned)(unsigned short)b << 16); }
+
+// grid (pushed streams, slices), 256 lanes
+__global__ __launch_bounds__(256) void stream_stitch_kernel(const StreamParams p) {
+    const StreamPush d = p.push[blockIdx.x];
+    const long long total = p.state[d.id].consumed;
+    const long long F = stream_frames(total, p.window, p.wshift);
+    const int c = (int)(total - F * p.wshift);  // carried samples of the next frame, < window
+    const int T = (int)(stream_frames(total + d.n, p.window, p.wshift) - F);
+    const int len = STREAM_LEAD + c + d.n;
+    const int16_t *cr = p.carry + (size_t)d.id * p.cstride;
+    const int16_t *nw = p.src + d.src;
+    const int q = blockIdx.y * 256 + threadIdx.x;  // which 8 samples of the slot
+    if (8 * q < len) {
+        int16_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int r = 8 * q + k - STREAM_LEAD;  // position from the next frame's first sample
+            int16_t x = 0;
+            if (r >= -1 && r < c) x = cr[r + 1];
+            else if (r >= c && r < c + d.n) x = nw[r - c];
+            v[k] = x;
+        }
+        *reinterpret_cast<uint4 *>(p.arena + d.slot + 8 * (long long)q) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+    }
+    if (blockIdx.y == 0) {
+        const int t0 = (int)(F < 0x3fffffff ? F : 0x3fffffff);  // frames ahead of the push; only "none" matters (file start)
+        for (int t = threadIdx.x; 64 * t < T; t += 256) {
+            const int idx = d.tile0 + t;
+            const long long sbase = d.slot + STREAM_LEAD + (long long)t * TILE * p.wshift, rbase = d.row0 + (long long)t * TILE;
+            int4 *w = reinterpret_cast<int4 *>(p.tiles + idx);
+            w[0] = make_int4((int)(sbase & 0xffffffff), (int)(sbase >> 32), (int)(rbase & 0xffffffff), (int)(rbase >> 32));
+            w[1] = make_int4(min(TILE, T - TILE * t), t0 + TILE * t, idx + p.grid < p.n_tiles ? idx + p.grid : -1, t0 + T);
+        }
+    }
+}
+
+// grid (pushed streams), 256 lanes: the slot's samples from T wshift - 1 frames on are the next carry
+__global__ __launch_bounds__(256) void stream_carry_kernel(const StreamParams p) {
+    const StreamPush d = p.push[blockIdx.x];
+    const long long total = p.state[d.id].consumed;
+    const long long F = stream_frames(total, p.window, p.wshift), F1 = stream_frames(total + d.n, p.window, p.wshift);
+    const int c1 = (int)(total + d.n - F1 * p.wshift);
+    const int16_t *from = p.arena + d.slot + (STREAM_LEAD - 1) + (F1 - F) * p.wshift;  // from[0]: the sample ahead of the next frame
+    int16_t *cr = p.carry + (size_t)d.id * p.cstride;
+    for (int q = threadIdx.x; 8 * q < p.cstride; q += 256) {
+        int16_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = 8 * q + k <= c1 ? from[8 * q + k] : (int16_t)0;
+        *reinterpret_cast<uint4 *>(cr + 8 * q) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+    }
+    __syncthreads();  // every lane has read the old count
+    if (threadIdx.x == 0) p.state[d.id].consumed = total + d.n;
+}
+
+}  // namespace

@@ -35,7 +35,9 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_plan_row_offsets", "ctu_arena_layout", "ctu_plan_total_samples", "ctu_plan_total_frames", "ctu_engine_run",
            "ctu_engine_run_host", "ctu_host_alloc", "ctu_host_free", "ctu_engine_reset_chain", "ctu_engine_set_vad_stream", "ctu_vad_ring_step", "ctu_plan_set_vad_ring", "ctu_vad_ring_rows", "ctu_decode_g711", "ctu_engine_last_kernel_ms", "ctu_engine_kernel_name", "ctu_engine_phase2_walk", "ctu_cmvn_cols", "ctu_cmvn_accumulate", "ctu_cmvn_apply",
            "ctu_cmvn_accumulate_host", "ctu_cmvn_apply_host", "ctu_plan_out_samples", "ctu_engine_run_signal",
-           "ctu_engine_run_signal_host", "ctu_rows_arena_layout", "ctu_engine_run_rows", "ctu_engine_run_rows_host"]
+           "ctu_engine_run_signal_host", "ctu_rows_arena_layout", "ctu_engine_run_rows", "ctu_engine_run_rows_host",
+           "ctu_streams_create", "ctu_streams_destroy", "ctu_streams_config_check", "ctu_streams_push", "ctu_streams_push_host",
+           "ctu_streams_finish", "ctu_streams_frames", "ctu_streams_step", "ctu_streams_last_push_ms"]
 
 _lib = None
 
@@ -107,6 +109,19 @@ def load_library():
     L.ctu_rows_arena_layout.argtypes = [ctypes.POINTER(i64), i32, i32, ctypes.POINTER(i64)]
     L.ctu_engine_run_rows.argtypes = [vp, vp, vp, vp, vp]
     L.ctu_engine_run_rows_host.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "ctu_streams_create"):  # (as above: older builds loaded for an A/B have no stream sets)
+        L.ctu_streams_create.argtypes = [vp, i32, i64, ctypes.POINTER(vp)]
+        L.ctu_streams_destroy.restype = None
+        L.ctu_streams_destroy.argtypes = [vp]
+        L.ctu_streams_config_check.argtypes = [ctypes.c_int, argv_t, ctypes.c_char_p, i64]
+        L.ctu_streams_push.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]
+        L.ctu_streams_push_host.argtypes = [vp, i32, vp, vp, vp, vp, i64, vp]
+        L.ctu_streams_finish.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64), vp]
+        L.ctu_streams_frames.restype = i64
+        L.ctu_streams_frames.argtypes = [vp, i32]
+        L.ctu_streams_step.restype = i64
+        L.ctu_streams_step.argtypes = [i32, i32, i64, ctypes.POINTER(i64)]
+        L.ctu_streams_last_push_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     _lib = L
     return L
 
@@ -152,6 +167,96 @@ def config_table(args, name):
     out = np.zeros(int(cnt), dtype=np.float64)
     L.ctu_config_table(n, arr, name.encode(), out.ctypes.data, cnt)
     return out
+
+
+def streams_config_check(args):
+    """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
+    CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give."""
+    L = load_library()
+    n, arr = _argv(args)
+    buf = ctypes.create_string_buffer(1024)
+    rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
+    return int(rc), buf.value.decode()
+
+
+def streams_step(window, wshift, total):
+    """(frames produced, samples the next frame already has) of a stream after `total` samples (ctu_streams_step)."""
+    carry = ctypes.c_int64(0)
+    f = load_library().ctu_streams_step(int(window), int(wshift), int(total), ctypes.byref(carry))
+    if f < 0:
+        raise CtuError(int(f), "ctu_streams_step: bad argument")
+    return int(f), int(carry.value)
+
+
+class Streams:
+    """A set of `n` streams on an engine (Engine.streams): PCM in per stream as it arrives, the rows of the frames it completes out."""
+
+    def __init__(self, engine, n, max_push):
+        L = load_library()
+        self.engine, self.n, self.max_push = engine, int(n), int(max_push)
+        h = ctypes.c_void_p()
+        rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
+        if rc != CTU_OK:
+            raise CtuError(rc, L.ctu_last_error(engine._h).decode())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ctu_streams_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def push(self, chunks):
+        """{stream id: int16 array} -> {stream id: float32 [rows, D]}: the frames the new samples complete (host buffers)."""
+        ids = np.array(list(chunks.keys()), dtype=np.int32)
+        arrs = [np.ascontiguousarray(chunks[k], dtype=np.int16).reshape(-1) for k in chunks]
+        ns = np.array([a.size for a in arrs], dtype=np.int64)
+        ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        D = self.engine.dims.row_floats
+        sh = self.engine.dims.wshift
+        cap = int(sum(int(a) // sh + 1 for a in ns))  # at most one frame more than whole hops per stream
+        rows = np.empty((cap, D), dtype=np.float32)
+        counts = np.zeros(max(len(arrs), 1), dtype=np.int64)
+        rc = load_library().ctu_streams_push_host(self._h, len(arrs), ids.ctypes.data, ptrs, ns.ctypes.data, rows.ctypes.data, cap, counts.ctypes.data)
+        self.engine._check(rc)
+        out, at = {}, 0
+        for k, c in zip(chunks, counts):
+            out[k] = rows[at:at + int(c)]
+            at += int(c)
+        return out
+
+    def push_device(self, ids, pcm, sample_off, n_samples, rows, stream=None):
+        """Device form: pcm a torch int16 CUDA tensor holding stream ids[i]'s n_samples[i] new samples at sample_off[i]; rows a float32
+        CUDA tensor [capacity, D].  Returns the row counts per stream (numpy int64); asynchronous on `stream`."""
+        import torch
+        assert pcm.is_cuda and pcm.dtype == torch.int16 and rows.is_cuda and rows.dtype == torch.float32
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int64)
+        assert ids.size == off.size == ns.size and (ns.size == 0 or int((off + ns).max()) <= pcm.numel())
+        counts = np.zeros(max(ids.size, 1), dtype=np.int64)
+        s = stream if stream is not None else torch.cuda.current_stream(pcm.device)
+        cap = rows.numel() // self.engine.dims.row_floats
+        self.engine._check(load_library().ctu_streams_push(self._h, int(ids.size), ids.ctypes.data, pcm.data_ptr(), off.ctypes.data, ns.ctypes.data,
+                                                           rows.data_ptr(), cap, counts.ctypes.data, s.cuda_stream))
+        return counts[:ids.size]
+
+    def finish(self, sid):
+        """Ends stream `sid`'s file: its remaining rows ([0, D]: the reference makes no frame of a trailing partial window); the stream then
+        starts a new file."""
+        cnt = ctypes.c_int64(0)
+        self.engine._check(load_library().ctu_streams_finish(self._h, int(sid), None, 0, ctypes.byref(cnt), None))
+        return np.empty((int(cnt.value), self.engine.dims.row_floats), dtype=np.float32)
+
+    def frames(self, sid):
+        return int(load_library().ctu_streams_frames(self._h, int(sid)))
+
+    def last_push_ms(self):
+        """(stream_stitch_kernel, front end and tails, stream_carry_kernel) of the last push, in ms (HIP events)."""
+        ms = (ctypes.c_float * 3)()
+        self.engine._check(load_library().ctu_streams_last_push_ms(self._h, ms))
+        return tuple(float(x) for x in ms)
 
 
 class Plan:
@@ -228,6 +333,10 @@ class Engine:
 
     def plan(self, nsamples):
         return Plan(self, nsamples)
+
+    def streams(self, n, max_push):
+        """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
+        return Streams(self, n, max_push)
 
     def _check(self, rc):
         if rc != CTU_OK:

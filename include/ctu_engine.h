@@ -36,6 +36,7 @@ extern "C" {
 
 typedef struct ctu_engine ctu_engine;
 typedef struct ctu_plan ctu_plan;
+typedef struct ctu_streams ctu_streams;
 
 enum {
     CTU_OK = 0,
@@ -150,6 +151,52 @@ int ctu_engine_run_rows(ctu_engine *, const ctu_plan *, const void *d_rows_in, f
 /* Host-buffer convenience, the same pipeline as ctu_engine_run_host: its 32 MiB rule decides on the ranges (the arena's bytes:
  * four per word; CTU_HOST_CHUNKS overrides), pageable buffers go through the runtime's staging.  Synchronised on return. */
 int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_in, float *h_rows);
+
+/* ---- streaming input: PCM pushed in chunks per stream, the rows of the offline run ---------------------------------
+ * Replaces the reference's online mode (-online_in: rawIN::new_file on stdin, src/io/in.cc:268, and the same get_frame loop) for
+ * many live channels at once: a stream is a file whose samples arrive in pushes, and a push computes every frame that its
+ * samples complete - frame t of a stream comes out with the push that brings sample t * wshift + window - 1.  The rows are those
+ * ctu_engine_run_host writes for the whole file: bit for bit when every push ends a multiple of eight frames into the file (the
+ * front ends step through a tile in groups of eight frames), else to rounding.  They do not depend on
+ * what else is in the push.
+ *
+ * Per stream the device keeps the samples the next frame still reads - the last window - wshift .. window - 1 samples and the
+ * one ahead of them that pre-emphasis reaches back to (src/io/in.cc:365,384) - and the count of samples taken; nothing but the
+ * row counts, which the host derives from the lengths, comes back between pushes.
+ *
+ * Streamed are the chains whose frames share nothing but samples: every feature kind, filter bank, FFT size and energy
+ * column ctu_engine_create accepts, without -nr_mode, -remove_dc1, the VAD module, -fea_delta / -fea_trap / trapdct, CMS,
+ * CMVN, speech output or HTK feature input.  ctu_streams_create refuses those with CTU_ERR_UNSUPPORTED and the option's name in
+ * ctu_last_error; ctu_streams_config_check says the same from the command line alone (no device; `reason` receives the text).
+ *
+ * A push names n different streams (a repeat, an id outside the set, more than max_push_samples for one stream or more rows
+ * than rows_capacity: CTU_ERR_INPUT before anything is launched or changed; the set stays usable).  Stream stream_ids[i] takes
+ * n_samples[i] >= 0 samples from d_pcm + sample_off[i] (2-byte aligned is enough).  The rows of the push are written to d_rows one
+ * stream after the other in the order of stream_ids, row_counts[i] of them for stream i (row_counts is host memory and is
+ * filled on return; it may be NULL).  Asynchronous on `stream`; d_pcm may be reused once the work enqueued has run.  The calls on
+ * one set must be ordered: one hipStream_t, or the caller's own synchronisation.  One set per engine runs at a time. */
+int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
+void ctu_streams_destroy(ctu_streams *);
+int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
+int ctu_streams_push(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *d_pcm, const int64_t *sample_off,
+                     const int64_t *n_samples, float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream);
+/* Host-buffer form: h_pcm[i] points at stream i's new samples, h_rows receives the rows; page-locked rows (ctu_host_alloc) are
+ * DMA-ed, pageable ones go through the runtime's staging, as in ctu_engine_run_host.  Synchronised on return. */
+int ctu_streams_push_host(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *const *h_pcm, const int64_t *n_samples,
+                          float *h_rows, int64_t rows_capacity, int64_t *row_counts);
+/* The end of a stream's file.  The reference's loop ends when fread comes up short (src/io/in.cc:314,438): a trailing partial
+ * window makes no frame, so every row of the file is out already and *row_count is 0 (d_rows / rows_capacity are there for the
+ * chains that will hold rows back: delta windows).  A file of 1 .. window - wshift - 1 samples is the reference's "IO: Signal
+ * shorter than one frame!": CTU_ERR_INPUT.  Either way the stream starts a new file with its next push. */
+int ctu_streams_finish(ctu_streams *, int32_t stream_id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream);
+/* Rows the stream's current file has produced so far. */
+int64_t ctu_streams_frames(const ctu_streams *, int32_t stream_id);
+/* The arithmetic of a stream on its own (pure): the frames a file has produced after `total` samples - the frame count of
+ * ctu_num_frames, 0 while it has none - and in *carry (may be NULL) the samples the next frame already has. */
+int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry);
+/* Times of the last push on the set, measured with HIP events on its stream: ms3[0] stream_stitch_kernel, ms3[1] the front end
+ * and its tails, ms3[2] stream_carry_kernel.  Blocks until that push has finished. */
+int ctu_streams_last_push_ms(ctu_streams *, float *ms3);
 
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53
  * (alaw2lin, called from src/io/in.cc:481-560) bit for bit.  The caller lays the codes of an utterance at the same offsets

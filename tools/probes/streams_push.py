@@ -1,0 +1,91 @@
+"""Streaming input, coverage figures: what a push costs beside the front end it feeds.
+
+MFCC-13 at 16 kHz, pushes of 10 hops to each of N concurrent streams (N = 1 000 and 10 000), device-resident samples and rows.
+Per N: the three spans of a push from HIP events on its stream (stream_stitch_kernel | front end | stream_carry_kernel, median
+of the timed pushes), the push rate in frames/s from the host's clock around synchronised pushes, and the rate of one offline
+device-resident run over the same frames (N utterances of 10 frames; the offline path is the parent commit's).
+
+    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+
+from ctucopy_amd import Engine  # noqa: E402
+from tests.util import C2, synth_utt  # noqa: E402
+
+
+def measure(n, pushes, warmup):
+    import torch
+    eng = Engine(C2)
+    w, s, D = eng.dims.window, eng.dims.wshift, eng.dims.row_floats
+    hop = 10 * s
+    total = w - s + hop * (warmup + pushes)
+    x = synth_utt(1, total)
+    pcm = torch.from_numpy(np.tile(x, n)).cuda()
+    ids = np.arange(n, dtype=np.int32)
+    base = np.arange(n, dtype=np.int64) * total
+    st = eng.streams(n, hop)
+    rows = torch.empty((n * 11, D), dtype=torch.float32, device="cuda")
+    cnt = st.push_device(ids, pcm, base, np.full(n, w - s), rows)   # the samples ahead of the first hop: no frame yet
+    assert int(cnt.sum()) == 0
+    spans, wall = [], []
+    for k in range(warmup + pushes):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        cnt = st.push_device(ids, pcm, base + (w - s) + k * hop, np.full(n, hop), rows)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        assert int(cnt.min()) == int(cnt.max()) == 10
+        if k >= warmup:
+            spans.append(st.last_push_ms())
+            wall.append(t1 - t0)
+    med = [statistics.median(v[i] for v in spans) for i in range(3)]
+    push_rate = 10 * n / statistics.median(wall)
+    # the same frames offline: N utterances of ten frames, device-resident
+    utts = [x[:w + 9 * s]] * n
+    plan = eng.plan([len(u) for u in utts])
+    arena = torch.from_numpy(plan.pack(utts)).cuda()
+    out = torch.empty((plan.total_frames, D), dtype=torch.float32, device="cuda")
+    off_wall, off_kernel = [], []
+    for k in range(warmup + pushes):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.run_device(plan, arena, rows=out)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if k >= warmup:
+            off_wall.append(t1 - t0)
+            off_kernel.append(eng.last_kernel_ms())
+    assert plan.total_frames == 10 * n
+    return med, push_rate, statistics.median(off_kernel), 10 * n / statistics.median(off_wall)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--pushes", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    lines = ["# tools/probes/streams_push.py: MFCC-13, 16 kHz, pushes of 10 hops per stream, device-resident; medians of %d pushes after %d" % (a.pushes, a.warmup),
+             "# spans from HIP events on the push's stream; rates from the host's clock around synchronised calls (launch overhead included)",
+             "# streams  stitch_ms  frontend_ms  carry_ms  push_frames_per_s  offline_frontend_ms  offline_frames_per_s"]
+    for n in (1000, 10000):
+        med, pr, ok, orate = measure(n, a.pushes, a.warmup)
+        lines.append("%7d  %.4f  %.4f  %.4f  %.3e  %.4f  %.3e" % (n, med[0], med[1], med[2], pr, ok, orate))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
