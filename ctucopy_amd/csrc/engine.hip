@@ -15,6 +15,7 @@
 //   bigfft_kernel.h    1024 .. 4096-point frames, a workgroup per frame; bigburg_kernel.h the Burg-cepstral criterion / detector there;
 //   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
 //   stream_kernels.h   streaming input: carry | new samples into the slots of a push arena, the tile records of the push, the next carry
+//   stream_rows_kernels.h  streaming input with row state: delta chain / stacking and CMS by absolute frame index, the base-row history
 //
 // Data layout in HBM
 //   pcm   : one packed int16 arena; utterance i starts at sample_off[i] (multiple of 8 samples)
@@ -112,6 +113,7 @@ enum BigPath { BIG_NONE, BIG_WAVE1K, BIG_SS, BIG_FFT };
 }  // namespace
 
 #include "post_kernels.h"
+#include "stream_rows_kernels.h"
 #include "signal_kernels.h"
 
 struct ctu_engine {
@@ -249,6 +251,14 @@ struct ctu_streams {
     int turn = 0;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around stream_stitch_kernel and stream_carry_kernel of the last push
     bool timed = false;
+    // CTU_STREAMS_ROW_STATE with a delta chain, stacking or CMS (stream_rows_kernels.h): the halo, the largest window, the history's rows,
+    // the two histories of every stream and which one is current, the running means, the descriptors of the row kernels
+    bool held = false;
+    int H = 0, wmax = 0, C = 0;
+    DevBuf<float> hist, means;
+    std::vector<uint8_t> hsel;
+    RowPush *h_rdesc[2] = {nullptr, nullptr};
+    DevBuf<RowPush> d_rdesc[2];
     // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
     int16_t *h_stage = nullptr;
     DevBuf<int16_t> d_stage;
@@ -256,6 +266,7 @@ struct ctu_streams {
     std::vector<int64_t> offs;
     ~ctu_streams() {
         for (StreamPush *h : h_desc) ctu_host_free(h);
+        for (RowPush *h : h_rdesc) ctu_host_free(h);
         ctu_host_free(h_stage);
         for (hipEvent_t v : desc_free)
             if (v) (void)hipEventDestroy(v);
@@ -446,7 +457,8 @@ std::string unsupported_reason(const ctu::Design &d) {
 
 // Streaming input (ctu_streams_create): what an accepted configuration carries from one frame of a file to the next beyond the samples
 // themselves.  A stream set keeps samples (stream_kernels.h), so every such chain is refused by the option that brings the state in.
-std::string streams_unsupported_reason(const ctu::Design &d) {
+// With CTU_STREAMS_ROW_STATE the set keeps base rows and running means as well (stream_rows_kernels.h): the delta chain, stacking and CMS pass.
+std::string streams_unsupported_reason(const ctu::Design &d, uint32_t flags = 0) {
     const ctu::Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
     if (d.signal_out) return "-format_out raw | wave (speech output: the overlap-add runs across a file's frames)";
@@ -454,8 +466,9 @@ std::string streams_unsupported_reason(const ctu::Design &d) {
     if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
     if (o.do_vad()) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";
     if (d.kind == ctu::FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
-    if (d.post_order > 0) return d.post_stack ? "-fea_trap (stacking spans 2 * trap_win + 1 frames)" : "-fea_delta (the delta chain spans the frames of its windows)";
-    if (d.cms) return d.cms == 1 ? "-fea_Z_exp (CMS: the running mean runs along the file)" : "-fea_Z_block (CMS: the block mean spans its window of frames)";
+    const bool row_state = (flags & CTU_STREAMS_ROW_STATE) != 0;
+    if (d.post_order > 0 && !row_state) return d.post_stack ? "-fea_trap (stacking spans 2 * trap_win + 1 frames)" : "-fea_delta (the delta chain spans the frames of its windows)";
+    if (d.cms && !row_state) return d.cms == 1 ? "-fea_Z_exp (CMS: the running mean runs along the file)" : "-fea_Z_block (CMS: the block mean spans its window of frames)";
     if (o.stat_cmvn || o.apply_cmvn) return "-stat_cmvn / -apply_cmvn (CMVN: statistics over whole lists)";
     if (d.wshift > d.window) return "-s above -w (frames that leave samples out)";
     return "";
@@ -1590,8 +1603,8 @@ void stage_dctw(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KParams 
 }
 
 // Delta chain / stacking from the base rows into the caller's rows (post_kernels.h)
-void stage_post(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
-    const ctu::Design &d = *e->design;
+// (the parameter block and the LDS bytes are also stream_post_kernel's)
+PostParams post_params(const ctu::Design &d, size_t *shm) {
     PostParams pp;
     std::memset(&pp, 0, sizeof pp);
     pp.fea_c = d.o.fea_ncepcoefs + 1; pp.Dbase = d.Dbase; pp.D = d.D;
@@ -1605,8 +1618,14 @@ void stage_post(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
         H += d.post_w[j];
     }
     const int R = 64 + 2 * H;
-    const size_t shm = ((size_t)R * d.Dbase + (size_t)(d.post_stack ? 0 : d.post_order) * R * pp.fea_c) * sizeof(float);
+    *shm = ((size_t)R * d.Dbase + (size_t)(d.post_stack ? 0 : d.post_order) * R * pp.fea_c) * sizeof(float);
     if ((size_t)R * d.Dbase > 256 * 12) throw std::runtime_error("delta tile larger than the prefetch registers");
+    return pp;
+}
+void stage_post(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    size_t shm = 0;
+    const PostParams pp = post_params(d, &shm);
     const int pgrid = std::min(pl->n_trap_chunks, e->n_cu * 8);
     const bool std39 = !d.post_stack && d.post_order == 2 && pp.fea_c == 13 && d.Dbase == 13 && d.D == 39 && pp.w[0] == 2 && pp.w[1] == 2;
     lift<0, 1>(std39, [&](auto v) {
@@ -1616,12 +1635,16 @@ void stage_post(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
 }
 
 // CMS, exponential or over a block window (post_kernels.h)
-void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
-    const ctu::Design &d = *e->design;
+CmsParams cms_params(const ctu::Design &d) {
     CmsParams cp;
     std::memset(&cp, 0, sizeof cp);
     cp.ncols = d.cms_cols; cp.Dbase = d.Dbase; cp.D = d.D; cp.copy_rest = d.post_order > 0 ? 0 : 1;
     cp.L = d.o.length_b; cp.z = d.o.fea_Z_exp; cp.omz = 1 - d.o.fea_Z_exp;
+    return cp;
+}
+void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+    const ctu::Design &d = *e->design;
+    const CmsParams cp = cms_params(d);
     if (d.cms == 1) hipLaunchKernelGGL(cms_exp_kernel, dim3((pl->n_utt + 1) / 2), dim3(64), 0, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->n_utt, cp);
     else
         hipLaunchKernelGGL(cms_block_kernel, dim3(pl->n_trap_chunks), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, pl->base_rows.p, d_rows,
@@ -2273,7 +2296,9 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
     return rc;
 }
 
-int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream) {
+// A run of a plan.  `row_stages` off stops ahead of stage_post and stage_cms with the base rows in the plan's scratch: a stream set with
+// row state runs its own forms of the two (stream_rows_kernels.h) over them and its history.
+static int run_chain(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
     if (e->rows_in) {
         set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows");
@@ -2326,14 +2351,18 @@ int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, floa
         if (lp_tail_runs(e)) stage_lp_tail(e, pl, s, kp);
         if (e->do_vad) stage_burg_vad(e, pl, s);
         if (d.kind == ctu::FeaKind::TrapDct) stage_trap(e, pl, s, d_rows);
-        if (d.post_order > 0) stage_post(e, pl, s, d_rows);
-        if (d.cms) stage_cms(e, pl, s, d_rows);
+        if (d.post_order > 0 && row_stages) stage_post(e, pl, s, d_rows);
+        if (d.cms && row_stages) stage_cms(e, pl, s, d_rows);
         if (e->do_vad && e->vf && pl->n_live > 0) stage_fused_vad(e, pl, s, d_vad);
         if (e->do_vad && !e->vf) stage_vad_decide(e, pl, s, d_rows, d_vad);
         if (e->do_vad && d.o.vad_filter_order > 1) stage_short_files(e, pl, s, d_vad);
         if (e->do_vad && !pl->ring_hidx.empty() && pl->total_frames > 0) stage_ring_gather(e, pl, s, d_rows);
         return CTU_OK;
     });
+}
+
+int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream) {
+    return run_chain(e, pl, d_pcm, d_rows, d_vad, stream, true);
 }
 
 void *ctu_host_alloc(size_t bytes) {
@@ -2856,7 +2885,26 @@ float ctu_engine_last_kernel_ms(ctu_engine *e) {
 
 
 // ---- streaming input ---------------------------------------------------------------------------------------------------------
+namespace {
+// The halo H and the largest window of a configuration's delta chain or stacking (0, 0 without either)
+void stream_halo(const ctu::Design &d, int *H, int *wmax) {
+    *H = *wmax = 0;
+    for (int j = 0; j < d.post_order; j++) {
+        if (!d.post_stack || j == 0) *H += d.post_w[j];
+        *wmax = std::max(*wmax, d.post_w[j]);
+    }
+}
+// Rows of a file that have gone out after F frames: all without a chain, else F - H once frame wmax + 2 exists
+int64_t stream_rows_out(int H, int wmax, int64_t F) { return H == 0 ? F : (F >= wmax + 2 ? std::max<int64_t>(F - H, 0) : 0); }
+int64_t stream_rows_of(const ctu_streams *st, int64_t F) { return stream_rows_out(st->H, st->wmax, F); }
+}  // namespace
+
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
+    return ctu_streams_config_check_ex(argc, argv, 0, reason, cap, nullptr);
+}
+
+int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flags, char *reason, int64_t cap, int32_t *halo) {
+    if (halo) *halo = 0;
     auto say = [&](const std::string &m) {
         g_create_error = m;
         if (reason && cap > 0) {
@@ -2873,10 +2921,17 @@ int ctu_streams_config_check(int argc, const char *const *argv, char *reason, in
             say("ENGINE: configuration not on the accelerated path: " + why);
             return CTU_ERR_UNSUPPORTED;
         }
-        if (const std::string why = streams_unsupported_reason(d); !why.empty()) {
+        if (flags & ~(uint32_t)CTU_STREAMS_ROW_STATE) {
+            say("ENGINE: unknown stream set flags");
+            return CTU_ERR_INPUT;
+        }
+        if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
             say("ENGINE: configuration cannot be streamed: " + why);
             return CTU_ERR_UNSUPPORTED;
         }
+        int H = 0, wmax = 0;
+        stream_halo(d, &H, &wmax);
+        if (halo) *halo = H;
         return CTU_OK;
     } catch (const std::exception &ex) {
         say(ex.what());
@@ -2891,15 +2946,30 @@ int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t 
     return F;
 }
 
+int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending) {
+    if (window < 1 || wshift < 1 || wshift > window || total < 0 || halo < 0 || wmax < 0 || wmax > halo || (halo > 0 && wmax < 1)) return CTU_ERR_INPUT;
+    const int64_t F = stream_frames(total, window, wshift), R = stream_rows_out(halo, wmax, F);
+    if (pending) *pending = F - R;
+    return R;
+}
+
 int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, ctu_streams **out) {
+    return ctu_streams_create_ex(e, n_streams, max_push_samples, 0, out);
+}
+
+int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out) {
     if (!e || !out) return CTU_ERR_INPUT;
     *out = nullptr;
+    if (flags & ~(uint32_t)CTU_STREAMS_ROW_STATE) {
+        set_error(e, "ENGINE: unknown stream set flags");
+        return CTU_ERR_INPUT;
+    }
     if (n_streams < 1 || max_push_samples < 1 || max_push_samples > (1 << 26)) {
         set_error(e, "ENGINE: a stream set needs at least one stream and pushes of 1 .. 2^26 samples");
         return CTU_ERR_INPUT;
     }
     const ctu::Design &d = *e->design;
-    if (const std::string why = streams_unsupported_reason(d); !why.empty()) {
+    if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
@@ -2915,8 +2985,14 @@ int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_sample
     st->max_wg = fe_max_wg(e);
     st->consumed.assign((size_t)n_streams, 0);
     st->seen.assign((size_t)n_streams, 0);
-    // the longest slot: the lead, a full carry, a full push
-    const std::vector<int64_t> longest((size_t)n_streams, (int64_t)STREAM_LEAD + d.window - 1 + max_push_samples);
+    st->held = d.post_order > 0 || d.cms;  // (only with CTU_STREAMS_ROW_STATE: refused above without)
+    stream_halo(d, &st->H, &st->wmax);
+    st->C = st->held ? std::max(2 * st->H, st->H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;
+    st->hsel.assign((size_t)n_streams, 0);
+    // the longest slot: the lead, a full carry, a full push (and no shorter than the shortest file a delta chain is defined on: the plan
+    // of a set whose pushes are shorter than that is still a plan of files that could be)
+    const std::vector<int64_t> longest((size_t)n_streams, std::max((int64_t)STREAM_LEAD + d.window - 1 + max_push_samples,
+                                                                   (int64_t)d.window + (int64_t)(st->wmax + 1) * d.wshift));
     ctu_plan *pl = nullptr;
     if (const int rc = ctu_plan_create(e, longest.data(), n_streams, &pl); rc != CTU_OK) return rc;
     st->plan.reset(pl);
@@ -2933,6 +3009,17 @@ int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_sample
             if (!st->h_desc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
             st->d_desc[k].alloc((size_t)n_streams);
             HIP_TRY(hipEventCreateWithFlags(&st->desc_free[k], hipEventDisableTiming));
+            if (st->held) {
+                st->h_rdesc[k] = static_cast<RowPush *>(ctu_host_alloc((size_t)n_streams * sizeof(RowPush)));
+                if (!st->h_rdesc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_rdesc[k].alloc((size_t)n_streams);
+            }
+        }
+        if (st->held) {
+            st->hist.alloc(std::max<size_t>((size_t)2 * n_streams * st->C * d.Dbase, 1));
+            st->means.alloc((size_t)n_streams * STREAM_MEANS);
+            HIP_TRY(hipMemset(st->hist.p, 0, st->hist.n * sizeof(float)));
+            HIP_TRY(hipMemset(st->means.p, 0, st->means.n * sizeof(float)));
         }
         for (hipEvent_t &v : st->ev) HIP_TRY(hipEventCreate(&v));
         return CTU_OK;
@@ -2952,8 +3039,40 @@ void ctu_streams_destroy(ctu_streams *st) {
 int64_t ctu_streams_frames(const ctu_streams *st, int32_t id) {
     if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
     const ctu::Design &d = *st->eng->design;
-    return stream_frames(st->consumed[(size_t)id], d.window, d.wshift);
+    return stream_rows_of(st, stream_frames(st->consumed[(size_t)id], d.window, d.wshift));
 }
+
+int64_t ctu_streams_pending(const ctu_streams *st, int32_t id) {
+    if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
+    const ctu::Design &d = *st->eng->design;
+    const int64_t F = stream_frames(st->consumed[(size_t)id], d.window, d.wshift);
+    return F - stream_rows_of(st, F);
+}
+
+namespace {
+// The row kernels of a push, or of a finish, over the n streams h_rdesc[k] describes (uploaded here); `most` is the largest row count among them
+void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finishing, float *d_rows, hipStream_t s) {
+    const ctu::Design &d = *st->eng->design;
+    HIP_TRY(hipMemcpyAsync(st->d_rdesc[k].p, st->h_rdesc[k], (size_t)n * sizeof(RowPush), hipMemcpyHostToDevice, s));
+    if (most == 0) return;
+    RowParams rp;
+    rp.push = st->d_rdesc[k].p; rp.fresh = st->plan->base_rows.p; rp.hist = st->hist.p; rp.means = st->means.p; rp.rows = d_rows;
+    rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase; rp.finishing = finishing ? 1 : 0;
+    const unsigned chunks = (unsigned)((most + 63) / 64);
+    if (d.post_order > 0) {
+        size_t shm = 0;
+        const PostParams pp = post_params(d, &shm);
+        if (d.post_stack) hipLaunchKernelGGL(stream_post_kernel<true>, dim3(chunks, (unsigned)n), dim3(256), shm, s, rp, pp);
+        else hipLaunchKernelGGL(stream_post_kernel<false>, dim3(chunks, (unsigned)n), dim3(256), shm, s, rp, pp);
+    }
+    if (d.cms) {
+        const CmsParams cp = cms_params(d);
+        if (d.cms == 1) hipLaunchKernelGGL(stream_cms_exp_kernel, dim3((unsigned)n), dim3(64), 0, s, rp, cp);
+        else hipLaunchKernelGGL(stream_cms_block_kernel, dim3(chunks, (unsigned)n), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, rp, cp);
+    }
+    HIP_TRY(hipGetLastError());
+}
+}  // namespace
 
 int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
                      float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream) {
@@ -2980,7 +3099,7 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         if (n_samples[i] < 0 || n_samples[i] > st->max_push) return refuse("push: more samples than the set's max_push_samples (or fewer than none)");
         if (n_samples[i] && (!sample_off || sample_off[i] < 0)) return refuse("push: null or negative sample offsets");
         const int64_t c = st->consumed[(size_t)ids[i]];
-        rows += stream_frames(c + n_samples[i], d.window, d.wshift) - stream_frames(c, d.window, d.wshift);
+        rows += stream_rows_of(st, stream_frames(c + n_samples[i], d.window, d.wshift)) - stream_rows_of(st, stream_frames(c, d.window, d.wshift));
         fresh += n_samples[i];
     }
     if (fresh && !d_pcm) return refuse("push: null sample buffer");
@@ -2992,7 +3111,7 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         st->turn ^= 1;
         HIP_TRY(hipEventSynchronize(st->desc_free[k]));  // (the push before last has read them; immediate before the first record)
         StreamPush *h = st->h_desc[k];
-        int64_t so = PCM_HEAD, ro = 0;
+        int64_t so = PCM_HEAD, ro = 0, oo = 0, most = 0;  // ro: base rows of the push, oo: rows that go out (the same without row state)
         int tiles = 0, slices = 1;
         for (int i = 0; i < n; i++) {
             const int64_t c = st->consumed[(size_t)ids[i]];
@@ -3009,7 +3128,17 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
             ro += T;
             tiles += (int)((T + TILE - 1) / TILE);
             slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
-            if (row_counts) row_counts[i] = T;
+            const int64_t r0 = stream_rows_of(st, F), nr = stream_rows_of(st, F + T) - r0;
+            if (st->held) {
+                RowPush &r = st->h_rdesc[k][i];
+                r.F0 = F; r.r0 = r0; r.out0 = oo; r.row0 = h[i].row0;
+                r.id = ids[i]; r.Tn = (int)T; r.nr = (int)nr;
+                r.hsel = st->hsel[(size_t)ids[i]];
+                if (T > 0) st->hsel[(size_t)ids[i]] ^= 1;  // stream_rows_carry_kernel writes the other history
+            }
+            oo += nr;
+            most = std::max(most, nr);
+            if (row_counts) row_counts[i] = nr;
             st->consumed[(size_t)ids[i]] = c + n_samples[i];
         }
         if (so + PCM_TAIL > pl->total_samples || tiles > (int)pl->tiles.n) throw std::runtime_error("internal: a push beyond the set's arena");
@@ -3027,9 +3156,17 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         pl->grid = sp.grid;
         pl->total_frames = ro;
         int rc = CTU_OK;
-        if (tiles) rc = ctu_engine_run(e, pl, st->arena.p, d_rows, nullptr, s);
+        if (tiles) rc = run_chain(e, pl, st->arena.p, st->held ? pl->base_rows.p : d_rows, nullptr, s, !st->held);
+        if (st->held && tiles && rc == CTU_OK) launch_stream_rows(st, k, n, most, false, d_rows, s);
         HIP_TRY(hipEventRecord(st->ev[2], s));
         hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
+        if (st->held && st->C > 0 && tiles && rc == CTU_OK) {
+            RowParams rp;
+            std::memset(&rp, 0, sizeof rp);
+            rp.push = st->d_rdesc[k].p; rp.fresh = pl->base_rows.p; rp.hist = st->hist.p;
+            rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase;
+            hipLaunchKernelGGL(stream_rows_carry_kernel, dim3((unsigned)n, (unsigned)((st->C * d.Dbase + 255) / 256)), dim3(256), 0, s, rp);
+        }
         HIP_TRY(hipEventRecord(st->ev[3], s));
         HIP_TRY(hipEventRecord(st->desc_free[k], s));
         HIP_TRY(hipGetLastError());
@@ -3062,7 +3199,8 @@ int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const 
             st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
             if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
             st->d_stage.alloc(cap);
-            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->row_off[st->plan->n_utt], 1) * D);
+            // (a push that brings a stream's frame wmax + 2 also delivers the rows of the wmax + 1 frames before it)
+            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->row_off[st->plan->n_utt] + (int64_t)st->n_streams * (st->wmax + 1), 1) * D);
         }
         st->offs.resize((size_t)n);
         int64_t at = 0;
@@ -3092,28 +3230,73 @@ int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const 
 }
 
 int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream) {
-    (void)d_rows;
-    (void)rows_capacity;
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
     if (id < 0 || id >= st->n_streams) {
         set_error(e, "ENGINE: finish: stream id out of range");
         return CTU_ERR_INPUT;
     }
     if (row_count) *row_count = 0;  // fread() comes up short on a trailing partial window and the file ends there (src/io/in.cc:314,438)
     const int64_t total = st->consumed[(size_t)id];
+    const int64_t F = stream_frames(total, d.window, d.wshift), r0 = stream_rows_of(st, F);
+    const bool too_short = st->H > 0 && F > 0 && F < st->wmax + 2;  // the plan's refusal: such a file has no defined rows, none go out
+    const int64_t pending = too_short ? 0 : F - r0;
+    if (pending > rows_capacity || (pending && !d_rows)) {  // ahead of any launch or change: the stream stays as it was
+        set_error(e, "ENGINE: finish: the rows held back for this stream do not fit rows_capacity");
+        return CTU_ERR_INPUT;
+    }
     st->consumed[(size_t)id] = 0;
+    hipStream_t s = (hipStream_t)stream;
     const int rc = guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), (hipStream_t)stream));
+        if (pending) {  // rows r0 .. F - 1 with the file's length known: every base row they read is in the history
+            const int k = st->turn;
+            st->turn ^= 1;
+            HIP_TRY(hipEventSynchronize(st->desc_free[k]));
+            RowPush &r = st->h_rdesc[k][0];
+            r.F0 = F; r.r0 = r0; r.out0 = 0; r.row0 = 0;
+            r.id = id; r.Tn = 0; r.nr = (int)pending;
+            r.hsel = st->hsel[(size_t)id];
+            launch_stream_rows(st, k, 1, pending, true, d_rows, s);
+            HIP_TRY(hipEventRecord(st->desc_free[k], s));
+        }
+        HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
+        if (st->held) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
         return CTU_OK;
     });
     if (rc != CTU_OK) return rc;
-    if (total > 0 && total < e->design->window - e->design->wshift) {
+    if (total > 0 && total < d.window - d.wshift) {
         set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
         return CTU_ERR_INPUT;
     }
+    if (too_short) {  // plan_layout's words; the stream is reset all the same
+        set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
+        return CTU_ERR_INPUT;
+    }
+    if (row_count) *row_count = pending;
     return CTU_OK;
+}
+
+int ctu_streams_finish_host(ctu_streams *st, int32_t id, float *h_rows, int64_t rows_capacity, int64_t *row_count) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const int D = e->design->D;
+    if (row_count) *row_count = 0;
+    const int64_t pending = ctu_streams_pending(st, id);  // (at most max(H, wmax + 1) rows; an id outside the set is ctu_streams_finish's to refuse)
+    DevBuf<float> rows;
+    int64_t cnt = 0;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        if (pending > 0) rows.alloc((size_t)pending * D);
+        const int rc = ctu_streams_finish(st, id, h_rows ? rows.p : nullptr, h_rows ? rows_capacity : 0, &cnt, nullptr);
+        if (rc != CTU_OK) return rc;
+        if (cnt) HIP_TRY(hipMemcpy(h_rows, rows.p, (size_t)cnt * D * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return CTU_OK;
+    });
+    if (rc == CTU_OK && row_count) *row_count = cnt;
+    return rc;
 }
 
 int ctu_streams_last_push_ms(ctu_streams *st, float *ms3) {

@@ -12,6 +12,7 @@ import numpy as np
 from . import build as _build
 
 CTU_OK, CTU_ERR_OPTS, CTU_ERR_UNSUPPORTED, CTU_ERR_DEVICE, CTU_ERR_INPUT = 0, -1, -2, -3, -4
+STREAMS_ROW_STATE = 1  # CTU_STREAMS_ROW_STATE
 
 
 class CtuError(RuntimeError):
@@ -37,7 +38,8 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_cmvn_accumulate_host", "ctu_cmvn_apply_host", "ctu_plan_out_samples", "ctu_engine_run_signal",
            "ctu_engine_run_signal_host", "ctu_rows_arena_layout", "ctu_engine_run_rows", "ctu_engine_run_rows_host",
            "ctu_streams_create", "ctu_streams_destroy", "ctu_streams_config_check", "ctu_streams_push", "ctu_streams_push_host",
-           "ctu_streams_finish", "ctu_streams_frames", "ctu_streams_step", "ctu_streams_last_push_ms"]
+           "ctu_streams_finish", "ctu_streams_frames", "ctu_streams_step", "ctu_streams_last_push_ms",
+           "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step"]
 
 _lib = None
 
@@ -122,6 +124,15 @@ def load_library():
         L.ctu_streams_step.restype = i64
         L.ctu_streams_step.argtypes = [i32, i32, i64, ctypes.POINTER(i64)]
         L.ctu_streams_last_push_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    if hasattr(L, "ctu_streams_create_ex"):  # (likewise: stream sets with row state)
+        u32 = ctypes.c_uint32
+        L.ctu_streams_create_ex.argtypes = [vp, i32, i64, u32, ctypes.POINTER(vp)]
+        L.ctu_streams_config_check_ex.argtypes = [ctypes.c_int, argv_t, u32, ctypes.c_char_p, i64, ctypes.POINTER(i32)]
+        L.ctu_streams_pending.restype = i64
+        L.ctu_streams_pending.argtypes = [vp, i32]
+        L.ctu_streams_finish_host.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64)]
+        L.ctu_streams_rows_step.restype = i64
+        L.ctu_streams_rows_step.argtypes = [i32, i32, i32, i32, i64, ctypes.POINTER(i64)]
     _lib = L
     return L
 
@@ -169,14 +180,19 @@ def config_table(args, name):
     return out
 
 
-def streams_config_check(args):
+def streams_config_check(args, row_state=False):
     """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
-    CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give."""
+    CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give.  With row_state (a set that
+    may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo)."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
-    rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
-    return int(rc), buf.value.decode()
+    if not row_state:
+        rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
+        return int(rc), buf.value.decode()
+    halo = ctypes.c_int32(0)
+    rc = L.ctu_streams_config_check_ex(n, arr, STREAMS_ROW_STATE, buf, len(buf), ctypes.byref(halo))
+    return int(rc), buf.value.decode(), int(halo.value)
 
 
 def streams_step(window, wshift, total):
@@ -188,22 +204,41 @@ def streams_step(window, wshift, total):
     return int(f), int(carry.value)
 
 
-class Streams:
-    """A set of `n` streams on an engine (Engine.streams): PCM in per stream as it arrives, the rows of the frames it completes out."""
+def streams_rows_step(window, wshift, halo, wmax, total):
+    """(rows delivered, rows held back) of a stream with row state after `total` samples, for a chain of halo `halo` and largest
+    window `wmax` (ctu_streams_rows_step)."""
+    pending = ctypes.c_int64(0)
+    r = load_library().ctu_streams_rows_step(int(window), int(wshift), int(halo), int(wmax), int(total), ctypes.byref(pending))
+    if r < 0:
+        raise CtuError(int(r), "ctu_streams_rows_step: bad argument")
+    return int(r), int(pending.value)
 
-    def __init__(self, engine, n, max_push):
+
+class Streams:
+    """A set of `n` streams on an engine (Engine.streams): PCM in per stream as it arrives, the rows of the frames it completes out.
+    With row_state the set takes delta chains, stacking and CMS too, and may deliver a frame's row with a later push or with finish."""
+
+    def __init__(self, engine, n, max_push, row_state=False):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
+        if row_state:
+            rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, STREAMS_ROW_STATE, ctypes.byref(h))
+        else:
+            rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
         if rc != CTU_OK:
             raise CtuError(rc, L.ctu_last_error(engine._h).decode())
         self._h = h
+        engine._sets.add(h.value)
 
     def close(self):
-        if getattr(self, "_h", None):
-            load_library().ctu_streams_destroy(self._h)
-            self._h = None
+        # ctu_streams_destroy reads its engine, so a set must go first.  The collector finalises the objects of a reference cycle in
+        # any order (a caught CtuError's traceback makes such cycles): the engine destroys the sets it still knows of ahead of itself
+        # (Engine.close), and a set that finds its handle gone from the engine's books has nothing left to destroy.
+        h, self._h = getattr(self, "_h", None), None
+        if h and h.value in self.engine._sets:
+            self.engine._sets.discard(h.value)
+            load_library().ctu_streams_destroy(h)
 
     __del__ = close
 
@@ -215,7 +250,8 @@ class Streams:
         ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
         D = self.engine.dims.row_floats
         sh = self.engine.dims.wshift
-        cap = int(sum(int(a) // sh + 1 for a in ns))  # at most one frame more than whole hops per stream
+        # at most one frame more than whole hops per stream, and what the stream held back
+        cap = int(sum(int(a) // sh + 1 + self.pending(int(k)) for k, a in zip(ids, ns) if 0 <= k < self.n))
         rows = np.empty((cap, D), dtype=np.float32)
         counts = np.zeros(max(len(arrs), 1), dtype=np.int64)
         rc = load_library().ctu_streams_push_host(self._h, len(arrs), ids.ctypes.data, ptrs, ns.ctypes.data, rows.ctypes.data, cap, counts.ctypes.data)
@@ -243,14 +279,21 @@ class Streams:
         return counts[:ids.size]
 
     def finish(self, sid):
-        """Ends stream `sid`'s file: its remaining rows ([0, D]: the reference makes no frame of a trailing partial window); the stream then
-        starts a new file."""
+        """Ends stream `sid`'s file: its remaining rows - the ones a set with row state held back, else [0, D]: the reference makes no
+        frame of a trailing partial window; the stream then starts a new file."""
         cnt = ctypes.c_int64(0)
-        self.engine._check(load_library().ctu_streams_finish(self._h, int(sid), None, 0, ctypes.byref(cnt), None))
-        return np.empty((int(cnt.value), self.engine.dims.row_floats), dtype=np.float32)
+        cap = max(self.pending(sid), 0)
+        rows = np.empty((cap, self.engine.dims.row_floats), dtype=np.float32)
+        self.engine._check(load_library().ctu_streams_finish_host(self._h, int(sid), rows.ctypes.data if cap else None, cap, ctypes.byref(cnt)))
+        return rows[:int(cnt.value)]
 
     def frames(self, sid):
+        """Rows of the current file delivered so far."""
         return int(load_library().ctu_streams_frames(self._h, int(sid)))
+
+    def pending(self, sid):
+        """Rows a finish would deliver now."""
+        return int(load_library().ctu_streams_pending(self._h, int(sid)))
 
     def last_push_ms(self):
         """(stream_stitch_kernel, front end and tails, stream_carry_kernel) of the last push, in ms (HIP events)."""
@@ -317,13 +360,17 @@ class Engine:
         if rc != CTU_OK:
             raise CtuError(rc, L.ctu_create_error().decode())
         self._h = h
+        self._sets = set()  # handles of the live stream sets on this engine (Streams)
         self.device = int(device)
         self.dims = Dims()
         L.ctu_engine_dims(h, ctypes.byref(self.dims))
 
     def close(self):
         if getattr(self, "_h", None):
-            load_library().ctu_engine_destroy(self._h)
+            L = load_library()
+            while getattr(self, "_sets", None):  # a stream set is destroyed ahead of its engine (see Streams.close)
+                L.ctu_streams_destroy(ctypes.c_void_p(self._sets.pop()))
+            L.ctu_engine_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -334,9 +381,9 @@ class Engine:
     def plan(self, nsamples):
         return Plan(self, nsamples)
 
-    def streams(self, n, max_push):
+    def streams(self, n, max_push, row_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
-        return Streams(self, n, max_push)
+        return Streams(self, n, max_push, row_state)
 
     def _check(self, rc):
         if rc != CTU_OK:

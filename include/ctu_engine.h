@@ -174,10 +174,23 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * n_samples[i] >= 0 samples from d_pcm + sample_off[i] (2-byte aligned is enough).  The rows of the push are written to d_rows one
  * stream after the other in the order of stream_ids, row_counts[i] of them for stream i (row_counts is host memory and is
  * filled on return; it may be NULL).  Asynchronous on `stream`; d_pcm may be reused once the work enqueued has run.  The calls on
- * one set must be ordered: one hipStream_t, or the caller's own synchronisation.  One set per engine runs at a time. */
+ * one set must be ordered: one hipStream_t, or the caller's own synchronisation.  One set per engine runs at a time.
+ *
+ * Row state (ctu_streams_create_ex with CTU_STREAMS_ROW_STATE): the set also keeps, per stream, the last base rows of the file and
+ * the running cepstral means, and so takes -fea_delta, -fea_trap, -fea_Z_exp and -fea_Z_block as well (the other refusals stand, and
+ * so does every size limit ctu_engine_create puts on those chains).  Row t of a file is what the offline run writes for any file of
+ * more than t + H frames (H, the halo: the sum of the chain's delta windows, or the stacking window; 0 with CMS alone), so after F
+ * frames a stream has delivered R(F) = F - H rows - none while F < wmax + 2 (wmax: the largest window), since no row may go out of a
+ * file that could still end where the offline plan refuses it - and holds F - R(F) back.  A push delivers the rows R(F) of its
+ * streams advance by (row_counts, and the capacity check, count those; up to wmax + 1 more than the frames it completes), and
+ * ctu_streams_finish delivers the rest with the file's end known.  On a chain without such state the flag changes nothing. */
+enum { CTU_STREAMS_ROW_STATE = 1 };
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
-void ctu_streams_destroy(ctu_streams *);
+void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
+/* The two calls above are these with flags 0.  *halo (may be NULL) receives H of an accepted configuration. */
+int ctu_streams_create_ex(ctu_engine *, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out);
+int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flags, char *reason, int64_t cap, int32_t *halo);
 int ctu_streams_push(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *d_pcm, const int64_t *sample_off,
                      const int64_t *n_samples, float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream);
 /* Host-buffer form: h_pcm[i] points at stream i's new samples, h_rows receives the rows; page-locked rows (ctu_host_alloc) are
@@ -185,17 +198,26 @@ int ctu_streams_push(ctu_streams *, int32_t n, const int32_t *stream_ids, const 
 int ctu_streams_push_host(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *const *h_pcm, const int64_t *n_samples,
                           float *h_rows, int64_t rows_capacity, int64_t *row_counts);
 /* The end of a stream's file.  The reference's loop ends when fread comes up short (src/io/in.cc:314,438): a trailing partial
- * window makes no frame, so every row of the file is out already and *row_count is 0 (d_rows / rows_capacity are there for the
- * chains that will hold rows back: delta windows).  A file of 1 .. window - wshift - 1 samples is the reference's "IO: Signal
- * shorter than one frame!": CTU_ERR_INPUT.  Either way the stream starts a new file with its next push. */
+ * window makes no frame, so without row state every row of the file is out already and *row_count is 0.  A set with row state
+ * writes the rows it held back (ctu_streams_pending of them) to d_rows, asynchronously on `stream`; room for fewer is CTU_ERR_INPUT
+ * ahead of any launch, and the stream stays as it was.  A file of 1 .. window - wshift - 1 samples is the reference's "IO: Signal
+ * shorter than one frame!", and a delta chain or stacking on a file of 1 .. wmax + 1 frames the offline plan's "fewer than window+2
+ * frames": CTU_ERR_INPUT and no rows.  In every case but the lack of room the stream starts a new file with its next push. */
 int ctu_streams_finish(ctu_streams *, int32_t stream_id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream);
+/* Host-buffer form of the above.  Synchronised on return. */
+int ctu_streams_finish_host(ctu_streams *, int32_t stream_id, float *h_rows, int64_t rows_capacity, int64_t *row_count);
 /* Rows the stream's current file has produced so far. */
 int64_t ctu_streams_frames(const ctu_streams *, int32_t stream_id);
+/* Rows a finish would deliver now: the frames of the current file whose rows are held back (0 without row state). */
+int64_t ctu_streams_pending(const ctu_streams *, int32_t stream_id);
 /* The arithmetic of a stream on its own (pure): the frames a file has produced after `total` samples - the frame count of
  * ctu_num_frames, 0 while it has none - and in *carry (may be NULL) the samples the next frame already has. */
 int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry);
+/* The same for the rows (pure): R(F) of a file after `total` samples for a chain of halo H >= wmax >= 0 (0, 0: no chain), and in
+ * *pending (may be NULL) F - R(F). */
+int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending);
 /* Times of the last push on the set, measured with HIP events on its stream: ms3[0] stream_stitch_kernel, ms3[1] the front end
- * and its tails, ms3[2] stream_carry_kernel.  Blocks until that push has finished. */
+ * and its tails (with row state: and the row kernels behind them), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel).  Blocks until that push has finished. */
 int ctu_streams_last_push_ms(ctu_streams *, float *ms3);
 
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53

@@ -4,8 +4,10 @@ MFCC-13 at 16 kHz, pushes of 10 hops to each of N concurrent streams (N = 1 000 
 Per N: the three spans of a push from HIP events on its stream (stream_stitch_kernel | front end | stream_carry_kernel, median
 of the timed pushes), the push rate in frames/s from the host's clock around synchronised pushes, and the rate of one offline
 device-resident run over the same frames (N utterances of 10 frames; the offline path is the parent commit's).
+With --row-state the same again for MFCC_0_D_A with a running mean (-fea_delta d_a -fea_Z_exp 500) on a set with row state, in the
+same run: its front-end span includes the streamed delta and CMS kernels, its carry span the base-row history.
 
-    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3]
+    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3] [--row-state]
 """
 import argparse
 import os
@@ -21,9 +23,12 @@ from ctucopy_amd import Engine  # noqa: E402
 from tests.util import C2, synth_utt  # noqa: E402
 
 
-def measure(n, pushes, warmup):
+CHAIN = ["-fea_delta", "d_a", "-fea_Z_exp", "500"]
+
+
+def measure(n, pushes, warmup, chain=False):
     import torch
-    eng = Engine(C2)
+    eng = Engine(C2 + (CHAIN if chain else []))
     w, s, D = eng.dims.window, eng.dims.wshift, eng.dims.row_floats
     hop = 10 * s
     total = w - s + hop * (warmup + pushes)
@@ -31,7 +36,7 @@ def measure(n, pushes, warmup):
     pcm = torch.from_numpy(np.tile(x, n)).cuda()
     ids = np.arange(n, dtype=np.int32)
     base = np.arange(n, dtype=np.int64) * total
-    st = eng.streams(n, hop)
+    st = eng.streams(n, hop, row_state=chain)
     rows = torch.empty((n * 11, D), dtype=torch.float32, device="cuda")
     cnt = st.push_device(ids, pcm, base, np.full(n, w - s), rows)   # the samples ahead of the first hop: no frame yet
     assert int(cnt.sum()) == 0
@@ -42,7 +47,7 @@ def measure(n, pushes, warmup):
         cnt = st.push_device(ids, pcm, base + (w - s) + k * hop, np.full(n, hop), rows)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        assert int(cnt.min()) == int(cnt.max()) == 10
+        assert int(cnt.min()) == int(cnt.max()) == (6 if chain and k == 0 else 10)   # (the first ten frames of a d_a file give six rows)
         if k >= warmup:
             spans.append(st.last_push_ms())
             wall.append(t1 - t0)
@@ -72,13 +77,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--pushes", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--row-state", action="store_true", help="also MFCC_0_D_A with exponential CMS on a set with row state")
     a = ap.parse_args()
     lines = ["# tools/probes/streams_push.py: MFCC-13, 16 kHz, pushes of 10 hops per stream, device-resident; medians of %d pushes after %d" % (a.pushes, a.warmup),
              "# spans from HIP events on the push's stream; rates from the host's clock around synchronised calls (launch overhead included)",
              "# streams  stitch_ms  frontend_ms  carry_ms  push_frames_per_s  offline_frontend_ms  offline_frames_per_s"]
-    for n in (1000, 10000):
-        med, pr, ok, orate = measure(n, a.pushes, a.warmup)
-        lines.append("%7d  %.4f  %.4f  %.4f  %.3e  %.4f  %.3e" % (n, med[0], med[1], med[2], pr, ok, orate))
+    for chain in ((False, True) if a.row_state else (False,)):
+        if chain:
+            lines.append("# the same with " + " ".join(CHAIN) + " on a set with row state (frontend_ms: with the streamed delta and CMS kernels; carry_ms: with"
+                         " the base-row history; offline_frontend_ms is the front end alone, the offline rate has post_kernel and cms_exp_kernel in it)")
+        for n in (1000, 10000):
+            med, pr, ok, orate = measure(n, a.pushes, a.warmup, chain)
+            lines.append("%7d  %.4f  %.4f  %.4f  %.3e  %.4f  %.3e" % (n, med[0], med[1], med[2], pr, ok, orate))
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
