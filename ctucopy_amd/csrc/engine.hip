@@ -428,6 +428,10 @@ std::string unsupported_reason(const ctu::Design &d) {
             if (nc > 32 || nc < 2) return "more than 32 (or fewer than 2) VAD cepstral coefficients";
         }
         if (o.vad_filter_order > 31) return "VAD filter order above 31";
+        // behind a delayed chain the flush calls the detector again on the vector VAD::silence_frame zeroed (src/vad/vad.cc:727-736): the Burg
+        // criterion divides by its energy and the reference aborts (src/vdet/Burg.h:72); the energy and `fea` criteria read the zeros unharmed
+        if (o.vad_apply_mode == "silence" && o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "lpc" && (d.post_order > 0 || d.kind == ctu::FeaKind::TrapDct))
+            return "-vad_apply_mode silence with the lpc criterion behind a delta, stacking or trapdct chain (the reference aborts in its Burg estimator at the flush)";
     }
     if (d.wfft >= 1024) {  // bigfft_kernel.h: the plain chain
         if (d.wfft > 4096) return "FFT size above 4096";

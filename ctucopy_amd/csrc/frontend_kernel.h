@@ -476,6 +476,9 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                 const bool file_start = (l16 == 0) && (rec.t0 + fc == 0);
                 STAMP(0);  // loop overhead / previous tail
                 float2 v[16];
+                // MODE 1: a frame of nothing but zeros (digital silence) must come out as an all-zero spectrum, as in the reference, whose
+                // logarithms are then -inf; packed with a frame of speech it would inherit that frame's rounding residue instead
+                bool zero_a = false, zero_b = false;
                 if constexpr (MODE == 1) {
                     // frames A = slot 2*fg, B = A+1 of this step's 8; sample n = 16 j + l16 of each goes to re / im
                     const int fa = slot0 + 2 * fg, fb_ = fa + 1;
@@ -483,7 +486,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     const int16_t *xa = p.pcm + rec.sbase + (int64_t)ca * p.wshift + l16;
                     const int16_t *xb = p.pcm + rec.sbase + (int64_t)cb_ * p.wshift + l16;
                     const bool start_a = (l16 == 0) && (rec.t0 + ca == 0), start_b = (l16 == 0) && (rec.t0 + cb_ == 0);
-                    float dca = 0.f, dcb = 0.f;
+                    float dca = 0.f, dcb = 0.f, absa = 0.f, absb = 0.f;
                     float ova[DCJ + 1], ovb[DCJ + 1];
                     if (o_dc1) {
                         dc1_load(ova, rbase + ca, rec.t0 + ca);
@@ -512,10 +515,14 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                         v[j] = make_float2(ya, yb);
                         dca += ya;
                         dcb += yb;
+                        absa += fabsf(ya);
+                        absb += fabsf(yb);
                     }
     #pragma unroll
                     for (int j = NZ; j < 16; j++) v[j] = make_float2(0.f, 0.f);
                     STAMP(1);
+                    zero_a = row16_allreduce_add(absa) == 0.f;
+                    zero_b = row16_allreduce_add(absb) == 0.f;
                     if (o_remove_dc) {
                         const float ma = row16_allreduce_add(dca) * p.inv_window, mb = row16_allreduce_add(dcb) * p.inv_window;
     #pragma unroll
@@ -623,7 +630,9 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                             bi = v[(16 - k2) & 15].y;
                         }
                         const float ar = v[k2].x, ai = v[k2].y;
-                        const float sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
+                        float sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
+                        if (zero_a) sr = si = 0.f;
+                        if (zero_b) dr = di = 0.f;
                         const int k = l16 + 16 * k2;
                         pa[k] = 0.25f * (sr * sr + si * si);
                         pb[k] = 0.25f * (dr * dr + di * di);
@@ -633,6 +642,8 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                         }
                     }
                     if (l16 == 0) {
+                        if (zero_a) v[8].x = 0.f;
+                        if (zero_b) v[8].y = 0.f;
                         pa[128] = v[8].x * v[8].x;
                         pb[128] = v[8].y * v[8].y;
                         if constexpr (SS && SY) {  // X_A[128] = Re Z[128], X_B[128] = Im Z[128]: their signs (out.cc:419, see the SS block)

@@ -884,6 +884,14 @@ static int design_all(ctuo_t *c) {
             return -1;
         }
         if (o->vad_filter_order < 1 || (o->vad_filter_order % 2) == 0) { set_err(c, "medianFilter: filter order must be positive, odd number!"); return -1; }
+        /* behind a delayed chain (delta, stacking, trapdct) the flush calls the detector again on the vector silence_frame() zeroed
+         * (vad.cc:727-736): the Burg criterion divides by its energy and the reference aborts (Burg.h:72, den != 0.0) - nothing to restate.
+         * The energy and `fea` criteria read the zeros without harm (tests/golden/ref_e2e.npz: c2_silence_energy). */
+        if (!strcmp(o->vad_apply_mode, "silence") && !strcmp(o->vad_cri_mode, "cepdist") && !strcmp(o->vad_cepdist_mode, "lpc") &&
+            (o->fea_delta || !strcmp(k, "trapdct"))) {
+            set_err(c, "oracle: -vad_apply_mode silence with the lpc criterion behind a delta, stacking or trapdct chain aborts in the reference (Burg.h:72)");
+            return -1;
+        }
     }
     c->last_power = calloc(o->wfftby2, sizeof(double));
     c->last_fbank = calloc(B, sizeof(double));

@@ -766,11 +766,19 @@ def test_apply_mode_silence(Engine):
     from ctucopy_amd import CtuError
     from tests.util import C4
     utts = [synth_utt(79, 16000, fs=8000), sig("CS3")[:20000]]
-    for extra in ([], ["-fea_delta", "d_a"]):
-        rn, vn = Engine(C4 + extra + ["-vad_apply_mode", "none"]).extract(utts, want_vad=True)
-        rs, vs = Engine(C4 + extra + ["-vad_apply_mode", "silence"]).extract(utts, want_vad=True)
+    # behind a delta chain the reference aborts with the lpc criterion (src/vdet/Burg.h:72 at the flush; tests/golden/ref_e2e.npz: c4_da_silence) and
+    # runs with the energy criterion (c2_silence_energy): the first is refused, the second is what `none` gives
+    e8 = "-fs 8000 -format_in raw -format_out htk -preset mfcc -preem 0.97 -vad_out_mode vad -vad_cri_mode energy -vad_thr_mode dyn -fea_delta d_a".split()
+    for cfg in (C4, e8):
+        rn, vn = Engine(cfg + ["-vad_apply_mode", "none"]).extract(utts, want_vad=True)
+        rs, vs = Engine(cfg + ["-vad_apply_mode", "silence"]).extract(utts, want_vad=True)
         for a, b, c, d in zip(rn, rs, vn, vs):
-            assert np.array_equal(a, b) and np.array_equal(c, d)
+            assert np.array_equal(a, b) and np.array_equal(c, d) and a.shape[0] == c.size > 0
+    for chain in (C4 + ["-fea_delta", "d_a"], C4 + ["-fea_trap", "9"], C5 + "-vad burg -vad_out_mode vad -vad_cri_mode cepdist -vad_cepdist_mode lpc".split()):
+        Engine(chain + ["-vad_apply_mode", "none"])
+        with pytest.raises(CtuError, match="reference aborts") as ei:
+            Engine(chain + ["-vad_apply_mode", "silence"])
+        assert ei.value.code == -2   # CTU_ERR_UNSUPPORTED
     with pytest.raises(CtuError, match="silence"):
         Engine(C2 + "-nr_mode fwss -vad burg -vad_out_mode vad -vad_apply_mode silence".split())
     with pytest.raises(CtuError, match="never constructs"):

@@ -60,3 +60,17 @@ def test_apply_mode_silence_changes_nothing_on_the_feature_path():
         Oracle(C2 + "-nr_mode fwss -vad burg -vad_out_mode vad -vad_apply_mode silence".split())
     with pytest.raises(OracleError, match="crashes in the reference"):
         Oracle("-fs 16000 -format_in raw -format_out raw -preset exten -vad_out_mode vad".split())
+    # behind a delayed chain the flush hands the zeroed vector to the detector again: the Burg criterion aborts in the reference (Burg.h:72,
+    # tests/golden/ref_e2e.npz: c4_da_silence) and is refused; the energy criterion runs there (c2_silence_energy) and changes nothing
+    from tests.util import C5
+    for chain in (C4 + ["-fea_delta", "d_a"], C4 + ["-fea_trap", "9"], C4 + ["-fea_delta", "d", "-d_win", "1"],
+                  C5 + "-vad burg -vad_out_mode vad -vad_cri_mode cepdist -vad_cepdist_mode lpc".split()):
+        Oracle(chain + ["-vad_apply_mode", "none"])
+        with pytest.raises(OracleError, match="aborts in the reference"):
+            Oracle(chain + ["-vad_apply_mode", "silence"])
+    u16 = synth_utt(78, 30000)
+    for cri in ("-vad_cri_mode energy -vad_thr_mode dyn", "-vad_cri_mode cepdist -vad_cepdist_mode fea -vad_thr_mode adapt"):
+        cfg = C2 + ["-vad_out_mode", "vad", "-fea_delta", "d_a"] + cri.split()
+        rows_n, vad_n = Oracle(cfg + ["-vad_apply_mode", "none"]).process(u16, want_vad=True)
+        rows_s, vad_s = Oracle(cfg + ["-vad_apply_mode", "silence"]).process(u16, want_vad=True)
+        assert np.array_equal(rows_n, rows_s) and np.array_equal(vad_n, vad_s) and vad_s.size == rows_s.shape[0] > 0
