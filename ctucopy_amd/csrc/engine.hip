@@ -297,6 +297,15 @@ bool ss_eligible(const ctu::Design &d);
 bool ss_big_eligible(const ctu::Design &d);
 int ss_mode_of(const ctu::Opts &o);
 
+// Entries of the vector the VAD's `fea` criterion measures: VADcri_cepdist sizes itself on the vector it is handed (src/vad/vad.cc:182),
+// which is the one OUT sees (src/io/batch.cc:76,122-130) - behind a delta or stacking chain every block of the chain's output
+// (fea_delta.cc:47), not the base vector alone.
+int vad_fea_entries(const ctu::Design &d) {
+    const int fea_c = d.o.fea_ncepcoefs + 1;
+    if (d.post_order == 0) return d.nfea;
+    return d.post_stack ? fea_c * (2 * d.post_w[0] + 1) : fea_c * (d.post_order + 1);
+}
+
 // the passes behind the front end - or behind the ingest of feature files: delta chain / stacking, CMVN, CMS
 std::string post_unsupported_reason(const ctu::Design &d) {
     const ctu::Opts &o = d.o;
@@ -426,6 +435,7 @@ std::string unsupported_reason(const ctu::Design &d) {
             if (o.vad_cepdist_mode == "fea" && d.kind != ctu::FeaKind::Dctc && d.kind != ctu::FeaKind::Lpc) return "-vad_cepdist_mode fea on non-cepstral features";
             const int nc = o.vad_cepdist_mode == "lpc" ? o.vad_lpc_coefs : d.nfea;
             if (nc > 32 || nc < 2) return "more than 32 (or fewer than 2) VAD cepstral coefficients";
+            if (o.vad_cepdist_mode == "fea" && vad_fea_entries(d) > 64 * VAD_FEA_WIDE) return "the `fea` VAD criterion on stacked vectors of more than 512 entries";
         }
         if (o.vad_filter_order > 31) return "VAD filter order above 31";
         // behind a delayed chain the flush calls the detector again on the vector VAD::silence_frame zeroed (src/vad/vad.cc:727-736): the Burg
@@ -1902,7 +1912,8 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
                 vp.wfft = e->user_wfft;
             }
             vp.cri = o.vad_cri_mode == "energy" ? 0 : (o.vad_cepdist_mode == "lpc" ? 1 : 2);
-            vp.ncoef = vp.cri == 1 ? o.vad_lpc_coefs : d.nfea;
+            vp.ncoef = vp.cri == 1 ? o.vad_lpc_coefs : vad_fea_entries(d);
+            vp.fea_blk = (d.post_order > 0 && !d.post_stack) ? o.fea_ncepcoefs + 1 : 0;
             vp.thr = o.vad_thr_mode == "absolute" ? 0 : o.vad_thr_mode == "perc" ? 1 : o.vad_thr_mode == "adapt" ? 2 : 3;
             vp.energy_db = o.vad_energy_db; vp.cep_init = o.vad_cepdist_init; vp.filter_order = o.vad_filter_order;
             vp.cep_p = o.vad_cepdist_p; vp.abs_thr = o.vad_absolute_thr; vp.perc_thr = o.vad_perc_thr;

@@ -40,7 +40,7 @@ enum FeatMode { FEAT_BANDS = 0, FEAT_DCTC = 2, FEAT_LP = 3, FEAT_LPD = 4 };  // 
 
 // VAD module parameters (src/vad/vad.cc, src/vad/vad.h; used by vad_kernels.h and by the fused path of the front end)
 struct VadParams {
-    int K, wfft, window, ncoef;  // ncoef = vad_lpc_coefs (cepdist lpc) or feature vector length (cepdist fea)
+    int K, wfft, window, ncoef;  // ncoef = vad_lpc_coefs (cepdist lpc) or the length of the vector OUT sees (cepdist fea: every block of a delta / stacking chain)
     int krow, kstride;           // cepdist lpc: the exported spectra's row length and the step from one of the K bins to the next (K, 1
                                  // unless an FFT size below 256 rides on the 256-point mode: then K and wfft are the configuration's own)
     int cri;                     // 0 energy, 1 cepdist-lpc, 2 cepdist-fea
@@ -49,6 +49,7 @@ struct VadParams {
     double cep_p, abs_thr, perc_thr, adapt_q, adapt_za, dyn_perc, dyn_min, qmaxinc, qmaxdec, qmindec, qmininc;
     int perc_init, adapt_init, dyn_init;
     int D, ncep, c0_slot;        // cepdist-fea: where the internal vector sits in a written row
+    int fea_blk;                 // cepdist-fea behind a delta chain: entries per block of the vector (fea_ncepcoefs + 1); 0: one block
     int delay;                   // delta / stacking ahead of the writer: the detector is called when a delayed vector comes out, on the
                                  // criterion of the newest input frame min(call + delay, T - 1) (src/io/batch.cc:172-192,230-241,251-291)
     int e_slot, e_delay;         // -fea_E: the writer reads the energy through a pointer when the median filter releases a

@@ -238,24 +238,8 @@ __device__ __forceinline__ void vad_push(VadRun &r, int v, int order) {
     r.hidx = (r.hidx + 1 == order) ? 0 : r.hidx + 1;
 }
 
-// Frame t of an utterance.  en: the energy criterion's value (cri 0); cil: coefficient `lane` of the frame's cepstrum
-// (0 beyond nc).  out: the utterance's VAD bytes (lane 0 writes; decisions leave (order-1)/2 frames late).
-__device__ __forceinline__ void vad_frame(VadRun &r, const VadParams &vp, int t, double en, double cil, int lane, uint8_t *out) {
-    const int nc = vp.cri == 0 ? 1 : vp.ncoef, order = vp.filter_order, h = (order - 1) / 2;
-    double cri;
-    if (vp.cri == 0) {
-        if (vp.energy_db) en = 10.0 * log10(2.2250738585072014e-308 + en);
-        cri = en;
-    } else {
-        if (t == 0) {
-            r.c0r = cil;
-            cri = 0.0;
-        } else {
-            if (t == 1) r.c0r = (r.c0r + cil) / 2.0;
-            const double dl = (lane >= 1 && lane < nc) ? cil - r.c0r : 0.0;  // c0 itself is not part of the distance
-            cri = 4.3429 * sqrt(2 * wave_sum_fast(dl * dl));
-        }
-    }
+// The raw decision of frame t on the criterion's value: the four threshold recurrences (src/vad/vad.cc:329-625).
+__device__ __forceinline__ int vad_threshold(VadRun &r, const VadParams &vp, int t, double cri) {
     int vad0;
     if (vp.thr == 0) vad0 = cri >= vp.abs_thr;
     else if (vp.thr == 1) {
@@ -297,13 +281,41 @@ __device__ __forceinline__ void vad_frame(VadRun &r, const VadParams &vp, int t,
             vad0 = (cri > r.dmin + (vp.dyn_perc / 100.0) * dyn) && (dyn > vp.dyn_min);
         }
     }
-    if (vp.cri != 0 && !(vad0 && t > vp.cep_init))  // background update (src/vad/vad.cc:288-294)
-        r.c0r = vp.cep_p * r.c0r + (1.0 - vp.cep_p) * cil;
+    return vad0;
+}
+
+// The raw decision into the majority filter; decisions leave (order-1)/2 frames late (lane 0 writes).
+__device__ __forceinline__ void vad_emit(VadRun &r, const VadParams &vp, int t, int vad0, int lane, uint8_t *out) {
+    const int order = vp.filter_order, h = (order - 1) / 2;
     vad_push(r, vad0, order);
     if (t >= h) {
         if (lane == 0) out[r.nout] = (2 * r.nsum >= order) ? '1' : '0';
         r.nout++;
     }
+}
+
+// Frame t of an utterance.  en: the energy criterion's value (cri 0); cil: coefficient `lane` of the frame's cepstrum
+// (0 beyond nc).  out: the utterance's VAD bytes (lane 0 writes; decisions leave (order-1)/2 frames late).
+__device__ __forceinline__ void vad_frame(VadRun &r, const VadParams &vp, int t, double en, double cil, int lane, uint8_t *out) {
+    const int nc = vp.cri == 0 ? 1 : vp.ncoef;
+    double cri;
+    if (vp.cri == 0) {
+        if (vp.energy_db) en = 10.0 * log10(2.2250738585072014e-308 + en);
+        cri = en;
+    } else {
+        if (t == 0) {
+            r.c0r = cil;
+            cri = 0.0;
+        } else {
+            if (t == 1) r.c0r = (r.c0r + cil) / 2.0;
+            const double dl = (lane >= 1 && lane < nc) ? cil - r.c0r : 0.0;  // c0 itself is not part of the distance
+            cri = 4.3429 * sqrt(2 * wave_sum_fast(dl * dl));
+        }
+    }
+    const int vad0 = vad_threshold(r, vp, t, cri);
+    if (vp.cri != 0 && !(vad0 && t > vp.cep_init))  // background update (src/vad/vad.cc:288-294)
+        r.c0r = vp.cep_p * r.c0r + (1.0 - vp.cep_p) * cil;
+    vad_emit(r, vp, t, vad0, lane, out);
 }
 
 // (The majority test (double)nsum / order >= 0.5 of src/vad/vad.h:139-150 is taken as 2 nsum >= order: the same for integers.)
@@ -451,6 +463,18 @@ __global__ __launch_bounds__(64) void vad_lanes_kernel(const float *__restrict__
     }
 }
 
+// Entry i of the vector the `fea` criterion reads, out of the written row: internal order, c0 first, then c1..cN
+// (src/fea/fea_impl.cc:104-131).  Behind a delta chain the vector is one such block per order (vp.fea_blk entries each, the writers put
+// c0 last in every block, src/io/out.cc:188-201); -fea_trap rows are the internal vector as it stands (the writers fall back to the
+// straight copy, src/io/out.cc:182).
+__device__ __forceinline__ double vad_fea_entry(const VadParams &vp, const float *row, int i) {
+    if (vp.c0_slot == -2) return (double)row[i];
+    const int blk = vp.fea_blk > 0 ? i / vp.fea_blk : 0, base = blk * vp.fea_blk, ii = i - base;
+    return ii == 0 ? (vp.c0_slot >= 0 ? (double)row[base + vp.c0_slot] : 0.0) : (double)row[base + ii - 1];
+}
+
+constexpr int VAD_FEA_WIDE = 8;  // entries per lane of the `fea` criterion on vectors of more than 32 entries: up to 512
+
 // One wave per utterance: stages 64 frames of criterion inputs in LDS with coalesced loads, then replays them.
 __global__ __launch_bounds__(64) void vad_decide_kernel(const double *__restrict__ ci_all, const float *__restrict__ cri_energy,
                                                          float *__restrict__ rows, const int64_t *__restrict__ row_off,
@@ -463,7 +487,45 @@ __global__ __launch_bounds__(64) void vad_decide_kernel(const double *__restrict
     const int nc = vp.cri == 0 ? 1 : vp.ncoef;
     VadRun run;
     vad_run_reset(run);
-    for (int tb = 0; tb < T; tb += 64) {
+    const bool wide = vp.cri == 2 && nc > 32;
+    if (wide) {
+        // The `fea` criterion behind a delta / stacking chain: VADcri_cepdist sizes c0 / ci on the vector it is handed (src/vad/vad.cc:182),
+        // and BATCH hands it the chain's output (src/io/batch.cc:76,122-130) - every block of it, 39 entries for d_a, 13 (2 w + 1) for
+        // -fea_trap.  Entry lane + 64 j of the vector in slot j of the lane, read from the row as it is needed.
+        double c0w[VAD_FEA_WIDE], ciw[VAD_FEA_WIDE];
+#pragma unroll
+        for (int j = 0; j < VAD_FEA_WIDE; j++) c0w[j] = 0.0;
+        for (int t = 0; t < T; t++) {
+            const float *row = rows + (r0 + t) * vp.D;
+#pragma unroll
+            for (int j = 0; j < VAD_FEA_WIDE; j++) {
+                const int i = lane + 64 * j;
+                ciw[j] = i < nc ? vad_fea_entry(vp, row, i) : 0.0;
+            }
+            double cri = 0.0;
+            if (t == 0) {
+#pragma unroll
+                for (int j = 0; j < VAD_FEA_WIDE; j++) c0w[j] = ciw[j];
+            } else {
+                double part = 0.0;
+#pragma unroll
+                for (int j = 0; j < VAD_FEA_WIDE; j++) {
+                    if (t == 1) c0w[j] = (c0w[j] + ciw[j]) / 2.0;
+                    const int i = lane + 64 * j;
+                    const double dl = (i >= 1 && i < nc) ? ciw[j] - c0w[j] : 0.0;  // entry 0 is not part of the distance
+                    part += dl * dl;
+                }
+                cri = 4.3429 * sqrt(2 * wave_sum_fast(part));
+            }
+            const int vad0 = vad_threshold(run, vp, t, cri);
+            if (!(vad0 && t > vp.cep_init)) {
+#pragma unroll
+                for (int j = 0; j < VAD_FEA_WIDE; j++) c0w[j] = vp.cep_p * c0w[j] + (1.0 - vp.cep_p) * ciw[j];
+            }
+            vad_emit(run, vp, t, vad0, lane, vad_out + r0);
+        }
+    }
+    for (int tb = 0; tb < T && !wide; tb += 64) {
         const int nt = min(64, T - tb);
         __syncthreads();
         if (vp.cri == 0) {
@@ -473,14 +535,11 @@ __global__ __launch_bounds__(64) void vad_decide_kernel(const double *__restrict
                 const int f = e / nc, i = e - f * nc;
                 stage[e] = ci_all[(r0 + min(tb + f + vp.delay, T - 1)) * nc + i];
             }
-        } else {  // internal vector order: c0 first, then c1..cN (src/fea/fea_impl.cc:104-131).  Behind a delta / stacking chain the `fea`
-                  // mode reads the vector OUT sees at this call - the chain's output, whose first block is the frame that comes out - so,
-                  // unlike the two criteria above, it is not ahead of the row by the chain's delay
+        } else {  // Behind a delta / stacking chain the `fea` mode reads the vector OUT sees at this call - the chain's output, whose first
+                  // block is the frame that comes out - so, unlike the two criteria above, it is not ahead of the row by the chain's delay
             for (int e = lane; e < nt * nc; e += 64) {
                 const int f = e / nc, i = e - f * nc;
-                const float *row = rows + (r0 + tb + f) * vp.D;
-                // -fea_trap rows are the internal vector as it stands (the writers fall back to the straight copy, src/io/out.cc:182)
-                stage[e] = vp.c0_slot == -2 ? (double)row[i] : (i == 0 ? (vp.c0_slot >= 0 ? (double)row[vp.c0_slot] : 0.0) : (double)row[i - 1]);
+                stage[e] = vad_fea_entry(vp, rows + (r0 + tb + f) * vp.D, i);
             }
         }
         __syncthreads();

@@ -532,7 +532,10 @@ class Engine:
         L = load_library()
         hi, hs = ctypes.c_int32(0), ctypes.c_int32(0)
         out = []
-        for n in nsamples:
+        for k, n in enumerate(nsamples):
+            if hs.value != 0:   # as bin/ctucopy does (host/main.cc, half_drained): not reproduced, and not passed over in silence
+                raise CtuError(CTU_ERR_UNSUPPORTED, f"VAD: file {k - 1} of the list has no more frames than the majority filter delays (-vad_filter_order {order}): "
+                               "the reference's filter stays half drained for the files behind it (src/vad/vad.h:156-175), which is not reproduced")
             out.append(hi.value)
             L.ctu_vad_ring_step(int(order), max(self.num_frames(int(n)), 0), ctypes.byref(hi), ctypes.byref(hs))
         return out

@@ -1419,7 +1419,7 @@ long ctuo_process(ctuo_t *c, const int16_t *pcm, long nsamples, float *rows, uns
         vs.hidx = c->med_hidx % order;   /* what the previous file of this process left (0, 0 for the first) */
         vs.hsize = c->med_hsize;
         if (!strcmp(o->vad_cri_mode, "cepdist")) {
-            vs.csize = !strcmp(o->vad_cepdist_mode, "lpc") ? o->vad_lpc_coefs : c->nfea;
+            vs.csize = !strcmp(o->vad_cepdist_mode, "lpc") ? o->vad_lpc_coefs : vlen;
             vs.c0 = calloc(vs.csize, sizeof(double));
             vs.ci = calloc(vs.csize, sizeof(double));
             hw1 = malloc(sizeof(double) * wfft); hw2 = malloc(sizeof(double) * wfft); tsig = malloc(sizeof(double) * wfft);

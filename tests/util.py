@@ -130,7 +130,10 @@ REF_E2E_CASES = {
 
 
 def ref_e2e_inputs(name):
-    """The files of one input set of REF_E2E_CASES, in list order."""
+    """The files of one input set of REF_E2E_CASES / REF_E2E_OPT_CASES, in list order."""
+    if name == "short3":
+        a, b = ref_e2e_inputs("short")
+        return [a, synth_utt(5, 300), b]
     if name == "ord":
         return [sig("CS0")[:30000].copy(), synth_utt(3, 16000)]
     if name == "short":
@@ -144,3 +147,154 @@ def ref_e2e_inputs(name):
 def ref_e2e():
     """What the compiled reference wrote for REF_E2E_CASES (keys: tests/golden/make_ref_e2e_fixtures.py)."""
     return np.load(os.path.join(GOLDEN, "ref_e2e.npz"))
+
+
+# ---- the rest of the option space against the compiled reference: tests/golden/ref_e2e_opts.npz (make_ref_e2e_fixtures.py opts)
+def _swap(cfg, key, value):
+    """cfg with the value behind option `key` replaced."""
+    out = list(cfg)
+    out[out.index(key) + 1] = value
+    return out
+
+
+VAD_FEA = "-vad_out_mode vad -vad_cri_mode cepdist -vad_cepdist_mode fea".split()
+VAD_ENERGY = "-vad_out_mode vad -vad_cri_mode energy".split()
+SIG_SS = "-format_in raw -format_out raw -w 25 -s 12.5".split()
+
+# Same shape and rules as REF_E2E_CASES.  "short3" = the two "short" files with a 300-sample file between them: no frame at 16 kHz (the *ss
+# modes and exten carry their state over it, window - shift <= 300 < window), two frames at 8 kHz.
+REF_E2E_OPT_CASES = {
+    # filter banks
+    "bank_bark": (C2 + ["-fb_scale", "bark"], "short"),
+    "bank_expolog": (C2 + ["-fb_scale", "expolog"], "short"),
+    "bank_lin_rect": (C2 + "-fb_scale lin -fb_shape rect -fb_definition 20filters".split(), "short"),
+    "bank_trapez": (C2 + ["-fb_shape", "trapez"], "short"),
+    "bank_eqld": (C2 + "-fb_norm off -fb_eqld on".split(), "short"),
+    "bank_two_ranges": (C2 + ["-fb_definition", "100-4000Hz:1-10/10filters,4000-8000Hz:3-6/8filters"], "short"),
+    "bank_bark_hires": (C2 + "-fb_scale bark -fb_definition 1-30/30filters -fea_ncepcoefs 29 -fea_E on".split(), "short"),
+    # feature kinds
+    "kind_spec_mag": (C2 + "-fb_power off -fea_kind spec".split(), "short"),
+    "kind_logspec_rawe": (C2 + "-fea_kind logspec -fea_E on -fea_rawenergy on".split(), "short"),
+    "kind_nolifter_noc0": (C2 + "-fea_lifter 0 -fea_c0 off -fea_ncepcoefs 20".split(), "short"),
+    "kind_lpc12": (C2 + "-fea_kind lpc -fea_lporder 12".split(), "short"),
+    "kind_lpa": (C3 + ["-fea_kind", "lpa"], "short"),
+    "kind_plp23": (C3 + "-fea_lporder 23 -fea_ncepcoefs 23 -fb_definition 30filters".split(), "short"),
+    # the 19 one-bark bands of the PLP bank take no count from -fb_definition: order 23 is not below them (the engine refuses that, DESIGN.md
+    # section 7, and the oracle is the reference's to the last bit all the same); order 23 on 30 mel bands is the case behind it
+    "kind_lpc23_mel30": (("-fs 16000 -format_in raw -format_out htk -preem 0.97 -fb_scale mel -fb_shape triang -fb_norm off -fb_power on -fb_eqld on "
+                         "-fb_inld on -fb_definition 30filters -fea_kind lpc -fea_lporder 23 -fea_ncepcoefs 23 -fea_E on").split(), "short"),
+    "kind_trapdct51": (C2 + "-fb_definition 23filters -fea_kind trapdct,51,8".split(), "short"),
+    "kind_odd_shift": (C2 + ["-s", "10.0625"], "short"),
+    # noise reduction, the state carried over a frameless file
+    "nr_hwss": (C2 + "-nr_mode hwss -vad burg".split(), "short3"),
+    "nr_2fwss": (C2 + "-nr_mode 2fwss -vad burg".split(), "short3"),
+    "nr_hwss_8k": (M8 + "-nr_mode hwss -vad burg -nr_a 2".split(), "short3"),
+    "nr_fwss_da_zexp_e": (C2 + "-nr_mode fwss -vad burg -fea_delta d_a -fea_Z_exp 300 -fea_E on".split(), "short3"),
+    "nr_exten_afterfb": (C2 + "-nr_mode exten -nr_when afterFB".split(), "short3"),
+    "nr_dc1_exten": (C2 + "-remove_dc1 on -nr_mode exten".split(), "short3"),
+    "sig_hwss": (["-fs", "16000"] + SIG_SS + "-nr_mode hwss -vad burg".split(), "short3"),
+    "sig_2fwss_8k": (["-fs", "8000"] + SIG_SS + "-nr_mode 2fwss -vad burg".split(), "short3"),
+    "nr_hwss_44k": (M44 + "-nr_mode hwss -vad burg".split(), "short"),
+    # the VAD module with its stream
+    "vad_c4_perc": (_swap(C4, "-vad_thr_mode", "perc"), "short3"),
+    "vad_c4_absolute": (_swap(C4, "-vad_thr_mode", "absolute") + ["-vad_absolute_thr", "6"], "short3"),      # distances there run from 1.9 to 10.3
+    "vad_c4_dyn": (_swap(C4, "-vad_thr_mode", "dyn"), "short3"),
+    "vad_c4_drop": (C4 + ["-vad_apply_mode", "drop"], "short3"),
+    "vad_c4_order7": (C4 + ["-vad_filter_order", "7"], "short3"),
+    "vad_c4_zexp": (C4 + ["-fea_Z_exp", "500"], "short3"),
+    "vad_fea_adapt": (C2 + VAD_FEA + ["-vad_thr_mode", "adapt"], "short"),
+    "vad_fea_dyn_da": (C2 + VAD_FEA + "-vad_thr_mode dyn -fea_delta d_a".split(), "short"),
+    "vad_fea_dyn_trap3": (C2 + VAD_FEA + "-vad_thr_mode dyn -fea_trap 3".split(), "short"),
+    "vad_fea_adapt_trap9": (C2 + VAD_FEA + "-vad_thr_mode adapt -fea_trap 9".split(), "short"),
+    "vad_energy_absolute": (C2 + VAD_ENERGY + "-vad_thr_mode absolute -vad_absolute_thr 96.5".split(), "short"),   # the first file's median
+    "vad_energy_perc": (C2 + VAD_ENERGY + ["-vad_thr_mode", "perc"], "short"),
+    "vad_energy_adapt_afterfb": (C2 + VAD_ENERGY + "-vad_thr_mode adapt -nr_mode exten -nr_when afterFB".split(), "short"),
+    "vad_energy_dyn_64pt": (M8 + "-w 8 -s 4 -fb_definition 1-10/10filters -fea_ncepcoefs 8".split() + VAD_ENERGY + ["-vad_thr_mode", "dyn"], "short"),
+    # delta chains of the third order
+    "post_dat_windows": (C2 + "-fea_delta d_a_t -d_win 3 -a_win 1 -t_win 2".split(), "short"),
+    "post_dat": (C2 + ["-fea_delta", "d_a_t"], "short"),
+}
+
+
+def g711_codes(n=9000):
+    return np.random.default_rng(711).integers(0, 256, size=n, dtype=np.uint8)
+
+
+def wave_image(x, fs=16000):
+    """int16 samples behind the 44-byte RIFF header."""
+    import struct
+    return (b"RIFF" + struct.pack("<I", 36 + 2 * x.size) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 1, 1, fs, 2 * fs, 2, 16)
+            + b"data" + struct.pack("<I", 2 * x.size) + x.astype("<i2").tobytes())
+
+
+def _raw_files(utts):
+    return {f"in{i}.raw": u.astype("<i2").tobytes() for i, u in enumerate(utts)}
+
+
+def _no_format_out(cfg):
+    i = cfg.index("-format_out")
+    return cfg[:i] + cfg[i + 2:]
+
+
+def ref_e2e_file_cases():
+    """Cases whose target is the FILES the reference writes: name -> (command line, {input file: bytes}, list text, output files).  Every path is
+    relative: the program runs in the directory that holds the inputs (the ark's .scp names the ark as the command line does)."""
+    short = ref_e2e_inputs("short")
+    two = "in0.raw out0\nin1.raw out1\n"
+    spk3 = [short[0], short[1], synth_utt(7, 9000)]
+    cmvn_list = "in0.raw out0 spkA\nin1.raw out1 spkB\nin2.raw out2 spkB\n"
+    return {
+        "file_ark": (_no_format_out(C2) + ["-format_out", "ark=out.ark"], _raw_files(short), "in0.raw utt0\nin1.raw utt1\n", ["out.ark", "out.scp"]),
+        "file_pfile": (_no_format_out(C2) + ["-format_out", "pfile=out.pfile"], _raw_files(short), "in0.raw utt0\nin1.raw utt1\n", ["out.pfile"]),
+        "file_big_endian": (C2 + ["-endian_out", "big"], _raw_files(short), two, ["out0", "out1"]),
+        "file_cmvn": (C1 + ["-apply_cmvn", "stat"], _raw_files(spk3), cmvn_list, ["stat", "out0", "out1", "out2"]),
+        "file_cmvn_da": (C1 + ["-fea_delta", "d_a", "-apply_cmvn", "stat"], _raw_files(spk3), cmvn_list, ["stat", "out0", "out1", "out2"]),
+        "file_alaw": (_swap(C2, "-format_in", "alaw"), {"in0.raw": g711_codes().tobytes()}, "in0.raw out0\n", ["out0"]),
+        "file_mulaw": (_swap(C2, "-format_in", "mulaw"), {"in0.raw": g711_codes().tobytes()}, "in0.raw out0\n", ["out0"]),
+        "file_wave": (_swap(C2, "-format_in", "wave"), {f"in{i}.raw": wave_image(u) for i, u in enumerate(short)}, two, ["out0", "out1"]),
+    }
+
+
+def ref_e2e_opts():
+    """What the compiled reference wrote for REF_E2E_OPT_CASES and ref_e2e_file_cases() (make_ref_e2e_fixtures.py opts)."""
+    return np.load(os.path.join(GOLDEN, "ref_e2e_opts.npz"))
+
+
+def split_written_file(name, data, big_endian=False):
+    """(float32 rows of every utterance in the file, the file's bytes with those floats zeroed) for what a file case wrote: an HTK file,
+    a Kaldi ark (key, " \\0BFM ", \\4 rows \\4 columns, little-endian floats) or a pfile (32768-byte header, rows of two big-endian
+    uint32 + floats, sentence index); any other file (.scp, statistics text) has no float payload."""
+    data = bytes(data)
+    rest = bytearray(data)
+    rows = []
+
+    def take(off, n, d, e):
+        rows.append(np.frombuffer(data, e + "f4", n * d, off).astype(np.float32).reshape(n, d))
+        rest[off:off + 4 * n * d] = bytes(4 * n * d)
+
+    if name.endswith(".ark"):
+        off = 0
+        while off < len(data):
+            off = data.index(b" \0BFM \4", off) + 7
+            n = int(np.frombuffer(data, "<i4", 1, off)[0])
+            d = int(np.frombuffer(data, "<i4", 1, off + 5)[0])
+            assert data[off + 4] == 4
+            take(off + 9, n, d, "<")
+            off += 9 + 4 * n * d
+    elif name.endswith(".pfile"):
+        head = data[:32768].split(b"\0")[0].decode()
+        field = lambda k: int(head.split(k + " ")[1].split()[0])
+        n, d, sents = field("-num_frames"), field("-num_features"), field("-num_sentences")
+        table = np.frombuffer(data, ">u4", sents + 1, 32768 + n * (8 + 4 * d))
+        body = np.frombuffer(data, ">f4", n * (2 + d), 32768).reshape(n, 2 + d)
+        for a, b in zip(table[:-1], table[1:]):
+            rows.append(body[a:b, 2:].astype(np.float32))
+        mask = np.frombuffer(rest, np.uint8, n * (8 + 4 * d), 32768).reshape(n, 8 + 4 * d)
+        mask[:, 8:] = 0
+    elif name.startswith("out") and "." not in name:
+        e = ">" if big_endian else "<"
+        n = int(np.frombuffer(data, e + "u4", 1, 0)[0])
+        size = int(np.frombuffer(data, e + "u2", 1, 8)[0])
+        assert size % 4 == 0 and len(data) == 12 + n * size, (name, n, size, len(data))
+        take(12, n, size // 4, e)
+    return rows, bytes(rest)
