@@ -203,7 +203,10 @@ struct ctu_plan {
         for (hipStream_t st : part_stream)
             if (st) (void)hipStreamDestroy(st);
     }
-    DevBuf<int> tile_utt;            // utterance of every tile (SS)
+    DevBuf<int> tile_utt;            // utterance of every tile (SS); the stream of every tile (a stream set with noise state)
+    // a stream set with noise state (ctu_streams_push): the chain heads of the push at hand instead of wg_first, and the streams' state
+    const int *push_heads = nullptr;
+    void *xstate = nullptr;
     DevBuf<float> ss_seed, ss_last;  // SS: noise seeds per utterance [n_utt][K] and the vectors the utterances leave behind
     DevBuf<unsigned char> ss_dirty;  // SS: utterances a pass of the seed iteration recomputes
     DevBuf<unsigned char> ss_vbits;  // SS: the detector's decision of every frame (first pass), reused by the later passes
@@ -259,6 +262,14 @@ struct ctu_streams {
     std::vector<uint8_t> hsel;
     RowPush *h_rdesc[2] = {nullptr, nullptr};
     DevBuf<RowPush> d_rdesc[2];
+    // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten: Navg | Yavg of every stream (frontend_kernel<..., XS>), the most chains a push
+    // is dealt onto and their heads, which travel as the descriptors do
+    bool chained = false;
+    DevBuf<float> xstate;
+    int max_chains = 0;
+    int *h_heads[2] = {nullptr, nullptr};
+    DevBuf<int> d_heads[2];
+    std::vector<int> chain_tail;     // (scratch of a push: the stream at the end of every chain so far)
     // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
     int16_t *h_stage = nullptr;
     DevBuf<int16_t> d_stage;
@@ -267,6 +278,7 @@ struct ctu_streams {
     ~ctu_streams() {
         for (StreamPush *h : h_desc) ctu_host_free(h);
         for (RowPush *h : h_rdesc) ctu_host_free(h);
+        for (int *h : h_heads) ctu_host_free(h);
         ctu_host_free(h_stage);
         for (hipEvent_t v : desc_free)
             if (v) (void)hipEventDestroy(v);
@@ -472,11 +484,16 @@ std::string unsupported_reason(const ctu::Design &d) {
 // Streaming input (ctu_streams_create): what an accepted configuration carries from one frame of a file to the next beyond the samples
 // themselves.  A stream set keeps samples (stream_kernels.h), so every such chain is refused by the option that brings the state in.
 // With CTU_STREAMS_ROW_STATE the set keeps base rows and running means as well (stream_rows_kernels.h): the delta chain, stacking and CMS pass.
+// With CTU_STREAMS_NR_STATE it keeps the noise estimate of -nr_mode exten on the spectrum (256- and 512-point front end): that passes too.
 std::string streams_unsupported_reason(const ctu::Design &d, uint32_t flags = 0) {
     const ctu::Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
     if (d.signal_out) return "-format_out raw | wave (speech output: the overlap-add runs across a file's frames)";
-    if (o.nr_mode != "none") return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
+    const bool nr_state = (flags & CTU_STREAMS_NR_STATE) != 0;
+    if (o.nr_mode == "exten" && nr_state) {  // the state of exten on the spectrum travels with the stream (frontend_kernel<..., XS>)
+        if (o.nr_when_afterFB) return "-nr_when afterFB (exten behind the filter bank keeps its noise estimate per band, inside the filter-bank walk: a stream set carries the estimate per bin)";
+        if (d.wfft >= 1024) return "-nr_mode exten on " + std::to_string(d.wfft) + "-point frames (-w: the noise estimate of the large transforms lives in their own kernels, a stream set carries the one of the 256- and 512-point front end)";
+    } else if (o.nr_mode != "none") return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
     if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
     if (o.do_vad()) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";
     if (d.kind == ctu::FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
@@ -1249,7 +1266,9 @@ void lift(int v, F &&f) {
     (void)((v == C && (f(std::integral_constant<int, C>{}), true)) || ...);
 }
 // The front-end launch of an engine: its FeSel lifted to template arguments, one at a time; fe_compiled decides which leaves exist.
-void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp) {
+// `xs`: the launch of a stream set with noise state (frontend_kernel<..., XS>; the generic walk: the same rows bit for bit).
+constexpr bool fe_streamed(const FeSel &k) { return !k.vx && !k.vf && !k.ss && !k.sy && (k.gen == GEN_EXTEN || k.gen == GEN_FULL); }
+void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp, bool xs = false) {
     const FeSel &k = e->sel;
 #define V(x) decltype(x)::value
     lift<13, 16>(k.nz, [&](auto NZ) {
@@ -1264,7 +1283,14 @@ void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp)
     lift<0, 1>(k.ss, [&](auto SS) {
     lift<0, 1>(k.sy, [&](auto SY) {
         constexpr FeSel K{V(NZ), V(FEAT), V(MODE), V(VX) != 0, V(NC), V(GEN), V(LPO), V(MD) != 0, V(VF) != 0, V(SS) != 0, V(SY) != 0, -1};
+        if constexpr (fe_compiled(K) && fe_streamed(K)) {
+            if (xs) {
+                launch_fe(e, &frontend_kernel<K.nz, K.feat, K.mode, K.vx, K.nc, K.gen, K.lpo, K.md, K.vf, K.ss, K.sy, walk_generic, true>, grid, s, kp);
+                return;
+            }
+        }
         if constexpr (fe_compiled(K)) {
+            if (xs) throw std::runtime_error("internal: no streamed front-end instantiation for this configuration (" + fe_name(K) + ")");
             bool walked = false;
             for_each_walk([&](auto w) {
                 typedef decltype(w) W;
@@ -1279,7 +1305,7 @@ void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp)
         }
     }); }); }); }); }); }); }); }); }); }); });
 #undef V
-    e->walk_launched = k.walk;
+    e->walk_launched = xs ? -1 : k.walk;
 }
 // A launch with dynamic LDS: past the 64 KiB default the instantiation's limit is raised first.
 template <class K, class... A>
@@ -1366,7 +1392,8 @@ KParams run_kparams(const ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
     kp.rows = (d.post_order > 0 || d.cms) ? pl->base_rows.p : d_rows;
     kp.logmel = pl->logmel.p; kp.xri = pl->xri.p; kp.pnr = pl->pnr.p; kp.ybuf = pl->ybuf.p;
     kp.vad_ci = pl->vad_ci.p; kp.vad_cf = pl->vad_cf.p; kp.lp_r = pl->lp_r.p; kp.dc1 = pl->dc1.p;
-    kp.tiles = pl->tiles.p; kp.wg_first = pl->wg_first.p; kp.tile_utt = pl->tile_utt.p;
+    kp.tiles = pl->tiles.p; kp.wg_first = pl->push_heads ? pl->push_heads : pl->wg_first.p; kp.tile_utt = pl->tile_utt.p;
+    kp.xstate = pl->xstate;
     kp.ss_seed = pl->ss_seed.p; kp.ss_last = pl->ss_last.p; kp.ss_dirty = pl->ss_dirty.p; kp.ss_vbits = pl->ss_vbits.p;
 #ifdef CTU_DIAG  // phase ablation (1 = phase 1 only, 2 = phase 2 only): diagnostic builds only
     kp.dbg = getenv("CTU_DEBUG_MODE") ? atoi(getenv("CTU_DEBUG_MODE")) : 0;
@@ -2344,7 +2371,7 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, fl
         if (d.o.remove_dc1) stage_dc1(e, pl, s, d_pcm);
         HIP_TRY(hipEventRecord(e->ev0, s));
         // the front end; with hwss / fwss / 2fwss `pass` is one pass of the seed iteration, which launches it
-        std::function<void()> pass = [&] { launch_frontend(e, dim3(grid), s, kp); };
+        std::function<void()> pass = [&] { launch_frontend(e, dim3(grid), s, kp, pl->xstate != nullptr); };
         switch (e->path) {
             case BIG_NONE: if (!e->ss) pass(); break;
             case BIG_WAVE1K: stage_wave1k(e, pl, s, bp); break;
@@ -2936,7 +2963,7 @@ int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flag
             say("ENGINE: configuration not on the accelerated path: " + why);
             return CTU_ERR_UNSUPPORTED;
         }
-        if (flags & ~(uint32_t)CTU_STREAMS_ROW_STATE) {
+        if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
             say("ENGINE: unknown stream set flags");
             return CTU_ERR_INPUT;
         }
@@ -2975,7 +3002,7 @@ int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_sample
 int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out) {
     if (!e || !out) return CTU_ERR_INPUT;
     *out = nullptr;
-    if (flags & ~(uint32_t)CTU_STREAMS_ROW_STATE) {
+    if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
         set_error(e, "ENGINE: unknown stream set flags");
         return CTU_ERR_INPUT;
     }
@@ -2988,7 +3015,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
-    if (e->per_wave || e->do_vad || e->ss) {
+    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || e->do_vad || e->ss || (e->per_wave && e->big)) {
         set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
         return CTU_ERR_UNSUPPORTED;
     }
@@ -3004,6 +3031,8 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
     stream_halo(d, &st->H, &st->wmax);
     st->C = st->held ? std::max(2 * st->H, st->H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;
     st->hsel.assign((size_t)n_streams, 0);
+    st->chained = e->per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
+    st->max_chains = st->max_wg * NWAVE;
     // the longest slot: the lead, a full carry, a full push (and no shorter than the shortest file a delta chain is defined on: the plan
     // of a set whose pushes are shorter than that is still a plan of files that could be)
     const std::vector<int64_t> longest((size_t)n_streams, std::max((int64_t)STREAM_LEAD + d.window - 1 + max_push_samples,
@@ -3028,6 +3057,19 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
                 st->h_rdesc[k] = static_cast<RowPush *>(ctu_host_alloc((size_t)n_streams * sizeof(RowPush)));
                 if (!st->h_rdesc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
                 st->d_rdesc[k].alloc((size_t)n_streams);
+            }
+        }
+        if (st->chained) {
+            const size_t per_stream = (size_t)2 * 64 * (e->sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1);  // [2][64 NJ] of xstate_t (frontend_kernel.h)
+            st->xstate.alloc((size_t)n_streams * per_stream);
+            HIP_TRY(hipMemset(st->xstate.p, 0, st->xstate.n * sizeof(float)));  // (never read ahead of a store: a file's first tile resets)
+            pl->tile_utt.alloc(pl->tiles.n);
+            HIP_TRY(hipMemset(pl->tile_utt.p, 0, pl->tile_utt.n * sizeof(int)));
+            pl->xstate = st->xstate.p;
+            for (int k = 0; k < 2; k++) {
+                st->h_heads[k] = static_cast<int *>(ctu_host_alloc((size_t)st->max_chains * sizeof(int)));
+                if (!st->h_heads[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_heads[k].alloc((size_t)st->max_chains);
             }
         }
         if (st->held) {
@@ -3127,7 +3169,20 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         HIP_TRY(hipEventSynchronize(st->desc_free[k]));  // (the push before last has read them; immediate before the first record)
         StreamPush *h = st->h_desc[k];
         int64_t so = PCM_HEAD, ro = 0, oo = 0, most = 0;  // ro: base rows of the push, oo: rows that go out (the same without row state)
-        int tiles = 0, slices = 1;
+        int tiles = 0, slices = 1, live = 0;
+        if (st->chained)  // the streams that complete a frame, dealt in turn onto at most max_chains chains, a wave each
+            for (int i = 0; i < n; i++) {
+                const int64_t c = st->consumed[(size_t)ids[i]];
+                live += stream_frames(c + n_samples[i], d.window, d.wshift) > stream_frames(c, d.window, d.wshift);
+            }
+        // chain c lives in wave c / G of workgroup c % G (as plan_chains deals them)
+        const int C = std::max(1, std::min(live, st->max_chains)), G = (C + NWAVE - 1) / NWAVE;
+        int *heads = st->chained ? st->h_heads[k] : nullptr;
+        if (heads) {
+            std::fill(heads, heads + (size_t)G * NWAVE, -1);
+            st->chain_tail.assign((size_t)C, -1);
+        }
+        live = 0;
         for (int i = 0; i < n; i++) {
             const int64_t c = st->consumed[(size_t)ids[i]];
             const int64_t F = stream_frames(c, d.window, d.wshift), T = stream_frames(c + n_samples[i], d.window, d.wshift) - F;
@@ -3138,7 +3193,14 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
             h[i].id = ids[i];
             h[i].n = (int)n_samples[i];
             h[i].tile0 = tiles;
-            h[i].pad = 0;
+            h[i].pad = -1;
+            if (heads && T > 0) {
+                const int ch = live++ % C;
+                int &tail = st->chain_tail[(size_t)ch];
+                if (tail < 0) heads[(ch % G) * NWAVE + ch / G] = tiles;
+                else h[tail].pad = tiles;
+                tail = i;
+            }
             so += (len + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN;
             ro += T;
             tiles += (int)((T + TILE - 1) / TILE);
@@ -3161,7 +3223,12 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         StreamParams sp;
         sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
         sp.cstride = st->cstride; sp.window = d.window; sp.wshift = d.wshift;
-        sp.n_tiles = tiles; sp.grid = std::max(1, std::min(tiles, st->max_wg));
+        sp.n_tiles = tiles; sp.grid = heads ? G : std::max(1, std::min(tiles, st->max_wg));
+        sp.tile_stream = heads ? pl->tile_utt.p : nullptr;
+        if (heads) {
+            HIP_TRY(hipMemcpyAsync(st->d_heads[k].p, heads, (size_t)G * NWAVE * sizeof(int), hipMemcpyHostToDevice, s));
+            pl->push_heads = st->d_heads[k].p;
+        }
         HIP_TRY(hipEventRecord(st->ev[0], s));
         hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)slices), dim3(256), 0, s, sp);
         HIP_TRY(hipEventRecord(st->ev[1], s));

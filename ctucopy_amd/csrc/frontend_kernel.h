@@ -83,6 +83,9 @@ namespace {
 // WALK:   walk_generic, or a compile-time walk signature of phase 2's filter bank (phase2_walks.h: the preset banks): the slot loop
 //         and every slot's chunk run are straight-line, with the chunk counts and table addresses as immediates.  Same tables, same
 //         lane mapping, same order of additions: the rows are those of the generic walk bit for bit.
+// XS:     a stream set with noise state (CTU_STREAMS_NR_STATE): the per-wave chains are chains of whole streams, and exten's state comes
+//         from, and goes back to, the stream's slot in HBM at the edges of a push (see xs_slot below).  A switch at compile time, not a
+//         pointer at run time: the offline instantiations keep their registers (see the note on 97 -> 96 VGPRs below).
 // The fused detector paths of the 512-point mode (VF / SS with MODE 0) keep both passes' transform outputs and a 25-sample
 // lattice per lane alive: 256 VGPRs, one workgroup per CU (their staging area takes the LDS of the second one anyway).
 #ifndef CTU_SY_LB
@@ -109,7 +112,7 @@ __device__ __forceinline__ void static_for(F &&f) {
     static_for_seq(f, std::make_integer_sequence<int, N>{});
 }
 
-template <int NZ, int FEAT, int MODE, bool VX, int NC, int GEN, int LPO = 0, bool MD = false, bool VF = false, bool SS = false, bool SY = false, class WALK = walk_generic>
+template <int NZ, int FEAT, int MODE, bool VX, int NC, int GEN, int LPO = 0, bool MD = false, bool VF = false, bool SS = false, bool SY = false, class WALK = walk_generic, bool XS = false>
 #if CTU_CAP_WAVES
 // also the MOST waves per SIMD the register file is laid out for: a workgroup is eight waves and the grid is at most two workgroups per
 // CU (engine.hip: max_wg), i.e. four per SIMD when they are dealt evenly.  An instantiation that needs 96 registers or fewer would be
@@ -124,6 +127,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
     static_assert(!SS || (!VX && !VF && (GEN == GEN_PLAIN || GEN == GEN_FULL)), "SS: the plain chain, or run-time flags (signal output, energy columns, -fb_inld, LP kinds, magnitude spectra)");
     static_assert(!((VF || SS) && MODE == 0) || NZ == 13, "VF / SS in the 512-point mode: 400-sample windows (16 lanes x 25 samples)");
     static_assert(!SY || (!VX && !VF && (GEN == GEN_FULL || GEN == GEN_DC1)), "SY: run-time flags, no export");
+    static_assert(!XS || (!VX && !VF && !SS && !SY && (GEN == GEN_EXTEN || GEN == GEN_FULL)), "XS: exten on the spectrum, nothing else that runs along a file");
     const int o_e_mode = FULL ? p.e_mode : 0, o_dbg = FULL ? p.dbg : 0;
     const bool o_fb_inld = FULL ? p.fb_inld != 0 : GEN == GEN_INLD, o_nr_exten = FULL ? p.nr_exten != 0 : GEN == GEN_EXTEN;
     const bool o_fb_power = FULL ? p.fb_power != 0 : true, o_remove_dc = FULL ? p.remove_dc != 0 : true;
@@ -184,6 +188,12 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         navg[j] = (xstate_t)0.95;
         yavg[j] = (xstate_t)0.05;
     }
+    // XS: the chain is one of whole streams (engine.hip: ctu_streams_push).  The state of a stream comes from its slot of p.xstate when
+    // the wave enters the first tile the stream has in this launch - unless that tile starts a file - and goes back behind the last
+    // one; between the tiles of a stream it stays in registers, as it does along an utterance.  Lane = bin: every access is a dword per
+    // lane, 256 contiguous bytes per wave; the floats travel as they stand, so a save and restore is exact.
+    bool xs_first = true;  // the tile at hand is the first its stream has in this launch
+    auto xs_slot = [&](int t) { return uniform_ptr(reinterpret_cast<xstate_t *>(p.xstate) + (size_t)as_const(p.tile_utt)[t] * (2 * 64 * NJ)); };
 
     // -remove_dc1: ov[0] = o_t, ov[j] = o_{t-j} of one frame; what position i of the frame has had subtracted so far
     constexpr int DCJ = 8;
@@ -954,6 +964,17 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     navg[j] = (xstate_t)0.95;
                     yavg[j] = (xstate_t)0.05;
                 }
+            } else {
+                if constexpr (XS) {
+                    if (xs_first && slot0 == 0 && f_lo == 0) {  // the file goes on: where the stream's last push left off
+                        const auto xs = xs_slot(tile);  // (a wave-uniform base and a 32-bit lane offset: no 64-bit address per lane)
+#pragma unroll
+                        for (int j = 0; j < NJ; j++) {
+                            navg[j] = xs[(unsigned)(lane + 64 * j)];
+                            yavg[j] = xs[(unsigned)(lane + 64 * (NJ + j))];
+                        }
+                    }
+                }
             }
             const xstate_t pp = (xstate_t)p.nr_p_d, qq = (xstate_t)1.0 - pp;
             // the next frame's values are read while this frame's recurrence runs (the chain goes through Navg / Yavg in
@@ -1435,6 +1456,17 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         }  // steps of 8 frames
+        if constexpr (XS) {
+            xs_first = rec.t0 + nvalid == rec.T;  // (stream_stitch_kernel: T = the frames of the file once this push is through)
+            if (xs_first) {  // the stream's last tile of this push: the next tile, if any, is another stream's first
+                const auto xs = xs_slot(tile);
+#pragma unroll
+                for (int j = 0; j < NJ; j++) {
+                    xs[(unsigned)(lane + 64 * j)] = navg[j];
+                    xs[(unsigned)(lane + 64 * (NJ + j))] = yavg[j];
+                }
+            }
+        }
         if (next < 0) break;
         rec = nrec;
         tile = next;  // SS looks its utterance up by tile (seed in, last vector out)

@@ -19,7 +19,12 @@
 // aligned, so every store is a b128.  A workgroup of 256 lanes per stream and slice of 2048 slot samples; no atomics: a stream id
 // appears once in a push.
 //
-// gfx950, hipcc -O3: stream_stitch_kernel 14 VGPRs, 56 SGPRs; stream_carry_kernel 17 VGPRs, 45 SGPRs; no spills, no scratch, no LDS.
+// Noise state (CTU_STREAMS_NR_STATE on a chain with -nr_mode exten): the front end walks chains of whole
+// streams, one per wave, as it walks chains of whole utterances offline.  The host deals the streams that complete a frame onto the
+// chains and sends the heads and, per stream, the tile behind its last one; stream_stitch_kernel links the records accordingly and
+// notes every tile's stream, where the front end finds the slot of the state.
+//
+// gfx950, hipcc -O3: stream_stitch_kernel 15 VGPRs, 58 SGPRs; stream_carry_kernel 17 VGPRs, 45 SGPRs; no spills, no scratch, no LDS.
 #pragma once
 
 namespace {
@@ -44,7 +49,7 @@ struct StreamPush {
     long long slot;   // where its slot starts in the push arena (samples, a multiple of PCM_ALIGN)
     long long row0;   // first row of the push it writes
     int id, n;        // stream, new samples
-    int tile0, pad;   // first tile record it fills
+    int tile0, pad;   // first tile record it fills; pad: with noise state, the tile that follows its last one on its chain (-1: none)
 };
 
 struct StreamParams {
@@ -56,6 +61,8 @@ struct StreamParams {
     TileRec *tiles;
     int cstride, window, wshift;
     int n_tiles, grid;      // tiles of the whole push and the workgroups of the front-end launch: tile i is followed by tile i + grid
+    int *tile_stream;       // noise state (null without): the stream of every tile, and chains of whole streams - a stream's tiles follow
+                            // each other, StreamPush::pad follows its last one
 };
 
 __device__ __forceinline__ unsigned pack2(const int16_t a, const int16_t b) { return (unsigned)(unsigned short)a | ((unsigned)(unsigned short)b << 16); }
@@ -90,7 +97,12 @@ __global__ __launch_bounds__(256) void stream_stitch_kernel(const StreamParams p
             const long long sbase = d.slot + STREAM_LEAD + (long long)t * TILE * p.wshift, rbase = d.row0 + (long long)t * TILE;
             int4 *w = reinterpret_cast<int4 *>(p.tiles + idx);
             w[0] = make_int4((int)(sbase & 0xffffffff), (int)(sbase >> 32), (int)(rbase & 0xffffffff), (int)(rbase >> 32));
-            w[1] = make_int4(min(TILE, T - TILE * t), t0 + TILE * t, idx + p.grid < p.n_tiles ? idx + p.grid : -1, t0 + T);
+            int next = idx + p.grid < p.n_tiles ? idx + p.grid : -1;
+            if (p.tile_stream) {
+                next = TILE * (t + 1) < T ? idx + 1 : d.pad;
+                p.tile_stream[idx] = d.id;
+            }
+            w[1] = make_int4(min(TILE, T - TILE * t), t0 + TILE * t, next, t0 + T);
         }
     }
 }

@@ -13,6 +13,7 @@ from . import build as _build
 
 CTU_OK, CTU_ERR_OPTS, CTU_ERR_UNSUPPORTED, CTU_ERR_DEVICE, CTU_ERR_INPUT = 0, -1, -2, -3, -4
 STREAMS_ROW_STATE = 1  # CTU_STREAMS_ROW_STATE
+STREAMS_NR_STATE = 4   # CTU_STREAMS_NR_STATE
 
 
 class CtuError(RuntimeError):
@@ -180,19 +181,21 @@ def config_table(args, name):
     return out
 
 
-def streams_config_check(args, row_state=False):
+def streams_config_check(args, row_state=False, nr_state=False):
     """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
     CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give.  With row_state (a set that
-    may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo)."""
+    may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo).  With nr_state the set keeps the noise
+    estimate of -nr_mode exten too."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
-    if not row_state:
+    if not row_state and not nr_state:
         rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
         return int(rc), buf.value.decode()
     halo = ctypes.c_int32(0)
-    rc = L.ctu_streams_config_check_ex(n, arr, STREAMS_ROW_STATE, buf, len(buf), ctypes.byref(halo))
-    return int(rc), buf.value.decode(), int(halo.value)
+    flags = (STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0)
+    rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
+    return (int(rc), buf.value.decode(), int(halo.value)) if row_state else (int(rc), buf.value.decode())
 
 
 def streams_step(window, wshift, total):
@@ -216,14 +219,16 @@ def streams_rows_step(window, wshift, halo, wmax, total):
 
 class Streams:
     """A set of `n` streams on an engine (Engine.streams): PCM in per stream as it arrives, the rows of the frames it completes out.
-    With row_state the set takes delta chains, stacking and CMS too, and may deliver a frame's row with a later push or with finish."""
+    With row_state the set takes delta chains, stacking and CMS too, and may deliver a frame's row with a later push or with finish.
+    With nr_state it takes -nr_mode exten (on the spectrum, 256- and 512-point front end): the noise estimate is kept per stream."""
 
-    def __init__(self, engine, n, max_push, row_state=False):
+    def __init__(self, engine, n, max_push, row_state=False, nr_state=False):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        if row_state:
-            rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, STREAMS_ROW_STATE, ctypes.byref(h))
+        if row_state or nr_state:
+            flags = (STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0)
+            rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))
         else:
             rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
         if rc != CTU_OK:
@@ -381,9 +386,9 @@ class Engine:
     def plan(self, nsamples):
         return Plan(self, nsamples)
 
-    def streams(self, n, max_push, row_state=False):
+    def streams(self, n, max_push, row_state=False, nr_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
-        return Streams(self, n, max_push, row_state)
+        return Streams(self, n, max_push, row_state, nr_state)
 
     def _check(self, rc):
         if rc != CTU_OK:

@@ -166,7 +166,8 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  *
  * Streamed are the chains whose frames share nothing but samples: every feature kind, filter bank, FFT size and energy
  * column ctu_engine_create accepts, without -nr_mode, -remove_dc1, the VAD module, -fea_delta / -fea_trap / trapdct, CMS,
- * CMVN, speech output or HTK feature input.  ctu_streams_create refuses those with CTU_ERR_UNSUPPORTED and the option's name in
+ * CMVN, speech output or HTK feature input (the flags of ctu_streams_create_ex below add the delta chains, stacking, CMS and
+ * -nr_mode exten).  ctu_streams_create refuses those with CTU_ERR_UNSUPPORTED and the option's name in
  * ctu_last_error; ctu_streams_config_check says the same from the command line alone (no device; `reason` receives the text).
  *
  * A push names n different streams (a repeat, an id outside the set, more than max_push_samples for one stream or more rows
@@ -183,8 +184,17 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * frames a stream has delivered R(F) = F - H rows - none while F < wmax + 2 (wmax: the largest window), since no row may go out of a
  * file that could still end where the offline plan refuses it - and holds F - R(F) back.  A push delivers the rows R(F) of its
  * streams advance by (row_counts, and the capacity check, count those; up to wmax + 1 more than the frames it completes), and
- * ctu_streams_finish delivers the rest with the file's end known.  On a chain without such state the flag changes nothing. */
-enum { CTU_STREAMS_ROW_STATE = 1 };
+ * ctu_streams_finish delivers the rest with the file's end known.  On a chain without such state the flag changes nothing.
+ *
+ * Noise state (CTU_STREAMS_NR_STATE; the two flags combine): the set also keeps, per stream, the noise estimate of extended spectral
+ * subtraction - Navg and Yavg of every bin (src/nr/nr.cc:86-140) - and so takes -nr_mode exten on the spectrum (-nr_when beforeFB) of the
+ * 256- and 512-point front end, FFT sizes below 256 included: the plain cepstral chain, band outputs, -fea_E, -fb_inld / PLP and the LP
+ * kinds, and with row state the delta chains, stacking and CMS behind them.  Exten is causal - frame t reads frames 0 .. t - so a row
+ * still goes out with the push that completes its frame, R(F) is unchanged and ctu_streams_finish has nothing to add; a stream's next
+ * file starts from the reference's initial estimate.  Still refused, by name, whatever the flags: -nr_when afterFB, exten on 1024 ..
+ * 4096 points, hwss / fwss / 2fwss, the VAD module, -remove_dc1, trapdct, CMVN, speech output, HTK feature input.  On a chain
+ * without -nr_mode exten the flag changes nothing. */
+enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4 };   /* (2 is no flag: sets refuse it as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);

@@ -6,8 +6,11 @@ of the timed pushes), the push rate in frames/s from the host's clock around syn
 device-resident run over the same frames (N utterances of 10 frames; the offline path is the parent commit's).
 With --row-state the same again for MFCC_0_D_A with a running mean (-fea_delta d_a -fea_Z_exp 500) on a set with row state, in the
 same run: its front-end span includes the streamed delta and CMS kernels, its carry span the base-row history.
+With --nr-state the same again for C4 without its VAD (MFCC-13 at 8 kHz behind -nr_mode exten -nr_a 2) on a set with noise state: its
+front end walks chains of whole streams, a wave each, and loads and stores the noise estimate at the edges of the push; the offline run
+beside it is ten-frame files, each of which starts from the initial estimate.
 
-    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3] [--row-state]
+    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3] [--row-state] [--nr-state]
 """
 import argparse
 import os
@@ -20,23 +23,23 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 from ctucopy_amd import Engine  # noqa: E402
-from tests.util import C2, synth_utt  # noqa: E402
+from tests.util import C2, C4_NOVAD, synth_utt  # noqa: E402
 
 
 CHAIN = ["-fea_delta", "d_a", "-fea_Z_exp", "500"]
 
 
-def measure(n, pushes, warmup, chain=False):
+def measure(n, pushes, warmup, chain=False, nr=False):
     import torch
-    eng = Engine(C2 + (CHAIN if chain else []))
+    eng = Engine(C4_NOVAD if nr else C2 + (CHAIN if chain else []))
     w, s, D = eng.dims.window, eng.dims.wshift, eng.dims.row_floats
     hop = 10 * s
     total = w - s + hop * (warmup + pushes)
-    x = synth_utt(1, total)
+    x = synth_utt(1, total, fs=eng.dims.fs)
     pcm = torch.from_numpy(np.tile(x, n)).cuda()
     ids = np.arange(n, dtype=np.int32)
     base = np.arange(n, dtype=np.int64) * total
-    st = eng.streams(n, hop, row_state=chain)
+    st = eng.streams(n, hop, row_state=chain, nr_state=nr)
     rows = torch.empty((n * 11, D), dtype=torch.float32, device="cuda")
     cnt = st.push_device(ids, pcm, base, np.full(n, w - s), rows)   # the samples ahead of the first hop: no frame yet
     assert int(cnt.sum()) == 0
@@ -78,16 +81,20 @@ def main():
     ap.add_argument("--pushes", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--row-state", action="store_true", help="also MFCC_0_D_A with exponential CMS on a set with row state")
+    ap.add_argument("--nr-state", action="store_true", help="also C4 without its VAD (-nr_mode exten) on a set with noise state")
     a = ap.parse_args()
     lines = ["# tools/probes/streams_push.py: MFCC-13, 16 kHz, pushes of 10 hops per stream, device-resident; medians of %d pushes after %d" % (a.pushes, a.warmup),
              "# spans from HIP events on the push's stream; rates from the host's clock around synchronised calls (launch overhead included)",
              "# streams  stitch_ms  frontend_ms  carry_ms  push_frames_per_s  offline_frontend_ms  offline_frames_per_s"]
-    for chain in ((False, True) if a.row_state else (False,)):
+    for chain, nr in [(False, False)] + ([(True, False)] if a.row_state else []) + ([(False, True)] if a.nr_state else []):
+        if nr:
+            lines.append("# " + " ".join(C4_NOVAD) + " on a set with noise state (frontend_ms: chains of whole streams, a wave each, the noise estimate loaded"
+                         " and stored at the edges of the push; the offline run is files of ten frames, each from the initial estimate)")
         if chain:
             lines.append("# the same with " + " ".join(CHAIN) + " on a set with row state (frontend_ms: with the streamed delta and CMS kernels; carry_ms: with"
                          " the base-row history; offline_frontend_ms is the front end alone, the offline rate has post_kernel and cms_exp_kernel in it)")
         for n in (1000, 10000):
-            med, pr, ok, orate = measure(n, a.pushes, a.warmup, chain)
+            med, pr, ok, orate = measure(n, a.pushes, a.warmup, chain, nr)
             lines.append("%7d  %.4f  %.4f  %.4f  %.3e  %.4f  %.3e" % (n, med[0], med[1], med[2], pr, ok, orate))
     text = "\n".join(lines) + "\n"
     print(text, end="")
