@@ -1,6 +1,6 @@
 // MI355X (gfx950) engine: host side of the C ABI (include/ctu_engine.h) - table design for the kernels, plans
 // (batch layout, tile chains), launches.  The kernels live in the headers included below, in one translation unit:
-//   kernel_common.h    constants, the kernel parameter block, DPP / LDS helpers, tile records
+//   kernel_common.h    constants (layout_constants.h: those host-only code shares), the kernel parameter block, DPP / LDS helpers, tile records
 //   frontend_kernel.h  PCM -> pre-emphasis * Hamming -> 512/256-pt real FFT in registers -> |.|^2 (P tile in LDS)
 //                      -> exten NR -> banded filter bank -> ^0.33 / log -> DCT-II + lifter | cosine iDFT + Levinson
 //   vad_kernels.h      Burg-cepstral criterion (packed inverse FFT + lattice), the detector's recurrences per utterance (one wave, or one
@@ -16,6 +16,8 @@
 //   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
 //   stream_kernels.h   streaming input: carry | new samples into the slots of a push arena, the tile records of the push, the next carry
 //   stream_rows_kernels.h  streaming input with row state: delta chain / stacking and CMS by absolute frame index, the base-row history
+//   stream_plan.h      streaming input, host only and HIP-free: the descriptors of a push and the planner that fills them (slots, chains, rows)
+//   streams_host.h     streaming input, host side: the stream set, create / push (check, plan, commit, launch) / finish
 //
 // Data layout in HBM
 //   pcm   : one packed int16 arena; utterance i starts at sample_off[i] (multiple of 8 samples)
@@ -174,13 +176,23 @@ struct ctu_engine {
     BigParams bp0;  // (`big` only)
 };
 
+// What a run covers of a plan's buffers: a plan's own extent is the whole of it (plan_layout, plan_chains, ctu_plan_create), a push of
+// a stream set runs the front of its set's plan with the extent of the push (streams_host.h).  Every stage launches by the extent it is
+// given; a plan is not written once it is created.
+struct RunExtent {
+    int n_tiles = 0;
+    int grid = 0;                  // workgroups of the front-end launch (tile chains are built for it)
+    int64_t total_frames = 0;
+    const int *heads = nullptr;    // first tile of every chain: a plan's wg_first, or the heads a push was dealt onto (null: a plan over rows)
+    void *xstate = nullptr;        // a stream set with noise state: exten's state of every stream (null: none, every file starts afresh)
+};
+
 struct ctu_plan {
     ctu_engine *eng = nullptr;
     int n_utt = 0;
     std::vector<int64_t> nsamples, sample_off, row_off, frames;
-    int64_t total_samples = 0, total_frames = 0;
-    int n_tiles = 0;
-    int grid = 0;               // workgroups of the front-end launch (tile chains are built for it)
+    int64_t total_samples = 0;
+    RunExtent ext;              // the whole plan
     DevBuf<TileRec> tiles;
     DevBuf<int> wg_first;
     // host-buffer runs: device copies of the arena / rows / VAD bytes, kept for the life of the plan
@@ -204,9 +216,6 @@ struct ctu_plan {
             if (st) (void)hipStreamDestroy(st);
     }
     DevBuf<int> tile_utt;            // utterance of every tile (SS); the stream of every tile (a stream set with noise state)
-    // a stream set with noise state (ctu_streams_push): the chain heads of the push at hand instead of wg_first, and the streams' state
-    const int *push_heads = nullptr;
-    void *xstate = nullptr;
     DevBuf<float> ss_seed, ss_last;  // SS: noise seeds per utterance [n_utt][K] and the vectors the utterances leave behind
     DevBuf<unsigned char> ss_dirty;  // SS: utterances a pass of the seed iteration recomputes
     DevBuf<unsigned char> ss_vbits;  // SS: the detector's decision of every frame (first pass), reused by the later passes
@@ -232,59 +241,6 @@ struct ctu_plan {
     DevBuf<int4> utt_info;
     DevBuf<int> trap_chunks, trap_chunks128;   // (utterance, first frame) of every 64- / 128-frame chunk
     int n_trap_chunks = 0, n_trap_chunks128 = 0;
-};
-
-// A stream set (ctu_streams_create): per-stream state in HBM, and what a push needs that does not change from push to push - a plan over
-// n_streams utterances of the longest stitched length, whose tile list, chain heads (workgroup g starts at tile g), arena size and scratch a
-// push uses the front of.  The tile records themselves are written by stream_stitch_kernel, push after push.
-struct ctu_streams {
-    ctu_engine *eng = nullptr;
-    int n_streams = 0, cstride = 0, max_wg = 1;
-    int64_t max_push = 0;
-    std::unique_ptr<ctu_plan> plan;
-    DevBuf<int16_t> arena, carry;
-    DevBuf<StreamState> state;
-    std::vector<int64_t> consumed;   // the host's mirror of StreamState::consumed: layout and row counts of a push need no copy back
-    std::vector<uint32_t> seen;      // the push a stream was last named in (a repeat inside one push is refused)
-    uint32_t push_no = 0;
-    // the descriptors of a push: two page-locked buffers and their device copies in turn, each guarded by the event behind its last reader
-    StreamPush *h_desc[2] = {nullptr, nullptr};
-    DevBuf<StreamPush> d_desc[2];
-    hipEvent_t desc_free[2] = {nullptr, nullptr};
-    int turn = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around stream_stitch_kernel and stream_carry_kernel of the last push
-    bool timed = false;
-    // CTU_STREAMS_ROW_STATE with a delta chain, stacking or CMS (stream_rows_kernels.h): the halo, the largest window, the history's rows,
-    // the two histories of every stream and which one is current, the running means, the descriptors of the row kernels
-    bool held = false;
-    int H = 0, wmax = 0, C = 0;
-    DevBuf<float> hist, means;
-    std::vector<uint8_t> hsel;
-    RowPush *h_rdesc[2] = {nullptr, nullptr};
-    DevBuf<RowPush> d_rdesc[2];
-    // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten: Navg | Yavg of every stream (frontend_kernel<..., XS>), the most chains a push
-    // is dealt onto and their heads, which travel as the descriptors do
-    bool chained = false;
-    DevBuf<float> xstate;
-    int max_chains = 0;
-    int *h_heads[2] = {nullptr, nullptr};
-    DevBuf<int> d_heads[2];
-    std::vector<int> chain_tail;     // (scratch of a push: the stream at the end of every chain so far)
-    // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
-    int16_t *h_stage = nullptr;
-    DevBuf<int16_t> d_stage;
-    DevBuf<float> d_rows;
-    std::vector<int64_t> offs;
-    ~ctu_streams() {
-        for (StreamPush *h : h_desc) ctu_host_free(h);
-        for (RowPush *h : h_rdesc) ctu_host_free(h);
-        for (int *h : h_heads) ctu_host_free(h);
-        ctu_host_free(h_stage);
-        for (hipEvent_t v : desc_free)
-            if (v) (void)hipEventDestroy(v);
-        for (hipEvent_t v : ev)
-            if (v) (void)hipEventDestroy(v);
-    }
 };
 
 namespace {
@@ -1385,25 +1341,25 @@ BigParams engine_bigparams(const ctu_engine *e) {
     return bp;
 }
 // A run's blocks: the engine's, with the caller's buffers and the plan's scratch.
-KParams run_kparams(const ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows) {
+KParams run_kparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const int16_t *d_pcm, float *d_rows) {
     const ctu::Design &d = *e->design;
     KParams kp = e->kp0;
     kp.pcm = d_pcm;
     kp.rows = (d.post_order > 0 || d.cms) ? pl->base_rows.p : d_rows;
     kp.logmel = pl->logmel.p; kp.xri = pl->xri.p; kp.pnr = pl->pnr.p; kp.ybuf = pl->ybuf.p;
     kp.vad_ci = pl->vad_ci.p; kp.vad_cf = pl->vad_cf.p; kp.lp_r = pl->lp_r.p; kp.dc1 = pl->dc1.p;
-    kp.tiles = pl->tiles.p; kp.wg_first = pl->push_heads ? pl->push_heads : pl->wg_first.p; kp.tile_utt = pl->tile_utt.p;
-    kp.xstate = pl->xstate;
+    kp.tiles = pl->tiles.p; kp.wg_first = x.heads; kp.tile_utt = pl->tile_utt.p;
+    kp.xstate = x.xstate;
     kp.ss_seed = pl->ss_seed.p; kp.ss_last = pl->ss_last.p; kp.ss_dirty = pl->ss_dirty.p; kp.ss_vbits = pl->ss_vbits.p;
 #ifdef CTU_DIAG  // phase ablation (1 = phase 1 only, 2 = phase 2 only): diagnostic builds only
     kp.dbg = getenv("CTU_DEBUG_MODE") ? atoi(getenv("CTU_DEBUG_MODE")) : 0;
 #endif
     return kp;
 }
-BigParams run_bigparams(const ctu_engine *e, const ctu_plan *pl, const KParams &kp) {
+BigParams run_bigparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const KParams &kp) {
     BigParams bp = e->bp0;
-    bp.pcm = kp.pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = pl->n_tiles;
-    bp.chain_first = pl->wg_first.p; bp.n_chains = (int)pl->wg_first.n;
+    bp.pcm = kp.pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = x.n_tiles;
+    bp.chain_first = x.heads; bp.n_chains = (int)pl->wg_first.n;  // (the count is the plan's: no stream set runs chains on the large-FFT kernels)
     bp.vad_en = (e->do_vad && e->vp.cri == 0) ? pl->pnr.p : nullptr;
     bp.dc1 = pl->dc1.p;
     // the spectra leave bigfft_kernel for bigsynth_kernel, bigburg_kernel (which reads them; the rows are projected as well) or bigss_kernel
@@ -1426,11 +1382,11 @@ void stage_dc1(const ctu_engine *e, const ctu_plan *pl, hipStream_t s, const int
 }
 
 // bigfft_kernel: a workgroup per frame over the tile list, as many as fit the chip at once; with exten one workgroup per chain of utterances
-void launch_bigfft(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigParams &bp) {
+void launch_bigfft(ctu_engine *e, const RunExtent &x, hipStream_t s, const BigParams &bp) {
     const LdsFit fit = bigfft_lds(*e->design, e->feat, e->ncoef_out, e->big_fb_total);
     if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
     if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without chains");
-    const dim3 g((unsigned)std::max(1, bp.nr_exten ? bp.n_chains : std::min(pl->n_tiles, e->n_cu * fit.per_cu)));
+    const dim3 g((unsigned)std::max(1, bp.nr_exten ? bp.n_chains : std::min(x.n_tiles, e->n_cu * fit.per_cu)));
     lift<4, 8, 16>(big_nit(e), [&](auto nit) {
         constexpr int NIT = decltype(nit)::value;
         if (bp.nr_exten) launch_lds(e, &bigfft_kernel<NIT, true>, g, dim3(256), fit.bytes, s, bp);
@@ -1438,35 +1394,35 @@ void launch_bigfft(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigPa
     });
 }
 // 1024 points: one wave per frame, the transform in registers (wave1k_kernel.h); tiles are dealt to waves
-void stage_wave1k(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigParams &bp) {
+void stage_wave1k(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, const BigParams &bp) {
     const ctu::Design &d = *e->design;
     const LdsFit fit = wave1k_lds(d, e->feat, e->ncoef_out, e->big_fb_total);
     if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the 1024-point kernel");
     if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without per-wave chains");
     // exten: one wave per chain of utterances, every chain gets its wave whatever fits the chip at once
     const int wg = bp.nr_exten ? std::max(1, (bp.n_chains + W1K_WAVES - 1) / W1K_WAVES)
-                               : std::max(1, std::min((pl->n_tiles + W1K_WAVES - 1) / W1K_WAVES, e->n_cu * fit.per_cu));
+                               : std::max(1, std::min((x.n_tiles + W1K_WAVES - 1) / W1K_WAVES, e->n_cu * fit.per_cu));
     lift<0, 1>(bp.nr_exten, [&](auto ex) {
         launch_lds(e, &wave1k_kernel<decltype(ex)::value != 0>, dim3(wg), dim3(64 * W1K_WAVES), fit.bytes, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
     });
 }
 // hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h): the spectra once (bigfft_kernel with the export on and the projection off),
 // the detector's cepstra and decisions once; returns the launch of bigss_kernel, one pass of the seed iteration (run_ss_chain)
-std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const BigParams &bp) {
+std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, const BigParams &bp) {
     const ctu::Design &d = *e->design;
     if (d.wfft != 2048 && d.wfft != 4096) throw std::runtime_error("internal: SS engine without an SS instantiation");
     BigParams xp = bp;
     xp.xri_only = 1;
-    launch_bigfft(e, pl, s, xp);
+    launch_bigfft(e, x, s, xp);
     HIP_TRY(hipGetLastError());
     if (!e->ss_file) {
         const LdsFit fit = bigburg_lds(d.wfft);
-        const dim3 bg((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * fit.per_cu));
+        const dim3 bg((unsigned)std::min<int64_t>(x.total_frames, (int64_t)e->n_cu * fit.per_cu));
         const int nc = d.o.fea_ncepcoefs, two = e->ss == 3;
         lift<8, 16>(big_nit(e), [&](auto nit) {
             lift<16, 32>(nc <= 16 ? 16 : 32, [&](auto cap) {
                 launch_lds(e, &bigssdet_kernel<decltype(nit)::value, decltype(cap)::value>, bg, dim3(256), fit.bytes, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, d.wfft,
-                           d.window, nc, (int64_t)pl->total_frames, e->big_tw.p, e->big_han.p, (float)d.o.nr_a, two);
+                           d.window, nc, (int64_t)x.total_frames, e->big_tw.p, e->big_han.p, (float)d.o.nr_a, two);
             });
         });
         HIP_TRY(hipGetLastError());
@@ -1491,7 +1447,7 @@ std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, hipSt
 // two or three passes.  Synchronous: each pass reads the vectors back.  `pass` launches one pass (the front end on kp, or bigss_kernel).
 // CTU_ERR_INPUT, with vad_pos and ss_stale untouched, when the -vad file= stream ends inside the run.
 template <class Pass>
-int run_ss_chain(ctu_engine *e, const ctu_plan *pl, hipStream_t s, KParams &kp, Pass &&pass) {
+int run_ss_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, KParams &kp, Pass &&pass) {
     const ctu::Design &d = *e->design;
     const size_t nk = (size_t)pl->n_utt * d.K;
     std::vector<float> seed(nk, 0.f), last(nk, 0.f), next(nk, 0.f);
@@ -1526,7 +1482,7 @@ int run_ss_chain(ctu_engine *e, const ctu_plan *pl, hipStream_t s, KParams &kp, 
         // -vad file=<f>: `char vad = fgetc(fvad); if (vad != EOF) return bool(vad); else throw` (nr.cc:297-302), one byte per frame in
         // list order, the stream running on from file to file and from run to run.  Every byte but NUL is speech; a byte 0xFF
         // compares equal to EOF in the reference's (signed) char and ends the run like the end of the file does.
-        const int64_t nf = pl->total_frames;
+        const int64_t nf = x.total_frames;
         std::vector<unsigned char> vb((size_t)std::max<int64_t>(nf, 1), 0);
         for (int64_t i = 0; i < nf; i++) {
             if (e->vad_pos + i >= (int64_t)e->vad_stream.size() || e->vad_stream[(size_t)(e->vad_pos + i)] == 0xFF) {
@@ -1566,9 +1522,9 @@ int run_ss_chain(ctu_engine *e, const ctu_plan *pl, hipStream_t s, KParams &kp, 
 }
 
 // Levinson-Durbin and a -> c on the lags the front end or wave1k_kernel left, one frame per lane (lp_tail_kernel.h)
-void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KParams &kp) {
+void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, const KParams &kp) {
     LpTailParams tp;
-    tp.lags = pl->lp_r.p; tp.rows = kp.rows; tp.total_frames = pl->total_frames;
+    tp.lags = pl->lp_r.p; tp.rows = kp.rows; tp.total_frames = x.total_frames;
     tp.lifter = e->big ? e->big_lifter.p : e->ftab.p + e->lift_off;
     tp.row_slot = e->big ? e->big_slot.p : e->itab.p + e->NS + 1;
     tp.stride = kp.lp_stride; tp.D = kp.D; tp.lporder = kp.lporder; tp.ncep = kp.ncep; tp.is_lpa = kp.lp_is_lpa;
@@ -1576,7 +1532,7 @@ void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KPara
     tp.inv_stride = (unsigned)((1ull << 32) / (unsigned)tp.stride) + 1u;
     tp.inv_D = (unsigned)((1ull << 32) / (unsigned)tp.D) + 1u;
     const LdsFit fit = lp_tail_lds(tp.stride, tp.D, lags_double(e));
-    const dim3 tg((unsigned)std::max<int64_t>(1, std::min<int64_t>((pl->total_frames + 255) / 256, (int64_t)e->n_cu * fit.per_cu)));
+    const dim3 tg((unsigned)std::max<int64_t>(1, std::min<int64_t>((x.total_frames + 255) / 256, (int64_t)e->n_cu * fit.per_cu)));
     if (lags_double(e)) launch_lds(e, &lp_tail_kernel<double, 0>, tg, dim3(256), fit.bytes, s, tp);
     else if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) launch_lds(e, &lp_tail_kernel<float, 12>, tg, dim3(256), fit.bytes, s, tp);
     else launch_lds(e, &lp_tail_kernel<float, 0>, tg, dim3(256), fit.bytes, s, tp);
@@ -1585,25 +1541,25 @@ void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KPara
 
 // The VAD's Burg-cepstral criterion outside the fused path, on the spectra the front end exported: bigburg_kernel at 1024 .. 4096 points
 // (a workgroup per frame), vad_burg_kernel below (a wave per frame; Q samples per lane: windows of up to 256 samples, or longer)
-void stage_burg_vad(ctu_engine *e, const ctu_plan *pl, hipStream_t s) {
+void stage_burg_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s) {
     const ctu::Design &d = *e->design;
     const int cap = e->vp.ncoef <= 16 ? 16 : 32;
-    if (e->vp.cri == 1 && e->big && pl->total_frames > 0) {
+    if (e->vp.cri == 1 && e->big && x.total_frames > 0) {
         const LdsFit fit = bigburg_lds(d.wfft);
-        const dim3 g((unsigned)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * fit.per_cu));
+        const dim3 g((unsigned)std::min<int64_t>(x.total_frames, (int64_t)e->n_cu * fit.per_cu));
         lift<4, 8, 16>(big_nit(e), [&](auto nit) {
             lift<16, 32>(cap, [&](auto nc) {
                 launch_lds(e, &bigburg_kernel<decltype(nit)::value, decltype(nc)::value>, g, dim3(256), fit.bytes, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp,
-                           (int64_t)pl->total_frames, e->big_tw.p);
+                           (int64_t)x.total_frames, e->big_tw.p);
             });
         });
     } else if (e->vp.cri == 1 && !e->vf && !e->big) {
-        const dim3 g((unsigned)std::min<int64_t>((pl->total_frames + 3) / 4, (int64_t)e->n_cu * 4));
+        const dim3 g((unsigned)std::min<int64_t>((x.total_frames + 3) / 4, (int64_t)e->n_cu * 4));
         const size_t bshm = (512 + (size_t)4 * 2 * (d.wfft / 2 + 4)) * 2 * sizeof(vreal);
         lift<4, 8>(d.window <= 256 ? 4 : 8, [&](auto q) {
             lift<16, 32>(cap, [&](auto nc) {
                 hipLaunchKernelGGL((vad_burg_kernel<decltype(q)::value, decltype(nc)::value>), g, dim3(256), bshm, s, pl->xri.p, pl->pnr.p, pl->vad_ci.p, e->vp,
-                                   pl->total_frames);
+                                   x.total_frames);
             });
         });
     }
@@ -1633,11 +1589,11 @@ void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
 }
 
 // The wide DCT tail (dctw_kernel.h) over the band logarithms the front end left, into the rows the front end would have written
-void stage_dctw(ctu_engine *e, const ctu_plan *pl, hipStream_t s, const KParams &kp) {
+void stage_dctw(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, const KParams &kp) {
     DctwParams wp;
-    wp.logmel = pl->logmel.p; wp.rows = kp.rows; wp.atab = e->dctw_tab.p; wp.total_frames = pl->total_frames;
+    wp.logmel = pl->logmel.p; wp.rows = kp.rows; wp.atab = e->dctw_tab.p; wp.total_frames = x.total_frames;
     wp.B = kp.B; wp.D = kp.D; wp.nout = e->dctw_nout; wp.chunks = e->dctw_chunks;
-    wp.n_tiles = (int)((pl->total_frames + DCTW_TILE - 1) / DCTW_TILE);
+    wp.n_tiles = (int)((x.total_frames + DCTW_TILE - 1) / DCTW_TILE);
     const dim3 g((unsigned)std::max(1, std::min(wp.n_tiles, e->n_cu * 8)));
     lift<2, 3, 4>((wp.nout + 15) / 16, [&](auto nrb) { hipLaunchKernelGGL(dct_wide_kernel<decltype(nrb)::value>, g, dim3(256), 0, s, wp); });
     HIP_TRY(hipGetLastError());
@@ -1695,9 +1651,9 @@ void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) 
 
 // The fused path left the lattice's output of every frame behind: the coefficient recursion and a -> c one frame per lane,
 // then the detector's recurrences, sixteen utterances per wave
-void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, hipStream_t s, uint8_t *d_vad) {
+void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, uint8_t *d_vad) {
     if (CTU_VF_A2C)
-        hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((pl->total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)pl->total_frames);
+        hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((x.total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)x.total_frames);
     lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
         hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((pl->n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->n_live,
                            pl->d_row_off.p, d_vad, e->vp);
@@ -1723,23 +1679,23 @@ void stage_short_files(ctu_engine *e, const ctu_plan *pl, hipStream_t s, uint8_t
 
 // The list behaviour of the reference's majority filter (ctu_plan_set_vad_ring): every column but the energy (which does not
 // go through the ring, src/io/batch.cc:101-120) of row k := the vector of frame ring_src[k], or zeros
-void stage_ring_gather(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
+void stage_ring_gather(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, float *d_rows) {
     const ctu::Design &d = *e->design;
-    const size_t n = (size_t)pl->total_frames * d.D;
+    const size_t n = (size_t)x.total_frames * d.D;
     HIP_TRY(hipMemcpyAsync(pl->ring_tmp.p, d_rows, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(vad_ring_gather_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535u * 16)), dim3(256), 0, s, pl->ring_tmp.p, d_rows,
-                       pl->ring_src.p, (int64_t)pl->total_frames, d.D, d.o.fea_E ? (d.post_order > 0 ? d.D - 1 : d.e_slot) : -1);
+                       pl->ring_src.p, (int64_t)x.total_frames, d.D, d.o.fea_E ? (d.post_order > 0 ? d.D - 1 : d.e_slot) : -1);
     HIP_TRY(hipGetLastError());
 }
 
 // Speech output at 1024 .. 4096 points (ctu_engine_run_signal): a workgroup per frame
-void launch_bigsynth(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float inv_n) {
+void launch_bigsynth(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, float inv_n) {
     const ctu::Design &d = *e->design;
     const LdsFit fit = bigsynth_lds(d.wfft);
-    const int g = (int)std::min<int64_t>(pl->total_frames, (int64_t)e->n_cu * fit.per_cu);
+    const int g = (int)std::min<int64_t>(x.total_frames, (int64_t)e->n_cu * fit.per_cu);
     lift<4, 8, 16>(big_nit(e), [&](auto nit) {
         launch_lds(e, &bigsynth_kernel<decltype(nit)::value>, dim3(g), dim3(256), fit.bytes, s, pl->xri.p, synth_reads_pss(e) ? pl->pss.p : pl->pnr.p, pl->ybuf.p,
-                   (long long)pl->total_frames, d.wfft, d.window, inv_n, e->big_tw.p);
+                   (long long)x.total_frames, d.wfft, d.window, inv_n, e->big_tw.p);
     });
     HIP_TRY(hipGetLastError());
 }
@@ -2094,8 +2050,8 @@ int plan_layout(ctu_engine *e, ctu_plan *pl, const int64_t *utt_n, int32_t n_utt
     }
     h.uts[n_utt] = (int)tiles.size();
     pl->row_off[n_utt] = ro;
-    pl->total_frames = ro;
-    pl->n_tiles = (int)tiles.size();
+    pl->ext.total_frames = ro;
+    pl->ext.n_tiles = (int)tiles.size();
     h.tiles = std::move(tiles);
     h.chunks = std::move(chunks);
     return CTU_OK;
@@ -2126,17 +2082,17 @@ void plan_chains(const ctu_engine *e, ctu_plan *pl, PlanHost &h) {
         std::stable_sort(live.begin(), live.end(), [&](int a, int b) { return pl->frames[a] > pl->frames[b]; });
         // (bigfft_kernel walks a chain with a whole workgroup of 256 threads: eight of them fit a CU at once)
         const int slots = (e->big && e->path != BIG_WAVE1K) ? e->n_cu * 8 : max_wg * NWAVE;
-        const int C = std::max(1, std::min<int>((int)live.size(), slots));
-        const int G = (C + NWAVE - 1) / NWAVE;
-        wg_first.assign((size_t)G * NWAVE, -1);
+        const ChainDeal deal = chain_deal((int)live.size(), slots);  // (stream_plan.h: where chain c sits among the heads)
+        const int C = deal.C, G = deal.G;
+        wg_first.assign((size_t)deal.heads(), -1);
         std::vector<int> tail(C, -1);  // last tile of each chain so far
         std::priority_queue<std::pair<int64_t, int>, std::vector<std::pair<int64_t, int>>, std::greater<std::pair<int64_t, int>>> load;
-        // chain c lives in wave c / G of workgroup c % G: the chains of one workgroup are spread over the length ranks
+        // (the chains of one workgroup are spread over the length ranks)
         for (int c = 0; c < C; c++) load.push({0, c});
         for (int u : live) {
             const auto top = load.top();
             load.pop();
-            const int c = top.second, slot = (c % G) * NWAVE + c / G;
+            const int c = top.second, slot = deal.slot(c);
             for (int t = uts[u]; t + 1 < uts[u + 1]; t++) tiles[t].next = t + 1;
             tiles[uts[u + 1] - 1].next = -1;
             if (tail[c] < 0) wg_first[slot] = uts[u];
@@ -2144,13 +2100,13 @@ void plan_chains(const ctu_engine *e, ctu_plan *pl, PlanHost &h) {
             tail[c] = uts[u + 1] - 1;
             load.push({top.first + pl->frames[u], c});
         }
-        pl->grid = G;
+        pl->ext.grid = G;
     } else {
-        const int G = std::max(1, std::min(pl->n_tiles, max_wg));
+        const int G = std::max(1, std::min(pl->ext.n_tiles, max_wg));
         wg_first.assign(G, -1);
-        for (int t = 0; t < pl->n_tiles; t++) tiles[t].next = (t + G < pl->n_tiles) ? t + G : -1;
-        for (int g = 0; g < G && g < pl->n_tiles; g++) wg_first[g] = g;
-        pl->grid = G;
+        for (int t = 0; t < pl->ext.n_tiles; t++) tiles[t].next = (t + G < pl->ext.n_tiles) ? t + G : -1;
+        for (int g = 0; g < G && g < pl->ext.n_tiles; g++) wg_first[g] = g;
+        pl->ext.grid = G;
     }
 }
 
@@ -2158,7 +2114,7 @@ void plan_chains(const ctu_engine *e, ctu_plan *pl, PlanHost &h) {
 void plan_alloc(ctu_engine *e, ctu_plan *pl, const PlanHost &h) {
     const ctu::Design &d = *e->design;
     const int n_utt = pl->n_utt;
-    const int64_t ro = pl->total_frames;
+    const int64_t ro = pl->ext.total_frames;
     HIP_TRY(hipSetDevice(e->device));
     pl->tiles.upload(h.tiles);
     // the passes that run a workgroup per 64-frame chunk (TRAP, delta / stacking, CMS, CMVN); a plan over rows has the list in any case
@@ -2172,6 +2128,7 @@ void plan_alloc(ctu_engine *e, ctu_plan *pl, const PlanHost &h) {
     if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
     if (e->rows_in) return;  // what follows serves the front end and the stages that read its scratch
     pl->wg_first.upload(h.wg_first);
+    pl->ext.heads = pl->wg_first.p;
     if (per_utt) pl->d_sample_off.upload(std::vector<long long>(pl->sample_off.begin(), pl->sample_off.end()));
     if (e->do_vad || (e->ss && e->big && !e->ss_file)) pl->d_row_off.upload(pl->row_off);
     if (e->ss) {
@@ -2246,7 +2203,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
     std::unique_ptr<ctu_plan> pl(new ctu_plan);
     PlanHost h;
     if (const int rc = plan_layout(e, pl.get(), utt_nsamples, n_utt, h); rc != CTU_OK) return rc;
-    if (e->rows_in) pl->grid = std::max(1, std::min((pl->n_tiles + 3) / 4, e->n_cu * ROWS_WG_PER_CU));
+    if (e->rows_in) pl->ext.grid = std::max(1, std::min((pl->ext.n_tiles + 3) / 4, e->n_cu * ROWS_WG_PER_CU));
     else plan_chains(e, pl.get(), h);
     const int rc = guarded(e, [&]() -> int {
         plan_alloc(e, pl.get(), h);
@@ -2261,7 +2218,7 @@ void ctu_plan_destroy(ctu_plan *p) { delete p; }
 const int64_t *ctu_plan_sample_offsets(const ctu_plan *p) { return p->sample_off.data(); }
 const int64_t *ctu_plan_row_offsets(const ctu_plan *p) { return p->row_off.data(); }
 int64_t ctu_plan_total_samples(const ctu_plan *p) { return p->total_samples; }
-int64_t ctu_plan_total_frames(const ctu_plan *p) { return p->total_frames; }
+int64_t ctu_plan_total_frames(const ctu_plan *p) { return p->ext.total_frames; }
 
 void ctu_vad_ring_step(int32_t order, int64_t frames, int32_t *hidx, int32_t *hsize) {
     // medianFilter::push / flush_frame / cleanFilter as VAD::process_frame, BATCH::flush_vad and VAD::clean drive them over one file
@@ -2321,7 +2278,7 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
     const int rc = guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         pl->ring_hidx.assign(hidx, hidx + pl->n_utt);
-        std::vector<int> src((size_t)std::max<int64_t>(pl->total_frames, 1), -1);
+        std::vector<int> src((size_t)std::max<int64_t>(pl->ext.total_frames, 1), -1);
         std::vector<int32_t> rel;
         for (int i = 0; i < pl->n_utt; i++) {
             const int64_t T = pl->frames[i], r0 = pl->row_off[i];
@@ -2331,22 +2288,23 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
             for (int64_t k = 0; k < T; k++) src[(size_t)(r0 + k)] = rel[(size_t)k] < 0 ? -1 : (int)(r0 + rel[(size_t)k]);
         }
         pl->ring_src.upload(src);
-        pl->ring_tmp.reserve((size_t)std::max<int64_t>(pl->total_frames, 1) * d.D);
+        pl->ring_tmp.reserve((size_t)std::max<int64_t>(pl->ext.total_frames, 1) * d.D);
         return CTU_OK;
     });
     if (rc != CTU_OK) pl->ring_hidx.clear();  // a plan without its ring is in phase
     return rc;
 }
 
-// A run of a plan.  `row_stages` off stops ahead of stage_post and stage_cms with the base rows in the plan's scratch: a stream set with
-// row state runs its own forms of the two (stream_rows_kernels.h) over them and its history.
-static int run_chain(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages) {
+// A run of a plan over the extent `x`: the plan's own, or the front of it a push of a stream set covers.  `row_stages` off stops ahead of
+// stage_post and stage_cms with the base rows in the plan's scratch: a stream set with row state runs its own forms of the two
+// (stream_rows_kernels.h) over them and its history.
+static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
     if (e->rows_in) {
         set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows");
         return CTU_ERR_INPUT;
     }
-    if (pl->n_tiles == 0) return CTU_OK;
+    if (x.n_tiles == 0) return CTU_OK;
     const ctu::Design &d = *e->design;
     const bool signal = d.signal_out;
     if (signal && !e->in_signal_call) {
@@ -2360,9 +2318,9 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, fl
     hipStream_t s = (hipStream_t)stream;
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
-        KParams kp = run_kparams(e, pl, d_pcm, d_rows);
-        const BigParams bp = e->big ? run_bigparams(e, pl, kp) : BigParams{};
-        const int grid = pl->grid;
+        KParams kp = run_kparams(e, pl, x, d_pcm, d_rows);
+        const BigParams bp = e->big ? run_bigparams(e, pl, x, kp) : BigParams{};
+        const int grid = x.grid;
 #if CTU_STAMP
         e->stamps.reserve((size_t)grid * NWAVE * 16);
         HIP_TRY(hipMemsetAsync(e->stamps.p, 0, e->stamps.n * 8, s));
@@ -2371,18 +2329,18 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, fl
         if (d.o.remove_dc1) stage_dc1(e, pl, s, d_pcm);
         HIP_TRY(hipEventRecord(e->ev0, s));
         // the front end; with hwss / fwss / 2fwss `pass` is one pass of the seed iteration, which launches it
-        std::function<void()> pass = [&] { launch_frontend(e, dim3(grid), s, kp, pl->xstate != nullptr); };
+        std::function<void()> pass = [&] { launch_frontend(e, dim3(grid), s, kp, x.xstate != nullptr); };
         switch (e->path) {
             case BIG_NONE: if (!e->ss) pass(); break;
-            case BIG_WAVE1K: stage_wave1k(e, pl, s, bp); break;
-            case BIG_SS: pass = stage_bigss_front(e, pl, s, bp); break;
-            case BIG_FFT: launch_bigfft(e, pl, s, bp); break;
+            case BIG_WAVE1K: stage_wave1k(e, pl, x, s, bp); break;
+            case BIG_SS: pass = stage_bigss_front(e, pl, x, s, bp); break;
+            case BIG_FFT: launch_bigfft(e, x, s, bp); break;
         }
         if (e->ss) {
-            const int rc = run_ss_chain(e, pl, s, kp, pass);
+            const int rc = run_ss_chain(e, pl, x, s, kp, pass);
             if (rc != CTU_OK) return rc;
         }
-        if (e->dctw) stage_dctw(e, pl, s, kp);  // (inside the timed span: the tail finishes what the front end of a narrower chain does itself)
+        if (e->dctw) stage_dctw(e, pl, x, s, kp);  // (inside the timed span: the tail finishes what the front end of a narrower chain does itself)
         HIP_TRY(hipEventRecord(e->ev1, s));
         e->timed = true;
         e->host_timed = false;
@@ -2390,21 +2348,22 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, fl
 #if CTU_STAMP
         if (const char *sf = getenv("CTU_STAMP_FILE")) dump_stamps(e, grid, s, sf);
 #endif
-        if (lp_tail_runs(e)) stage_lp_tail(e, pl, s, kp);
-        if (e->do_vad) stage_burg_vad(e, pl, s);
+        if (lp_tail_runs(e)) stage_lp_tail(e, pl, x, s, kp);
+        if (e->do_vad) stage_burg_vad(e, pl, x, s);
         if (d.kind == ctu::FeaKind::TrapDct) stage_trap(e, pl, s, d_rows);
         if (d.post_order > 0 && row_stages) stage_post(e, pl, s, d_rows);
         if (d.cms && row_stages) stage_cms(e, pl, s, d_rows);
-        if (e->do_vad && e->vf && pl->n_live > 0) stage_fused_vad(e, pl, s, d_vad);
+        if (e->do_vad && e->vf && pl->n_live > 0) stage_fused_vad(e, pl, x, s, d_vad);
         if (e->do_vad && !e->vf) stage_vad_decide(e, pl, s, d_rows, d_vad);
         if (e->do_vad && d.o.vad_filter_order > 1) stage_short_files(e, pl, s, d_vad);
-        if (e->do_vad && !pl->ring_hidx.empty() && pl->total_frames > 0) stage_ring_gather(e, pl, s, d_rows);
+        if (e->do_vad && !pl->ring_hidx.empty() && x.total_frames > 0) stage_ring_gather(e, pl, x, s, d_rows);
         return CTU_OK;
     });
 }
 
 int ctu_engine_run(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream) {
-    return run_chain(e, pl, d_pcm, d_rows, d_vad, stream, true);
+    if (!pl) return CTU_ERR_INPUT;
+    return run_chain(e, pl, pl->ext, d_pcm, d_rows, d_vad, stream, true);
 }
 
 void *ctu_host_alloc(size_t bytes) {
@@ -2523,12 +2482,12 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
     RangeEvents events;
     auto download = [&](int k) {
         ctu_plan *sp = part(k);
-        if (sp->total_frames == 0) return;
+        if (sp->ext.total_frames == 0) return;
         float *dst = h_rows + pl->row_off[first(k)] * D;
-        if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->total_frames * D * 4, hipMemcpyDeviceToHost, st[k & 1]));
+        if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->ext.total_frames * D * 4, hipMemcpyDeviceToHost, st[k & 1]));
         else {
             HIP_TRY(hipStreamSynchronize(st[k & 1]));
-            HIP_TRY(hipMemcpy(dst, sp->h_rows.p, (size_t)sp->total_frames * D * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(dst, sp->h_rows.p, (size_t)sp->ext.total_frames * D * 4, hipMemcpyDeviceToHost));
         }
     };
     for (int k = 0; k < np; k++) {
@@ -2537,9 +2496,9 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
             const int rc = in.ring(sp, first(k));
             if (rc != CTU_OK) return rc;
         }
-        if (sp->total_frames) {
+        if (sp->ext.total_frames) {
             void *d_in = in.stage(sp);
-            sp->h_rows.reserve((size_t)sp->total_frames * D);
+            sp->h_rows.reserve((size_t)sp->ext.total_frames * D);
             // a part's arena is the slice of the caller's that starts `head` elements ahead of its first utterance (split_host_parts)
             const char *src = static_cast<const char *>(in.base) + (pl->sample_off[first(k)] - in.head) * (int64_t)in.elem;
             if (pin_in) HIP_TRY(hipMemcpyAsync(d_in, src, (size_t)sp->total_samples * in.elem, hipMemcpyHostToDevice, st[k & 1]));
@@ -2565,7 +2524,7 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
     }
     if (in.vad)
         for (int k = 0; k < np; k++)
-            if (part(k)->total_frames) in.vad(part(k), pl->row_off[first(k)]);
+            if (part(k)->ext.total_frames) in.vad(part(k), pl->row_off[first(k)]);
     return CTU_OK;
 }
 }  // namespace
@@ -2581,23 +2540,23 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
     const ctu::Design &d = *e->design;
     if (rows_per_utt)
         for (int i = 0; i < pl->n_utt; i++) rows_per_utt[i] = pl->frames[i];
-    if (pl->total_frames == 0) return CTU_OK;
+    if (pl->ext.total_frames == 0) return CTU_OK;
     if (!h_pcm || !h_rows) {
         set_error(e, "ENGINE: null host buffer");
         return CTU_ERR_INPUT;
     }
     return guarded(e, [&]() -> int {
-        std::vector<uint8_t> v(e->do_vad ? (size_t)pl->total_frames : 0);
+        std::vector<uint8_t> v(e->do_vad ? (size_t)pl->ext.total_frames : 0);
         HostInput in{h_pcm, sizeof(int16_t), PCM_HEAD};
         in.stage = [&](ctu_plan *p) {
             p->h_pcm.reserve((size_t)p->total_samples);
-            if (e->do_vad) p->h_vad.reserve((size_t)p->total_frames);
+            if (e->do_vad) p->h_vad.reserve((size_t)p->ext.total_frames);
             return p->h_pcm.p;
         };
         in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run(e, p, p->h_pcm.p, p->h_rows.p, p->h_vad.p, s); };
         if (e->do_vad) {
             in.ring = [&](ctu_plan *sub, int first) { return ctu_plan_set_vad_ring(sub, pl->ring_hidx.empty() ? nullptr : pl->ring_hidx.data() + first); };
-            in.vad = [&](const ctu_plan *p, int64_t row0) { HIP_TRY(hipMemcpy(v.data() + row0, p->h_vad.p, (size_t)p->total_frames, hipMemcpyDeviceToHost)); };
+            in.vad = [&](const ctu_plan *p, int64_t row0) { HIP_TRY(hipMemcpy(v.data() + row0, p->h_vad.p, (size_t)p->ext.total_frames, hipMemcpyDeviceToHost)); };
         }
         if (const int rc = run_host_ranges(e, pl, in, h_rows); rc != CTU_OK) return rc;
         if (e->do_vad) {
@@ -2633,7 +2592,7 @@ int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in
         set_error(e, "ENGINE: this configuration starts from samples: use ctu_engine_run (ctu_engine_run_rows needs -format_in htk)");
         return CTU_ERR_INPUT;
     }
-    if (pl->n_tiles == 0) return CTU_OK;
+    if (pl->ext.n_tiles == 0) return CTU_OK;
     if (!d_rows_in || !d_rows) {
         set_error(e, "ENGINE: null device buffer");
         return CTU_ERR_INPUT;
@@ -2647,8 +2606,8 @@ int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in
         HIP_TRY(hipEventRecord(e->ev0, s));
         lift<0, 1>(d.o.swap_in, [&](auto sw) {
             lift<0, 1>(d.post_stack, [&](auto rot) {
-                hipLaunchKernelGGL((rows_ingest_kernel<decltype(sw)::value != 0, decltype(rot)::value != 0>), dim3(pl->grid), dim3(256), 0, s,
-                                   static_cast<const uint32_t *>(d_rows_in), dst, pl->tiles.p, pl->n_tiles, d.Dbase);
+                hipLaunchKernelGGL((rows_ingest_kernel<decltype(sw)::value != 0, decltype(rot)::value != 0>), dim3(pl->ext.grid), dim3(256), 0, s,
+                                   static_cast<const uint32_t *>(d_rows_in), dst, pl->tiles.p, pl->ext.n_tiles, d.Dbase);
             });
         });
         HIP_TRY(hipEventRecord(e->ev1, s));
@@ -2668,7 +2627,7 @@ int ctu_engine_run_rows_host(ctu_engine *e, const ctu_plan *pl_, const void *h_r
         return CTU_ERR_INPUT;
     }
     ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
-    if (pl->total_frames == 0) return CTU_OK;
+    if (pl->ext.total_frames == 0) return CTU_OK;
     if (!h_rows_in || !h_rows) {
         set_error(e, "ENGINE: null host buffer");
         return CTU_ERR_INPUT;
@@ -2735,8 +2694,8 @@ int ctu_cmvn_accumulate(ctu_engine *e, const ctu_plan *pl, const float *d_rows, 
                         const double *mean, double *acc, void *stream) {
     int rc = cmvn_check(e, pl, spk_of_utt, n_spk);
     if (rc != CTU_OK) return rc;
-    if (!acc || (pl->total_frames && !d_rows)) return CTU_ERR_INPUT;
-    if (pl->total_frames == 0) return CTU_OK;
+    if (!acc || (pl->ext.total_frames && !d_rows)) return CTU_ERR_INPUT;
+    if (pl->ext.total_frames == 0) return CTU_OK;
     hipStream_t s = (hipStream_t)stream;
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
@@ -2762,8 +2721,8 @@ int ctu_cmvn_apply(ctu_engine *e, const ctu_plan *pl, float *d_rows, const int32
                    const double *mean, const double *var, void *stream) {
     int rc = cmvn_check(e, pl, spk_of_utt, n_spk);
     if (rc != CTU_OK) return rc;
-    if (!mean || !var || (pl->total_frames && !d_rows)) return CTU_ERR_INPUT;
-    if (pl->total_frames == 0) return CTU_OK;
+    if (!mean || !var || (pl->ext.total_frames && !d_rows)) return CTU_ERR_INPUT;
+    if (pl->ext.total_frames == 0) return CTU_OK;
     hipStream_t s = (hipStream_t)stream;
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
@@ -2805,10 +2764,10 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
         sp.K = d.K; sp.wfft = d.wfft; sp.window = d.window; sp.wshift = d.wshift;
         sp.inv_n = 1.0f / (float)d.wfft;
         sp.corr = d.ola_corr;
-        if (pl->total_frames > 0 && e->big) launch_bigsynth(e, pl, s, sp.inv_n);
-        else if (pl->total_frames > 0 && !e->sy) {
-            const int g = (int)std::min<int64_t>((pl->total_frames + 7) / 8, (int64_t)e->n_cu * 8);
-            hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)pl->total_frames, sp);
+        if (pl->ext.total_frames > 0 && e->big) launch_bigsynth(e, pl, pl->ext, s, sp.inv_n);
+        else if (pl->ext.total_frames > 0 && !e->sy) {
+            const int g = (int)std::min<int64_t>((pl->ext.total_frames + 7) / 8, (int64_t)e->n_cu * 8);
+            hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)pl->ext.total_frames, sp);
             HIP_TRY(hipGetLastError());
         }
         int64_t longest = 0;
@@ -2841,11 +2800,11 @@ int ctu_engine_run_signal_host(ctu_engine *e, const ctu_plan *pl, const int16_t 
 int ctu_cmvn_accumulate_host(ctu_engine *e, const ctu_plan *pl, const float *h_rows, const int32_t *spk_of_utt, int32_t n_spk,
                              const double *mean, double *acc) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
-    if (pl->total_frames == 0) return CTU_OK;
+    if (pl->ext.total_frames == 0) return CTU_OK;
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         DevBuf<float> rows;
-        rows.alloc((size_t)pl->total_frames * e->design->D);
+        rows.alloc((size_t)pl->ext.total_frames * e->design->D);
         HIP_TRY(hipMemcpy(rows.p, h_rows, rows.n * sizeof(float), hipMemcpyHostToDevice));
         return ctu_cmvn_accumulate(e, pl, rows.p, spk_of_utt, n_spk, mean, acc, nullptr);
     });
@@ -2854,11 +2813,11 @@ int ctu_cmvn_accumulate_host(ctu_engine *e, const ctu_plan *pl, const float *h_r
 int ctu_cmvn_apply_host(ctu_engine *e, const ctu_plan *pl, float *h_rows, const int32_t *spk_of_utt, int32_t n_spk,
                         const double *mean, const double *var) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
-    if (pl->total_frames == 0) return CTU_OK;
+    if (pl->ext.total_frames == 0) return CTU_OK;
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         DevBuf<float> rows;
-        rows.alloc((size_t)pl->total_frames * e->design->D);
+        rows.alloc((size_t)pl->ext.total_frames * e->design->D);
         HIP_TRY(hipMemcpy(rows.p, h_rows, rows.n * sizeof(float), hipMemcpyHostToDevice));
         const int rc = ctu_cmvn_apply(e, pl, rows.p, spk_of_utt, n_spk, mean, var, nullptr);
         if (rc != CTU_OK) return rc;
@@ -2926,468 +2885,7 @@ float ctu_engine_last_kernel_ms(ctu_engine *e) {
 }
 
 
-// ---- streaming input ---------------------------------------------------------------------------------------------------------
-namespace {
-// The halo H and the largest window of a configuration's delta chain or stacking (0, 0 without either)
-void stream_halo(const ctu::Design &d, int *H, int *wmax) {
-    *H = *wmax = 0;
-    for (int j = 0; j < d.post_order; j++) {
-        if (!d.post_stack || j == 0) *H += d.post_w[j];
-        *wmax = std::max(*wmax, d.post_w[j]);
-    }
-}
-// Rows of a file that have gone out after F frames: all without a chain, else F - H once frame wmax + 2 exists
-int64_t stream_rows_out(int H, int wmax, int64_t F) { return H == 0 ? F : (F >= wmax + 2 ? std::max<int64_t>(F - H, 0) : 0); }
-int64_t stream_rows_of(const ctu_streams *st, int64_t F) { return stream_rows_out(st->H, st->wmax, F); }
-}  // namespace
-
-int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
-    return ctu_streams_config_check_ex(argc, argv, 0, reason, cap, nullptr);
-}
-
-int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flags, char *reason, int64_t cap, int32_t *halo) {
-    if (halo) *halo = 0;
-    auto say = [&](const std::string &m) {
-        g_create_error = m;
-        if (reason && cap > 0) {
-            std::strncpy(reason, m.c_str(), (size_t)cap - 1);
-            reason[cap - 1] = 0;
-        }
-    };
-    say("");
-    try {
-        ctu::Opts o = ctu::Opts::from_args(to_args(argc, argv));
-        ctu::Design d(o);
-        spread_small_fft(d);
-        if (const std::string why = unsupported_reason(d); !why.empty()) {
-            say("ENGINE: configuration not on the accelerated path: " + why);
-            return CTU_ERR_UNSUPPORTED;
-        }
-        if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
-            say("ENGINE: unknown stream set flags");
-            return CTU_ERR_INPUT;
-        }
-        if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
-            say("ENGINE: configuration cannot be streamed: " + why);
-            return CTU_ERR_UNSUPPORTED;
-        }
-        int H = 0, wmax = 0;
-        stream_halo(d, &H, &wmax);
-        if (halo) *halo = H;
-        return CTU_OK;
-    } catch (const std::exception &ex) {
-        say(ex.what());
-        return CTU_ERR_OPTS;
-    }
-}
-
-int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry) {
-    if (window < 1 || wshift < 1 || wshift > window || total < 0) return CTU_ERR_INPUT;
-    const int64_t F = stream_frames(total, window, wshift);
-    if (carry) *carry = total - F * wshift;
-    return F;
-}
-
-int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending) {
-    if (window < 1 || wshift < 1 || wshift > window || total < 0 || halo < 0 || wmax < 0 || wmax > halo || (halo > 0 && wmax < 1)) return CTU_ERR_INPUT;
-    const int64_t F = stream_frames(total, window, wshift), R = stream_rows_out(halo, wmax, F);
-    if (pending) *pending = F - R;
-    return R;
-}
-
-int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, ctu_streams **out) {
-    return ctu_streams_create_ex(e, n_streams, max_push_samples, 0, out);
-}
-
-int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out) {
-    if (!e || !out) return CTU_ERR_INPUT;
-    *out = nullptr;
-    if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
-        set_error(e, "ENGINE: unknown stream set flags");
-        return CTU_ERR_INPUT;
-    }
-    if (n_streams < 1 || max_push_samples < 1 || max_push_samples > (1 << 26)) {
-        set_error(e, "ENGINE: a stream set needs at least one stream and pushes of 1 .. 2^26 samples");
-        return CTU_ERR_INPUT;
-    }
-    const ctu::Design &d = *e->design;
-    if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
-        set_error(e, "ENGINE: configuration cannot be streamed: " + why);
-        return CTU_ERR_UNSUPPORTED;
-    }
-    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || e->do_vad || e->ss || (e->per_wave && e->big)) {
-        set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
-        return CTU_ERR_UNSUPPORTED;
-    }
-    std::unique_ptr<ctu_streams> st(new ctu_streams);
-    st->eng = e;
-    st->n_streams = n_streams;
-    st->max_push = max_push_samples;
-    st->cstride = (d.window + 7) / 8 * 8;
-    st->max_wg = fe_max_wg(e);
-    st->consumed.assign((size_t)n_streams, 0);
-    st->seen.assign((size_t)n_streams, 0);
-    st->held = d.post_order > 0 || d.cms;  // (only with CTU_STREAMS_ROW_STATE: refused above without)
-    stream_halo(d, &st->H, &st->wmax);
-    st->C = st->held ? std::max(2 * st->H, st->H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;
-    st->hsel.assign((size_t)n_streams, 0);
-    st->chained = e->per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
-    st->max_chains = st->max_wg * NWAVE;
-    // the longest slot: the lead, a full carry, a full push (and no shorter than the shortest file a delta chain is defined on: the plan
-    // of a set whose pushes are shorter than that is still a plan of files that could be)
-    const std::vector<int64_t> longest((size_t)n_streams, std::max((int64_t)STREAM_LEAD + d.window - 1 + max_push_samples,
-                                                                   (int64_t)d.window + (int64_t)(st->wmax + 1) * d.wshift));
-    ctu_plan *pl = nullptr;
-    if (const int rc = ctu_plan_create(e, longest.data(), n_streams, &pl); rc != CTU_OK) return rc;
-    st->plan.reset(pl);
-    const int rc = guarded(e, [&]() -> int {
-        HIP_TRY(hipSetDevice(e->device));
-        st->arena.alloc((size_t)pl->total_samples);
-        st->carry.alloc((size_t)n_streams * st->cstride);
-        st->state.alloc((size_t)n_streams);
-        HIP_TRY(hipMemset(st->arena.p, 0, st->arena.n * sizeof(int16_t)));
-        HIP_TRY(hipMemset(st->carry.p, 0, st->carry.n * sizeof(int16_t)));
-        HIP_TRY(hipMemset(st->state.p, 0, st->state.n * sizeof(StreamState)));
-        for (int k = 0; k < 2; k++) {
-            st->h_desc[k] = static_cast<StreamPush *>(ctu_host_alloc((size_t)n_streams * sizeof(StreamPush)));
-            if (!st->h_desc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
-            st->d_desc[k].alloc((size_t)n_streams);
-            HIP_TRY(hipEventCreateWithFlags(&st->desc_free[k], hipEventDisableTiming));
-            if (st->held) {
-                st->h_rdesc[k] = static_cast<RowPush *>(ctu_host_alloc((size_t)n_streams * sizeof(RowPush)));
-                if (!st->h_rdesc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
-                st->d_rdesc[k].alloc((size_t)n_streams);
-            }
-        }
-        if (st->chained) {
-            const size_t per_stream = (size_t)2 * 64 * (e->sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1);  // [2][64 NJ] of xstate_t (frontend_kernel.h)
-            st->xstate.alloc((size_t)n_streams * per_stream);
-            HIP_TRY(hipMemset(st->xstate.p, 0, st->xstate.n * sizeof(float)));  // (never read ahead of a store: a file's first tile resets)
-            pl->tile_utt.alloc(pl->tiles.n);
-            HIP_TRY(hipMemset(pl->tile_utt.p, 0, pl->tile_utt.n * sizeof(int)));
-            pl->xstate = st->xstate.p;
-            for (int k = 0; k < 2; k++) {
-                st->h_heads[k] = static_cast<int *>(ctu_host_alloc((size_t)st->max_chains * sizeof(int)));
-                if (!st->h_heads[k]) throw std::runtime_error("page-locked descriptors of a stream set");
-                st->d_heads[k].alloc((size_t)st->max_chains);
-            }
-        }
-        if (st->held) {
-            st->hist.alloc(std::max<size_t>((size_t)2 * n_streams * st->C * d.Dbase, 1));
-            st->means.alloc((size_t)n_streams * STREAM_MEANS);
-            HIP_TRY(hipMemset(st->hist.p, 0, st->hist.n * sizeof(float)));
-            HIP_TRY(hipMemset(st->means.p, 0, st->means.n * sizeof(float)));
-        }
-        for (hipEvent_t &v : st->ev) HIP_TRY(hipEventCreate(&v));
-        return CTU_OK;
-    });
-    if (rc != CTU_OK) return rc;
-    *out = st.release();
-    return CTU_OK;
-}
-
-void ctu_streams_destroy(ctu_streams *st) {
-    if (!st) return;
-    (void)hipSetDevice(st->eng->device);
-    (void)hipDeviceSynchronize();  // pushes may still be in flight on the caller's streams
-    delete st;
-}
-
-int64_t ctu_streams_frames(const ctu_streams *st, int32_t id) {
-    if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
-    const ctu::Design &d = *st->eng->design;
-    return stream_rows_of(st, stream_frames(st->consumed[(size_t)id], d.window, d.wshift));
-}
-
-int64_t ctu_streams_pending(const ctu_streams *st, int32_t id) {
-    if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
-    const ctu::Design &d = *st->eng->design;
-    const int64_t F = stream_frames(st->consumed[(size_t)id], d.window, d.wshift);
-    return F - stream_rows_of(st, F);
-}
-
-namespace {
-// The row kernels of a push, or of a finish, over the n streams h_rdesc[k] describes (uploaded here); `most` is the largest row count among them
-void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finishing, float *d_rows, hipStream_t s) {
-    const ctu::Design &d = *st->eng->design;
-    HIP_TRY(hipMemcpyAsync(st->d_rdesc[k].p, st->h_rdesc[k], (size_t)n * sizeof(RowPush), hipMemcpyHostToDevice, s));
-    if (most == 0) return;
-    RowParams rp;
-    rp.push = st->d_rdesc[k].p; rp.fresh = st->plan->base_rows.p; rp.hist = st->hist.p; rp.means = st->means.p; rp.rows = d_rows;
-    rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase; rp.finishing = finishing ? 1 : 0;
-    const unsigned chunks = (unsigned)((most + 63) / 64);
-    if (d.post_order > 0) {
-        size_t shm = 0;
-        const PostParams pp = post_params(d, &shm);
-        if (d.post_stack) hipLaunchKernelGGL(stream_post_kernel<true>, dim3(chunks, (unsigned)n), dim3(256), shm, s, rp, pp);
-        else hipLaunchKernelGGL(stream_post_kernel<false>, dim3(chunks, (unsigned)n), dim3(256), shm, s, rp, pp);
-    }
-    if (d.cms) {
-        const CmsParams cp = cms_params(d);
-        if (d.cms == 1) hipLaunchKernelGGL(stream_cms_exp_kernel, dim3((unsigned)n), dim3(64), 0, s, rp, cp);
-        else hipLaunchKernelGGL(stream_cms_block_kernel, dim3(chunks, (unsigned)n), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, rp, cp);
-    }
-    HIP_TRY(hipGetLastError());
-}
-}  // namespace
-
-int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
-                     float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream) {
-    if (!st) return CTU_ERR_INPUT;
-    ctu_engine *e = st->eng;
-    const ctu::Design &d = *e->design;
-    ctu_plan *pl = st->plan.get();
-    auto refuse = [&](const char *m) {
-        set_error(e, std::string("ENGINE: ") + m);
-        return CTU_ERR_INPUT;
-    };
-    // ---- everything that can be refused is refused here, ahead of the first launch and of any change to the set
-    if (n < 0 || n > st->n_streams || (n && (!ids || !n_samples))) return refuse("push: bad stream count or null argument");
-    if (n == 0) return CTU_OK;
-    if (++st->push_no == 0) {  // (the counter wrapped: forget the marks)
-        std::fill(st->seen.begin(), st->seen.end(), 0u);
-        st->push_no = 1;
-    }
-    int64_t rows = 0, fresh = 0;
-    for (int i = 0; i < n; i++) {
-        if (ids[i] < 0 || ids[i] >= st->n_streams) return refuse("push: stream id out of range");
-        if (st->seen[(size_t)ids[i]] == st->push_no) return refuse("push: a stream id appears twice");
-        st->seen[(size_t)ids[i]] = st->push_no;
-        if (n_samples[i] < 0 || n_samples[i] > st->max_push) return refuse("push: more samples than the set's max_push_samples (or fewer than none)");
-        if (n_samples[i] && (!sample_off || sample_off[i] < 0)) return refuse("push: null or negative sample offsets");
-        const int64_t c = st->consumed[(size_t)ids[i]];
-        rows += stream_rows_of(st, stream_frames(c + n_samples[i], d.window, d.wshift)) - stream_rows_of(st, stream_frames(c, d.window, d.wshift));
-        fresh += n_samples[i];
-    }
-    if (fresh && !d_pcm) return refuse("push: null sample buffer");
-    if (rows > rows_capacity || (rows && !d_rows)) return refuse("push: the rows of this push do not fit rows_capacity");
-    hipStream_t s = (hipStream_t)stream;
-    return guarded(e, [&]() -> int {
-        HIP_TRY(hipSetDevice(e->device));
-        const int k = st->turn;
-        st->turn ^= 1;
-        HIP_TRY(hipEventSynchronize(st->desc_free[k]));  // (the push before last has read them; immediate before the first record)
-        StreamPush *h = st->h_desc[k];
-        int64_t so = PCM_HEAD, ro = 0, oo = 0, most = 0;  // ro: base rows of the push, oo: rows that go out (the same without row state)
-        int tiles = 0, slices = 1, live = 0;
-        if (st->chained)  // the streams that complete a frame, dealt in turn onto at most max_chains chains, a wave each
-            for (int i = 0; i < n; i++) {
-                const int64_t c = st->consumed[(size_t)ids[i]];
-                live += stream_frames(c + n_samples[i], d.window, d.wshift) > stream_frames(c, d.window, d.wshift);
-            }
-        // chain c lives in wave c / G of workgroup c % G (as plan_chains deals them)
-        const int C = std::max(1, std::min(live, st->max_chains)), G = (C + NWAVE - 1) / NWAVE;
-        int *heads = st->chained ? st->h_heads[k] : nullptr;
-        if (heads) {
-            std::fill(heads, heads + (size_t)G * NWAVE, -1);
-            st->chain_tail.assign((size_t)C, -1);
-        }
-        live = 0;
-        for (int i = 0; i < n; i++) {
-            const int64_t c = st->consumed[(size_t)ids[i]];
-            const int64_t F = stream_frames(c, d.window, d.wshift), T = stream_frames(c + n_samples[i], d.window, d.wshift) - F;
-            const int64_t len = STREAM_LEAD + (c - F * d.wshift) + n_samples[i];  // the stitched utterance, laid out by ctu_arena_layout's rule
-            h[i].src = n_samples[i] ? sample_off[i] : 0;
-            h[i].slot = so;
-            h[i].row0 = ro;
-            h[i].id = ids[i];
-            h[i].n = (int)n_samples[i];
-            h[i].tile0 = tiles;
-            h[i].pad = -1;
-            if (heads && T > 0) {
-                const int ch = live++ % C;
-                int &tail = st->chain_tail[(size_t)ch];
-                if (tail < 0) heads[(ch % G) * NWAVE + ch / G] = tiles;
-                else h[tail].pad = tiles;
-                tail = i;
-            }
-            so += (len + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN;
-            ro += T;
-            tiles += (int)((T + TILE - 1) / TILE);
-            slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
-            const int64_t r0 = stream_rows_of(st, F), nr = stream_rows_of(st, F + T) - r0;
-            if (st->held) {
-                RowPush &r = st->h_rdesc[k][i];
-                r.F0 = F; r.r0 = r0; r.out0 = oo; r.row0 = h[i].row0;
-                r.id = ids[i]; r.Tn = (int)T; r.nr = (int)nr;
-                r.hsel = st->hsel[(size_t)ids[i]];
-                if (T > 0) st->hsel[(size_t)ids[i]] ^= 1;  // stream_rows_carry_kernel writes the other history
-            }
-            oo += nr;
-            most = std::max(most, nr);
-            if (row_counts) row_counts[i] = nr;
-            st->consumed[(size_t)ids[i]] = c + n_samples[i];
-        }
-        if (so + PCM_TAIL > pl->total_samples || tiles > (int)pl->tiles.n) throw std::runtime_error("internal: a push beyond the set's arena");
-        HIP_TRY(hipMemcpyAsync(st->d_desc[k].p, h, (size_t)n * sizeof(StreamPush), hipMemcpyHostToDevice, s));
-        StreamParams sp;
-        sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
-        sp.cstride = st->cstride; sp.window = d.window; sp.wshift = d.wshift;
-        sp.n_tiles = tiles; sp.grid = heads ? G : std::max(1, std::min(tiles, st->max_wg));
-        sp.tile_stream = heads ? pl->tile_utt.p : nullptr;
-        if (heads) {
-            HIP_TRY(hipMemcpyAsync(st->d_heads[k].p, heads, (size_t)G * NWAVE * sizeof(int), hipMemcpyHostToDevice, s));
-            pl->push_heads = st->d_heads[k].p;
-        }
-        HIP_TRY(hipEventRecord(st->ev[0], s));
-        hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)slices), dim3(256), 0, s, sp);
-        HIP_TRY(hipEventRecord(st->ev[1], s));
-        HIP_TRY(hipGetLastError());
-        // the front end and its tails, as a run of the set's plan cut down to this push
-        pl->n_tiles = tiles;
-        pl->grid = sp.grid;
-        pl->total_frames = ro;
-        int rc = CTU_OK;
-        if (tiles) rc = run_chain(e, pl, st->arena.p, st->held ? pl->base_rows.p : d_rows, nullptr, s, !st->held);
-        if (st->held && tiles && rc == CTU_OK) launch_stream_rows(st, k, n, most, false, d_rows, s);
-        HIP_TRY(hipEventRecord(st->ev[2], s));
-        hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
-        if (st->held && st->C > 0 && tiles && rc == CTU_OK) {
-            RowParams rp;
-            std::memset(&rp, 0, sizeof rp);
-            rp.push = st->d_rdesc[k].p; rp.fresh = pl->base_rows.p; rp.hist = st->hist.p;
-            rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase;
-            hipLaunchKernelGGL(stream_rows_carry_kernel, dim3((unsigned)n, (unsigned)((st->C * d.Dbase + 255) / 256)), dim3(256), 0, s, rp);
-        }
-        HIP_TRY(hipEventRecord(st->ev[3], s));
-        HIP_TRY(hipEventRecord(st->desc_free[k], s));
-        HIP_TRY(hipGetLastError());
-        st->timed = true;
-        return rc;
-    });
-}
-
-int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples, float *h_rows,
-                          int64_t rows_capacity, int64_t *row_counts) {
-    if (!st) return CTU_ERR_INPUT;
-    ctu_engine *e = st->eng;
-    const int D = e->design->D;
-    if (n < 0 || n > st->n_streams || (n && (!ids || !n_samples || !h_pcm))) {
-        set_error(e, "ENGINE: push: bad stream count or null argument");
-        return CTU_ERR_INPUT;
-    }
-    int64_t fresh = 0;
-    for (int i = 0; i < n; i++) {
-        if (n_samples[i] < 0 || n_samples[i] > st->max_push || (n_samples[i] && !h_pcm[i])) {
-            set_error(e, "ENGINE: push: more samples than the set's max_push_samples (or fewer than none), or a null sample buffer");
-            return CTU_ERR_INPUT;
-        }
-        fresh += n_samples[i];
-    }
-    return guarded(e, [&]() -> int {
-        HIP_TRY(hipSetDevice(e->device));
-        const size_t cap = (size_t)st->n_streams * (size_t)st->max_push;
-        if (!st->h_stage) {
-            st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
-            if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
-            st->d_stage.alloc(cap);
-            // (a push that brings a stream's frame wmax + 2 also delivers the rows of the wmax + 1 frames before it)
-            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->row_off[st->plan->n_utt] + (int64_t)st->n_streams * (st->wmax + 1), 1) * D);
-        }
-        st->offs.resize((size_t)n);
-        int64_t at = 0;
-        for (int i = 0; i < n; i++) {
-            st->offs[(size_t)i] = at;
-            if (n_samples[i]) std::memcpy(st->h_stage + at, h_pcm[i], (size_t)n_samples[i] * sizeof(int16_t));
-            at += n_samples[i];
-        }
-        if (fresh) HIP_TRY(hipMemcpyAsync(st->d_stage.p, st->h_stage, (size_t)fresh * sizeof(int16_t), hipMemcpyHostToDevice, nullptr));
-        std::vector<int64_t> counts((size_t)std::max(n, 1));
-        // the device rows hold any push of the set; what the caller's buffer holds is the device form's check
-        const int rc = ctu_streams_push(st, n, ids, st->d_stage.p, st->offs.data(), n_samples, h_rows ? st->d_rows.p : nullptr, h_rows ? rows_capacity : 0,
-                                        counts.data(), nullptr);
-        if (rc != CTU_OK) return rc;
-        int64_t rows = 0;
-        for (int i = 0; i < n; i++) {
-            rows += counts[(size_t)i];
-            if (row_counts) row_counts[i] = counts[(size_t)i];
-        }
-        if (rows) {  // page-locked rows at the link rate, pageable ones through the runtime's staging (as run_host_ranges downloads)
-            if (is_pinned(h_rows)) HIP_TRY(hipMemcpyAsync(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost, nullptr));
-            else HIP_TRY(hipMemcpy(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost));
-        }
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return CTU_OK;
-    });
-}
-
-int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream) {
-    if (!st) return CTU_ERR_INPUT;
-    ctu_engine *e = st->eng;
-    const ctu::Design &d = *e->design;
-    if (id < 0 || id >= st->n_streams) {
-        set_error(e, "ENGINE: finish: stream id out of range");
-        return CTU_ERR_INPUT;
-    }
-    if (row_count) *row_count = 0;  // fread() comes up short on a trailing partial window and the file ends there (src/io/in.cc:314,438)
-    const int64_t total = st->consumed[(size_t)id];
-    const int64_t F = stream_frames(total, d.window, d.wshift), r0 = stream_rows_of(st, F);
-    const bool too_short = st->H > 0 && F > 0 && F < st->wmax + 2;  // the plan's refusal: such a file has no defined rows, none go out
-    const int64_t pending = too_short ? 0 : F - r0;
-    if (pending > rows_capacity || (pending && !d_rows)) {  // ahead of any launch or change: the stream stays as it was
-        set_error(e, "ENGINE: finish: the rows held back for this stream do not fit rows_capacity");
-        return CTU_ERR_INPUT;
-    }
-    st->consumed[(size_t)id] = 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = guarded(e, [&]() -> int {
-        HIP_TRY(hipSetDevice(e->device));
-        if (pending) {  // rows r0 .. F - 1 with the file's length known: every base row they read is in the history
-            const int k = st->turn;
-            st->turn ^= 1;
-            HIP_TRY(hipEventSynchronize(st->desc_free[k]));
-            RowPush &r = st->h_rdesc[k][0];
-            r.F0 = F; r.r0 = r0; r.out0 = 0; r.row0 = 0;
-            r.id = id; r.Tn = 0; r.nr = (int)pending;
-            r.hsel = st->hsel[(size_t)id];
-            launch_stream_rows(st, k, 1, pending, true, d_rows, s);
-            HIP_TRY(hipEventRecord(st->desc_free[k], s));
-        }
-        HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
-        if (st->held) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
-        return CTU_OK;
-    });
-    if (rc != CTU_OK) return rc;
-    if (total > 0 && total < d.window - d.wshift) {
-        set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
-        return CTU_ERR_INPUT;
-    }
-    if (too_short) {  // plan_layout's words; the stream is reset all the same
-        set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
-        return CTU_ERR_INPUT;
-    }
-    if (row_count) *row_count = pending;
-    return CTU_OK;
-}
-
-int ctu_streams_finish_host(ctu_streams *st, int32_t id, float *h_rows, int64_t rows_capacity, int64_t *row_count) {
-    if (!st) return CTU_ERR_INPUT;
-    ctu_engine *e = st->eng;
-    const int D = e->design->D;
-    if (row_count) *row_count = 0;
-    const int64_t pending = ctu_streams_pending(st, id);  // (at most max(H, wmax + 1) rows; an id outside the set is ctu_streams_finish's to refuse)
-    DevBuf<float> rows;
-    int64_t cnt = 0;
-    const int rc = guarded(e, [&]() -> int {
-        HIP_TRY(hipSetDevice(e->device));
-        if (pending > 0) rows.alloc((size_t)pending * D);
-        const int rc = ctu_streams_finish(st, id, h_rows ? rows.p : nullptr, h_rows ? rows_capacity : 0, &cnt, nullptr);
-        if (rc != CTU_OK) return rc;
-        if (cnt) HIP_TRY(hipMemcpy(h_rows, rows.p, (size_t)cnt * D * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return CTU_OK;
-    });
-    if (rc == CTU_OK && row_count) *row_count = cnt;
-    return rc;
-}
-
-int ctu_streams_last_push_ms(ctu_streams *st, float *ms3) {
-    if (!st || !ms3 || !st->timed) return CTU_ERR_INPUT;
-    if (hipEventSynchronize(st->ev[3]) != hipSuccess) return CTU_ERR_DEVICE;
-    if (hipEventElapsedTime(&ms3[0], st->ev[0], st->ev[1]) != hipSuccess) return CTU_ERR_DEVICE;
-    if (hipEventElapsedTime(&ms3[1], st->ev[1], st->ev[2]) != hipSuccess) return CTU_ERR_DEVICE;
-    if (hipEventElapsedTime(&ms3[2], st->ev[2], st->ev[3]) != hipSuccess) return CTU_ERR_DEVICE;
-    return CTU_OK;
-}
+// ---- streaming input: stream sets, pushes (planned by stream_plan.h), finishes
+#include "streams_host.h"
 
 }  // extern "C"

@@ -2,20 +2,16 @@
 // Included by engine.hip (one translation unit: the kernels and their host launchers share types).
 #pragma once
 
+#include "layout_constants.h"  // TILE, WG, NWAVE, PCM_ALIGN, PCM_HEAD, PCM_TAIL: what host-only code shares with the kernels
+
 namespace {
 
-constexpr int TILE = 64;       // frames per tile (= lanes of the per-frame phase)
-constexpr int WG = 512;        // threads per workgroup (8 waves)
-constexpr int NWAVE = WG / 64;
 constexpr int PSTRIDE = 260;   // floats per P-tile row: 257 bins padded so rows stay 16-byte aligned (b128 reads in phase 2)
 constexpr int LDS_2WG = 80 * 1024;  // two workgroups per CU fit when a workgroup's LDS stays at or under this
 constexpr int MAX_LP = 23;     // LP order / cepstral order limit: the front end accumulates MAXC = 24 lags (R[0..23]) per frame, lp_tail_kernel keeps one frame's recursion in a lane's registers
 constexpr int GEN_PLAIN = 0, GEN_INLD = 1, GEN_EXTEN = 2, GEN_FULL = 3, GEN_DC1 = 4;  // front-end option specialisations (frontend_kernel.h)
 constexpr int MAXC = 24;       // most coefficients accumulated per frame in phase 2 (cepstra incl. c0, or LP lags): the in-kernel limit.  A dctc chain of
                                // 25 to 64 values runs its front end band-valued and takes dct_wide_kernel (dctw_kernel.h) for the DCT
-constexpr int PCM_ALIGN = 8;   // utterance starts are multiples of this many samples
-constexpr int PCM_HEAD = 8;    // samples of padding before the first utterance (x[-2..-1] of frame 0 is loaded)
-constexpr int PCM_TAIL = 512;  // padding after the last one: the generic instantiation loads 16 rows of 32 samples whatever the window
 
 // Host side: the dynamic LDS of a launch and the workgroups of it that share a CU's 160 KiB (at most `cap`).  Each kernel's header has the
 // function that sizes it, beside the carve-up it must match.

@@ -27,29 +27,12 @@
 // gfx950, hipcc -O3: stream_stitch_kernel 15 VGPRs, 58 SGPRs; stream_carry_kernel 17 VGPRs, 45 SGPRs; no spills, no scratch, no LDS.
 #pragma once
 
+#include "stream_plan.h"  // StreamPush, stream_frames, STREAM_LEAD, STREAM_SLICE: the host plans a push by them
+
 namespace {
-
-constexpr int STREAM_LEAD = 8;       // samples of a slot ahead of the next frame's first one (= PCM_ALIGN: the frame starts 16-byte aligned)
-constexpr int STREAM_SLICE = 2048;   // slot samples per workgroup of stream_stitch_kernel: 256 lanes x one b128 store
-
-// Frames a file of `total` samples has produced: floor((total - (window - wshift)) / wshift), none while it is shorter than the
-// window - wshift samples rawIN::new_file loads first (src/io/in.cc:277,314).  A trailing partial window never makes a frame.
-__host__ __device__ inline long long stream_frames(long long total, int window, int wshift) {
-    const long long pre = window - wshift;
-    return total < pre ? 0 : (total - pre) / wshift;
-}
 
 struct StreamState {
     long long consumed;  // samples of the current file taken so far
-};
-
-// One stream of a push (host-built: the prefix sums over the push are the host's, which mirrors the counts)
-struct StreamPush {
-    long long src;    // where its new samples start in the caller's arena (samples)
-    long long slot;   // where its slot starts in the push arena (samples, a multiple of PCM_ALIGN)
-    long long row0;   // first row of the push it writes
-    int id, n;        // stream, new samples
-    int tile0, pad;   // first tile record it fills; pad: with noise state, the tile that follows its last one on its chain (-1: none)
 };
 
 struct StreamParams {

@@ -1,0 +1,188 @@
+// Streaming input: what a push is, worked out on the host before anything reaches the device.  Plain C++ (no HIP call, no HIP type):
+// engine.hip includes it through stream_kernels.h / stream_rows_kernels.h, tests/host/stream_plan_check.cc compiles it with g++ alone.
+//
+//   StreamPush, RowPush   the descriptors the stream kernels read, one per pushed stream
+//   stream_frames, stream_halo, stream_rows_out   frames of a file after so many samples, rows that have gone out after so many frames
+//   chain_deal            where chain c of C sits among the chain heads of a launch (plan_chains deals utterances by it, a push streams)
+//   stream_plan_push      a whole push from the set's geometry and mirrors: slots, prefix sums, chains, row descriptors, the launch's
+//                         sizes, the mirrors' next values.  It writes its output only; ctu_streams_push commits and launches from it
+//   stream_plan_finish    the same for ctu_streams_finish: the rows held back, the refusal of a file too short for its chain
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+#include "layout_constants.h"
+
+#ifdef __HIPCC__
+#define CTU_HOST_DEVICE __host__ __device__
+#else
+#define CTU_HOST_DEVICE
+#endif
+
+namespace {
+
+constexpr int STREAM_LEAD = 8;       // samples of a slot ahead of the next frame's first one (= PCM_ALIGN: the frame starts 16-byte aligned)
+constexpr int STREAM_SLICE = 2048;   // slot samples per workgroup of stream_stitch_kernel: 256 lanes x one b128 store
+
+// Frames a file of `total` samples has produced: floor((total - (window - wshift)) / wshift), none while it is shorter than the
+// window - wshift samples rawIN::new_file loads first (src/io/in.cc:277,314).  A trailing partial window never makes a frame.
+CTU_HOST_DEVICE inline long long stream_frames(long long total, int window, int wshift) {
+    const long long pre = window - wshift;
+    return total < pre ? 0 : (total - pre) / wshift;
+}
+
+// The halo H and the largest window of a delta chain (`order` stages of half-widths w[]) or of a stacking (0, 0 without either)
+inline void stream_halo(int order, const int *w, bool stack, int *H, int *wmax) {
+    *H = *wmax = 0;
+    for (int j = 0; j < order; j++) {
+        if (!stack || j == 0) *H += w[j];
+        *wmax = std::max(*wmax, w[j]);
+    }
+}
+// Rows of a file that have gone out after F frames: all without a chain, else F - H once frame wmax + 2 exists
+inline int64_t stream_rows_out(int H, int wmax, int64_t F) { return H == 0 ? F : (F >= wmax + 2 ? std::max<int64_t>(F - H, 0) : 0); }
+
+// One stream of a push (host-built: the prefix sums over the push are the host's, which mirrors the counts)
+struct StreamPush {
+    long long src;    // where its new samples start in the caller's arena (samples)
+    long long slot;   // where its slot starts in the push arena (samples, a multiple of PCM_ALIGN)
+    long long row0;   // first row of the push it writes
+    int id, n;        // stream, new samples
+    int tile0, pad;   // first tile record it fills; pad: with noise state, the tile that follows its last one on its chain (-1: none)
+};
+
+// One stream of a push, or the stream that finishes (host-built from the mirrored counts)
+struct RowPush {
+    long long F0;    // frames of the file ahead of this push
+    long long r0;    // rows of the file that have gone out ahead of it
+    long long out0;  // first row of the caller's buffer it writes
+    long long row0;  // first of its new base rows among the push's
+    int id, Tn;      // stream; frames this push completes
+    int nr;          // rows that go out now
+    int hsel;        // which of the stream's two histories holds frames F0 - C .. F0 - 1
+};
+
+// Chains per wave: `live` files dealt onto C chains, at most `slots` of them, in G workgroups of NWAVE waves.  Chain c lives in wave
+// c / G of workgroup c % G, so the chains of one workgroup are spread over the ranks of whatever order the files are dealt in.
+struct ChainDeal {
+    int C, G;
+    int heads() const { return G * NWAVE; }  // entries of the chain-head list the launch reads (-1: a wave without a chain)
+    int slot(int c) const { return (c % G) * NWAVE + c / G; }
+};
+inline ChainDeal chain_deal(int live, int slots) {
+    const int C = std::max(1, std::min(live, slots));
+    return {C, (C + NWAVE - 1) / NWAVE};
+}
+
+// What a stream set is, as far as the layout of a push goes
+struct PushGeom {
+    int window, wshift;
+    int H, wmax;             // halo and largest window of the set's delta chain or stacking (0, 0: a frame's row goes out with it)
+    bool held;               // row state: RowPush descriptors, the history flip
+    bool chained;            // noise state: chains of whole streams, a wave each
+    int max_chains, max_wg;  // the most chains, and without chains the most workgroups, the front end is launched with
+    int64_t arena_samples;   // the push arena, PCM_TAIL included
+    int64_t tile_cap;        // tile records the set has room for
+};
+
+// A planned push.  The arrays are the caller's (a stream set keeps them from create on, so a push allocates nothing): n entries each,
+// `heads` and `tail` chain_deal(n_streams, max_chains).heads() entries.  Entries past those a plan fills are left alone and never read.
+struct PushLayout {
+    StreamPush *push = nullptr;
+    RowPush *rows = nullptr;         // (held only)
+    int *heads = nullptr;            // (chained only) first tile of every chain, by ChainDeal::slot
+    int *tail = nullptr;             // (chained only) scratch: the stream at the end of every chain so far
+    int64_t *row_counts = nullptr;   // rows every pushed stream delivers now
+    int64_t *consumed = nullptr;     // the mirrors' next values, by position in the push
+    uint8_t *hsel = nullptr;
+    int n_heads = 0;                 // entries of `heads` the launch reads (0 without chains: the plan's own heads serve)
+    int tiles = 0, slices = 1, grid = 1;
+    int64_t base_rows = 0, rows_out = 0, most = 0;  // frames of the push, rows that go out (the same without row state), the most of one stream
+};
+
+// Plans the push of n_samples[i] new samples to stream ids[i], i < n (ids in range and distinct, counts >= 0: the caller has checked).
+// false, with nothing the caller may use in L, when the push does not fit the arena or the tile list.
+inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const uint8_t *hsel, int n, const int32_t *ids, const int64_t *n_samples,
+                             const int64_t *sample_off, PushLayout &L) {
+    int live = 0;
+    if (g.chained)  // the streams that complete a frame, dealt in turn onto at most max_chains chains
+        for (int i = 0; i < n; i++) {
+            const int64_t c = consumed[ids[i]];
+            live += stream_frames(c + n_samples[i], g.window, g.wshift) > stream_frames(c, g.window, g.wshift);
+        }
+    const ChainDeal deal = chain_deal(live, g.max_chains);
+    L.n_heads = g.chained ? deal.heads() : 0;
+    if (g.chained) {
+        std::fill(L.heads, L.heads + L.n_heads, -1);
+        std::fill(L.tail, L.tail + deal.C, -1);
+    }
+    int64_t so = PCM_HEAD, ro = 0, oo = 0, most = 0;
+    int tiles = 0, slices = 1;
+    live = 0;
+    for (int i = 0; i < n; i++) {
+        const int64_t c = consumed[ids[i]];
+        const int64_t F = stream_frames(c, g.window, g.wshift), T = stream_frames(c + n_samples[i], g.window, g.wshift) - F;
+        const int64_t len = STREAM_LEAD + (c - F * g.wshift) + n_samples[i];  // the stitched utterance, laid out by ctu_arena_layout's rule
+        StreamPush &p = L.push[i];
+        p.src = n_samples[i] ? sample_off[i] : 0;
+        p.slot = so;
+        p.row0 = ro;
+        p.id = ids[i];
+        p.n = (int)n_samples[i];
+        p.tile0 = tiles;
+        p.pad = -1;
+        if (g.chained && T > 0) {
+            const int ch = live++ % deal.C;
+            int &tail = L.tail[ch];
+            if (tail < 0) L.heads[deal.slot(ch)] = tiles;
+            else L.push[tail].pad = tiles;
+            tail = i;
+        }
+        so += (len + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN;
+        ro += T;
+        tiles += (int)((T + TILE - 1) / TILE);
+        slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
+        const int64_t r0 = stream_rows_out(g.H, g.wmax, F), nr = stream_rows_out(g.H, g.wmax, F + T) - r0;
+        if (g.held) {
+            RowPush &r = L.rows[i];
+            r.F0 = F; r.r0 = r0; r.out0 = oo; r.row0 = p.row0;
+            r.id = ids[i]; r.Tn = (int)T; r.nr = (int)nr;
+            r.hsel = hsel[ids[i]];
+        }
+        oo += nr;
+        most = std::max(most, nr);
+        L.row_counts[i] = nr;
+        L.consumed[i] = c + n_samples[i];
+        L.hsel[i] = (uint8_t)(hsel[ids[i]] ^ (g.held && T > 0 ? 1 : 0));  // stream_rows_carry_kernel writes the other history
+    }
+    if (so + PCM_TAIL > g.arena_samples || tiles > g.tile_cap) return false;
+    L.tiles = tiles;
+    L.slices = slices;
+    L.grid = g.chained ? deal.G : std::max(1, std::min(tiles, g.max_wg));
+    L.base_rows = ro;
+    L.rows_out = oo;
+    L.most = most;
+    return true;
+}
+
+// A stream that finishes after `consumed` samples: the rows held back for it, which go out now (RowPush `row`, meaningful while
+// pending > 0), or none from a file too short for its chain (the plan's refusal: such a file has no defined rows)
+struct FinishLayout {
+    int64_t frames, pending;
+    bool too_short;
+    RowPush row;
+};
+inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel) {
+    FinishLayout f;
+    f.frames = stream_frames(consumed, window, wshift);
+    const int64_t r0 = stream_rows_out(H, wmax, f.frames);
+    f.too_short = H > 0 && f.frames > 0 && f.frames < wmax + 2;
+    f.pending = f.too_short ? 0 : f.frames - r0;
+    f.row.F0 = f.frames; f.row.r0 = r0; f.row.out0 = 0; f.row.row0 = 0;  // rows r0 .. F - 1 with the file's length known
+    f.row.id = id; f.row.Tn = 0; f.row.nr = (int)f.pending;
+    f.row.hsel = hsel;
+    return f;
+}
+
+}  // namespace

@@ -27,20 +27,11 @@
 // the size post_kernel / cms_block_kernel take: (64 + 2H) (Dbase + order fea_c) floats, (64 + L - 1) ncols floats; none in the other two.
 #pragma once
 
+#include "stream_plan.h"  // RowPush: the host plans a push by it
+
 namespace {
 
 constexpr int STREAM_MEANS = 32;  // CMS columns at most (engine.hip: "more than 32 CMS columns")
-
-// One stream of a push, or the stream that finishes (host-built from the mirrored counts)
-struct RowPush {
-    long long F0;    // frames of the file ahead of this push
-    long long r0;    // rows of the file that have gone out ahead of it
-    long long out0;  // first row of the caller's buffer it writes
-    long long row0;  // first of its new base rows among the push's
-    int id, Tn;      // stream; frames this push completes
-    int nr;          // rows that go out now
-    int hsel;        // which of the stream's two histories holds frames F0 - C .. F0 - 1
-};
 
 struct RowParams {
     const RowPush *push;

@@ -1,0 +1,484 @@
+// Streaming input (include/ctu_engine.h: ctu_streams_*), host side: the stream set, its creation, pushes and finishes.
+// Included by engine.hip inside its extern "C" block, behind everything a run is made of (one translation unit).
+//
+// A push is check, plan, commit, launch.  The checks refuse ahead of everything else.  stream_plan_push (stream_plan.h, host only, also
+// compiled and tested without HIP) then lays the whole push out from the set's mirrors without touching them.  The commit copies the
+// mirrors' next values into the set, and from there on a push is HIP calls alone, sized by the plan (two HIP calls come ahead of the
+// plan: the device is selected, and the plan waits for this turn's page-locked descriptors, which it writes, to be free): the run goes over the front of the
+// set's ctu_plan with the extent of the push (RunExtent), so the plan itself is not written after ctu_streams_create_ex.
+// A HIP call that fails behind the commit (CTU_ERR_DEVICE) leaves mirrors and device state out of step: include/ctu_engine.h says what
+// the caller may still do with the set.
+#pragma once
+
+// A stream set (ctu_streams_create): per-stream state in HBM, and what a push needs that does not change from push to push - a plan over
+// n_streams utterances of the longest stitched length, whose tile list, chain heads (workgroup g starts at tile g), arena size and scratch a
+// push uses the front of.  The tile records themselves are written by stream_stitch_kernel, push after push.
+struct ctu_streams {
+    ctu_engine *eng = nullptr;
+    int n_streams = 0, cstride = 0;
+    int64_t max_push = 0;
+    PushGeom g{};                    // what stream_plan_push lays a push out by: window and hop, halo, row / noise state, chain and arena limits
+    std::unique_ptr<const ctu_plan> plan;  // (const: a push runs the front of it by a RunExtent of its own, nothing writes it after create)
+    DevBuf<int16_t> arena, carry;
+    DevBuf<StreamState> state;
+    std::vector<int64_t> consumed;   // the host's mirror of StreamState::consumed: layout and row counts of a push need no copy back
+    std::vector<int64_t> next_consumed;  // (of the push at hand, by position in it: PushLayout::consumed)
+    std::vector<int64_t> counts;         // (PushLayout::row_counts of a push whose caller passes no array; the host form reads them here)
+    std::vector<uint32_t> seen;      // the push a stream was last named in (a repeat inside one push is refused)
+    uint32_t push_no = 0;
+    // the descriptors of a push: two page-locked buffers and their device copies in turn, each guarded by the event behind its last reader
+    StreamPush *h_desc[2] = {nullptr, nullptr};
+    DevBuf<StreamPush> d_desc[2];
+    hipEvent_t desc_free[2] = {nullptr, nullptr};
+    int turn = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around stream_stitch_kernel and stream_carry_kernel of the last push
+    bool timed = false;
+    // CTU_STREAMS_ROW_STATE with a delta chain, stacking or CMS (stream_rows_kernels.h; g.held, g.H, g.wmax): the history's rows, the two
+    // histories of every stream and which one is current, the running means, the descriptors of the row kernels
+    int C = 0;
+    DevBuf<float> hist, means;
+    std::vector<uint8_t> hsel, next_hsel;
+    RowPush *h_rdesc[2] = {nullptr, nullptr};
+    DevBuf<RowPush> d_rdesc[2];
+    // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten (g.chained, g.max_chains): Navg | Yavg of every stream (frontend_kernel<..., XS>),
+    // the heads of the chains a push is dealt onto, which travel as the descriptors do, and the stream of every tile
+    DevBuf<float> xstate;
+    int *h_heads[2] = {nullptr, nullptr};
+    DevBuf<int> d_heads[2];
+    std::vector<int> chain_tail;     // (scratch of stream_plan_push)
+    // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
+    int16_t *h_stage = nullptr;
+    DevBuf<int16_t> d_stage;
+    DevBuf<float> d_rows;
+    std::vector<int64_t> offs;
+    ~ctu_streams() {
+        for (StreamPush *h : h_desc) ctu_host_free(h);
+        for (RowPush *h : h_rdesc) ctu_host_free(h);
+        for (int *h : h_heads) ctu_host_free(h);
+        ctu_host_free(h_stage);
+        for (hipEvent_t v : desc_free)
+            if (v) (void)hipEventDestroy(v);
+        for (hipEvent_t v : ev)
+            if (v) (void)hipEventDestroy(v);
+    }
+};
+
+namespace {
+void design_halo(const ctu::Design &d, int *H, int *wmax) { stream_halo(d.post_order, d.post_w, d.post_stack, H, wmax); }
+int64_t stream_rows_of(const ctu_streams *st, int64_t F) { return stream_rows_out(st->g.H, st->g.wmax, F); }
+}  // namespace
+
+int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
+    return ctu_streams_config_check_ex(argc, argv, 0, reason, cap, nullptr);
+}
+
+int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flags, char *reason, int64_t cap, int32_t *halo) {
+    if (halo) *halo = 0;
+    auto say = [&](const std::string &m) {
+        g_create_error = m;
+        if (reason && cap > 0) {
+            std::strncpy(reason, m.c_str(), (size_t)cap - 1);
+            reason[cap - 1] = 0;
+        }
+    };
+    say("");
+    try {
+        ctu::Opts o = ctu::Opts::from_args(to_args(argc, argv));
+        ctu::Design d(o);
+        spread_small_fft(d);
+        if (const std::string why = unsupported_reason(d); !why.empty()) {
+            say("ENGINE: configuration not on the accelerated path: " + why);
+            return CTU_ERR_UNSUPPORTED;
+        }
+        if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
+            say("ENGINE: unknown stream set flags");
+            return CTU_ERR_INPUT;
+        }
+        if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
+            say("ENGINE: configuration cannot be streamed: " + why);
+            return CTU_ERR_UNSUPPORTED;
+        }
+        int H = 0, wmax = 0;
+        design_halo(d, &H, &wmax);
+        if (halo) *halo = H;
+        return CTU_OK;
+    } catch (const std::exception &ex) {
+        say(ex.what());
+        return CTU_ERR_OPTS;
+    }
+}
+
+int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry) {
+    if (window < 1 || wshift < 1 || wshift > window || total < 0) return CTU_ERR_INPUT;
+    const int64_t F = stream_frames(total, window, wshift);
+    if (carry) *carry = total - F * wshift;
+    return F;
+}
+
+int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending) {
+    if (window < 1 || wshift < 1 || wshift > window || total < 0 || halo < 0 || wmax < 0 || wmax > halo || (halo > 0 && wmax < 1)) return CTU_ERR_INPUT;
+    const int64_t F = stream_frames(total, window, wshift), R = stream_rows_out(halo, wmax, F);
+    if (pending) *pending = F - R;
+    return R;
+}
+
+int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, ctu_streams **out) {
+    return ctu_streams_create_ex(e, n_streams, max_push_samples, 0, out);
+}
+
+int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out) {
+    if (!e || !out) return CTU_ERR_INPUT;
+    *out = nullptr;
+    if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
+        set_error(e, "ENGINE: unknown stream set flags");
+        return CTU_ERR_INPUT;
+    }
+    if (n_streams < 1 || max_push_samples < 1 || max_push_samples > (1 << 26)) {
+        set_error(e, "ENGINE: a stream set needs at least one stream and pushes of 1 .. 2^26 samples");
+        return CTU_ERR_INPUT;
+    }
+    const ctu::Design &d = *e->design;
+    if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
+        set_error(e, "ENGINE: configuration cannot be streamed: " + why);
+        return CTU_ERR_UNSUPPORTED;
+    }
+    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || e->do_vad || e->ss || (e->per_wave && e->big)) {
+        set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
+        return CTU_ERR_UNSUPPORTED;
+    }
+    std::unique_ptr<ctu_streams> st(new ctu_streams);
+    st->eng = e;
+    st->n_streams = n_streams;
+    st->max_push = max_push_samples;
+    st->cstride = (d.window + 7) / 8 * 8;
+    PushGeom &g = st->g;
+    g.window = d.window;
+    g.wshift = d.wshift;
+    g.max_wg = fe_max_wg(e);
+    g.held = d.post_order > 0 || d.cms;  // (only with CTU_STREAMS_ROW_STATE: refused above without)
+    design_halo(d, &g.H, &g.wmax);
+    g.chained = e->per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
+    g.max_chains = g.max_wg * NWAVE;
+    st->C = g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;
+    st->consumed.assign((size_t)n_streams, 0);
+    st->seen.assign((size_t)n_streams, 0);
+    st->hsel.assign((size_t)n_streams, 0);
+    st->offs.assign((size_t)n_streams, 0);
+    // what a planned push is written into: a push allocates nothing
+    st->next_consumed.assign((size_t)n_streams, 0);
+    st->counts.assign((size_t)n_streams, 0);
+    st->next_hsel.assign((size_t)n_streams, 0);
+    const size_t n_heads = (size_t)chain_deal(n_streams, g.max_chains).heads();
+    if (g.chained) st->chain_tail.assign(n_heads, -1);
+    // the longest slot: the lead, a full carry, a full push (and no shorter than the shortest file a delta chain is defined on: the plan
+    // of a set whose pushes are shorter than that is still a plan of files that could be)
+    const std::vector<int64_t> longest((size_t)n_streams, std::max((int64_t)STREAM_LEAD + d.window - 1 + max_push_samples,
+                                                                   (int64_t)d.window + (int64_t)(g.wmax + 1) * d.wshift));
+    ctu_plan *pl = nullptr;
+    if (const int rc = ctu_plan_create(e, longest.data(), n_streams, &pl); rc != CTU_OK) return rc;
+    st->plan.reset(pl);
+    g.arena_samples = pl->total_samples;
+    g.tile_cap = (int64_t)pl->tiles.n;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        st->arena.alloc((size_t)pl->total_samples);
+        st->carry.alloc((size_t)n_streams * st->cstride);
+        st->state.alloc((size_t)n_streams);
+        HIP_TRY(hipMemset(st->arena.p, 0, st->arena.n * sizeof(int16_t)));
+        HIP_TRY(hipMemset(st->carry.p, 0, st->carry.n * sizeof(int16_t)));
+        HIP_TRY(hipMemset(st->state.p, 0, st->state.n * sizeof(StreamState)));
+        for (int k = 0; k < 2; k++) {
+            st->h_desc[k] = static_cast<StreamPush *>(ctu_host_alloc((size_t)n_streams * sizeof(StreamPush)));
+            if (!st->h_desc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+            st->d_desc[k].alloc((size_t)n_streams);
+            HIP_TRY(hipEventCreateWithFlags(&st->desc_free[k], hipEventDisableTiming));
+            if (g.held) {
+                st->h_rdesc[k] = static_cast<RowPush *>(ctu_host_alloc((size_t)n_streams * sizeof(RowPush)));
+                if (!st->h_rdesc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_rdesc[k].alloc((size_t)n_streams);
+            }
+        }
+        if (g.chained) {
+            const size_t per_stream = (size_t)2 * 64 * (e->sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1);  // [2][64 NJ] of xstate_t (frontend_kernel.h)
+            st->xstate.alloc((size_t)n_streams * per_stream);
+            HIP_TRY(hipMemset(st->xstate.p, 0, st->xstate.n * sizeof(float)));  // (never read ahead of a store: a file's first tile resets)
+            pl->tile_utt.alloc(pl->tiles.n);
+            HIP_TRY(hipMemset(pl->tile_utt.p, 0, pl->tile_utt.n * sizeof(int)));
+            for (int k = 0; k < 2; k++) {
+                st->h_heads[k] = static_cast<int *>(ctu_host_alloc(n_heads * sizeof(int)));
+                if (!st->h_heads[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_heads[k].alloc(n_heads);
+            }
+        }
+        if (g.held) {
+            st->hist.alloc(std::max<size_t>((size_t)2 * n_streams * st->C * d.Dbase, 1));
+            st->means.alloc((size_t)n_streams * STREAM_MEANS);
+            HIP_TRY(hipMemset(st->hist.p, 0, st->hist.n * sizeof(float)));
+            HIP_TRY(hipMemset(st->means.p, 0, st->means.n * sizeof(float)));
+        }
+        for (hipEvent_t &v : st->ev) HIP_TRY(hipEventCreate(&v));
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) return rc;
+    *out = st.release();
+    return CTU_OK;
+}
+
+void ctu_streams_destroy(ctu_streams *st) {
+    if (!st) return;
+    (void)hipSetDevice(st->eng->device);
+    (void)hipDeviceSynchronize();  // pushes may still be in flight on the caller's streams
+    delete st;
+}
+
+int64_t ctu_streams_frames(const ctu_streams *st, int32_t id) {
+    if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
+    const ctu::Design &d = *st->eng->design;
+    return stream_rows_of(st, stream_frames(st->consumed[(size_t)id], d.window, d.wshift));
+}
+
+int64_t ctu_streams_pending(const ctu_streams *st, int32_t id) {
+    if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
+    const ctu::Design &d = *st->eng->design;
+    const int64_t F = stream_frames(st->consumed[(size_t)id], d.window, d.wshift);
+    return F - stream_rows_of(st, F);
+}
+
+namespace {
+// The row kernels of a push, or of a finish, over the n streams h_rdesc[k] describes (uploaded here); `most` is the largest row count among them
+void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finishing, float *d_rows, hipStream_t s) {
+    const ctu::Design &d = *st->eng->design;
+    HIP_TRY(hipMemcpyAsync(st->d_rdesc[k].p, st->h_rdesc[k], (size_t)n * sizeof(RowPush), hipMemcpyHostToDevice, s));
+    if (most == 0) return;
+    RowParams rp;
+    rp.push = st->d_rdesc[k].p; rp.fresh = st->plan->base_rows.p; rp.hist = st->hist.p; rp.means = st->means.p; rp.rows = d_rows;
+    rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase; rp.finishing = finishing ? 1 : 0;
+    const unsigned chunks = (unsigned)((most + 63) / 64);
+    if (d.post_order > 0) {
+        size_t shm = 0;
+        const PostParams pp = post_params(d, &shm);
+        if (d.post_stack) hipLaunchKernelGGL(stream_post_kernel<true>, dim3(chunks, (unsigned)n), dim3(256), shm, s, rp, pp);
+        else hipLaunchKernelGGL(stream_post_kernel<false>, dim3(chunks, (unsigned)n), dim3(256), shm, s, rp, pp);
+    }
+    if (d.cms) {
+        const CmsParams cp = cms_params(d);
+        if (d.cms == 1) hipLaunchKernelGGL(stream_cms_exp_kernel, dim3((unsigned)n), dim3(64), 0, s, rp, cp);
+        else hipLaunchKernelGGL(stream_cms_block_kernel, dim3(chunks, (unsigned)n), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, rp, cp);
+    }
+    HIP_TRY(hipGetLastError());
+}
+// The argument checks the device and the host form of a push share (each refuses in its own words)
+bool push_args_ok(const ctu_streams *st, int32_t n, const int32_t *ids, const int64_t *n_samples) { return n >= 0 && n <= st->n_streams && (!n || (ids && n_samples)); }
+bool push_count_ok(const ctu_streams *st, int64_t n_samples) { return n_samples >= 0 && n_samples <= st->max_push; }
+}  // namespace
+
+int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
+                     float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
+    const ctu_plan *pl = st->plan.get();
+    auto refuse = [&](const char *m) {
+        set_error(e, std::string("ENGINE: ") + m);
+        return CTU_ERR_INPUT;
+    };
+    // ---- everything that can be refused is refused here, ahead of the first launch and of any change to the set
+    if (!push_args_ok(st, n, ids, n_samples)) return refuse("push: bad stream count or null argument");
+    if (n == 0) return CTU_OK;
+    if (++st->push_no == 0) {  // (the counter wrapped: forget the marks)
+        std::fill(st->seen.begin(), st->seen.end(), 0u);
+        st->push_no = 1;
+    }
+    int64_t rows = 0, fresh = 0;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= st->n_streams) return refuse("push: stream id out of range");
+        if (st->seen[(size_t)ids[i]] == st->push_no) return refuse("push: a stream id appears twice");
+        st->seen[(size_t)ids[i]] = st->push_no;
+        if (!push_count_ok(st, n_samples[i])) return refuse("push: more samples than the set's max_push_samples (or fewer than none)");
+        if (n_samples[i] && (!sample_off || sample_off[i] < 0)) return refuse("push: null or negative sample offsets");
+        const int64_t c = st->consumed[(size_t)ids[i]];
+        rows += stream_rows_of(st, stream_frames(c + n_samples[i], d.window, d.wshift)) - stream_rows_of(st, stream_frames(c, d.window, d.wshift));
+        fresh += n_samples[i];
+    }
+    if (fresh && !d_pcm) return refuse("push: null sample buffer");
+    if (rows > rows_capacity || (rows && !d_rows)) return refuse("push: the rows of this push do not fit rows_capacity");
+    hipStream_t s = (hipStream_t)stream;
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const int k = st->turn;
+        HIP_TRY(hipEventSynchronize(st->desc_free[k]));  // (the push before last has read them; immediate before the first record)
+        // ---- plan: the whole push, into this turn's page-locked descriptors and the set's scratch; the set itself is only read
+        PushLayout L;
+        L.push = st->h_desc[k]; L.rows = st->h_rdesc[k]; L.heads = st->h_heads[k]; L.tail = st->chain_tail.data();
+        L.row_counts = row_counts ? row_counts : st->counts.data();  // (the caller's array is output of the call: planned in place)
+        L.consumed = st->next_consumed.data(); L.hsel = st->next_hsel.data();
+        if (!stream_plan_push(st->g, st->consumed.data(), st->hsel.data(), n, ids, n_samples, sample_off, L))
+            throw std::runtime_error("internal: a push beyond the set's arena");
+        // ---- commit: nothing refuses this push any more.  The mirrors take their next values; what follows is HIP calls alone
+        st->turn ^= 1;
+        for (int i = 0; i < n; i++) st->consumed[(size_t)ids[i]] = L.consumed[i];
+        if (st->g.held)
+            for (int i = 0; i < n; i++) st->hsel[(size_t)ids[i]] = L.hsel[i];
+        // ---- launch
+        const bool held = st->g.held;
+        HIP_TRY(hipMemcpyAsync(st->d_desc[k].p, L.push, (size_t)n * sizeof(StreamPush), hipMemcpyHostToDevice, s));
+        RunExtent x;  // the front end and its tails run over the front of the set's plan: this push
+        x.n_tiles = L.tiles; x.grid = L.grid; x.total_frames = L.base_rows;
+        x.heads = L.n_heads ? st->d_heads[k].p : pl->ext.heads;
+        x.xstate = st->xstate.p;
+        StreamParams sp;
+        sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
+        sp.cstride = st->cstride; sp.window = d.window; sp.wshift = d.wshift;
+        sp.n_tiles = L.tiles; sp.grid = L.grid;
+        sp.tile_stream = L.n_heads ? pl->tile_utt.p : nullptr;
+        if (L.n_heads) HIP_TRY(hipMemcpyAsync(st->d_heads[k].p, L.heads, (size_t)L.n_heads * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(st->ev[0], s));
+        hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)L.slices), dim3(256), 0, s, sp);
+        HIP_TRY(hipEventRecord(st->ev[1], s));
+        HIP_TRY(hipGetLastError());
+        int rc = CTU_OK;
+        if (L.tiles) rc = run_chain(e, pl, x, st->arena.p, held ? pl->base_rows.p : d_rows, nullptr, s, !held);
+        if (held && L.tiles && rc == CTU_OK) launch_stream_rows(st, k, n, L.most, false, d_rows, s);
+        HIP_TRY(hipEventRecord(st->ev[2], s));
+        hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
+        if (held && st->C > 0 && L.tiles && rc == CTU_OK) {
+            RowParams rp;
+            std::memset(&rp, 0, sizeof rp);
+            rp.push = st->d_rdesc[k].p; rp.fresh = pl->base_rows.p; rp.hist = st->hist.p;
+            rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase;
+            hipLaunchKernelGGL(stream_rows_carry_kernel, dim3((unsigned)n, (unsigned)((st->C * d.Dbase + 255) / 256)), dim3(256), 0, s, rp);
+        }
+        HIP_TRY(hipEventRecord(st->ev[3], s));
+        HIP_TRY(hipEventRecord(st->desc_free[k], s));
+        HIP_TRY(hipGetLastError());
+        st->timed = true;
+        return rc;
+    });
+}
+
+int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples, float *h_rows,
+                          int64_t rows_capacity, int64_t *row_counts) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const int D = e->design->D;
+    if (!push_args_ok(st, n, ids, n_samples) || (n && !h_pcm)) {
+        set_error(e, "ENGINE: push: bad stream count or null argument");
+        return CTU_ERR_INPUT;
+    }
+    int64_t fresh = 0;
+    for (int i = 0; i < n; i++) {
+        if (!push_count_ok(st, n_samples[i]) || (n_samples[i] && !h_pcm[i])) {
+            set_error(e, "ENGINE: push: more samples than the set's max_push_samples (or fewer than none), or a null sample buffer");
+            return CTU_ERR_INPUT;
+        }
+        fresh += n_samples[i];
+    }
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const size_t cap = (size_t)st->n_streams * (size_t)st->max_push;
+        if (!st->h_stage) {
+            st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
+            if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
+            st->d_stage.alloc(cap);
+            // (a push that brings a stream's frame wmax + 2 also delivers the rows of the wmax + 1 frames before it)
+            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->row_off[st->plan->n_utt] + (int64_t)st->n_streams * (st->g.wmax + 1), 1) * D);
+        }
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            st->offs[(size_t)i] = at;
+            if (n_samples[i]) std::memcpy(st->h_stage + at, h_pcm[i], (size_t)n_samples[i] * sizeof(int16_t));
+            at += n_samples[i];
+        }
+        if (fresh) HIP_TRY(hipMemcpyAsync(st->d_stage.p, st->h_stage, (size_t)fresh * sizeof(int16_t), hipMemcpyHostToDevice, nullptr));
+        // the device rows hold any push of the set; what the caller's buffer holds is the device form's check
+        const int rc = ctu_streams_push(st, n, ids, st->d_stage.p, st->offs.data(), n_samples, h_rows ? st->d_rows.p : nullptr, h_rows ? rows_capacity : 0,
+                                        row_counts, nullptr);
+        if (rc != CTU_OK) return rc;
+        const int64_t *counts = row_counts ? row_counts : st->counts.data();  // (where the push planned them)
+        int64_t rows = 0;
+        for (int i = 0; i < n; i++) rows += counts[i];
+        if (rows) {  // page-locked rows at the link rate, pageable ones through the runtime's staging (as run_host_ranges downloads)
+            if (is_pinned(h_rows)) HIP_TRY(hipMemcpyAsync(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost, nullptr));
+            else HIP_TRY(hipMemcpy(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost));
+        }
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return CTU_OK;
+    });
+}
+
+int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
+    if (id < 0 || id >= st->n_streams) {
+        set_error(e, "ENGINE: finish: stream id out of range");
+        return CTU_ERR_INPUT;
+    }
+    if (row_count) *row_count = 0;  // fread() comes up short on a trailing partial window and the file ends there (src/io/in.cc:314,438)
+    const int64_t total = st->consumed[(size_t)id];
+    const FinishLayout fin = stream_plan_finish(d.window, d.wshift, st->g.H, st->g.wmax, total, id, st->hsel[(size_t)id]);
+    const int64_t pending = fin.pending;
+    const bool too_short = fin.too_short;
+    if (pending > rows_capacity || (pending && !d_rows)) {  // ahead of any launch or change: the stream stays as it was
+        set_error(e, "ENGINE: finish: the rows held back for this stream do not fit rows_capacity");
+        return CTU_ERR_INPUT;
+    }
+    st->consumed[(size_t)id] = 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        if (pending) {  // rows r0 .. F - 1 with the file's length known: every base row they read is in the history
+            const int k = st->turn;
+            st->turn ^= 1;
+            HIP_TRY(hipEventSynchronize(st->desc_free[k]));
+            st->h_rdesc[k][0] = fin.row;
+            launch_stream_rows(st, k, 1, pending, true, d_rows, s);
+            HIP_TRY(hipEventRecord(st->desc_free[k], s));
+        }
+        HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
+        if (st->g.held) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) return rc;
+    if (total > 0 && total < d.window - d.wshift) {
+        set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
+        return CTU_ERR_INPUT;
+    }
+    if (too_short) {  // plan_layout's words; the stream is reset all the same
+        set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
+        return CTU_ERR_INPUT;
+    }
+    if (row_count) *row_count = pending;
+    return CTU_OK;
+}
+
+int ctu_streams_finish_host(ctu_streams *st, int32_t id, float *h_rows, int64_t rows_capacity, int64_t *row_count) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const int D = e->design->D;
+    if (row_count) *row_count = 0;
+    const int64_t pending = ctu_streams_pending(st, id);  // (at most max(H, wmax + 1) rows; an id outside the set is ctu_streams_finish's to refuse)
+    DevBuf<float> rows;
+    int64_t cnt = 0;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        if (pending > 0) rows.alloc((size_t)pending * D);
+        const int rc = ctu_streams_finish(st, id, h_rows ? rows.p : nullptr, h_rows ? rows_capacity : 0, &cnt, nullptr);
+        if (rc != CTU_OK) return rc;
+        if (cnt) HIP_TRY(hipMemcpy(h_rows, rows.p, (size_t)cnt * D * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return CTU_OK;
+    });
+    if (rc == CTU_OK && row_count) *row_count = cnt;
+    return rc;
+}
+
+int ctu_streams_last_push_ms(ctu_streams *st, float *ms3) {
+    if (!st || !ms3 || !st->timed) return CTU_ERR_INPUT;
+    if (hipEventSynchronize(st->ev[3]) != hipSuccess) return CTU_ERR_DEVICE;
+    if (hipEventElapsedTime(&ms3[0], st->ev[0], st->ev[1]) != hipSuccess) return CTU_ERR_DEVICE;
+    if (hipEventElapsedTime(&ms3[1], st->ev[1], st->ev[2]) != hipSuccess) return CTU_ERR_DEVICE;
+    if (hipEventElapsedTime(&ms3[2], st->ev[2], st->ev[3]) != hipSuccess) return CTU_ERR_DEVICE;
+    return CTU_OK;
+}
+

@@ -176,6 +176,9 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * stream after the other in the order of stream_ids, row_counts[i] of them for stream i (row_counts is host memory and is
  * filled on return; it may be NULL).  Asynchronous on `stream`; d_pcm may be reused once the work enqueued has run.  The calls on
  * one set must be ordered: one hipStream_t, or the caller's own synchronisation.  One set per engine runs at a time.
+ * A push that returns CTU_ERR_DEVICE may have failed after the set had taken the push's sample counts for its own, so what the host
+ * and the device hold for the set may differ, and nothing is rolled back.  Discard the rows of that push and call ctu_streams_finish
+ * for every stream of the set (discarding those rows too) before pushing again: finish resets host and device state of a stream alike.
  *
  * Row state (ctu_streams_create_ex with CTU_STREAMS_ROW_STATE): the set also keeps, per stream, the last base rows of the file and
  * the running cepstral means, and so takes -fea_delta, -fea_trap, -fea_Z_exp and -fea_Z_block as well (the other refusals stand, and

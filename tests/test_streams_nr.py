@@ -168,6 +168,39 @@ def test_streams_in_different_phases_share_a_push(Engine):
     assert np.array_equal(np.concatenate(got[D]), fresh_d)
 
 
+def test_offline_plans_between_pushes_share_nothing_with_the_set(Engine):
+    """What a run covers travels with the run: a set's pushes (two tiles, a live chain, noise state) and offline plans of two other
+    sizes, taken in turn on one engine, each give the rows they give alone, bit for bit."""
+    cfg = C4_NOVAD
+    eng = Engine(cfg)
+    w, s = eng.dims.window, eng.dims.wshift
+    utts3 = [_signal(eng, 70, seed=60 + k)[:w + 69 * s] for k in range(3)]   # two tiles each
+    utts1 = [_signal(eng, 10, seed=70)[:w + 9 * s]]
+    plans = [(eng.plan([u.size for u in utts]), utts) for utts in (utts3, utts1)]
+    assert [p.total_frames for p, _ in plans] == [210, 10]
+    offline = lambda: [eng.run_host(p, p.pack(utts)).copy() for p, utts in plans]
+    alone = offline()
+    xs = [_signal(eng, 96, seed=80), _signal(eng, 40, seed=81), _signal(eng, 20, seed=82)]
+    first = {0: w + 69 * s, 1: w + 9 * s}   # 70 frames to stream 0, 10 to stream 1; then the rest, and a third stream
+
+    def streamed(between):
+        st = _set(eng, cfg, 3, max(x.size for x in xs))
+        got = [st.push({k: xs[k][:c] for k, c in first.items()})]
+        assert [got[0][k].shape[0] for k in (0, 1)] == [70, 10]
+        mid = between()
+        got.append(st.push({k: xs[k][first.get(k, 0):] for k in (2, 0, 1)}))
+        assert [got[1][k].shape[0] for k in (0, 1, 2)] == [26, 30, 20]
+        got.append({k: st.finish(k) for k in range(3)})
+        return got, mid
+
+    want, _ = streamed(lambda: None)
+    got, mid = streamed(offline)
+    for a, b in zip(got, want):
+        assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    for a, b in zip(mid + offline(), alone + alone):
+        assert a.shape == b.shape and np.isfinite(a).all() and np.array_equal(a, b)
+
+
 def test_the_flag_on_a_chain_without_noise_reduction_changes_nothing(Engine):
     eng = Engine(C2)
     w, s = eng.dims.window, eng.dims.wshift
