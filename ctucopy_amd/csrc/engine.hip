@@ -116,6 +116,7 @@ enum BigPath { BIG_NONE, BIG_WAVE1K, BIG_SS, BIG_FFT };
 
 #include "post_kernels.h"
 #include "stream_rows_kernels.h"
+#include "stream_vad_kernels.h"
 #include "signal_kernels.h"
 
 struct ctu_engine {
@@ -263,6 +264,7 @@ int guarded(ctu_engine *e, F &&body) {
 bool dct_wide(const ctu::Design &d) { return !d.rows_in && !d.signal_out && d.kind == ctu::FeaKind::Dctc && d.nfea > MAXC; }
 bool ss_eligible(const ctu::Design &d);
 bool ss_big_eligible(const ctu::Design &d);
+bool vf_eligible(const ctu::Design &d);
 int ss_mode_of(const ctu::Opts &o);
 
 // Entries of the vector the VAD's `fea` criterion measures: VADcri_cepdist sizes itself on the vector it is handed (src/vad/vad.cc:182),
@@ -451,7 +453,20 @@ std::string streams_unsupported_reason(const ctu::Design &d, uint32_t flags = 0)
         if (d.wfft >= 1024) return "-nr_mode exten on " + std::to_string(d.wfft) + "-point frames (-w: the noise estimate of the large transforms lives in their own kernels, a stream set carries the one of the 256- and 512-point front end)";
     } else if (o.nr_mode != "none") return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
     if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
-    if (o.do_vad()) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";
+    if (o.do_vad() && !(flags & CTU_STREAMS_VAD_STATE)) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";
+    if (o.do_vad()) {  // the detector's state travels with the stream (stream_vad_kernels.h); what it cannot carry is refused by name
+        const bool burg = o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "lpc";
+        if (o.vad_apply_mode == "drop") return "-vad_apply_mode drop (the row count of a push would depend on the data)";
+        if (o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "fea") return "-vad_cepdist_mode fea (the criterion reads finished rows)";
+        if (d.kind == ctu::FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
+        if (d.post_order > 0)
+            return std::string(d.post_stack ? "-fea_trap" : "-fea_delta") + " together with the VAD module (the detector is called when a vector reaches the writer, on frame min(t + H, T - 1))";
+        if (d.cms) return std::string(d.cms == 1 ? "-fea_Z_exp" : "-fea_Z_block") + " together with the VAD module (CMS behind the detector's delayed rows is not carried by a stream set)";
+        if (o.fea_E && (o.vad_filter_order - 1) / 2 > 0) return "-fea_E with the VAD module's majority filter (the offline run shifts the energy column along the file)";
+        if (d.wfft >= 1024) return "the VAD module on 1024-point and larger frames (-w: a stream set carries the detector behind the 256- and 512-point front end)";
+        if (o.nr_mode == "exten" && !(burg && vf_eligible(d)))
+            return "-nr_mode exten with a VAD criterion outside the fused shapes (25 ms frames at 8 or 16 kHz, the lpc criterion with 14 coefficients: the exported spectra are not carried behind exten's state)";
+    }
     if (d.kind == ctu::FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
     const bool row_state = (flags & CTU_STREAMS_ROW_STATE) != 0;
     if (d.post_order > 0 && !row_state) return d.post_stack ? "-fea_trap (stacking spans 2 * trap_win + 1 frames)" : "-fea_delta (the delta chain spans the frames of its windows)";
@@ -1223,7 +1238,8 @@ void lift(int v, F &&f) {
 }
 // The front-end launch of an engine: its FeSel lifted to template arguments, one at a time; fe_compiled decides which leaves exist.
 // `xs`: the launch of a stream set with noise state (frontend_kernel<..., XS>; the generic walk: the same rows bit for bit).
-constexpr bool fe_streamed(const FeSel &k) { return !k.vx && !k.vf && !k.ss && !k.sy && (k.gen == GEN_EXTEN || k.gen == GEN_FULL); }
+// (with detector state as well: the fused Burg-cepstral criterion behind exten, C4's front end - its cepstra go to the scratch by frame, nothing of it runs along a file)
+constexpr bool fe_streamed(const FeSel &k) { return !k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf)); }
 void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp, bool xs = false) {
     const FeSel &k = e->sel;
 #define V(x) decltype(x)::value
@@ -1651,10 +1667,10 @@ void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) 
 
 // The fused path left the lattice's output of every frame behind: the coefficient recursion and a -> c one frame per lane,
 // then the detector's recurrences, sixteen utterances per wave
-void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, uint8_t *d_vad) {
+void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, uint8_t *d_vad, bool replay) {
     if (CTU_VF_A2C)
         hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((x.total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)x.total_frames);
-    lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
+    if (replay) lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
         hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((pl->n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->n_live,
                            pl->d_row_off.p, d_vad, e->vp);
     });
@@ -2297,8 +2313,11 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
 
 // A run of a plan over the extent `x`: the plan's own, or the front of it a push of a stream set covers.  `row_stages` off stops ahead of
 // stage_post and stage_cms with the base rows in the plan's scratch: a stream set with row state runs its own forms of the two
-// (stream_rows_kernels.h) over them and its history.
-static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages) {
+// (stream_rows_kernels.h) over them and its history.  `vad_stages` off likewise leaves the VAD's sequential stages out - the detector's
+// replay, the short files' bytes, the ring - with the criterion's input of every frame in the plan's scratch (vad_cf / vad_ci / the
+// energy): a stream set with detector state replays them from its own state (stream_vad_kernels.h) and needs no d_vad here.
+static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages,
+                     bool vad_stages = true) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
     if (e->rows_in) {
         set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows");
@@ -2311,7 +2330,7 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
         set_error(e, "ENGINE: this configuration writes speech (-format_out raw|wave): use ctu_engine_run_signal");
         return CTU_ERR_INPUT;
     }
-    if (!d_pcm || (!signal && !d_rows) || (e->do_vad && !d_vad)) {
+    if (!d_pcm || (!signal && !d_rows) || (e->do_vad && vad_stages && !d_vad)) {
         set_error(e, "ENGINE: null device buffer");
         return CTU_ERR_INPUT;
     }
@@ -2353,10 +2372,10 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
         if (d.kind == ctu::FeaKind::TrapDct) stage_trap(e, pl, s, d_rows);
         if (d.post_order > 0 && row_stages) stage_post(e, pl, s, d_rows);
         if (d.cms && row_stages) stage_cms(e, pl, s, d_rows);
-        if (e->do_vad && e->vf && pl->n_live > 0) stage_fused_vad(e, pl, x, s, d_vad);
-        if (e->do_vad && !e->vf) stage_vad_decide(e, pl, s, d_rows, d_vad);
-        if (e->do_vad && d.o.vad_filter_order > 1) stage_short_files(e, pl, s, d_vad);
-        if (e->do_vad && !pl->ring_hidx.empty() && x.total_frames > 0) stage_ring_gather(e, pl, x, s, d_rows);
+        if (e->do_vad && e->vf && pl->n_live > 0) stage_fused_vad(e, pl, x, s, d_vad, vad_stages);
+        if (e->do_vad && !e->vf && vad_stages) stage_vad_decide(e, pl, s, d_rows, d_vad);
+        if (e->do_vad && d.o.vad_filter_order > 1 && vad_stages) stage_short_files(e, pl, s, d_vad);
+        if (e->do_vad && !pl->ring_hidx.empty() && x.total_frames > 0 && vad_stages) stage_ring_gather(e, pl, x, s, d_rows);
         return CTU_OK;
     });
 }

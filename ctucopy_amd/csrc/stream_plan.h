@@ -7,6 +7,8 @@
 //   stream_plan_push      a whole push from the set's geometry and mirrors: slots, prefix sums, chains, row descriptors, the launch's
 //                         sizes, the mirrors' next values.  It writes its output only; ctu_streams_push commits and launches from it
 //   stream_plan_finish    the same for ctu_streams_finish: the rows held back, the refusal of a file too short for its chain
+//   stream_vad_halo       detector state (CTU_STREAMS_VAD_STATE): the majority filter's delay h as the halo of the row arithmetic, so that
+//                         a frame's row and its decision leave together; PushGeom::vad then adds the list of the streams that run the replay
 #pragma once
 
 #include <algorithm>
@@ -42,6 +44,14 @@ inline void stream_halo(int order, const int *w, bool stack, int *H, int *wmax) 
 }
 // Rows of a file that have gone out after F frames: all without a chain, else F - H once frame wmax + 2 exists
 inline int64_t stream_rows_out(int H, int wmax, int64_t F) { return H == 0 ? F : (F >= wmax + 2 ? std::max<int64_t>(F - H, 0) : 0); }
+
+// The VAD's majority filter of order `order` releases a decision h = (order - 1) / 2 frames late, and the reference's writer releases the
+// row with it: R(F) = F - h once F > h, none before (a file of no more than h frames writes nothing).  That is stream_rows_out with
+// H = h and wmax = h - 1; with h = 0 nothing is held back.
+inline void stream_vad_halo(int order, int *H, int *wmax) {
+    *H = (order - 1) / 2;
+    *wmax = *H > 0 ? *H - 1 : 0;
+}
 
 // One stream of a push (host-built: the prefix sums over the push are the host's, which mirrors the counts)
 struct StreamPush {
@@ -80,6 +90,7 @@ struct PushGeom {
     int window, wshift;
     int H, wmax;             // halo and largest window of the set's delta chain or stacking (0, 0: a frame's row goes out with it)
     bool held;               // row state: RowPush descriptors, the history flip
+    bool vad = false;        // detector state: RowPush descriptors (whether rows are held or not), the list of the streams that run the replay
     bool chained;            // noise state: chains of whole streams, a wave each
     int max_chains, max_wg;  // the most chains, and without chains the most workgroups, the front end is launched with
     int64_t arena_samples;   // the push arena, PCM_TAIL included
@@ -90,7 +101,10 @@ struct PushGeom {
 // `heads` and `tail` chain_deal(n_streams, max_chains).heads() entries.  Entries past those a plan fills are left alone and never read.
 struct PushLayout {
     StreamPush *push = nullptr;
-    RowPush *rows = nullptr;         // (held only)
+    RowPush *rows = nullptr;         // (held or vad only)
+    int *replay = nullptr;           // (vad only) positions in the push of the streams that complete a frame, in push order: the detector's
+                                     // replay runs over these alone (16 to a wave); a stream that completes none is not touched
+    int n_replay = 0;                // entries of `replay`
     int *heads = nullptr;            // (chained only) first tile of every chain, by ChainDeal::slot
     int *tail = nullptr;             // (chained only) scratch: the stream at the end of every chain so far
     int64_t *row_counts = nullptr;   // rows every pushed stream delivers now
@@ -118,7 +132,7 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
         std::fill(L.tail, L.tail + deal.C, -1);
     }
     int64_t so = PCM_HEAD, ro = 0, oo = 0, most = 0;
-    int tiles = 0, slices = 1;
+    int tiles = 0, slices = 1, n_replay = 0;
     live = 0;
     for (int i = 0; i < n; i++) {
         const int64_t c = consumed[ids[i]];
@@ -144,7 +158,8 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
         tiles += (int)((T + TILE - 1) / TILE);
         slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
         const int64_t r0 = stream_rows_out(g.H, g.wmax, F), nr = stream_rows_out(g.H, g.wmax, F + T) - r0;
-        if (g.held) {
+        if (g.vad && T > 0) L.replay[n_replay++] = i;
+        if (g.held || g.vad) {  // (vad: decision byte k of the push belongs to row k, so out0 serves both; F0 is the replay's absolute frame index)
             RowPush &r = L.rows[i];
             r.F0 = F; r.r0 = r0; r.out0 = oo; r.row0 = p.row0;
             r.id = ids[i]; r.Tn = (int)T; r.nr = (int)nr;
@@ -160,6 +175,7 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
     L.tiles = tiles;
     L.slices = slices;
     L.grid = g.chained ? deal.G : std::max(1, std::min(tiles, g.max_wg));
+    L.n_replay = n_replay;
     L.base_rows = ro;
     L.rows_out = oo;
     L.most = most;
@@ -167,18 +183,21 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
 }
 
 // A stream that finishes after `consumed` samples: the rows held back for it, which go out now (RowPush `row`, meaningful while
-// pending > 0), or none from a file too short for its chain (the plan's refusal: such a file has no defined rows)
+// pending > 0), or none from a file too short for its chain (the plan's refusal: such a file has no defined rows).
+// vad: H, wmax are stream_vad_halo's; a file of 1 .. h frames is no refusal there - the reference writes nothing for it - and the
+// pending min(F, h) rows come with as many decisions, which the majority filter's flush makes (row.F0 = the file's frames).
 struct FinishLayout {
     int64_t frames, pending;
     bool too_short;
     RowPush row;
 };
-inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel) {
+inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel, bool vad = false) {
     FinishLayout f;
     f.frames = stream_frames(consumed, window, wshift);
     const int64_t r0 = stream_rows_out(H, wmax, f.frames);
     f.too_short = H > 0 && f.frames > 0 && f.frames < wmax + 2;
     f.pending = f.too_short ? 0 : f.frames - r0;
+    if (vad) f.too_short = false;  // (pending stays 0: neither rows nor decisions)
     f.row.F0 = f.frames; f.row.r0 = r0; f.row.out0 = 0; f.row.row0 = 0;  // rows r0 .. F - 1 with the file's length known
     f.row.id = id; f.row.Tn = 0; f.row.nr = (int)f.pending;
     f.row.hsel = hsel;

@@ -6,6 +6,8 @@
 // mirrors' next values into the set, and from there on a push is HIP calls alone, sized by the plan (two HIP calls come ahead of the
 // plan: the device is selected, and the plan waits for this turn's page-locked descriptors, which it writes, to be free): the run goes over the front of the
 // set's ctu_plan with the extent of the push (RunExtent), so the plan itself is not written after ctu_streams_create_ex.
+// On a set with detector state the run stops ahead of the VAD's sequential stages (run_chain: vad_stages off) and launch_stream_vad
+// replays them from the set's own state, by the plan's RowPush descriptors and its list of the streams that complete a frame.
 // A HIP call that fails behind the commit (CTU_ERR_DEVICE) leaves mirrors and device state out of step: include/ctu_engine.h says what
 // the caller may still do with the set.
 #pragma once
@@ -46,6 +48,15 @@ struct ctu_streams {
     int *h_heads[2] = {nullptr, nullptr};
     DevBuf<int> d_heads[2];
     std::vector<int> chain_tail;     // (scratch of stream_plan_push)
+    // CTU_STREAMS_VAD_STATE on a configuration with the VAD module (stream_vad_kernels.h; g.vad, g.H = h, g.wmax = h - 1): the detector's
+    // record of every stream, the base rows of a push ahead of their delayed copy (h > 0: the histories above hold the last h of them),
+    // the decisions of a push nobody asked for (and of the host forms, ahead of the download), the streams of a push that run the replay
+    bool vad = false;
+    DevBuf<double> vstate;
+    DevBuf<float> vbase;
+    DevBuf<uint8_t> vsink;
+    int *h_replay[2] = {nullptr, nullptr};
+    DevBuf<int> d_replay[2];
     // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
     int16_t *h_stage = nullptr;
     DevBuf<int16_t> d_stage;
@@ -55,6 +66,7 @@ struct ctu_streams {
         for (StreamPush *h : h_desc) ctu_host_free(h);
         for (RowPush *h : h_rdesc) ctu_host_free(h);
         for (int *h : h_heads) ctu_host_free(h);
+        for (int *h : h_replay) ctu_host_free(h);
         ctu_host_free(h_stage);
         for (hipEvent_t v : desc_free)
             if (v) (void)hipEventDestroy(v);
@@ -66,6 +78,9 @@ struct ctu_streams {
 namespace {
 void design_halo(const ctu::Design &d, int *H, int *wmax) { stream_halo(d.post_order, d.post_w, d.post_stack, H, wmax); }
 int64_t stream_rows_of(const ctu_streams *st, int64_t F) { return stream_rows_out(st->g.H, st->g.wmax, F); }
+constexpr uint32_t STREAMS_FLAGS = CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE | CTU_STREAMS_VAD_STATE;
+// a set with detector state on a configuration with the VAD module: the majority filter's delay is the halo (nothing else holds rows there)
+bool streams_vad(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STREAMS_VAD_STATE) && d.o.do_vad(); }
 }  // namespace
 
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
@@ -90,7 +105,7 @@ int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flag
             say("ENGINE: configuration not on the accelerated path: " + why);
             return CTU_ERR_UNSUPPORTED;
         }
-        if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
+        if (flags & ~STREAMS_FLAGS) {
             say("ENGINE: unknown stream set flags");
             return CTU_ERR_INPUT;
         }
@@ -100,6 +115,7 @@ int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flag
         }
         int H = 0, wmax = 0;
         design_halo(d, &H, &wmax);
+        if (streams_vad(d, flags)) stream_vad_halo(d.o.vad_filter_order, &H, &wmax);
         if (halo) *halo = H;
         return CTU_OK;
     } catch (const std::exception &ex) {
@@ -122,6 +138,15 @@ int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int3
     return R;
 }
 
+int64_t ctu_streams_vad_step(int32_t window, int32_t wshift, int32_t filter_order, int64_t total, int64_t *pending) {
+    if (window < 1 || wshift < 1 || wshift > window || total < 0 || filter_order < 1 || filter_order > 31) return CTU_ERR_INPUT;
+    int H = 0, wmax = 0;
+    stream_vad_halo(filter_order, &H, &wmax);
+    const int64_t F = stream_frames(total, window, wshift), R = stream_rows_out(H, wmax, F);
+    if (pending) *pending = F - R;
+    return R;
+}
+
 int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, ctu_streams **out) {
     return ctu_streams_create_ex(e, n_streams, max_push_samples, 0, out);
 }
@@ -129,7 +154,7 @@ int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_sample
 int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out) {
     if (!e || !out) return CTU_ERR_INPUT;
     *out = nullptr;
-    if (flags & ~(uint32_t)(CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE)) {
+    if (flags & ~STREAMS_FLAGS) {
         set_error(e, "ENGINE: unknown stream set flags");
         return CTU_ERR_INPUT;
     }
@@ -142,7 +167,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
-    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || e->do_vad || e->ss || (e->per_wave && e->big)) {
+    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->ss || (e->per_wave && e->big) || (e->do_vad && e->big)) {
         set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
         return CTU_ERR_UNSUPPORTED;
     }
@@ -157,9 +182,14 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
     g.max_wg = fe_max_wg(e);
     g.held = d.post_order > 0 || d.cms;  // (only with CTU_STREAMS_ROW_STATE: refused above without)
     design_halo(d, &g.H, &g.wmax);
+    st->vad = g.vad = streams_vad(d, flags);
+    if (st->vad) {  // (no chain, no CMS beside the detector: refused above) the filter's delay holds the rows back
+        stream_vad_halo(d.o.vad_filter_order, &g.H, &g.wmax);
+        g.held = g.H > 0;
+    }
     g.chained = e->per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
     g.max_chains = g.max_wg * NWAVE;
-    st->C = g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;
+    st->C = st->vad ? g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
     st->consumed.assign((size_t)n_streams, 0);
     st->seen.assign((size_t)n_streams, 0);
     st->hsel.assign((size_t)n_streams, 0);
@@ -192,7 +222,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             if (!st->h_desc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
             st->d_desc[k].alloc((size_t)n_streams);
             HIP_TRY(hipEventCreateWithFlags(&st->desc_free[k], hipEventDisableTiming));
-            if (g.held) {
+            if (g.held || g.vad) {
                 st->h_rdesc[k] = static_cast<RowPush *>(ctu_host_alloc((size_t)n_streams * sizeof(RowPush)));
                 if (!st->h_rdesc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
                 st->d_rdesc[k].alloc((size_t)n_streams);
@@ -208,6 +238,18 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
                 st->h_heads[k] = static_cast<int *>(ctu_host_alloc(n_heads * sizeof(int)));
                 if (!st->h_heads[k]) throw std::runtime_error("page-locked descriptors of a stream set");
                 st->d_heads[k].alloc(n_heads);
+            }
+        }
+        if (st->vad) {
+            const int64_t ro = pl->row_off[pl->n_utt];
+            st->vstate.alloc((size_t)n_streams * VST_DOUBLES);
+            HIP_TRY(hipMemset(st->vstate.p, 0, st->vstate.n * sizeof(double)));  // (never read ahead of a store: a file's first push resets)
+            st->vsink.alloc((size_t)std::max<int64_t>(ro + (int64_t)n_streams * g.H, 1));
+            if (g.held) st->vbase.alloc((size_t)std::max<int64_t>(ro, 1) * d.D);
+            for (int k = 0; k < 2; k++) {
+                st->h_replay[k] = static_cast<int *>(ctu_host_alloc((size_t)n_streams * sizeof(int)));
+                if (!st->h_replay[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_replay[k].alloc((size_t)n_streams);
             }
         }
         if (g.held) {
@@ -267,6 +309,33 @@ void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finish
     }
     HIP_TRY(hipGetLastError());
 }
+// The detector's kernels of a push over the n streams h_rdesc[k] describes and the L.n_replay of them h_replay[k] lists (both uploaded
+// here): the replay from every stream's record, then the rows the majority filter releases with the decisions
+void launch_stream_vad(ctu_streams *st, int k, int n, const PushLayout &L, float *d_rows, uint8_t *d_vad, hipStream_t s) {
+    ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
+    const ctu_plan *pl = st->plan.get();
+    HIP_TRY(hipMemcpyAsync(st->d_rdesc[k].p, st->h_rdesc[k], (size_t)n * sizeof(RowPush), hipMemcpyHostToDevice, s));
+    if (L.n_replay == 0) return;
+    HIP_TRY(hipMemcpyAsync(st->d_replay[k].p, st->h_replay[k], (size_t)L.n_replay * sizeof(int), hipMemcpyHostToDevice, s));
+    StreamVadParams vp;
+    vp.push = st->d_rdesc[k].p; vp.replay = st->d_replay[k].p; vp.n_replay = L.n_replay;
+    vp.cf = pl->vad_cf.p; vp.ci = pl->vad_ci.p; vp.energy = pl->pnr.p;
+    vp.vstate = st->vstate.p; vp.vad = d_vad ? d_vad : st->vsink.p;
+    if (e->vf)
+        lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
+            hipLaunchKernelGGL((stream_vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((unsigned)((L.n_replay + 15) / 16)), dim3(64), 0, s, vp, e->vp);
+        });
+    else hipLaunchKernelGGL(stream_vad_decide_kernel, dim3((unsigned)n), dim3(64), 0, s, vp, e->vp);
+    if (st->g.held && L.most > 0) {
+        RowParams rp;
+        std::memset(&rp, 0, sizeof rp);
+        rp.push = st->d_rdesc[k].p; rp.fresh = st->vbase.p; rp.hist = st->hist.p; rp.rows = d_rows;
+        rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase;
+        hipLaunchKernelGGL(stream_vad_rows_kernel, dim3((unsigned)((L.most + 63) / 64), (unsigned)n), dim3(256), 0, s, rp, d.D);
+    }
+    HIP_TRY(hipGetLastError());
+}
 // The argument checks the device and the host form of a push share (each refuses in its own words)
 bool push_args_ok(const ctu_streams *st, int32_t n, const int32_t *ids, const int64_t *n_samples) { return n >= 0 && n <= st->n_streams && (!n || (ids && n_samples)); }
 bool push_count_ok(const ctu_streams *st, int64_t n_samples) { return n_samples >= 0 && n_samples <= st->max_push; }
@@ -274,6 +343,11 @@ bool push_count_ok(const ctu_streams *st, int64_t n_samples) { return n_samples 
 
 int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
                      float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream) {
+    return ctu_streams_push_vad(st, n, ids, d_pcm, sample_off, n_samples, d_rows, rows_capacity, row_counts, nullptr, stream);
+}
+
+int ctu_streams_push_vad(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
+                         float *d_rows, int64_t rows_capacity, int64_t *row_counts, uint8_t *d_vad, void *stream) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
     const ctu::Design &d = *e->design;
@@ -283,6 +357,7 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         return CTU_ERR_INPUT;
     };
     // ---- everything that can be refused is refused here, ahead of the first launch and of any change to the set
+    if (d_vad && !st->vad) return refuse("push: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
     if (!push_args_ok(st, n, ids, n_samples)) return refuse("push: bad stream count or null argument");
     if (n == 0) return CTU_OK;
     if (++st->push_no == 0) {  // (the counter wrapped: forget the marks)
@@ -311,7 +386,7 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         PushLayout L;
         L.push = st->h_desc[k]; L.rows = st->h_rdesc[k]; L.heads = st->h_heads[k]; L.tail = st->chain_tail.data();
         L.row_counts = row_counts ? row_counts : st->counts.data();  // (the caller's array is output of the call: planned in place)
-        L.consumed = st->next_consumed.data(); L.hsel = st->next_hsel.data();
+        L.consumed = st->next_consumed.data(); L.hsel = st->next_hsel.data(); L.replay = st->h_replay[k];
         if (!stream_plan_push(st->g, st->consumed.data(), st->hsel.data(), n, ids, n_samples, sample_off, L))
             throw std::runtime_error("internal: a push beyond the set's arena");
         // ---- commit: nothing refuses this push any more.  The mirrors take their next values; what follows is HIP calls alone
@@ -337,14 +412,16 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
         HIP_TRY(hipEventRecord(st->ev[1], s));
         HIP_TRY(hipGetLastError());
         int rc = CTU_OK;
-        if (L.tiles) rc = run_chain(e, pl, x, st->arena.p, held ? pl->base_rows.p : d_rows, nullptr, s, !held);
-        if (held && L.tiles && rc == CTU_OK) launch_stream_rows(st, k, n, L.most, false, d_rows, s);
+        float *const base = st->vad ? st->vbase.p : pl->base_rows.p;  // (held) where the front end leaves the push's rows
+        if (L.tiles) rc = run_chain(e, pl, x, st->arena.p, held ? base : d_rows, nullptr, s, !held, !st->vad);
+        if (st->vad && L.tiles && rc == CTU_OK) launch_stream_vad(st, k, n, L, d_rows, d_vad, s);
+        else if (held && L.tiles && rc == CTU_OK) launch_stream_rows(st, k, n, L.most, false, d_rows, s);
         HIP_TRY(hipEventRecord(st->ev[2], s));
         hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
         if (held && st->C > 0 && L.tiles && rc == CTU_OK) {
             RowParams rp;
             std::memset(&rp, 0, sizeof rp);
-            rp.push = st->d_rdesc[k].p; rp.fresh = pl->base_rows.p; rp.hist = st->hist.p;
+            rp.push = st->d_rdesc[k].p; rp.fresh = base; rp.hist = st->hist.p;
             rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase;
             hipLaunchKernelGGL(stream_rows_carry_kernel, dim3((unsigned)n, (unsigned)((st->C * d.Dbase + 255) / 256)), dim3(256), 0, s, rp);
         }
@@ -358,8 +435,17 @@ int ctu_streams_push(ctu_streams *st, int32_t n, const int32_t *ids, const int16
 
 int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples, float *h_rows,
                           int64_t rows_capacity, int64_t *row_counts) {
+    return ctu_streams_push_vad_host(st, n, ids, h_pcm, n_samples, h_rows, rows_capacity, row_counts, nullptr);
+}
+
+int ctu_streams_push_vad_host(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples, float *h_rows,
+                              int64_t rows_capacity, int64_t *row_counts, uint8_t *h_vad) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
+    if (h_vad && !st->vad) {
+        set_error(e, "ENGINE: push: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
+        return CTU_ERR_INPUT;
+    }
     const int D = e->design->D;
     if (!push_args_ok(st, n, ids, n_samples) || (n && !h_pcm)) {
         set_error(e, "ENGINE: push: bad stream count or null argument");
@@ -391,8 +477,8 @@ int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const 
         }
         if (fresh) HIP_TRY(hipMemcpyAsync(st->d_stage.p, st->h_stage, (size_t)fresh * sizeof(int16_t), hipMemcpyHostToDevice, nullptr));
         // the device rows hold any push of the set; what the caller's buffer holds is the device form's check
-        const int rc = ctu_streams_push(st, n, ids, st->d_stage.p, st->offs.data(), n_samples, h_rows ? st->d_rows.p : nullptr, h_rows ? rows_capacity : 0,
-                                        row_counts, nullptr);
+        const int rc = ctu_streams_push_vad(st, n, ids, st->d_stage.p, st->offs.data(), n_samples, h_rows ? st->d_rows.p : nullptr, h_rows ? rows_capacity : 0,
+                                            row_counts, h_vad ? st->vsink.p : nullptr, nullptr);
         if (rc != CTU_OK) return rc;
         const int64_t *counts = row_counts ? row_counts : st->counts.data();  // (where the push planned them)
         int64_t rows = 0;
@@ -400,6 +486,7 @@ int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const 
         if (rows) {  // page-locked rows at the link rate, pageable ones through the runtime's staging (as run_host_ranges downloads)
             if (is_pinned(h_rows)) HIP_TRY(hipMemcpyAsync(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost, nullptr));
             else HIP_TRY(hipMemcpy(h_rows, st->d_rows.p, (size_t)rows * D * 4, hipMemcpyDeviceToHost));
+            if (h_vad) HIP_TRY(hipMemcpyAsync(h_vad, st->vsink.p, (size_t)rows, hipMemcpyDeviceToHost, nullptr));
         }
         HIP_TRY(hipStreamSynchronize(nullptr));
         return CTU_OK;
@@ -407,16 +494,24 @@ int ctu_streams_push_host(ctu_streams *st, int32_t n, const int32_t *ids, const 
 }
 
 int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream) {
+    return ctu_streams_finish_vad(st, id, d_rows, rows_capacity, row_count, nullptr, stream);
+}
+
+int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *d_vad, void *stream) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
     const ctu::Design &d = *e->design;
+    if (d_vad && !st->vad) {
+        set_error(e, "ENGINE: finish: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
+        return CTU_ERR_INPUT;
+    }
     if (id < 0 || id >= st->n_streams) {
         set_error(e, "ENGINE: finish: stream id out of range");
         return CTU_ERR_INPUT;
     }
     if (row_count) *row_count = 0;  // fread() comes up short on a trailing partial window and the file ends there (src/io/in.cc:314,438)
     const int64_t total = st->consumed[(size_t)id];
-    const FinishLayout fin = stream_plan_finish(d.window, d.wshift, st->g.H, st->g.wmax, total, id, st->hsel[(size_t)id]);
+    const FinishLayout fin = stream_plan_finish(d.window, d.wshift, st->g.H, st->g.wmax, total, id, st->hsel[(size_t)id], st->vad);
     const int64_t pending = fin.pending;
     const bool too_short = fin.too_short;
     if (pending > rows_capacity || (pending && !d_rows)) {  // ahead of any launch or change: the stream stays as it was
@@ -432,11 +527,19 @@ int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_
             st->turn ^= 1;
             HIP_TRY(hipEventSynchronize(st->desc_free[k]));
             st->h_rdesc[k][0] = fin.row;
-            launch_stream_rows(st, k, 1, pending, true, d_rows, s);
+            if (st->vad) {  // the filter's flush and the h rows it releases, with the file's length known
+                HIP_TRY(hipMemcpyAsync(st->d_rdesc[k].p, st->h_rdesc[k], sizeof(RowPush), hipMemcpyHostToDevice, s));
+                RowParams rp;
+                std::memset(&rp, 0, sizeof rp);
+                rp.push = st->d_rdesc[k].p; rp.hist = st->hist.p; rp.rows = d_rows;
+                rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase; rp.finishing = 1;
+                hipLaunchKernelGGL(stream_vad_finish_kernel, dim3(1), dim3(256), 0, s, rp, d.D, st->vstate.p, d_vad, d.o.vad_filter_order);
+                HIP_TRY(hipGetLastError());
+            } else launch_stream_rows(st, k, 1, pending, true, d_rows, s);
             HIP_TRY(hipEventRecord(st->desc_free[k], s));
         }
         HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
-        if (st->g.held) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
+        if (st->g.held && !st->vad) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
         return CTU_OK;
     });
     if (rc != CTU_OK) return rc;
@@ -453,8 +556,16 @@ int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_
 }
 
 int ctu_streams_finish_host(ctu_streams *st, int32_t id, float *h_rows, int64_t rows_capacity, int64_t *row_count) {
+    return ctu_streams_finish_vad_host(st, id, h_rows, rows_capacity, row_count, nullptr);
+}
+
+int ctu_streams_finish_vad_host(ctu_streams *st, int32_t id, float *h_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *h_vad) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
+    if (h_vad && !st->vad) {
+        set_error(e, "ENGINE: finish: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
+        return CTU_ERR_INPUT;
+    }
     const int D = e->design->D;
     if (row_count) *row_count = 0;
     const int64_t pending = ctu_streams_pending(st, id);  // (at most max(H, wmax + 1) rows; an id outside the set is ctu_streams_finish's to refuse)
@@ -463,9 +574,10 @@ int ctu_streams_finish_host(ctu_streams *st, int32_t id, float *h_rows, int64_t 
     const int rc = guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         if (pending > 0) rows.alloc((size_t)pending * D);
-        const int rc = ctu_streams_finish(st, id, h_rows ? rows.p : nullptr, h_rows ? rows_capacity : 0, &cnt, nullptr);
+        const int rc = ctu_streams_finish_vad(st, id, h_rows ? rows.p : nullptr, h_rows ? rows_capacity : 0, &cnt, h_vad ? st->vsink.p : nullptr, nullptr);
         if (rc != CTU_OK) return rc;
         if (cnt) HIP_TRY(hipMemcpy(h_rows, rows.p, (size_t)cnt * D * 4, hipMemcpyDeviceToHost));
+        if (cnt && h_vad) HIP_TRY(hipMemcpy(h_vad, st->vsink.p, (size_t)cnt, hipMemcpyDeviceToHost));
         HIP_TRY(hipStreamSynchronize(nullptr));
         return CTU_OK;
     });

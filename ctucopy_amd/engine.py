@@ -14,6 +14,7 @@ from . import build as _build
 CTU_OK, CTU_ERR_OPTS, CTU_ERR_UNSUPPORTED, CTU_ERR_DEVICE, CTU_ERR_INPUT = 0, -1, -2, -3, -4
 STREAMS_ROW_STATE = 1  # CTU_STREAMS_ROW_STATE
 STREAMS_NR_STATE = 4   # CTU_STREAMS_NR_STATE
+STREAMS_VAD_STATE = 8  # CTU_STREAMS_VAD_STATE
 
 
 class CtuError(RuntimeError):
@@ -40,7 +41,8 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_engine_run_signal_host", "ctu_rows_arena_layout", "ctu_engine_run_rows", "ctu_engine_run_rows_host",
            "ctu_streams_create", "ctu_streams_destroy", "ctu_streams_config_check", "ctu_streams_push", "ctu_streams_push_host",
            "ctu_streams_finish", "ctu_streams_frames", "ctu_streams_step", "ctu_streams_last_push_ms",
-           "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step"]
+           "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step",
+           "ctu_streams_push_vad", "ctu_streams_push_vad_host", "ctu_streams_finish_vad", "ctu_streams_finish_vad_host", "ctu_streams_vad_step"]
 
 _lib = None
 
@@ -134,6 +136,13 @@ def load_library():
         L.ctu_streams_finish_host.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64)]
         L.ctu_streams_rows_step.restype = i64
         L.ctu_streams_rows_step.argtypes = [i32, i32, i32, i32, i64, ctypes.POINTER(i64)]
+    if hasattr(L, "ctu_streams_vad_step"):  # (likewise: stream sets with detector state)
+        L.ctu_streams_push_vad.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]
+        L.ctu_streams_push_vad_host.argtypes = [vp, i32, vp, vp, vp, vp, i64, vp, vp]
+        L.ctu_streams_finish_vad.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64), vp, vp]
+        L.ctu_streams_finish_vad_host.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64), vp]
+        L.ctu_streams_vad_step.restype = i64
+        L.ctu_streams_vad_step.argtypes = [i32, i32, i32, i64, ctypes.POINTER(i64)]
     _lib = L
     return L
 
@@ -181,19 +190,23 @@ def config_table(args, name):
     return out
 
 
-def streams_config_check(args, row_state=False, nr_state=False):
+def _stream_flags(row_state, nr_state, vad_state):
+    return (STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0) | (STREAMS_VAD_STATE if vad_state else 0)
+
+
+def streams_config_check(args, row_state=False, nr_state=False, vad_state=False):
     """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
     CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give.  With row_state (a set that
     may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo).  With nr_state the set keeps the noise
-    estimate of -nr_mode exten too."""
+    estimate of -nr_mode exten too, with vad_state the VAD module's detector state."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
-    if not row_state and not nr_state:
+    if not row_state and not nr_state and not vad_state:
         rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
         return int(rc), buf.value.decode()
     halo = ctypes.c_int32(0)
-    flags = (STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0)
+    flags = _stream_flags(row_state, nr_state, vad_state)
     rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
     return (int(rc), buf.value.decode(), int(halo.value)) if row_state else (int(rc), buf.value.decode())
 
@@ -217,17 +230,29 @@ def streams_rows_step(window, wshift, halo, wmax, total):
     return int(r), int(pending.value)
 
 
+def streams_vad_step(window, wshift, filter_order, total):
+    """(rows and decisions delivered, frames held back) of a stream with detector state after `total` samples, for a majority filter
+    of order `filter_order` (ctu_streams_vad_step)."""
+    pending = ctypes.c_int64(0)
+    r = load_library().ctu_streams_vad_step(int(window), int(wshift), int(filter_order), int(total), ctypes.byref(pending))
+    if r < 0:
+        raise CtuError(int(r), "ctu_streams_vad_step: bad argument")
+    return int(r), int(pending.value)
+
+
 class Streams:
     """A set of `n` streams on an engine (Engine.streams): PCM in per stream as it arrives, the rows of the frames it completes out.
     With row_state the set takes delta chains, stacking and CMS too, and may deliver a frame's row with a later push or with finish.
-    With nr_state it takes -nr_mode exten (on the spectrum, 256- and 512-point front end): the noise estimate is kept per stream."""
+    With nr_state it takes -nr_mode exten (on the spectrum, 256- and 512-point front end): the noise estimate is kept per stream.
+    With vad_state it takes the VAD module (energy and Burg-cepstral criteria): the detector's state is kept per stream, and a frame's
+    row leaves with its decision, (vad_filter_order - 1) / 2 frames late."""
 
-    def __init__(self, engine, n, max_push, row_state=False, nr_state=False):
+    def __init__(self, engine, n, max_push, row_state=False, nr_state=False, vad_state=False):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        if row_state or nr_state:
-            flags = (STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0)
+        if row_state or nr_state or vad_state:
+            flags = _stream_flags(row_state, nr_state, vad_state)
             rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))
         else:
             rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
@@ -247,8 +272,9 @@ class Streams:
 
     __del__ = close
 
-    def push(self, chunks):
-        """{stream id: int16 array} -> {stream id: float32 [rows, D]}: the frames the new samples complete (host buffers)."""
+    def push(self, chunks, want_vad=False):
+        """{stream id: int16 array} -> {stream id: float32 [rows, D]}: the frames the new samples complete (host buffers).
+        With want_vad (a set with detector state): {stream id: (rows, uint8 [rows] decisions '0' / '1')}."""
         ids = np.array(list(chunks.keys()), dtype=np.int32)
         arrs = [np.ascontiguousarray(chunks[k], dtype=np.int16).reshape(-1) for k in chunks]
         ns = np.array([a.size for a in arrs], dtype=np.int64)
@@ -259,17 +285,23 @@ class Streams:
         cap = int(sum(int(a) // sh + 1 + self.pending(int(k)) for k, a in zip(ids, ns) if 0 <= k < self.n))
         rows = np.empty((cap, D), dtype=np.float32)
         counts = np.zeros(max(len(arrs), 1), dtype=np.int64)
-        rc = load_library().ctu_streams_push_host(self._h, len(arrs), ids.ctypes.data, ptrs, ns.ctypes.data, rows.ctypes.data, cap, counts.ctypes.data)
+        if want_vad:
+            vad = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = load_library().ctu_streams_push_vad_host(self._h, len(arrs), ids.ctypes.data, ptrs, ns.ctypes.data, rows.ctypes.data, cap, counts.ctypes.data,
+                                                          vad.ctypes.data)
+        else:
+            rc = load_library().ctu_streams_push_host(self._h, len(arrs), ids.ctypes.data, ptrs, ns.ctypes.data, rows.ctypes.data, cap, counts.ctypes.data)
         self.engine._check(rc)
         out, at = {}, 0
         for k, c in zip(chunks, counts):
-            out[k] = rows[at:at + int(c)]
+            out[k] = (rows[at:at + int(c)], vad[at:at + int(c)]) if want_vad else rows[at:at + int(c)]
             at += int(c)
         return out
 
-    def push_device(self, ids, pcm, sample_off, n_samples, rows, stream=None):
+    def push_device(self, ids, pcm, sample_off, n_samples, rows, stream=None, vad=None):
         """Device form: pcm a torch int16 CUDA tensor holding stream ids[i]'s n_samples[i] new samples at sample_off[i]; rows a float32
-        CUDA tensor [capacity, D].  Returns the row counts per stream (numpy int64); asynchronous on `stream`."""
+        CUDA tensor [capacity, D]; vad (a set with detector state) a uint8 CUDA tensor [capacity] for the rows' decisions.  Returns the
+        row counts per stream (numpy int64); asynchronous on `stream`."""
         import torch
         assert pcm.is_cuda and pcm.dtype == torch.int16 and rows.is_cuda and rows.dtype == torch.float32
         ids = np.ascontiguousarray(ids, dtype=np.int32)
@@ -279,16 +311,26 @@ class Streams:
         counts = np.zeros(max(ids.size, 1), dtype=np.int64)
         s = stream if stream is not None else torch.cuda.current_stream(pcm.device)
         cap = rows.numel() // self.engine.dims.row_floats
+        if vad is not None:
+            assert vad.is_cuda and vad.dtype == torch.uint8 and vad.numel() >= cap
+            self.engine._check(load_library().ctu_streams_push_vad(self._h, int(ids.size), ids.ctypes.data, pcm.data_ptr(), off.ctypes.data, ns.ctypes.data,
+                                                                   rows.data_ptr(), cap, counts.ctypes.data, vad.data_ptr(), s.cuda_stream))
+            return counts[:ids.size]
         self.engine._check(load_library().ctu_streams_push(self._h, int(ids.size), ids.ctypes.data, pcm.data_ptr(), off.ctypes.data, ns.ctypes.data,
                                                            rows.data_ptr(), cap, counts.ctypes.data, s.cuda_stream))
         return counts[:ids.size]
 
-    def finish(self, sid):
-        """Ends stream `sid`'s file: its remaining rows - the ones a set with row state held back, else [0, D]: the reference makes no
-        frame of a trailing partial window; the stream then starts a new file."""
+    def finish(self, sid, want_vad=False):
+        """Ends stream `sid`'s file: its remaining rows - the ones a set with row or detector state held back, else [0, D]: the reference
+        makes no frame of a trailing partial window; the stream then starts a new file.  With want_vad: (rows, their decisions)."""
         cnt = ctypes.c_int64(0)
         cap = max(self.pending(sid), 0)
         rows = np.empty((cap, self.engine.dims.row_floats), dtype=np.float32)
+        if want_vad:
+            vad = np.zeros(max(cap, 1), dtype=np.uint8)
+            self.engine._check(load_library().ctu_streams_finish_vad_host(self._h, int(sid), rows.ctypes.data if cap else None, cap, ctypes.byref(cnt),
+                                                                          vad.ctypes.data))
+            return rows[:int(cnt.value)], vad[:int(cnt.value)]
         self.engine._check(load_library().ctu_streams_finish_host(self._h, int(sid), rows.ctypes.data if cap else None, cap, ctypes.byref(cnt)))
         return rows[:int(cnt.value)]
 
@@ -386,9 +428,9 @@ class Engine:
     def plan(self, nsamples):
         return Plan(self, nsamples)
 
-    def streams(self, n, max_push, row_state=False, nr_state=False):
+    def streams(self, n, max_push, row_state=False, nr_state=False, vad_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
-        return Streams(self, n, max_push, row_state, nr_state)
+        return Streams(self, n, max_push, row_state, nr_state, vad_state)
 
     def _check(self, rc):
         if rc != CTU_OK:

@@ -195,9 +195,27 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * kinds, and with row state the delta chains, stacking and CMS behind them.  Exten is causal - frame t reads frames 0 .. t - so a row
  * still goes out with the push that completes its frame, R(F) is unchanged and ctu_streams_finish has nothing to add; a stream's next
  * file starts from the reference's initial estimate.  Still refused, by name, whatever the flags: -nr_when afterFB, exten on 1024 ..
- * 4096 points, hwss / fwss / 2fwss, the VAD module, -remove_dc1, trapdct, CMVN, speech output, HTK feature input.  On a chain
- * without -nr_mode exten the flag changes nothing. */
-enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4 };   /* (2 is no flag: sets refuse it as unknown, and callers may rely on that) */
+ * 4096 points, hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct, CMVN, speech output, HTK feature
+ * input.  On a chain without -nr_mode exten the flag changes nothing.
+ *
+ * Detector state (CTU_STREAMS_VAD_STATE; combines with the other two): the set also keeps, per stream, the state of the VAD module's
+ * sequential part - the threshold recurrences, the background cepstrum, the majority filter's ring (src/vad/vad.cc:220-625,
+ * src/vad/vad.h:126-175) - and so takes the VAD module on the 256- and 512-point front end, FFT sizes below 256 included: the energy
+ * criterion and the Burg-cepstral one (-vad_cepdist_mode lpc), all four threshold modes, filter orders 1 .. 31, -vad_apply_mode none
+ * (or silence, which is none on the feature path); with CTU_STREAMS_NR_STATE as well, -nr_mode exten ahead of the fused detector (25 ms
+ * frames at 8 or 16 kHz, 14 coefficients: C4).  A frame's row and its decision leave together, as the reference's writer releases a
+ * row when the majority filter releases its decision: with h = (vad_filter_order - 1) / 2, after F frames a stream has delivered
+ * R(F) = F - h rows and decisions if F > h, else none (a file of no more than h frames writes nothing in the reference), and holds
+ * F - R(F) back; ctu_streams_finish pushes h zeros through the filter and delivers the last min(F, h) of both - nothing, with CTU_OK,
+ * for a file of 1 .. h frames.  The decisions are those of ctu_engine_run on the whole file, byte for byte, however it is cut into
+ * pushes; every file of a stream is treated as the first file of a process (the rule above for the majority filter's ring: in phase).
+ * The calls that deliver decisions are the *_vad forms below: d_vad / h_vad holds rows_capacity bytes, byte i is the decision of row
+ * i of the same call ('0' / '1', as ctu_engine_run writes them); ctu_streams_push and ctu_streams_finish work on such a set and
+ * deliver the rows only.  On a set without detector state a non-NULL vad buffer is CTU_ERR_INPUT before anything changes.  Refused by
+ * name whatever the flags: -vad_apply_mode drop, -vad_cepdist_mode fea, the VAD module with -fea_delta / -fea_trap / -fea_Z_exp /
+ * -fea_Z_block, -fea_E where the offline run shifts the energy column (filter orders above 2), the VAD on 1024-point and larger
+ * frames, -nr_mode exten with a criterion outside the fused shapes.  On a configuration without the VAD module the flag changes nothing. */
+enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8 };   /* (2 is no flag: sets refuse it as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
@@ -219,6 +237,14 @@ int ctu_streams_push_host(ctu_streams *, int32_t n, const int32_t *stream_ids, c
 int ctu_streams_finish(ctu_streams *, int32_t stream_id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream);
 /* Host-buffer form of the above.  Synchronised on return. */
 int ctu_streams_finish_host(ctu_streams *, int32_t stream_id, float *h_rows, int64_t rows_capacity, int64_t *row_count);
+/* The same four calls with the decisions of the rows they deliver (detector state): byte i of d_vad / h_vad belongs to row i of the call.
+ * A NULL vad buffer makes them the calls above. */
+int ctu_streams_push_vad(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *d_pcm, const int64_t *sample_off,
+                         const int64_t *n_samples, float *d_rows, int64_t rows_capacity, int64_t *row_counts, uint8_t *d_vad, void *stream);
+int ctu_streams_push_vad_host(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *const *h_pcm, const int64_t *n_samples,
+                              float *h_rows, int64_t rows_capacity, int64_t *row_counts, uint8_t *h_vad);
+int ctu_streams_finish_vad(ctu_streams *, int32_t stream_id, float *d_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *d_vad, void *stream);
+int ctu_streams_finish_vad_host(ctu_streams *, int32_t stream_id, float *h_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *h_vad);
 /* Rows the stream's current file has produced so far. */
 int64_t ctu_streams_frames(const ctu_streams *, int32_t stream_id);
 /* Rows a finish would deliver now: the frames of the current file whose rows are held back (0 without row state). */
@@ -229,8 +255,10 @@ int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t 
 /* The same for the rows (pure): R(F) of a file after `total` samples for a chain of halo H >= wmax >= 0 (0, 0: no chain), and in
  * *pending (may be NULL) F - R(F). */
 int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending);
+/* The same for a set with detector state (pure): R(F) for the majority filter of order filter_order (1 .. 31), F - R(F) in *pending. */
+int64_t ctu_streams_vad_step(int32_t window, int32_t wshift, int32_t filter_order, int64_t total, int64_t *pending);
 /* Times of the last push on the set, measured with HIP events on its stream: ms3[0] stream_stitch_kernel, ms3[1] the front end
- * and its tails (with row state: and the row kernels behind them), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel).  Blocks until that push has finished. */
+ * and its tails (with row state: and the row kernels behind them; with detector state: and the replay), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel).  Blocks until that push has finished. */
 int ctu_streams_last_push_ms(ctu_streams *, float *ms3);
 
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53

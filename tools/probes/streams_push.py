@@ -9,8 +9,11 @@ same run: its front-end span includes the streamed delta and CMS kernels, its ca
 With --nr-state the same again for C4 without its VAD (MFCC-13 at 8 kHz behind -nr_mode exten -nr_a 2) on a set with noise state: its
 front end walks chains of whole streams, a wave each, and loads and stores the noise estimate at the edges of the push; the offline run
 beside it is ten-frame files, each of which starts from the initial estimate.
+With --vad-state the same again for C4 itself (exten and the fused Burg-cepstral VAD, adapt threshold) on a set with noise and detector
+state: its front-end span has the fused detector's lattices, vad_a2c_kernel, the replay from the detector's state and the delayed
+row copy in it, its carry span the history of the held rows; decisions are delivered with the rows.
 
-    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3] [--row-state] [--nr-state]
+    python tools/probes/streams_push.py [--out profiles/streams_push_times.txt] [--pushes 8] [--warmup 3] [--row-state] [--nr-state] [--vad-state]
 """
 import argparse
 import os
@@ -23,15 +26,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 from ctucopy_amd import Engine  # noqa: E402
-from tests.util import C2, C4_NOVAD, synth_utt  # noqa: E402
+from tests.util import C2, C4, C4_NOVAD, synth_utt  # noqa: E402
 
 
 CHAIN = ["-fea_delta", "d_a", "-fea_Z_exp", "500"]
 
 
-def measure(n, pushes, warmup, chain=False, nr=False):
+def measure(n, pushes, warmup, chain=False, nr=False, vad=False):
     import torch
-    eng = Engine(C4_NOVAD if nr else C2 + (CHAIN if chain else []))
+    eng = Engine(C4 if vad else C4_NOVAD if nr else C2 + (CHAIN if chain else []))
     w, s, D = eng.dims.window, eng.dims.wshift, eng.dims.row_floats
     hop = 10 * s
     total = w - s + hop * (warmup + pushes)
@@ -39,18 +42,20 @@ def measure(n, pushes, warmup, chain=False, nr=False):
     pcm = torch.from_numpy(np.tile(x, n)).cuda()
     ids = np.arange(n, dtype=np.int32)
     base = np.arange(n, dtype=np.int64) * total
-    st = eng.streams(n, hop, row_state=chain, nr_state=nr)
+    st = eng.streams(n, hop, row_state=chain, nr_state=nr or vad, vad_state=vad)
     rows = torch.empty((n * 11, D), dtype=torch.float32, device="cuda")
-    cnt = st.push_device(ids, pcm, base, np.full(n, w - s), rows)   # the samples ahead of the first hop: no frame yet
+    dec = torch.empty(n * 11, dtype=torch.uint8, device="cuda") if vad else None
+    cnt = st.push_device(ids, pcm, base, np.full(n, w - s), rows, vad=dec)   # the samples ahead of the first hop: no frame yet
     assert int(cnt.sum()) == 0
     spans, wall = [], []
     for k in range(warmup + pushes):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        cnt = st.push_device(ids, pcm, base + (w - s) + k * hop, np.full(n, hop), rows)
+        cnt = st.push_device(ids, pcm, base + (w - s) + k * hop, np.full(n, hop), rows, vad=dec)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        assert int(cnt.min()) == int(cnt.max()) == (6 if chain and k == 0 else 10)   # (the first ten frames of a d_a file give six rows)
+        # (the first ten frames of a d_a file give six rows, of a file behind the VAD's majority filter of order 3 nine)
+        assert int(cnt.min()) == int(cnt.max()) == ((6 if chain else 9 if vad else 10) if k == 0 else 10)
         if k >= warmup:
             spans.append(st.last_push_ms())
             wall.append(t1 - t0)
@@ -61,11 +66,12 @@ def measure(n, pushes, warmup, chain=False, nr=False):
     plan = eng.plan([len(u) for u in utts])
     arena = torch.from_numpy(plan.pack(utts)).cuda()
     out = torch.empty((plan.total_frames, D), dtype=torch.float32, device="cuda")
+    out_vad = torch.empty(max(plan.total_frames, 1), dtype=torch.uint8, device="cuda") if vad else None
     off_wall, off_kernel = [], []
     for k in range(warmup + pushes):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        eng.run_device(plan, arena, rows=out)
+        eng.run_device(plan, arena, rows=out, vad=out_vad)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if k >= warmup:
@@ -82,11 +88,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--row-state", action="store_true", help="also MFCC_0_D_A with exponential CMS on a set with row state")
     ap.add_argument("--nr-state", action="store_true", help="also C4 without its VAD (-nr_mode exten) on a set with noise state")
+    ap.add_argument("--vad-state", action="store_true", help="also C4 (exten and the fused Burg-cepstral VAD) on a set with noise and detector state")
     a = ap.parse_args()
     lines = ["# tools/probes/streams_push.py: MFCC-13, 16 kHz, pushes of 10 hops per stream, device-resident; medians of %d pushes after %d" % (a.pushes, a.warmup),
              "# spans from HIP events on the push's stream; rates from the host's clock around synchronised calls (launch overhead included)",
              "# streams  stitch_ms  frontend_ms  carry_ms  push_frames_per_s  offline_frontend_ms  offline_frames_per_s"]
-    for chain, nr in [(False, False)] + ([(True, False)] if a.row_state else []) + ([(False, True)] if a.nr_state else []):
+    for chain, nr, vad in [(False, False, False)] + ([(True, False, False)] if a.row_state else []) + ([(False, True, False)] if a.nr_state else []) + \
+            ([(False, False, True)] if a.vad_state else []):
+        if vad:
+            lines.append("# " + " ".join(C4) + " on a set with noise and detector state (frontend_ms: with the fused detector, vad_a2c_kernel, the replay"
+                         " from the detector's state and the delayed row copy; carry_ms: with the history of the held rows; the offline run is files of ten"
+                         " frames with vad_lanes_kernel behind the front end, outside offline_frontend_ms)")
         if nr:
             lines.append("# " + " ".join(C4_NOVAD) + " on a set with noise state (frontend_ms: chains of whole streams, a wave each, the noise estimate loaded"
                          " and stored at the edges of the push; the offline run is files of ten frames, each from the initial estimate)")
@@ -94,7 +106,7 @@ def main():
             lines.append("# the same with " + " ".join(CHAIN) + " on a set with row state (frontend_ms: with the streamed delta and CMS kernels; carry_ms: with"
                          " the base-row history; offline_frontend_ms is the front end alone, the offline rate has post_kernel and cms_exp_kernel in it)")
         for n in (1000, 10000):
-            med, pr, ok, orate = measure(n, a.pushes, a.warmup, chain, nr)
+            med, pr, ok, orate = measure(n, a.pushes, a.warmup, chain, nr, vad)
             lines.append("%7d  %.4f  %.4f  %.4f  %.3e  %.4f  %.3e" % (n, med[0], med[1], med[2], pr, ok, orate))
     text = "\n".join(lines) + "\n"
     print(text, end="")
