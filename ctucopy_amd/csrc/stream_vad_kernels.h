@@ -8,7 +8,7 @@
 // the state frames 0 .. t - 1 left.  So the replay of a push starts from the state the stream's last push stored and stores it again
 // behind its last frame.  Every branch of the recurrences that names a frame (t == 0, t == 1, perc_init, adapt_init, dyn_init, cep_init,
 // the filter's t >= h) takes the ABSOLUTE frame index t = F0 + i, with F0 the host's mirror of the file's frames ahead of the push
-// (RowPush::F0), never the index within the push.  A file's first push (F0 == 0) starts from vad_run_reset and loads nothing, so neither
+// (RowPush::F0), never the index within the push.  A file's first push (F0 == 0) starts from the zero state and loads nothing, so neither
 // create nor finish clears device state.
 //
 // The majority filter releases a decision h = (filter_order - 1) / 2 frames late and the reference's writer releases the row with it
@@ -17,14 +17,15 @@
 // (byte k of a push belongs to row k of the same push: out0 serves both), the two histories per stream keep the last h base rows, and
 // stream_rows_carry_kernel moves them.  Nothing counts on the device: where a byte goes is r0 = R(F0) of the host.
 //
-//   stream_vad_lanes_kernel<NCL, THR>  the fused criterion's replay (vad_lanes_kernel's step): 16 pushed streams per wave, four lanes each
+//   stream_vad_lanes_kernel<NCL, THR>  the fused criterion's replay (vad_quad_step, which vad_lanes_kernel calls too): 16 pushed streams per
+//                                      wave, four lanes each
 //   stream_vad_decide_kernel           the energy and the non-fused Burg criterion: VadRun + vad_frame as they stand, a wave per pushed
 //                                      stream.  Coverage, not a tuned path: 64 lanes do one stream's scalar work
 //   stream_vad_rows_kernel             rows r0 .. r0 + nr - 1 of every pushed stream, copied h frames late (stream_base_row's two sources)
 //   stream_vad_finish_kernel           the end of a file: vad_flush's zeros through the filter, the last min(F, h) bytes and rows
 //
 // State (vstate): one record of VST_DOUBLES doubles per stream, 384 bytes, 128-byte aligned when the array is:
-//   [0..6]   crimin, crimax, crimean, crimean2, crivar, dmin, dmax          (VadRun's seven doubles)
+//   [0..6]   crimin, crimax, crimean, crimean2, crivar, dmin, dmax          (VadThr's seven doubles)
 //   [7]      hist: the majority filter's ring of raw decisions, bit k = slot k   (64 bits, stored as they stand)
 //   [8]      adapt_vad (low word) | hidx (high word)
 //   [9]      nsum (low word) | spare.  VadRun::nout, the fourth int, is not kept: it is R(F0), which the host mirrors
@@ -34,12 +35,14 @@
 // wave-uniform address and written by lane 0.  A quad of stream_vad_lanes_kernel keeps coefficients 4 pq .. 4 pq + 3 in lane pq: two
 // 16-byte accesses per lane, 128 contiguous bytes per stream; the header is read by all four lanes (one address per quad) and written
 // by lane pq == 0.  Doubles and bit patterns travel as they stand: a store and load is exact, so a file's decisions do not depend on
-// how it was cut into pushes.
+// how it was cut into pushes.  vst_unpack / vst_pack alone know the header's slots; the kernels move its ten doubles.
 // House rules of the stream kernels: nothing is read back, no atomics (a stream id appears once in a push), plain vector stores.
 //
-// gfx950, hipcc -O3: stream_vad_lanes_kernel<14, THR> 70 / 74 / 72 / 74 VGPRs and 40 / 42 / 44 / 52 SGPRs for THR 0 .. 3;
-// stream_vad_decide_kernel 75 VGPRs, 99 SGPRs, 16 KB of LDS; stream_vad_rows_kernel 20 VGPRs, 33 SGPRs; stream_vad_finish_kernel 24 VGPRs,
-// 43 SGPRs; no spills, no scratch.
+// gfx950, hipcc -O3, for THR 0 .. 3 (in brackets: with the step restated here, before it was shared with vad_lanes_kernel):
+// stream_vad_lanes_kernel<14, THR> 72 / 74 / 74 / 80 VGPRs (70 / 74 / 72 / 74), 40 / 40 / 44 / 52 SGPRs (40 / 42 / 44 / 52), 340 / 373 / 385 /
+// 422 instructions (358 / 376 / 390 / 442); stream_vad_decide_kernel 78 VGPRs (75), 99 SGPRs, 875 instructions (730: the replay loop now comes
+// in two versions, with and without the energy criterion), 16 KB of LDS; stream_vad_rows_kernel 20 VGPRs, 33 SGPRs; stream_vad_finish_kernel
+// 24 VGPRs, 43 SGPRs, 161 instructions (the same); no spills, no scratch.  Times against the restated step: profiles/vad_step_ab.txt.
 #pragma once
 
 namespace {
@@ -57,93 +60,25 @@ struct StreamVadParams {
     uint8_t *vad;          // decision bytes of the push
 };
 
-__device__ __forceinline__ double vst_bits(unsigned lo, unsigned hi) { return __hiloint2double((int)hi, (int)lo); }
-
-// The detector's state of one stream in a quad of lanes (vad_lanes_kernel keeps the same in plain registers)
-struct LanesRun {
-    double crimin, crimax, crimean, crimean2, crivar, dmin, dmax;
-    double c0[4];  // coefficients 4 pq .. 4 pq + 3 of the background cepstrum
-    int adapt_vad, hidx, nsum;
-    unsigned long long hist;
-};
-
-// Frame t of a file on the fused criterion: vad_lanes_kernel's step, statement for statement (quad summation order included), with
-// the state in `r`.  Returns the raw decision.  Every lane of the quad runs it on the same values.
-template <int NCL, int THR>
-__device__ __forceinline__ int stream_vad_lanes_step(LanesRun &r, const VadParams &vp, const int t, const double (&ci)[4], const int pq) {
-    double cri;
-    if (t == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) r.c0[i] = ci[i];
-        cri = 0.0;
-    } else {
-        if (t == 1) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) r.c0[i] = (r.c0[i] + ci[i]) / 2.0;
-        }
-        double sum = 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int k = 4 * pq + i;
-            const double dl = (CTU_VF_A2C || (k >= 1 && k < NCL)) ? ci[i] - r.c0[i] : 0.0;
-            sum += dl * dl;
-        }
-        sum += dpp_mov<0xB1>(sum);  // quad_perm [1,0,3,2]
-        sum += dpp_mov<0x4E>(sum);  // quad_perm [2,3,0,1]
-        cri = 4.3429 * sqrt(2 * sum);
-    }
-    int vad0;
-    if (THR == 0) vad0 = cri >= vp.abs_thr;
-    else if (THR == 1) {
-        if (t == 0 || (double)t < (double)vp.perc_init) r.crimin = r.crimax = cri;
-        else {
-            r.crimin = cri < r.crimin ? cri : r.crimin;
-            r.crimax = cri > r.crimax ? cri : r.crimax;
-        }
-        vad0 = cri >= r.crimin + (vp.perc_thr / 100.0) * (r.crimax - r.crimin);
-    } else if (THR == 2) {
-        if (t == 0) {
-            r.crimean = cri;
-            r.crimean2 = cri * cri;
-            r.crivar = 0.0;
-            r.adapt_vad = 0;
-        } else {
-            const double thr = r.crimean + vp.adapt_za * sqrt(r.crivar);
-            if (cri < thr || t <= vp.adapt_init) {
-                r.crimean = vp.adapt_q * r.crimean + (1.0 - vp.adapt_q) * cri;
-                r.crimean2 = vp.adapt_q * r.crimean2 + (1.0 - vp.adapt_q) * cri * cri;
-                r.crivar = r.crimean2 - r.crimean * r.crimean;
-                r.adapt_vad = 0;
-            } else r.adapt_vad = 1;
-        }
-        vad0 = r.adapt_vad;
-    } else {
-        const int init = vp.dyn_init > 1 ? vp.dyn_init : 1;
-        if (t < init) {
-            r.dmax = r.dmin = cri;
-            vad0 = 0;
-        } else if (t == init) {
-            r.dmax = (cri > r.dmax ? cri : r.dmax) + vp.dyn_min / 10.0;
-            r.dmin = (cri < r.dmin ? cri : r.dmin) - vp.dyn_min / 10.0;
-            vad0 = 0;
-        } else {
-            r.dmax = r.dmax < cri ? vp.qmaxinc * r.dmax + (1.0 - vp.qmaxinc) * cri : vp.qmaxdec * r.dmax + (1.0 - vp.qmaxdec) * cri;
-            r.dmin = r.dmin > cri ? vp.qmindec * r.dmin + (1.0 - vp.qmindec) * cri : vp.qmininc * r.dmin + (1.0 - vp.qmininc) * cri;
-            const double dyn = r.dmax - r.dmin;
-            vad0 = (cri > r.dmin + (vp.dyn_perc / 100.0) * dyn) && (dyn > vp.dyn_min);
-        }
-    }
-    if (!(vad0 && t > vp.cep_init)) {  // background update (src/vad/vad.cc:288-294)
-#pragma unroll
-        for (int i = 0; i < 4; i++) r.c0[i] = vp.cep_p * r.c0[i] + (1.0 - vp.cep_p) * ci[i];
-    }
-    return vad0;
+// The scalar header of a record, slots [0 .. VST_HEADER) as the table above has them, to and from registers: the kernels move `hd`
+// between registers and memory with the access width of their lanes.
+constexpr int VST_HEADER = 10;
+__device__ __forceinline__ void vst_unpack(VadThr &s, VadFilter &f, const double (&hd)[VST_HEADER]) {
+    s.crimin = hd[0]; s.crimax = hd[1]; s.crimean = hd[2]; s.crimean2 = hd[3]; s.crivar = hd[4]; s.dmin = hd[5]; s.dmax = hd[6];
+    f.hist = (unsigned long long)__double_as_longlong(hd[7]);
+    s.adapt_vad = __double2loint(hd[8]); f.hidx = __double2hiint(hd[8]);
+    f.nsum = __double2loint(hd[9]);
+}
+__device__ __forceinline__ void vst_pack(const VadThr &s, const VadFilter &f, double (&hd)[VST_HEADER]) {
+    hd[0] = s.crimin; hd[1] = s.crimax; hd[2] = s.crimean; hd[3] = s.crimean2; hd[4] = s.crivar; hd[5] = s.dmin; hd[6] = s.dmax;
+    hd[7] = __longlong_as_double((long long)f.hist);
+    hd[8] = __hiloint2double(f.hidx, s.adapt_vad);
+    hd[9] = __hiloint2double(0, f.nsum);
 }
 
 // grid ceil(n_replay / 16), 64 lanes: quad q of wave w is the stream at position replay[16 w + q] of the push
 template <int NCL, int THR>
 __global__ __launch_bounds__(64) void stream_vad_lanes_kernel(const StreamVadParams p, const VadParams vp) {
-    static_assert(NCL <= 16, "four lanes x four coefficients");
     const int lane = threadIdx.x, pq = lane & 3;
     const int gidx = blockIdx.x * 16 + (lane >> 2);
     const bool live = gidx < p.n_replay;
@@ -156,20 +91,17 @@ __global__ __launch_bounds__(64) void stream_vad_lanes_kernel(const StreamVadPar
 #pragma unroll
     for (int off = 32; off >= 4; off >>= 1) Tmax = max(Tmax, __shfl_xor(Tmax, off, 64));
     const int order_f = vp.filter_order, h = (order_f - 1) / 2;
-    LanesRun r;
-    r.crimin = r.crimax = r.crimean = r.crimean2 = r.crivar = r.dmin = r.dmax = 0.0;
-    r.c0[0] = r.c0[1] = r.c0[2] = r.c0[3] = 0.0;
-    r.adapt_vad = r.hidx = r.nsum = 0;
-    r.hist = 0;
+    VadQuad r = {};
     double *vs = p.vstate + (size_t)d.id * VST_DOUBLES;
+    double2 *h2 = reinterpret_cast<double2 *>(vs), *c2 = reinterpret_cast<double2 *>(vs + VST_C0 + 4 * pq);
     if (live && d.F0 > 0) {  // the file goes on: where the stream's last push left off
-        const double2 *h2 = reinterpret_cast<const double2 *>(vs);
-        const double2 a = h2[0], b = h2[1], c = h2[2], e = h2[3], f = h2[4];
-        r.crimin = a.x; r.crimax = a.y; r.crimean = b.x; r.crimean2 = b.y; r.crivar = c.x; r.dmin = c.y; r.dmax = e.x;
-        r.hist = (unsigned long long)__double_as_longlong(e.y);
-        r.adapt_vad = __double2loint(f.x); r.hidx = __double2hiint(f.x);
-        r.nsum = __double2loint(f.y);
-        const double2 *c2 = reinterpret_cast<const double2 *>(vs + VST_C0 + 4 * pq);
+        double hd[VST_HEADER];
+#pragma unroll
+        for (int k = 0; k < VST_HEADER / 2; k++) {
+            const double2 v = h2[k];
+            hd[2 * k] = v.x; hd[2 * k + 1] = v.y;
+        }
+        vst_unpack(r.thr, r.f, hd);
         const double2 u = c2[0], v = c2[1];
         r.c0[0] = u.x; r.c0[1] = u.y; r.c0[2] = v.x; r.c0[3] = v.y;
     }
@@ -184,42 +116,36 @@ __global__ __launch_bounds__(64) void stream_vad_lanes_kernel(const StreamVadPar
             const long long t = d.F0 + i;
             // the recurrences name frames up to the init counts (ints): beyond 2^30 frames of one file every such branch is long decided
             const int tt = (int)min(t, (long long)0x40000000);
-            const int vad0 = stream_vad_lanes_step<NCL, THR>(r, vp, tt, ci, pq);
-            const int old = (int)((r.hist >> r.hidx) & 1ull);
-            r.hist = (r.hist & ~(1ull << r.hidx)) | ((unsigned long long)vad0 << r.hidx);
-            r.nsum += vad0 - old;
-            r.hidx = (r.hidx + 1 == order_f) ? 0 : r.hidx + 1;
-            if (t >= h && pq == 0) out[t - h] = (2 * r.nsum >= order_f) ? '1' : '0';
+            const int vad0 = vad_quad_step<NCL, THR>(r, vp, tt, ci, pq);
+            vad_push(r.f, vad0, order_f);
+            if (t >= h && pq == 0) out[t - h] = vad_byte(r.f, order_f);
         }
     }
     if (live) {  // behind the push's last frame
-        double2 *h2 = reinterpret_cast<double2 *>(vs);
         if (pq == 0) {
-            h2[0] = make_double2(r.crimin, r.crimax);
-            h2[1] = make_double2(r.crimean, r.crimean2);
-            h2[2] = make_double2(r.crivar, r.dmin);
-            h2[3] = make_double2(r.dmax, __longlong_as_double((long long)r.hist));
-            h2[4] = make_double2(vst_bits((unsigned)r.adapt_vad, (unsigned)r.hidx), vst_bits((unsigned)r.nsum, 0u));
+            double hd[VST_HEADER];
+            vst_pack(r.thr, r.f, hd);
+#pragma unroll
+            for (int k = 0; k < VST_HEADER / 2; k++) h2[k] = make_double2(hd[2 * k], hd[2 * k + 1]);
         }
-        double2 *c2 = reinterpret_cast<double2 *>(vs + VST_C0 + 4 * pq);
         c2[0] = make_double2(r.c0[0], r.c0[1]);
         c2[1] = make_double2(r.c0[2], r.c0[3]);
     }
 }
 
 __device__ __forceinline__ void vst_load(VadRun &r, const double *vs, int lane) {
-    r.crimin = vs[0]; r.crimax = vs[1]; r.crimean = vs[2]; r.crimean2 = vs[3]; r.crivar = vs[4]; r.dmin = vs[5]; r.dmax = vs[6];
-    r.hist = (unsigned long long)__double_as_longlong(vs[7]);
-    r.adapt_vad = __double2loint(vs[8]); r.hidx = __double2hiint(vs[8]);
-    r.nsum = __double2loint(vs[9]);
+    double hd[VST_HEADER];
+#pragma unroll
+    for (int k = 0; k < VST_HEADER; k++) hd[k] = vs[k];
+    vst_unpack(r.thr, r.f, hd);
     r.c0r = lane < 32 ? vs[VST_C0 + lane] : 0.0;
 }
 __device__ __forceinline__ void vst_store(const VadRun &r, double *vs, int lane) {
     if (lane == 0) {
-        vs[0] = r.crimin; vs[1] = r.crimax; vs[2] = r.crimean; vs[3] = r.crimean2; vs[4] = r.crivar; vs[5] = r.dmin; vs[6] = r.dmax;
-        vs[7] = __longlong_as_double((long long)r.hist);
-        vs[8] = vst_bits((unsigned)r.adapt_vad, (unsigned)r.hidx);
-        vs[9] = vst_bits((unsigned)r.nsum, 0u);
+        double hd[VST_HEADER];
+        vst_pack(r.thr, r.f, hd);
+#pragma unroll
+        for (int k = 0; k < VST_HEADER; k++) vs[k] = hd[k];
     }
     if (lane < 32) vs[VST_C0 + lane] = r.c0r;
 }
@@ -234,8 +160,7 @@ __global__ __launch_bounds__(64) void stream_vad_decide_kernel(const StreamVadPa
     if (T == 0) return;  // completes no frame: not touched
     const int nc = vp.cri == 0 ? 1 : vp.ncoef;
     double *vs = p.vstate + (size_t)d.id * VST_DOUBLES;
-    VadRun run;
-    vad_run_reset(run);
+    VadRun run = {};
     if (d.F0 > 0) vst_load(run, vs, lane);
     // vad_emit writes out[run.nout] and counts on: row k of the file has byte out0 + k - r0 of the push, and R(F0) rows are out
     run.nout = (int)min(d.r0, (long long)0x40000000);
@@ -274,7 +199,7 @@ __global__ __launch_bounds__(256) void stream_vad_rows_kernel(const RowParams p,
 
 // One workgroup, 256 lanes: the stream that finishes (p.push[0]: F0 = the file's frames, Tn = 0, r0 = R(F0), nr = min(F0, h) > 0).
 // The held rows come from the history alone; lane 0 pushes vad_flush's zeros through the filter (src/vad/vad.h:156-175) for their bytes.
-// The stream's record is left as it stands: the next file's first push starts from vad_run_reset.
+// The stream's record is left as it stands: the next file's first push starts from the zero state.
 __global__ __launch_bounds__(256) void stream_vad_finish_kernel(const RowParams p, const int D, const double *__restrict__ vstate, uint8_t *__restrict__ vad,
                                                                  const int order) {
     const RowPush d = p.push[0];
@@ -285,14 +210,15 @@ __global__ __launch_bounds__(256) void stream_vad_finish_kernel(const RowParams 
         }
     if (threadIdx.x == 0 && vad) {
         const double *vs = vstate + (size_t)d.id * VST_DOUBLES;
-        VadRun r;
-        vad_run_reset(r);
-        r.hist = (unsigned long long)__double_as_longlong(vs[7]);
-        r.hidx = __double2hiint(vs[8]);
-        r.nsum = __double2loint(vs[9]);
+        double hd[VST_HEADER];
+#pragma unroll
+        for (int k = 0; k < VST_HEADER; k++) hd[k] = vs[k];
+        VadThr thr;  // (not used: the filter's three fields are all that is read)
+        VadFilter f;
+        vst_unpack(thr, f, hd);
         for (int k = 0; k < d.nr; k++) {  // vad_flush: k < h && nout < T
-            vad_push(r, 0, order);
-            vad[d.out0 + k] = (2 * r.nsum >= order) ? '1' : '0';
+            vad_push(f, 0, order);
+            vad[d.out0 + k] = vad_byte(f, order);
         }
     }
 }

@@ -212,44 +212,29 @@ __global__ __launch_bounds__(256) void vad_burg_kernel(const float2 *__restrict_
     }  // frames
 }
 
-// The sequential part of the VAD, one frame at a time, every lane of a wave in step (the state is wave-uniform except
-// c0r, the background cepstrum, which lane i keeps for coefficient i): cepstral distance to the adaptive background
-// (src/vad/vad.cc:220-294), the four threshold recurrences (:329-625), the majority filter (src/vad/vad.h:126-175).
-struct VadRun {
+// The sequential part of the VAD, one frame at a time: cepstral distance to the adaptive background (src/vad/vad.cc:220-294), the four
+// threshold recurrences (:329-625), the majority filter (src/vad/vad.h:126-175).  Each is stated once here; the offline and the streamed
+// kernels (stream_vad_kernels.h), a wave or a quad of lanes per utterance, differ in where the state lives between launches.
+
+// State of the threshold recurrences
+struct VadThr {
     double crimin, crimax, crimean, crimean2, crivar, dmin, dmax;
-    double c0r;  // background cepstrum, coefficient `lane`
     int adapt_vad;
-    unsigned long long hist;  // the last `order` (<= 31) raw decisions as bits, with a running count
-    int hidx, nout, nsum;
 };
 
-__device__ __forceinline__ void vad_run_reset(VadRun &r) {
-    r.crimin = r.crimax = r.crimean = r.crimean2 = r.crivar = r.dmin = r.dmax = 0.0;
-    r.c0r = 0.0;
-    r.adapt_vad = 0;
-    r.hist = 0;
-    r.hidx = r.nout = r.nsum = 0;
-}
-
-__device__ __forceinline__ void vad_push(VadRun &r, int v, int order) {
-    const int old = (int)((r.hist >> r.hidx) & 1ull);
-    r.hist = (r.hist & ~(1ull << r.hidx)) | ((unsigned long long)v << r.hidx);
-    r.nsum += v - old;
-    r.hidx = (r.hidx + 1 == order) ? 0 : r.hidx + 1;
-}
-
-// The raw decision of frame t on the criterion's value: the four threshold recurrences (src/vad/vad.cc:329-625).
-__device__ __forceinline__ int vad_threshold(VadRun &r, const VadParams &vp, int t, double cri) {
+// The raw decision of frame t on the criterion's value, threshold mode THR (vp.thr): src/vad/vad.cc:329-625.
+template <int THR>
+__device__ __forceinline__ int vad_threshold(VadThr &r, const VadParams &vp, int t, double cri) {
     int vad0;
-    if (vp.thr == 0) vad0 = cri >= vp.abs_thr;
-    else if (vp.thr == 1) {
+    if (THR == 0) vad0 = cri >= vp.abs_thr;
+    else if (THR == 1) {
         if (t == 0 || (double)t < (double)vp.perc_init) r.crimin = r.crimax = cri;
         else {
             r.crimin = cri < r.crimin ? cri : r.crimin;
             r.crimax = cri > r.crimax ? cri : r.crimax;
         }
         vad0 = cri >= r.crimin + (vp.perc_thr / 100.0) * (r.crimax - r.crimin);
-    } else if (vp.thr == 2) {
+    } else if (THR == 2) {
         if (t == 0) {
             r.crimean = cri;
             r.crimean2 = cri * cri;
@@ -283,13 +268,68 @@ __device__ __forceinline__ int vad_threshold(VadRun &r, const VadParams &vp, int
     }
     return vad0;
 }
+// (the mode at run time: the kernels that are not instantiated per mode)
+__device__ __forceinline__ int vad_threshold(VadThr &r, const VadParams &vp, int t, double cri) {
+    return vp.thr == 0 ? vad_threshold<0>(r, vp, t, cri) : vp.thr == 1 ? vad_threshold<1>(r, vp, t, cri)
+         : vp.thr == 2 ? vad_threshold<2>(r, vp, t, cri) : vad_threshold<3>(r, vp, t, cri);
+}
+
+// The majority ("median") filter: the last `order` (<= 31) raw decisions as bits, with a running count
+struct VadFilter {
+    unsigned long long hist;
+    int hidx, nsum;
+};
+__device__ __forceinline__ void vad_push(VadFilter &f, int v, int order) {
+    const int old = (int)((f.hist >> f.hidx) & 1ull);
+    f.hist = (f.hist & ~(1ull << f.hidx)) | ((unsigned long long)v << f.hidx);
+    f.nsum += v - old;
+    f.hidx = (f.hidx + 1 == order) ? 0 : f.hidx + 1;
+}
+// (The majority test (double)nsum / order >= 0.5 of src/vad/vad.h:139-150 is taken as 2 nsum >= order: the same for integers.)
+__device__ __forceinline__ uint8_t vad_byte(const VadFilter &f, int order) { return (2 * f.nsum >= order) ? '1' : '0'; }
+
+// Frame t on the cepstral criterion, one utterance per wave: entry lane + 64 j of the frame's vector in ci[j] (0 beyond nc), of the
+// adaptive background in c0[j].  Distance (entry 0, c0 itself, is not part of it), raw decision, background update behind cep_init
+// (src/vad/vad.cc:220-294).  The lane's partial sum, then wave_sum_fast.
+template <int J>
+__device__ __forceinline__ int vad_cep_frame(VadThr &r, double *c0, const double *ci, const VadParams &vp, int t, int nc, int lane) {
+    double cri = 0.0;
+    if (t == 0) {
+#pragma unroll
+        for (int j = 0; j < J; j++) c0[j] = ci[j];
+    } else {
+        double part = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; j++) {
+            if (t == 1) c0[j] = (c0[j] + ci[j]) / 2.0;
+            const int i = lane + 64 * j;
+            const double dl = (i >= 1 && i < nc) ? ci[j] - c0[j] : 0.0;
+            part += dl * dl;
+        }
+        cri = 4.3429 * sqrt(2 * wave_sum_fast(part));
+    }
+    const int vad0 = vad_threshold(r, vp, t, cri);
+    if (!(vad0 && t > vp.cep_init)) {  // background update (src/vad/vad.cc:288-294)
+#pragma unroll
+        for (int j = 0; j < J; j++) c0[j] = vp.cep_p * c0[j] + (1.0 - vp.cep_p) * ci[j];
+    }
+    return vad0;
+}
+
+// One utterance's detector in a wave, every lane in step: the state is wave-uniform except c0r.  An utterance starts from zeros ({}).
+struct VadRun {
+    VadThr thr;
+    double c0r;  // background cepstrum, coefficient `lane`
+    VadFilter f;
+    int nout;
+};
 
 // The raw decision into the majority filter; decisions leave (order-1)/2 frames late (lane 0 writes).
 __device__ __forceinline__ void vad_emit(VadRun &r, const VadParams &vp, int t, int vad0, int lane, uint8_t *out) {
     const int order = vp.filter_order, h = (order - 1) / 2;
-    vad_push(r, vad0, order);
+    vad_push(r.f, vad0, order);
     if (t >= h) {
-        if (lane == 0) out[r.nout] = (2 * r.nsum >= order) ? '1' : '0';
+        if (lane == 0) out[r.nout] = vad_byte(r.f, order);
         r.nout++;
     }
 }
@@ -297,52 +337,85 @@ __device__ __forceinline__ void vad_emit(VadRun &r, const VadParams &vp, int t, 
 // Frame t of an utterance.  en: the energy criterion's value (cri 0); cil: coefficient `lane` of the frame's cepstrum
 // (0 beyond nc).  out: the utterance's VAD bytes (lane 0 writes; decisions leave (order-1)/2 frames late).
 __device__ __forceinline__ void vad_frame(VadRun &r, const VadParams &vp, int t, double en, double cil, int lane, uint8_t *out) {
-    const int nc = vp.cri == 0 ? 1 : vp.ncoef;
-    double cri;
+    int vad0;
     if (vp.cri == 0) {
         if (vp.energy_db) en = 10.0 * log10(2.2250738585072014e-308 + en);
-        cri = en;
-    } else {
-        if (t == 0) {
-            r.c0r = cil;
-            cri = 0.0;
-        } else {
-            if (t == 1) r.c0r = (r.c0r + cil) / 2.0;
-            const double dl = (lane >= 1 && lane < nc) ? cil - r.c0r : 0.0;  // c0 itself is not part of the distance
-            cri = 4.3429 * sqrt(2 * wave_sum_fast(dl * dl));
-        }
-    }
-    const int vad0 = vad_threshold(r, vp, t, cri);
-    if (vp.cri != 0 && !(vad0 && t > vp.cep_init))  // background update (src/vad/vad.cc:288-294)
-        r.c0r = vp.cep_p * r.c0r + (1.0 - vp.cep_p) * cil;
+        vad0 = vad_threshold(r.thr, vp, t, en);
+    } else vad0 = vad_cep_frame<1>(r.thr, &r.c0r, &cil, vp, t, vp.ncoef, lane);
     vad_emit(r, vp, t, vad0, lane, out);
 }
 
-// (The majority test (double)nsum / order >= 0.5 of src/vad/vad.h:139-150 is taken as 2 nsum >= order: the same for integers.)
 // End of an utterance of T frames: zeros are pushed until every frame has its byte (src/vad/vad.h:156-175).
 __device__ __forceinline__ void vad_flush(VadRun &r, const VadParams &vp, int T, int lane, uint8_t *out) {
     const int order = vp.filter_order, h = (order - 1) / 2;
     for (int k = 0; k < h && r.nout < T; k++) {
-        vad_push(r, 0, order);
-        if (lane == 0) out[r.nout] = (2 * r.nsum >= order) ? '1' : '0';
+        vad_push(r.f, 0, order);
+        if (lane == 0) out[r.nout] = vad_byte(r.f, order);
         r.nout++;
     }
 }
 
 // The same recurrences for the fused Burg-cepstral path (vad_fused.h) with the utterances spread over the LANES: the front end
-// leaves the cepstra of every frame in a scratch row (VFC_STRIDE floats) and a wave of this kernel walks 16 utterances at once, four
-// lanes each - a lane keeps four coefficients of the background cepstrum and adds four terms to the distance (two quad_perm adds
-// bring the four partial sums together, the same value in the four lanes); the scalar state is replicated in the quad and evolves
-// identically.  Inside the front end the replay ran eight strictly sequential frames per wave step with all 64 lanes doing one
-// utterance's scalar work - a quarter of that kernel (profiles/r02_c4_vf_stamps.txt).  The launch lasts as long as its longest
-// utterance; everything but the distance's summation order is vad_frame / vad_flush statement for statement.
+// leaves the cepstra of every frame in a scratch row (VFC_STRIDE floats) and a wave walks 16 utterances at once, four lanes each - a
+// lane keeps four coefficients of the background cepstrum and adds four terms to the distance (two quad_perm adds bring the four
+// partial sums together, the same value in the four lanes); the scalar state is replicated in the quad and evolves identically.
+// Inside the front end the replay ran eight strictly sequential frames per wave step with all 64 lanes doing one utterance's scalar
+// work - a quarter of that kernel (profiles/r02_c4_vf_stamps.txt).  gfx950, hipcc -O3, vad_lanes_kernel<14, THR> for THR 0 .. 3 (in
+// brackets: with the step written out in the kernel and the state in loose locals): 66 / 72 / 77 / 74 VGPRs (70 / 75 / 78 / 90), 40 / 38 /
+// 42 / 52 SGPRs (43 / 42 / 45 / 53), 1023 / 1132 / 1202 / 1293 instructions (1053 / 1155 / 1244 / 1312), no scratch; vad_decide_kernel 99
+// VGPRs, 106 SGPRs, 3462 instructions (3403), 16 KB of LDS, no scratch.  Times of the two forms: profiles/vad_step_ab.txt.
 constexpr int VFC_STRIDE = 16;  // floats per frame in the cepstra scratch: the fused path's 14 coefficients, 64-byte rows
 
-template <int NCL, int THR>  // cepstral coefficients (<= 16); threshold mode (vp.thr) at compile time: the launch lasts as long as its longest
-                              // utterance's chain of frames, one wave per SIMD - every instruction of a frame's step is on the critical path
+// The detector's state of one utterance in a quad of lanes; an utterance starts from zeros ({})
+struct VadQuad {
+    VadThr thr;
+    double c0[4];  // coefficients 4 pq .. 4 pq + 3 of the background cepstrum
+    VadFilter f;
+};
+
+// Frame t on the fused criterion, the step of vad_lanes_kernel and stream_vad_lanes_kernel: ci holds coefficients 4 pq .. 4 pq + 3 of
+// the frame's cepstrum.  vad_cep_frame but for the distance's summation order; returns the raw decision, which the caller pushes into
+// r.f.  Every lane of the quad runs it on the same values.
+template <int NCL, int THR>  // cepstral coefficients (<= 16); threshold mode (vp.thr)
+__device__ __forceinline__ int vad_quad_step(VadQuad &r, const VadParams &vp, const int t, const double (&ci)[4], const int pq) {
+    static_assert(NCL <= 16, "four lanes x four coefficients");
+    double cri;
+    if (t < 1) {  // t == 0: frames count from 0.  (As an equality the compiler folds this test and t == 1 below into one switch, whose
+                  // lowering costs stream_vad_lanes_kernel<14, 2> 204 instructions per frame for 188 and 6 % of its time:
+                  // profiles/vad_step_ab.txt)
+#pragma unroll
+        for (int i = 0; i < 4; i++) r.c0[i] = ci[i];
+        cri = 0.0;
+    } else {
+        if (t == 1) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) r.c0[i] = (r.c0[i] + ci[i]) / 2.0;
+        }
+        double sum = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int k = 4 * pq + i;
+            // c0 itself is not part of the distance; vad_a2c_kernel stores zeros there and in the row's padding
+            const double dl = (CTU_VF_A2C || (k >= 1 && k < NCL)) ? ci[i] - r.c0[i] : 0.0;
+            sum += dl * dl;
+        }
+        sum += dpp_mov<0xB1>(sum);  // quad_perm [1,0,3,2]
+        sum += dpp_mov<0x4E>(sum);  // quad_perm [2,3,0,1]
+        cri = 4.3429 * sqrt(2 * sum);
+    }
+    const int vad0 = vad_threshold<THR>(r.thr, vp, t, cri);
+    if (!(vad0 && t > vp.cep_init)) {  // background update (src/vad/vad.cc:288-294)
+#pragma unroll
+        for (int i = 0; i < 4; i++) r.c0[i] = vp.cep_p * r.c0[i] + (1.0 - vp.cep_p) * ci[i];
+    }
+    return vad0;
+}
+
+// grid ceil(n_live / 16), 64 lanes: quad q of wave w is utterance order[16 w + q].  The launch lasts as long as its longest utterance's
+// chain of frames, one wave per SIMD: every instruction of a frame's step is on the critical path, hence the mode at compile time.
+template <int NCL, int THR>
 __global__ __launch_bounds__(64) void vad_lanes_kernel(const float *__restrict__ cf, const int *__restrict__ order, int n_live,
                                                         const int64_t *__restrict__ row_off, uint8_t *__restrict__ vad_out, VadParams vp) {
-    static_assert(NCL <= 16, "four lanes x four coefficients");
     const int lane = threadIdx.x, pq = lane & 3;
     const int gidx = blockIdx.x * 16 + (lane >> 2);
     const bool live = gidx < n_live;
@@ -353,17 +426,9 @@ __global__ __launch_bounds__(64) void vad_lanes_kernel(const float *__restrict__
 #pragma unroll
     for (int off = 32; off >= 4; off >>= 1) Tmax = max(Tmax, __shfl_xor(Tmax, off, 64));
     const int order_f = vp.filter_order, h = (order_f - 1) / 2;
-    double crimin = 0, crimax = 0, crimean = 0, crimean2 = 0, crivar = 0, dmin = 0, dmax = 0;
-    double c0[4] = {0.0, 0.0, 0.0, 0.0};   // coefficients 4 pq .. 4 pq + 3 of the background cepstrum
-    int adapt_vad = 0, hidx = 0, nout = 0, nsum = 0;
-    unsigned long long hist = 0;
+    VadQuad r = {};
+    int nout = 0;
     uint8_t *out = vad_out + r0;
-    auto push = [&](int v) {
-        const int old = (int)((hist >> hidx) & 1ull);
-        hist = (hist & ~(1ull << hidx)) | ((unsigned long long)v << hidx);
-        nsum += v - old;
-        hidx = (hidx + 1 == order_f) ? 0 : hidx + 1;
-    };
     constexpr int AHEAD = 4;  // frames whose cepstra are in flight while the current ones are worked on (few waves per SIMD: no other cover)
     float4 q[AHEAD];
     auto fetch = [&](int slot, int t) {
@@ -377,88 +442,21 @@ __global__ __launch_bounds__(64) void vad_lanes_kernel(const float *__restrict__
             const int t = tb + a;
             const double ci[4] = {(double)q[a].x, (double)q[a].y, (double)q[a].z, (double)q[a].w};
             fetch(a, t + AHEAD);
-            // the quad's lanes run the same scalar code on the same values: a lane beyond its utterance's end just idles in step
-            double cri;
-            if (t == 0) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) c0[i] = ci[i];
-                cri = 0.0;
-            } else {
-                if (t == 1) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) c0[i] = (c0[i] + ci[i]) / 2.0;
-                }
-                double sum = 0.0;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int k = 4 * pq + i;
-                    // c0 itself is not part of the distance; vad_a2c_kernel stores zeros there and in the row's padding
-                    const double dl = (CTU_VF_A2C || (k >= 1 && k < NCL)) ? ci[i] - c0[i] : 0.0;
-                    sum += dl * dl;
-                }
-                sum += dpp_mov<0xB1>(sum);  // quad_perm [1,0,3,2]
-                sum += dpp_mov<0x4E>(sum);  // quad_perm [2,3,0,1]
-                cri = 4.3429 * sqrt(2 * sum);
-            }
-            {   // a quad beyond its utterance's end keeps stepping on zeros: its detector state is spent, only the filter and the stores below are guarded
-                int vad0;
-                if (THR == 0) vad0 = cri >= vp.abs_thr;
-                else if (THR == 1) {
-                    if (t == 0 || (double)t < (double)vp.perc_init) crimin = crimax = cri;
-                    else {
-                        crimin = cri < crimin ? cri : crimin;
-                        crimax = cri > crimax ? cri : crimax;
-                    }
-                    vad0 = cri >= crimin + (vp.perc_thr / 100.0) * (crimax - crimin);
-                } else if (THR == 2) {
-                    if (t == 0) {
-                        crimean = cri;
-                        crimean2 = cri * cri;
-                        crivar = 0.0;
-                        adapt_vad = 0;
-                    } else {
-                        const double thr = crimean + vp.adapt_za * sqrt(crivar);
-                        if (cri < thr || t <= vp.adapt_init) {
-                            crimean = vp.adapt_q * crimean + (1.0 - vp.adapt_q) * cri;
-                            crimean2 = vp.adapt_q * crimean2 + (1.0 - vp.adapt_q) * cri * cri;
-                            crivar = crimean2 - crimean * crimean;
-                            adapt_vad = 0;
-                        } else adapt_vad = 1;
-                    }
-                    vad0 = adapt_vad;
-                } else {
-                    const int init = vp.dyn_init > 1 ? vp.dyn_init : 1;
-                    if (t < init) {
-                        dmax = dmin = cri;
-                        vad0 = 0;
-                    } else if (t == init) {
-                        dmax = (cri > dmax ? cri : dmax) + vp.dyn_min / 10.0;
-                        dmin = (cri < dmin ? cri : dmin) - vp.dyn_min / 10.0;
-                        vad0 = 0;
-                    } else {
-                        dmax = dmax < cri ? vp.qmaxinc * dmax + (1.0 - vp.qmaxinc) * cri : vp.qmaxdec * dmax + (1.0 - vp.qmaxdec) * cri;
-                        dmin = dmin > cri ? vp.qmindec * dmin + (1.0 - vp.qmindec) * cri : vp.qmininc * dmin + (1.0 - vp.qmininc) * cri;
-                        const double dyn = dmax - dmin;
-                        vad0 = (cri > dmin + (vp.dyn_perc / 100.0) * dyn) && (dyn > vp.dyn_min);
-                    }
-                }
-                if (!(vad0 && t > vp.cep_init)) {  // background update (src/vad/vad.cc:288-294)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) c0[i] = vp.cep_p * c0[i] + (1.0 - vp.cep_p) * ci[i];
-                }
-                if (t < T) {
-                    push(vad0);
-                    if (t >= h) {
-                        if (pq == 0) out[nout] = (2 * nsum >= order_f) ? '1' : '0';
-                        nout++;
-                    }
+            // a quad beyond its utterance's end keeps stepping on zeros, in step with the wave: its detector state is spent, only the
+            // filter and the stores are guarded
+            const int vad0 = vad_quad_step<NCL, THR>(r, vp, t, ci, pq);
+            if (t < T) {
+                vad_push(r.f, vad0, order_f);
+                if (t >= h) {
+                    if (pq == 0) out[nout] = vad_byte(r.f, order_f);
+                    nout++;
                 }
             }
         }
     }
     for (int k = 0; k < h && nout < T; k++) {  // end of the utterance: zeros until every frame has its byte (src/vad/vad.h:156-175)
-        push(0);
-        if (pq == 0) out[nout] = (2 * nsum >= order_f) ? '1' : '0';
+        vad_push(r.f, 0, order_f);
+        if (pq == 0) out[nout] = vad_byte(r.f, order_f);
         nout++;
     }
 }
@@ -485,8 +483,7 @@ __global__ __launch_bounds__(64) void vad_decide_kernel(const double *__restrict
     const int64_t r0 = row_off[u];
     const int T = (int)(row_off[u + 1] - r0);
     const int nc = vp.cri == 0 ? 1 : vp.ncoef;
-    VadRun run;
-    vad_run_reset(run);
+    VadRun run = {};
     const bool wide = vp.cri == 2 && nc > 32;
     if (wide) {
         // The `fea` criterion behind a delta / stacking chain: VADcri_cepdist sizes c0 / ci on the vector it is handed (src/vad/vad.cc:182),
@@ -502,26 +499,7 @@ __global__ __launch_bounds__(64) void vad_decide_kernel(const double *__restrict
                 const int i = lane + 64 * j;
                 ciw[j] = i < nc ? vad_fea_entry(vp, row, i) : 0.0;
             }
-            double cri = 0.0;
-            if (t == 0) {
-#pragma unroll
-                for (int j = 0; j < VAD_FEA_WIDE; j++) c0w[j] = ciw[j];
-            } else {
-                double part = 0.0;
-#pragma unroll
-                for (int j = 0; j < VAD_FEA_WIDE; j++) {
-                    if (t == 1) c0w[j] = (c0w[j] + ciw[j]) / 2.0;
-                    const int i = lane + 64 * j;
-                    const double dl = (i >= 1 && i < nc) ? ciw[j] - c0w[j] : 0.0;  // entry 0 is not part of the distance
-                    part += dl * dl;
-                }
-                cri = 4.3429 * sqrt(2 * wave_sum_fast(part));
-            }
-            const int vad0 = vad_threshold(run, vp, t, cri);
-            if (!(vad0 && t > vp.cep_init)) {
-#pragma unroll
-                for (int j = 0; j < VAD_FEA_WIDE; j++) c0w[j] = vp.cep_p * c0w[j] + (1.0 - vp.cep_p) * ciw[j];
-            }
+            const int vad0 = vad_cep_frame<VAD_FEA_WIDE>(run.thr, c0w, ciw, vp, t, nc, lane);
             vad_emit(run, vp, t, vad0, lane, vad_out + r0);
         }
     }

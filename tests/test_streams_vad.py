@@ -26,8 +26,10 @@ BURG = "-vad burg -vad_out_mode vad -vad_cri_mode cepdist -vad_cepdist_mode lpc"
 ENERGY = "-vad_out_mode vad -vad_cri_mode energy".split()
 CONFIGS = [C4, _swap(C4, "-vad_thr_mode", "dyn"), C4 + ["-vad_filter_order", "7"], C2 + BURG + ["-vad_thr_mode", "adapt"],
            C2 + ["-w", "20"] + BURG + ["-vad_thr_mode", "dyn"], C2 + ENERGY + ["-vad_thr_mode", "dyn"],
-           C2 + ENERGY + ["-vad_thr_mode", "perc", "-vad_filter_order", "5"]]
-IDS = ["c4_adapt", "c4_dyn", "c4_order7", "mfcc_burg_adapt_fused512", "mfcc_w20_burg_dyn", "mfcc_energy_dyn", "mfcc_energy_perc_order5"]
+           C2 + ENERGY + ["-vad_thr_mode", "perc", "-vad_filter_order", "5"],
+           _swap(C4, "-vad_thr_mode", "perc"), _swap(C4, "-vad_thr_mode", "absolute") + ["-vad_absolute_thr", "5"]]
+IDS = ["c4_adapt", "c4_dyn", "c4_order7", "mfcc_burg_adapt_fused512", "mfcc_w20_burg_dyn", "mfcc_energy_dyn", "mfcc_energy_perc_order5",
+       "c4_perc", "c4_absolute5"]
 
 
 @pytest.fixture(scope="module")
