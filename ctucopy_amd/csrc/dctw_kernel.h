@@ -23,7 +23,7 @@ namespace {
 // contraction is per row, so a tile may span utterances and needs no tile record; the last tile is partial.  The 64 x B block of logmel a
 // tile reads and the 64 x nout block of the rows it writes are each one contiguous run in HBM (rows: but for the energy column).
 // Results go through the LDS tile so that a wave stores whole rows, one row per store instruction.
-constexpr int DCTW_TILE = 64, DCTW_KC = 64, DCTW_LD = 68, DCTW_MAX = 64;
+constexpr int DCTW_TILE = 64, DCTW_LD = 68;  // (DCTW_KC, DCTW_MAX: layout_constants.h)
 
 struct DctwParams {
     const float *logmel;   // [total_frames][B]

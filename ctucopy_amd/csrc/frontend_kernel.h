@@ -27,9 +27,6 @@ namespace {
 #else
 #define STAMP(i) do { } while (0)
 #endif
-#ifndef CTU_DUAL
-#define CTU_DUAL 1      // the two passes of the 512-point mode side by side in the headline instantiation (see DUAL below)
-#endif
 #ifndef CTU_PK
 #define CTU_PK 1        // 1: DUAL with the two passes in the halves of packed registers (v_pk_*_f32 for all of phase 1's arithmetic); 0: scalar lock step (round 3)
 #endif
@@ -97,10 +94,7 @@ namespace {
 constexpr int fe_waves_per_simd(int mode, bool vf, bool ss, bool sy = false) {
     return ((vf || ss) && mode == 0) ? 2 : (sy ? CTU_SY_LB : ((vf || ss) ? CTU_VF1_LB : CTU_LB));
 }
-// The DUAL instantiations (phase 1 below).  They take their window table scaled by 1/2 (engine.hip: build_tables asks this same function).
-constexpr bool fe_dual(int nz, int mode, bool vx, int gen, bool vf, bool ss, bool sy) {
-    return CTU_DUAL && mode == 0 && (gen == GEN_PLAIN || gen == GEN_INLD) && !vx && nz < 16 && !vf && !ss && !sy;
-}
+// (fe_dual, the DUAL instantiations of phase 1 below, and its switch CTU_DUAL: layout_constants.h - tables.cc halves their window table)
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
 template <class F, int... S>

@@ -2,16 +2,11 @@
 // Included by engine.hip (one translation unit: the kernels and their host launchers share types).
 #pragma once
 
-#include "layout_constants.h"  // TILE, WG, NWAVE, PCM_ALIGN, PCM_HEAD, PCM_TAIL: what host-only code shares with the kernels
+#include "layout_constants.h"  // every constant, enum, build switch and VadParams: what host-only code shares with the kernels
 
 namespace {
 
-constexpr int PSTRIDE = 260;   // floats per P-tile row: 257 bins padded so rows stay 16-byte aligned (b128 reads in phase 2)
 constexpr int LDS_2WG = 80 * 1024;  // two workgroups per CU fit when a workgroup's LDS stays at or under this
-constexpr int MAX_LP = 23;     // LP order / cepstral order limit: the front end accumulates MAXC = 24 lags (R[0..23]) per frame, lp_tail_kernel keeps one frame's recursion in a lane's registers
-constexpr int GEN_PLAIN = 0, GEN_INLD = 1, GEN_EXTEN = 2, GEN_FULL = 3, GEN_DC1 = 4;  // front-end option specialisations (frontend_kernel.h)
-constexpr int MAXC = 24;       // most coefficients accumulated per frame in phase 2 (cepstra incl. c0, or LP lags): the in-kernel limit.  A dctc chain of
-                               // 25 to 64 values runs its front end band-valued and takes dct_wide_kernel (dctw_kernel.h) for the DCT
 
 // Host side: the dynamic LDS of a launch and the workgroups of it that share a CU's 160 KiB (at most `cap`).  Each kernel's header has the
 // function that sizes it, beside the carve-up it must match.
@@ -20,37 +15,6 @@ struct LdsFit {
     int per_cu;
 };
 LdsFit lds_fit(size_t bytes, size_t cap) { return {bytes, (int)std::max<size_t>(1, std::min<size_t>(cap, (160 * 1024) / bytes))}; }
-
-// Per-lane constant record, one per l16 = lane & 15, streamed from L1 every pass instead of pinning
-// 70+ VGPRs:  [0,32) Hamming pairs (w[32j+2l], w[32j+2l+1]) j=0..15 | [32,64) 1/0 "sample is inside the
-// window" pairs for DC removal | [64,96) inter-stage twiddles W256^(l*k1), k1=1..15 (+pad) |
-// [96,112) W512^(l+16*k2), k2=0..7
-constexpr int LC_WIN = 0, LC_MASK = 32, LC_TW = 64, LC_UT = 96, LANEC = 112;
-// The records are copied into LDS per workgroup: PCM streaming keeps evicting them from L1 and a miss costs
-// ~1k cycles.  Row stride 116 floats makes the 16 lanes' ds_read_b128 conflict-free (116 mod 64 = 52).
-constexpr int LTW_STRIDE = 116, LTW_FLOATS = 16 * LTW_STRIDE;
-
-// Kernel variants by feature tail.  BANDS covers spec / logspec / the log-mel scratch of TRAP and of the wide DCT tail (runtime flags
-// band_log, band_to_scratch); LP covers lpc and lpa (runtime flag lp_is_lpa).
-enum FeatMode { FEAT_BANDS = 0, FEAT_DCTC = 2, FEAT_LP = 3, FEAT_LPD = 4 };  // LPD: LP analysis with the autocorrelation and the recursions in double
-
-// VAD module parameters (src/vad/vad.cc, src/vad/vad.h; used by vad_kernels.h and by the fused path of the front end)
-struct VadParams {
-    int K, wfft, window, ncoef;  // ncoef = vad_lpc_coefs (cepdist lpc) or the length of the vector OUT sees (cepdist fea: every block of a delta / stacking chain)
-    int krow, kstride;           // cepdist lpc: the exported spectra's row length and the step from one of the K bins to the next (K, 1
-                                 // unless an FFT size below 256 rides on the 256-point mode: then K and wfft are the configuration's own)
-    int cri;                     // 0 energy, 1 cepdist-lpc, 2 cepdist-fea
-    int thr;                     // 0 absolute, 1 perc, 2 adapt, 3 dyn
-    int energy_db, cep_init, filter_order;
-    double cep_p, abs_thr, perc_thr, adapt_q, adapt_za, dyn_perc, dyn_min, qmaxinc, qmaxdec, qmindec, qmininc;
-    int perc_init, adapt_init, dyn_init;
-    int D, ncep, c0_slot;        // cepdist-fea: where the internal vector sits in a written row
-    int fea_blk;                 // cepdist-fea behind a delta chain: entries per block of the vector (fea_ncepcoefs + 1); 0: one block
-    int delay;                   // delta / stacking ahead of the writer: the detector is called when a delayed vector comes out, on the
-                                 // criterion of the newest input frame min(call + delay, T - 1) (src/io/batch.cc:172-192,230-241,251-291)
-    int e_slot, e_delay;         // -fea_E: the writer reads the energy through a pointer when the median filter releases a
-                                 // vector, so row j carries the energy of row min(j + e_delay, T - 1); e_slot < 0: no such column
-};
 
 struct KParams {
     const int16_t *pcm;

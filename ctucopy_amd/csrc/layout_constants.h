@@ -1,6 +1,34 @@
-// The constants of the arena, tile and chain layout that host-only code needs as well as the kernels: plain C++, no HIP.
-// Included by kernel_common.h (the kernels) and stream_plan.h (the push planner, which also compiles without hipcc).
+// Every constant, enum and build switch that host-only code shares with the kernels: plain C++, no HIP.
+// Included by kernel_common.h (the kernels), by accept.cc / tables.cc (what is accepted, which instantiation runs, what the tables
+// hold) and by stream_plan.h (the push planner); all of these but the kernels compile without hipcc.  The kernel headers define none
+// of these themselves, and every #ifndef CTU_... switch below is defined here only, so the host units and engine.hip see one value.
 #pragma once
+
+// ---- build switches (A/B and diagnostic builds pass -DCTU_...=0)
+#ifndef CTU_MD
+#define CTU_MD 1        // the DCT tail on the matrix cores for the plain cepstral chains (what fe_select instantiates with MD)
+#endif
+#ifndef CTU_VF
+#define CTU_VF 1        // the Burg-cepstral VAD criterion fused into the front end (vad_fused.h)
+#endif
+#ifndef CTU_SY
+#define CTU_SY 1        // 0: speech-enhancement output through the exported spectra and synth_kernel (round 1's path)
+#endif
+#ifndef CTU_LP_MD
+#define CTU_LP_MD 1     // 0: the lags of the compressed-band LP chain on the VALU (cell_accumulate + cells_reduce), for A/B
+#endif
+#ifndef CTU_SS_CACHE
+#define CTU_SS_CACHE 1  // 0: every pass of the *ss modes' seed iteration runs the detector again (A/B)
+#endif
+#ifndef CTU_DUAL
+#define CTU_DUAL 1      // the two passes of the 512-point mode side by side in the headline instantiation (frontend_kernel.h: DUAL)
+#endif
+#ifndef CTU_TRAP_BF16
+#define CTU_TRAP_BF16 1  // 0: TRAP-DCT on the fp32 matrix pipe only (trapdct_mfma_kernel)
+#endif
+#ifndef CTU_TRAP_F16
+#define CTU_TRAP_F16 1   // 1: two fp16 terms, three products; 0: three bf16 terms, six products (trap_kernel.h)
+#endif
 
 namespace {
 
@@ -10,5 +38,65 @@ constexpr int NWAVE = WG / 64;
 constexpr int PCM_ALIGN = 8;   // utterance starts are multiples of this many samples
 constexpr int PCM_HEAD = 8;    // samples of padding before the first utterance (x[-2..-1] of frame 0 is loaded)
 constexpr int PCM_TAIL = 512;  // padding after the last one: the generic instantiation loads 16 rows of 32 samples whatever the window
+constexpr int ROWS_ALIGN = 4;  // HTK feature input: utterance starts in the arena are multiples of this many 32-bit words (16 bytes)
+
+constexpr int PSTRIDE = 260;   // floats per P-tile row: 257 bins padded so rows stay 16-byte aligned (b128 reads in phase 2)
+constexpr int MAX_LP = 23;     // LP order / cepstral order limit: the front end accumulates MAXC = 24 lags (R[0..23]) per frame, lp_tail_kernel keeps one frame's recursion in a lane's registers
+constexpr int GEN_PLAIN = 0, GEN_INLD = 1, GEN_EXTEN = 2, GEN_FULL = 3, GEN_DC1 = 4;  // front-end option specialisations (frontend_kernel.h)
+constexpr int MAXC = 24;       // most coefficients accumulated per frame in phase 2 (cepstra incl. c0, or LP lags): the in-kernel limit.  A dctc chain of
+                               // 25 to 64 values runs its front end band-valued and takes dct_wide_kernel (dctw_kernel.h) for the DCT
+
+// Per-lane constant record, one per l16 = lane & 15, streamed from L1 every pass instead of pinning
+// 70+ VGPRs:  [0,32) Hamming pairs (w[32j+2l], w[32j+2l+1]) j=0..15 | [32,64) 1/0 "sample is inside the
+// window" pairs for DC removal | [64,96) inter-stage twiddles W256^(l*k1), k1=1..15 (+pad) |
+// [96,112) W512^(l+16*k2), k2=0..7
+constexpr int LC_WIN = 0, LC_MASK = 32, LC_TW = 64, LC_UT = 96, LANEC = 112;
+// The records are copied into LDS per workgroup: PCM streaming keeps evicting them from L1 and a miss costs
+// ~1k cycles.  Row stride 116 floats makes the 16 lanes' ds_read_b128 conflict-free (116 mod 64 = 52).
+constexpr int LTW_STRIDE = 116, LTW_FLOATS = 16 * LTW_STRIDE;
+
+// Kernel variants by feature tail.  BANDS covers spec / logspec / the log-mel scratch of TRAP and of the wide DCT tail (runtime flags
+// band_log, band_to_scratch); LP covers lpc and lpa (runtime flag lp_is_lpa).
+enum FeatMode { FEAT_BANDS = 0, FEAT_DCTC = 2, FEAT_LP = 3, FEAT_LPD = 4 };  // LPD: LP analysis with the autocorrelation and the recursions in double
+
+// The fused detector paths (vad_fused.h)
+constexpr int VF_NC = 14;         // cepstral coefficients of the fused path (-vad_lpc_coefs default: Burg order 13)
+constexpr int SS_NC = 16;         // the *ss modes' detector uses -fea_ncepcoefs coefficients (src/nr/nr.cc:266-268: 12 in the presets): the lattice is
+                                  // unrolled for up to 16 (one coefficient per lane of a frame's 16) and stops at the run-time count (KParams::ss_nc)
+constexpr int VF_WINDOW = 200;    // the window the fused path is built for (8 kHz, 25 ms); other windows take the separate kernels
+constexpr int VF_SPL = 13;        // samples per lane of a frame: 16 lanes x 13 = 208 >= window
+// The 512-point mode (16 kHz, 25 ms): one frame per 16-lane group, four frames per half step
+constexpr int VF0_WINDOW = 400;   // the window the fused path of the 512-point mode is built for
+constexpr int VF0_SPL = 25;       // 16 lanes x 25 = 400 samples
+constexpr int VF0_FSTRIDE = 432;  // floats per staged frame: >= 416 (13 rows of 32 samples are written) and = 16 (mod 32): the two frame
+                                  // groups of a half wave read 25 l16 + j from different banks
+constexpr int VF0_STAGE = 4 * VF0_FSTRIDE;  // floats of staging per wave (behind the tables: these instantiations run one workgroup per CU)
+
+constexpr int VAD_FEA_WIDE = 8;  // vad_kernels.h: entries per lane of the `fea` criterion on vectors of more than 32 entries: up to 512
+constexpr int TB_OFF = 56;       // trap_kernel.h: tile origin tc - 56: a multiple of 8 not below half = 50
+constexpr int DCTW_KC = 64, DCTW_MAX = 64;  // dctw_kernel.h: bands per chunk of the contraction, most values per frame (four row blocks of 16)
+
+// The DUAL instantiations of frontend_kernel (its phase 1).  They take their window table scaled by 1/2 (tables.cc asks this same function).
+constexpr bool fe_dual(int nz, int mode, bool vx, int gen, bool vf, bool ss, bool sy) {
+    return CTU_DUAL && mode == 0 && (gen == GEN_PLAIN || gen == GEN_INLD) && !vx && nz < 16 && !vf && !ss && !sy;
+}
+
+// VAD module parameters (src/vad/vad.cc, src/vad/vad.h; filled by tables.cc, used by vad_kernels.h and by the fused path of the front end)
+struct VadParams {
+    int K, wfft, window, ncoef;  // ncoef = vad_lpc_coefs (cepdist lpc) or the length of the vector OUT sees (cepdist fea: every block of a delta / stacking chain)
+    int krow, kstride;           // cepdist lpc: the exported spectra's row length and the step from one of the K bins to the next (K, 1
+                                 // unless an FFT size below 256 rides on the 256-point mode: then K and wfft are the configuration's own)
+    int cri;                     // 0 energy, 1 cepdist-lpc, 2 cepdist-fea
+    int thr;                     // 0 absolute, 1 perc, 2 adapt, 3 dyn
+    int energy_db, cep_init, filter_order;
+    double cep_p, abs_thr, perc_thr, adapt_q, adapt_za, dyn_perc, dyn_min, qmaxinc, qmaxdec, qmindec, qmininc;
+    int perc_init, adapt_init, dyn_init;
+    int D, ncep, c0_slot;        // cepdist-fea: where the internal vector sits in a written row
+    int fea_blk;                 // cepdist-fea behind a delta chain: entries per block of the vector (fea_ncepcoefs + 1); 0: one block
+    int delay;                   // delta / stacking ahead of the writer: the detector is called when a delayed vector comes out, on the
+                                 // criterion of the newest input frame min(call + delay, T - 1) (src/io/batch.cc:172-192,230-241,251-291)
+    int e_slot, e_delay;         // -fea_E: the writer reads the energy through a pointer when the median filter releases a
+                                 // vector, so row j carries the energy of row min(j + e_delay, T - 1); e_slot < 0: no such column
+};
 
 }  // namespace

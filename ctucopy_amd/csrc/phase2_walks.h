@@ -1,6 +1,6 @@
 // Compile-time walk signatures of frontend_kernel's phase 2 (the filter-bank walk of the preset banks).
 //
-// build_phase2 (engine.hip) deals the bands to slots of eight cells; every cell of slot s walks slot_chunk[s+1] - slot_chunk[s]
+// build_phase2 (tables.cc) deals the bands to slots of eight cells; every cell of slot s walks slot_chunk[s+1] - slot_chunk[s]
 // chunks of four bins.  For a preset bank these counts are always the same, so the kernel can walk them straight-line: chunk
 // counts, weight addresses and DCT operand addresses become immediates (frontend_kernel.h, phase 2).  A bank that matches no
 // entry below takes the generic walk over the run-time records.
@@ -9,7 +9,7 @@
 // that the three preset configurations still match.
 #pragma once
 
-#include "kernel_common.h"
+#include "layout_constants.h"  // FEAT_*, GEN_*: this header is plain C++ too, tables.cc matches banks against it
 
 namespace {
 

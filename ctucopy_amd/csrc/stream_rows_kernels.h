@@ -31,7 +31,7 @@
 
 namespace {
 
-constexpr int STREAM_MEANS = 32;  // CMS columns at most (engine.hip: "more than 32 CMS columns")
+constexpr int STREAM_MEANS = 32;  // CMS columns at most (accept.cc: "more than 32 CMS columns")
 
 struct RowParams {
     const RowPush *push;

@@ -78,7 +78,6 @@ struct ctu_streams {
 namespace {
 void design_halo(const ctu::Design &d, int *H, int *wmax) { stream_halo(d.post_order, d.post_w, d.post_stack, H, wmax); }
 int64_t stream_rows_of(const ctu_streams *st, int64_t F) { return stream_rows_out(st->g.H, st->g.wmax, F); }
-constexpr uint32_t STREAMS_FLAGS = CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE | CTU_STREAMS_VAD_STATE;
 // a set with detector state on a configuration with the VAD module: the majority filter's delay is the halo (nothing else holds rows there)
 bool streams_vad(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STREAMS_VAD_STATE) && d.o.do_vad(); }
 }  // namespace
@@ -101,17 +100,10 @@ int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flag
         ctu::Opts o = ctu::Opts::from_args(to_args(argc, argv));
         ctu::Design d(o);
         spread_small_fft(d);
-        if (const std::string why = unsupported_reason(d); !why.empty()) {
-            say("ENGINE: configuration not on the accelerated path: " + why);
-            return CTU_ERR_UNSUPPORTED;
-        }
-        if (flags & ~STREAMS_FLAGS) {
-            say("ENGINE: unknown stream set flags");
-            return CTU_ERR_INPUT;
-        }
-        if (const std::string why = streams_unsupported_reason(d, flags); !why.empty()) {
-            say("ENGINE: configuration cannot be streamed: " + why);
-            return CTU_ERR_UNSUPPORTED;
+        std::string why;
+        if (const int rc = streams_check(d, flags, why)) {
+            say(why);
+            return rc;
         }
         int H = 0, wmax = 0;
         design_halo(d, &H, &wmax);
@@ -167,7 +159,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
-    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->ss || (e->per_wave && e->big) || (e->do_vad && e->big)) {
+    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->tab.ss || (e->per_wave && e->tab.big) || (e->do_vad && e->tab.big)) {
         set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
         return CTU_ERR_UNSUPPORTED;
     }
@@ -229,7 +221,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             }
         }
         if (g.chained) {
-            const size_t per_stream = (size_t)2 * 64 * (e->sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1);  // [2][64 NJ] of xstate_t (frontend_kernel.h)
+            const size_t per_stream = (size_t)2 * 64 * (e->tab.sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1);  // [2][64 NJ] of xstate_t (frontend_kernel.h)
             st->xstate.alloc((size_t)n_streams * per_stream);
             HIP_TRY(hipMemset(st->xstate.p, 0, st->xstate.n * sizeof(float)));  // (never read ahead of a store: a file's first tile resets)
             pl->tile_utt.alloc(pl->tiles.n);
@@ -322,7 +314,7 @@ void launch_stream_vad(ctu_streams *st, int k, int n, const PushLayout &L, float
     vp.push = st->d_rdesc[k].p; vp.replay = st->d_replay[k].p; vp.n_replay = L.n_replay;
     vp.cf = pl->vad_cf.p; vp.ci = pl->vad_ci.p; vp.energy = pl->pnr.p;
     vp.vstate = st->vstate.p; vp.vad = d_vad ? d_vad : st->vsink.p;
-    if (e->vf)
+    if (e->tab.sel.vf)
         lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
             hipLaunchKernelGGL((stream_vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((unsigned)((L.n_replay + 15) / 16)), dim3(64), 0, s, vp, e->vp);
         });

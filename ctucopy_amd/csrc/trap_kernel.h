@@ -93,7 +93,6 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int TB_TT = 264;   // tile row in frames: 8 * 15 + 127 < 256 used; 528 bytes per row spreads the bands over the banks and keeps 16-byte alignment
-constexpr int TB_OFF = 56;   // tile origin tc - 56: a multiple of 8 not below half = 50
 
 // Workgroup barrier for LDS hand-overs only: __syncthreads() also drains the vector-memory counter, which would put the
 // latency of a phase's row stores in front of the next phase.

@@ -18,22 +18,12 @@ __device__ __forceinline__ void idft16(float2 (&v)[16]) {
     for (int i = 0; i < 16; i++) v[i] = make_float2(v[i].y, v[i].x);
 }
 
-constexpr int VF_NC = 14;         // cepstral coefficients of the fused path (-vad_lpc_coefs default: Burg order 13)
-constexpr int SS_NC = 16;         // the *ss modes' detector uses -fea_ncepcoefs coefficients (src/nr/nr.cc:266-268: 12 in the presets): the lattice is
-                                  // unrolled for up to 16 (one coefficient per lane of a frame's 16) and stops at the run-time count (KParams::ss_nc)
-constexpr int VF_WINDOW = 200;    // the window the fused path is built for (8 kHz, 25 ms); other windows take the separate kernels
-constexpr int VF_SPL = 13;        // samples per lane of a frame: 16 lanes x 13 = 208 >= window
+// (VF_NC, SS_NC, VF_WINDOW, VF_SPL and the 512-point mode's VF0_WINDOW, VF0_SPL, VF0_FSTRIDE, VF0_STAGE: layout_constants.h)
 constexpr int VF_LW = (VF_WINDOW - 1) / VF_SPL, VF_JW = (VF_WINDOW - 1) % VF_SPL;  // lane / register of the window's last sample
 constexpr int VF8_SPL = 25;       // the same window as 8 lanes x 25 samples (the VAD module's float lattice, frontend_kernel.h VF8)
 constexpr int VF_FSTRIDE = 216;   // floats per time-domain frame in the LDS staging area: 2 x 216 = 16 (mod 32), so the two
                                   // frame groups of a half wave read different banks; 8 x 216 <= the wave's 8 x 260
-// The 512-point mode (16 kHz, 25 ms): one frame per 16-lane group, four frames per half step
-constexpr int VF0_WINDOW = 400;   // the window the fused path of the 512-point mode is built for
-constexpr int VF0_SPL = 25;       // 16 lanes x 25 = 400 samples
-constexpr int VF0_LW = (VF0_WINDOW - 1) / VF0_SPL, VF0_JW = (VF0_WINDOW - 1) % VF0_SPL;
-constexpr int VF0_FSTRIDE = 432;  // floats per staged frame: >= 416 (13 rows of 32 samples are written) and = 16 (mod 32): the two frame
-                                  // groups of a half wave read 25 l16 + j from different banks
-constexpr int VF0_STAGE = 4 * VF0_FSTRIDE;  // floats of staging per wave (behind the tables: these instantiations run one workgroup per CU)
+constexpr int VF0_LW = (VF0_WINDOW - 1) / VF0_SPL, VF0_JW = (VF0_WINDOW - 1) % VF0_SPL;  // the 512-point mode: one frame per 16-lane group
 
 // Stage A.  vz[r] = Z[l16 + 16 r] of the forward transform of (frame A + i frame B).  Every bin is scaled to the
 // magnitude the noise reduction left (P rows of the two frames) while it keeps its direction:

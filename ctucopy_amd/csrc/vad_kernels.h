@@ -471,7 +471,6 @@ __device__ __forceinline__ double vad_fea_entry(const VadParams &vp, const float
     return ii == 0 ? (vp.c0_slot >= 0 ? (double)row[base + vp.c0_slot] : 0.0) : (double)row[base + ii - 1];
 }
 
-constexpr int VAD_FEA_WIDE = 8;  // entries per lane of the `fea` criterion on vectors of more than 32 entries: up to 512
 
 // One wave per utterance: stages 64 frames of criterion inputs in LDS with coalesced loads, then replays them.
 __global__ __launch_bounds__(64) void vad_decide_kernel(const double *__restrict__ ci_all, const float *__restrict__ cri_energy,

@@ -85,7 +85,16 @@ int ctu_config_dims(int argc, const char *const *argv, ctu_dims *out);
  *        depends on the instantiation too: ctu_engine_phase2_walk] |
  *        "frontend" [12: the frontend_kernel instantiation ctu_engine_create selects for the configuration, as its template arguments
  *        NZ, FEAT, MODE, VX, NC, GEN, LPO, MD, VF, SS, SY and last the index of its straight-line walk or -1 (CTU_PHASE2_GENERIC is
- *        honoured); eleven zeros and -1 for the large-FFT kernels (1024 points and above), which the FFT size alone selects].
+ *        honoured); eleven zeros and -1 for the large-FFT kernels (1024 points and above), which the FFT size alone selects] |
+ *        "host_tables" [everything ctu_engine_create decides and lays out for the kernels before it touches the device, in this order:
+ *          36 scalars: the twelve values of "frontend"; feat, big, path, ss, ss_file, dctw, trap_bf16, lds_bytes, dctw_nout,
+ *            dctw_chunks, big_fb_total; lift_off, tab_floats, ck_off, cf_off, cfd_off, am_off, han_off, NS, CW, ncoef_out; kstride
+ *            and the configuration's own FFT size and bin count;
+ *          16 table images, each as its length in 32-bit words followed by the words' unsigned values (never as floats: the tables
+ *            carry ints whose bit patterns are NaNs; a double is two words, low then high): lanec, ftab, itab, trapG, trapG16,
+ *            dctw_tab, big_win, big_tw, big_fbw, big_range, big_seg, big_coef, big_coef_d, big_slot, big_lifter, big_han;
+ *          the 32 fields of the kernels' VAD parameter block (VadParams, layout_constants.h) in declaration order, as values.
+ *        Not for HTK feature input, which has no tables.  tests/golden/host_tables.json pins it].
  * Returns the number of values (written up to cap), or a negative error code. */
 int64_t ctu_config_table(int argc, const char *const *argv, const char *name, double *out, int64_t cap);
 

@@ -1,4 +1,4 @@
-"""The front-end instantiation a configuration runs on (fe_select in engine.hip), checked without a GPU.
+"""The front-end instantiation a configuration runs on (fe_select in tables.cc), checked without a GPU.
 
 ctu_config_table(..., "frontend") reports frontend_kernel's template arguments as ctu_engine_create selects them.  The expected
 values in tests/golden/frontend_selection.json are not this selector's: they are the template arguments of the frontend_kernel that
@@ -14,7 +14,7 @@ from tests import util
 from tests.util import GOLDEN
 
 FIELDS = ("nz", "feat", "mode", "vx", "nc", "gen", "lpo", "md", "vf", "ss", "sy", "walk")
-FEAT = {0: "BANDS", 2: "DCTC", 3: "LP", 4: "LPD"}            # kernel_common.h: FeatMode
+FEAT = {0: "BANDS", 2: "DCTC", 3: "LP", 4: "LPD"}            # layout_constants.h: FeatMode
 GEN = {0: "plain", 1: "inld", 2: "exten", 3: "full", 4: "full"}  # GEN_PLAIN .. GEN_DC1 (-remove_dc1 is the run-time-flag kernel too)
 
 with open(os.path.join(GOLDEN, "frontend_selection.json")) as f:
@@ -36,7 +36,7 @@ def name_of(sel):
 
 
 def is_dual(sel):
-    """frontend_kernel.h, fe_dual: the instantiations whose window table is scaled by 1/2."""
+    """layout_constants.h, fe_dual: the instantiations whose window table is scaled by 1/2."""
     k = dict(zip(FIELDS, sel))
     return k["mode"] == 0 and k["gen"] in (0, 1) and not k["vx"] and k["nz"] < 16 and not (k["vf"] or k["ss"] or k["sy"])
 

@@ -18,7 +18,7 @@ REACH = [(HI, 40), (B64, 65), (HI + ["-fea_c0", "off"], 39), (K8, 40), (HI + ["-
          (HI + ["-nr_mode", "exten"], 40), (HI + ["-fea_delta", "d_a"], 120),
          (C2 + ["-fea_ncepcoefs", "30"], 31), (C2 + ["-fb_definition", "1-30/30filters", "-fea_ncepcoefs", "29", "-fea_Z_exp", "500"], 30)]
 FIELDS = ("nz", "feat", "mode", "vx", "nc", "gen", "lpo", "md", "vf", "ss", "sy", "walk")
-BANDS, DCTC = 0, 2   # kernel_common.h: FeatMode
+BANDS, DCTC = 0, 2   # layout_constants.h: FeatMode
 
 
 def ident(c):
