@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "libctu_engine.so")
 CLI = os.path.join(ROOT, "bin", "ctucopy")
 SYNTH_LIB = os.path.join(HERE, "libctu_synth.so")  # the input generator alone (include/ctu_synth.h): no HIP runtime behind it
 
-ENGINE_SRCS = ["engine.hip", "accept.cc", "tables.cc", "opts.cc", "design.cc", "synth.cc"]
+ENGINE_SRCS = ["engine.hip", "accept.cc", "tables.cc", "plan.cc", "opts.cc", "design.cc", "synth.cc"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 

@@ -1,8 +1,9 @@
-// MI355X (gfx950) engine: host side of the C ABI (include/ctu_engine.h) - uploads of the tables, plans (batch layout, tile chains),
-// launches.  What is accepted (accept.cc), which front-end instantiation runs and what the tables hold (tables.cc) is decided in host-only
-// units of their own; this unit uploads their EngineTables value and launches by it.  The kernels live in the headers included below, in
-// one translation unit:
-//   kernel_common.h    the kernel parameter block, DPP / LDS helpers, tile records (layout_constants.h: every constant host-only code shares)
+// MI355X (gfx950) engine: host side of the C ABI (include/ctu_engine.h) - uploads of the tables and of the plans, launches.  What is
+// accepted (accept.cc), which front-end instantiation runs and what the tables hold (tables.cc), and the plan of an offline run - batch
+// layout, tile chains, the stages' lists, the size of every scratch buffer (plan.cc) - is decided in host-only units of their own; this
+// unit uploads their EngineTables and HostPlan values, allocates by them and launches by them.  The kernels live in the headers included
+// below, in one translation unit:
+//   kernel_common.h    the kernel parameter block, DPP / LDS helpers (layout_constants.h: every constant host-only code shares, the tile record)
 //   frontend_kernel.h  PCM -> pre-emphasis * Hamming -> 512/256-pt real FFT in registers -> |.|^2 (P tile in LDS)
 //                      -> exten NR -> banded filter bank -> ^0.33 / log -> DCT-II + lifter | cosine iDFT + Levinson
 //   vad_kernels.h      Burg-cepstral criterion (packed inverse FFT + lattice), the detector's recurrences per utterance (one wave, or one
@@ -35,7 +36,6 @@
 #include <functional>
 #include <memory>
 #include <mutex>
-#include <queue>
 #include <set>
 #include <string>
 #include <vector>
@@ -44,6 +44,7 @@
 #include "accept.h"
 #include "design.h"
 #include "opts.h"
+#include "plan_host.h"
 #include "tables.h"
 
 #include "kernel_common.h"
@@ -132,26 +133,24 @@ struct ctu_engine {
     // -vad file=<f> (tab.ss_file): ONE byte stream for all files of the process, a byte per frame, never rewound (nr.cc:205-209, 273, 297-302)
     std::vector<unsigned char> vad_stream;
     int64_t vad_pos = 0;
-    bool per_wave = false;  // chains per wave (state along an utterance lives in a wave's registers)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     bool host_timed = false;    // the last run was a host run cut into ranges: host_kernel_ms = sum over the ranges' front-end launches
     float host_kernel_ms = 0.f;
     bool in_signal_call = false;
-    bool rows_in = false;   // -format_in htk: runs start from rows (ctu_engine_run_rows), no front end, no tables
     // CMVN (row N2): statistic slot <-> row column maps, and per-call scratch
     std::vector<int> col_of_slot, slot_of_col;
     DevBuf<int> d_col_of_slot, d_slot_of_col, d_spk;
     DevBuf<double> d_stat_a, d_stat_b;
     DevBuf<unsigned long long> stamps;
     std::set<const void *> attr_done;  // kernels whose dynamic-LDS limit has been raised on this engine's device
-    bool do_vad = false;
+    ctu::PlanGeom geom;     // what a plan needs to know of this engine, and which lists and buffers its stages need (plan_host.h)
     VadParams vp;
     KParams kp0;    // the kernels' parameter blocks as far as design and tables fix them (ctu_engine_create); a run adds its buffers
     BigParams bp0;  // (`big` only)
 };
 
-// What a run covers of a plan's buffers: a plan's own extent is the whole of it (plan_layout, plan_chains, ctu_plan_create), a push of
+// What a run covers of a plan's buffers: a plan's own extent is the whole of it (ctu_plan_create), a push of
 // a stream set runs the front of its set's plan with the extent of the push (streams_host.h).  Every stage launches by the extent it is
 // given; a plan is not written once it is created.
 struct RunExtent {
@@ -164,9 +163,7 @@ struct RunExtent {
 
 struct ctu_plan {
     ctu_engine *eng = nullptr;
-    int n_utt = 0;
-    std::vector<int64_t> nsamples, sample_off, row_off, frames;
-    int64_t total_samples = 0;
+    ctu::HostPlan hp;           // the plan itself (plan_host.h); what follows are its images on the device, the scratch it sizes, and run state
     RunExtent ext;              // the whole plan
     DevBuf<TileRec> tiles;
     DevBuf<int> wg_first;
@@ -194,28 +191,23 @@ struct ctu_plan {
     DevBuf<float> ss_seed, ss_last;  // SS: noise seeds per utterance [n_utt][K] and the vectors the utterances leave behind
     DevBuf<unsigned char> ss_dirty;  // SS: utterances a pass of the seed iteration recomputes
     DevBuf<unsigned char> ss_vbits;  // SS: the detector's decision of every frame (first pass), reused by the later passes
-    DevBuf<float2> xri;         // VAD scratch
+    DevBuf<float2> xri;         // the exported spectra (PlanGeom::spectra)
     DevBuf<float> pnr;
     DevBuf<float> pss;          // hwss / fwss / 2fwss with speech output at 2048 / 4096 points: the subtracted magnitudes (pnr stays as exported)
     DevBuf<double> vad_ci;
     DevBuf<float> vad_cf;      // fused Burg-cepstral VAD: cepstra of every frame [total_frames][VFC_STRIDE] ahead of vad_lanes_kernel
     DevBuf<int> vf_order;      // utterances with at least one frame, longest first (a wave of vad_lanes_kernel takes 16 in a row)
-    int n_live = 0;
     DevBuf<int64_t> d_row_off;
     DevBuf<double> dc1m;       // -remove_dc1: frame means, then
     DevBuf<float> dc1;         // the offsets the frames subtract (decode_kernels.h)
-    int max_frames = 0;        // longest utterance of the plan
     // scratch between the kernels of one run; owned by the plan, so plans can run concurrently on different streams
     DevBuf<float> logmel;      // TRAP: log-mel rows [total_frames][B]
     DevBuf<double> lp_r;       // LP kinds: autocorrelation lags [total_frames][lporder + 1] (used as float rows by the fp32 path) ahead of lp_tail_kernel
     DevBuf<float> base_rows;   // front-end rows ahead of the delta / stacking / CMS passes [total_frames][Dbase]
     DevBuf<float> ybuf;        // signal output: time-domain frames ahead of the overlap-add [total_frames][window]
-    std::vector<int64_t> out_samples;   // signal output: samples written per utterance
     DevBuf<long long> d_sample_off;
-    // TRAP
     DevBuf<int4> utt_info;
     DevBuf<int> trap_chunks, trap_chunks128;   // (utterance, first frame) of every 64- / 128-frame chunk
-    int n_trap_chunks = 0, n_trap_chunks128 = 0;
 };
 
 namespace {
@@ -326,14 +318,6 @@ void launch_lds(ctu_engine *e, K kern, dim3 grid, dim3 block, size_t shm, hipStr
     hipLaunchKernelGGL(kern, grid, block, shm, s, args...);
 }
 
-// ---- what ctu_plan_create allocates for and the runs launch by, one name each
-// The LP kinds' recursions run in lp_tail_kernel, on the lags the front end or wave1k_kernel left (bigfft_kernel and bigss_kernel finish the LP
-// analysis themselves; nothing is projected with speech output)
-bool lp_tail_runs(const ctu_engine *e) { return (e->tab.feat == FEAT_LP || e->tab.feat == FEAT_LPD) && (!e->tab.big || e->tab.path == BIG_WAVE1K) && !e->design->signal_out; }
-// its lags are double: LP analysis on uncompressed band energies, and wave1k_kernel's lags
-bool lags_double(const ctu_engine *e) { return e->tab.feat == FEAT_LPD || e->tab.big; }
-// hwss / fwss / 2fwss with speech output at 2048 / 4096 points: the synthesis reads the subtracted magnitudes (pss), pnr stays as exported
-bool synth_reads_pss(const ctu_engine *e) { return e->tab.big && e->tab.ss && e->design->signal_out; }
 // NIT of the large-FFT kernels (samples per thread of a workgroup's 256): 4, 8 or 16
 int big_nit(const ctu_engine *e) { return e->design->wfft / 256; }
 
@@ -348,7 +332,7 @@ KParams engine_kparams(const ctu_engine *e) {
     kp.band_to_scratch = d.kind == ctu::FeaKind::TrapDct ? 1 : e->tab.dctw ? 2 : 0;  // 2: the bands to the scratch, the energy column (-fea_E) to its slot of the row
     kp.lp_is_lpa = d.kind == ctu::FeaKind::Lpa;
     kp.syn_scale = 1.0f / (float)d.wfft;
-    kp.vad_export = (signal && !e->tab.sel.sy) ? 1 : ((!e->do_vad || e->tab.sel.vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0)));
+    kp.vad_export = (signal && !e->tab.sel.sy) ? 1 : ((!e->geom.do_vad || e->tab.sel.vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0)));
     kp.vad_nc = e->vp.ncoef;
     kp.ss_mode = e->tab.ss; kp.ss_init = d.o.nr_initsegs; kp.ss_nc = d.o.fea_ncepcoefs; kp.han_off = t.han_off;
     kp.nr_b = (float)d.o.nr_b; kp.ss_q = d.o.nr_q;
@@ -371,7 +355,7 @@ KParams engine_kparams(const ctu_engine *e) {
     kp.fb_power = d.o.fb_power; kp.fb_inld = d.o.fb_inld; kp.lifter_on = d.o.fea_lifter > 1;
     kp.nr_exten = d.o.nr_mode == "exten"; kp.nr_after_fb = d.o.nr_when_afterFB ? 1 : 0;
     kp.nr_p = (float)d.o.nr_p; kp.nr_p_d = d.o.nr_p; kp.nr_a = (float)d.o.nr_a;
-    kp.per_wave = e->per_wave ? 1 : 0;
+    kp.per_wave = e->geom.per_wave ? 1 : 0;
     return kp;
 }
 // ... and of the large-FFT kernels, from the block above
@@ -402,7 +386,7 @@ KParams run_kparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent &x,
     const ctu::Design &d = *e->design;
     KParams kp = e->kp0;
     kp.pcm = d_pcm;
-    kp.rows = (d.post_order > 0 || d.cms) ? pl->base_rows.p : d_rows;
+    kp.rows = e->geom.staged ? pl->base_rows.p : d_rows;
     kp.logmel = pl->logmel.p; kp.xri = pl->xri.p; kp.pnr = pl->pnr.p; kp.ybuf = pl->ybuf.p;
     kp.vad_ci = pl->vad_ci.p; kp.vad_cf = pl->vad_cf.p; kp.lp_r = pl->lp_r.p; kp.dc1 = pl->dc1.p;
     kp.tiles = pl->tiles.p; kp.wg_first = x.heads; kp.tile_utt = pl->tile_utt.p;
@@ -417,11 +401,10 @@ BigParams run_bigparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent
     BigParams bp = e->bp0;
     bp.pcm = kp.pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = x.n_tiles;
     bp.chain_first = x.heads; bp.n_chains = (int)pl->wg_first.n;  // (the count is the plan's: no stream set runs chains on the large-FFT kernels)
-    bp.vad_en = (e->do_vad && e->vp.cri == 0) ? pl->pnr.p : nullptr;
+    bp.vad_en = e->geom.vad_energy ? pl->pnr.p : nullptr;
     bp.dc1 = pl->dc1.p;
     // the spectra leave bigfft_kernel for bigsynth_kernel, bigburg_kernel (which reads them; the rows are projected as well) or bigss_kernel
-    const bool exported = e->design->signal_out || (e->do_vad && e->vp.cri == 1) || e->tab.ss;
-    bp.xri = exported ? pl->xri.p : nullptr; bp.pnr = exported ? pl->pnr.p : nullptr;
+    bp.xri = e->geom.spectra ? pl->xri.p : nullptr; bp.pnr = e->geom.spectra ? pl->pnr.p : nullptr;
     bp.pss = pl->pss.p;
     bp.ss_seed = pl->ss_seed.p; bp.ss_last = pl->ss_last.p; bp.ss_dirty = pl->ss_dirty.p; bp.ss_vbits = pl->ss_vbits.p; bp.tile_utt = pl->tile_utt.p;
     return bp;
@@ -433,16 +416,16 @@ BigParams run_bigparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent
 // -remove_dc1: the frames' means, then the offsets the frames subtract (decode_kernels.h)
 void stage_dc1(const ctu_engine *e, const ctu_plan *pl, hipStream_t s, const int16_t *d_pcm) {
     const ctu::Design &d = *e->design;
-    const int gx = std::max(1, std::min((pl->max_frames + 3) / 4, 64));
-    hipLaunchKernelGGL(dc1_means_kernel, dim3(gx, pl->n_utt), dim3(256), 0, s, d_pcm, pl->utt_info.p, pl->d_sample_off.p, pl->dc1m.p, pl->n_utt, d.window, d.wshift);
-    hipLaunchKernelGGL(dc1_offsets_kernel, dim3((pl->n_utt + 63) / 64), dim3(64), 0, s, pl->dc1m.p, pl->utt_info.p, pl->dc1.p, pl->n_utt, d.window, d.wshift);
+    const int gx = std::max(1, std::min((pl->hp.max_frames + 3) / 4, 64));
+    hipLaunchKernelGGL(dc1_means_kernel, dim3(gx, pl->hp.n_utt), dim3(256), 0, s, d_pcm, pl->utt_info.p, pl->d_sample_off.p, pl->dc1m.p, pl->hp.n_utt, d.window, d.wshift);
+    hipLaunchKernelGGL(dc1_offsets_kernel, dim3((pl->hp.n_utt + 63) / 64), dim3(64), 0, s, pl->dc1m.p, pl->utt_info.p, pl->dc1.p, pl->hp.n_utt, d.window, d.wshift);
 }
 
 // bigfft_kernel: a workgroup per frame over the tile list, as many as fit the chip at once; with exten one workgroup per chain of utterances
 void launch_bigfft(ctu_engine *e, const RunExtent &x, hipStream_t s, const BigParams &bp) {
     const LdsFit fit = bigfft_lds(*e->design, e->tab.feat, e->tab.p2.ncoef_out, e->tab.big_fb_total);
     if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
-    if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without chains");
+    if (bp.nr_exten && !e->geom.per_wave) throw std::runtime_error("internal: exten without chains");
     const dim3 g((unsigned)std::max(1, bp.nr_exten ? bp.n_chains : std::min(x.n_tiles, e->n_cu * fit.per_cu)));
     lift<4, 8, 16>(big_nit(e), [&](auto nit) {
         constexpr int NIT = decltype(nit)::value;
@@ -455,7 +438,7 @@ void stage_wave1k(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStre
     const ctu::Design &d = *e->design;
     const LdsFit fit = wave1k_lds(d, e->tab.feat, e->tab.p2.ncoef_out, e->tab.big_fb_total);
     if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the 1024-point kernel");
-    if (bp.nr_exten && !e->per_wave) throw std::runtime_error("internal: exten without per-wave chains");
+    if (bp.nr_exten && !e->geom.per_wave) throw std::runtime_error("internal: exten without per-wave chains");
     // exten: one wave per chain of utterances, every chain gets its wave whatever fits the chip at once
     const int wg = bp.nr_exten ? std::max(1, (bp.n_chains + W1K_WAVES - 1) / W1K_WAVES)
                                : std::max(1, std::min((x.n_tiles + W1K_WAVES - 1) / W1K_WAVES, e->n_cu * fit.per_cu));
@@ -483,13 +466,13 @@ std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, const
             });
         });
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->n_utt, nc, d.o.nr_initsegs,
+        hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->hp.n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->hp.n_utt, nc, d.o.nr_initsegs,
                            (double)d.o.nr_p, (double)d.o.nr_q, pl->ss_vbits.p);
         HIP_TRY(hipGetLastError());
     }
     const LdsFit fit = bigss_lds(d, e->tab.feat, e->tab.p2.ncoef_out, e->tab.big_fb_total);
     if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
-    if (!e->per_wave) throw std::runtime_error("internal: hwss / fwss / 2fwss without chains");
+    if (!e->geom.per_wave) throw std::runtime_error("internal: hwss / fwss / 2fwss without chains");
     return [e, s, &bp, shm = fit.bytes] {
         lift<8, 16>(big_nit(e), [&](auto nit) {
             launch_lds(e, &bigss_kernel<decltype(nit)::value>, dim3((unsigned)std::max(1, bp.n_chains)), dim3(256), shm, s, bp);
@@ -506,7 +489,7 @@ std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, const
 template <class Pass>
 int run_ss_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, KParams &kp, Pass &&pass) {
     const ctu::Design &d = *e->design;
-    const size_t nk = (size_t)pl->n_utt * d.K;
+    const size_t nk = (size_t)pl->hp.n_utt * d.K;
     std::vector<float> seed(nk, 0.f), last(nk, 0.f), next(nk, 0.f);
     if (e->ss_stale.size() != (size_t)d.K) e->ss_stale.assign(d.K, 0.f);
     // new_file() seeds the estimate from the vector and then scales the vector by 0.1 (nr.cc:217-220, 402-407); a
@@ -521,9 +504,9 @@ int run_ss_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStrea
     };
     auto propagate = [&](std::vector<float> &dst) {  // seeds of every file from `last` (files with frames) and e->ss_stale
         int prev = -1, skipped = 0;
-        for (int i = 0; i < pl->n_utt; i++) {
+        for (int i = 0; i < pl->hp.n_utt; i++) {
             scaled(&dst[(size_t)i * d.K], prev >= 0 ? &last[(size_t)prev * d.K] : e->ss_stale.data(), skipped);
-            if (pl->frames[i] > 0) {
+            if (pl->hp.frames[i] > 0) {
                 prev = i;
                 skipped = 0;
             } else
@@ -534,7 +517,7 @@ int run_ss_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStrea
     propagate(seed);  // `last` is still zero: only the seeds ahead of the first file with a frame are final
     // An utterance's rows and last vector depend on its samples and its seed only: a pass recomputes just the utterances
     // whose seed changed since the pass before (all of them in the first one).
-    std::vector<unsigned char> dirty(std::max(pl->n_utt, 1), 1);
+    std::vector<unsigned char> dirty(std::max(pl->hp.n_utt, 1), 1);
     if (e->tab.ss_file) {
         // -vad file=<f>: `char vad = fgetc(fvad); if (vad != EOF) return bool(vad); else throw` (nr.cc:297-302), one byte per frame in
         // list order, the stream running on from file to file and from run to run.  Every byte but NUL is speech; a byte 0xFF
@@ -562,12 +545,12 @@ int run_ss_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStrea
         HIP_TRY(hipStreamSynchronize(s));
         propagate(next);
         bool any = false;
-        for (int i = 0; i < pl->n_utt; i++) {
+        for (int i = 0; i < pl->hp.n_utt; i++) {
             dirty[i] = std::memcmp(&next[(size_t)i * d.K], &seed[(size_t)i * d.K], d.K * sizeof(float)) != 0;
             any = any || dirty[i];
         }
         if (!any) break;
-        if (iter > pl->n_utt) throw std::runtime_error("internal: noise seeds of the *ss chain did not settle");
+        if (iter > pl->hp.n_utt) throw std::runtime_error("internal: noise seeds of the *ss chain did not settle");
         seed = next;
     }
     // what this run leaves for the next one
@@ -588,9 +571,9 @@ void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStr
     tp.lifter_on = kp.lifter_on; tp.e_mode = kp.e_mode; tp.e_slot = kp.e_slot;
     tp.inv_stride = (unsigned)((1ull << 32) / (unsigned)tp.stride) + 1u;
     tp.inv_D = (unsigned)((1ull << 32) / (unsigned)tp.D) + 1u;
-    const LdsFit fit = lp_tail_lds(tp.stride, tp.D, lags_double(e));
+    const LdsFit fit = lp_tail_lds(tp.stride, tp.D, e->geom.lags_double);
     const dim3 tg((unsigned)std::max<int64_t>(1, std::min<int64_t>((x.total_frames + 255) / 256, (int64_t)e->n_cu * fit.per_cu)));
-    if (lags_double(e)) launch_lds(e, &lp_tail_kernel<double, 0>, tg, dim3(256), fit.bytes, s, tp);
+    if (e->geom.lags_double) launch_lds(e, &lp_tail_kernel<double, 0>, tg, dim3(256), fit.bytes, s, tp);
     else if (kp.lporder == 12 && kp.ncep == 12 && !kp.lp_is_lpa) launch_lds(e, &lp_tail_kernel<float, 12>, tg, dim3(256), fit.bytes, s, tp);
     else launch_lds(e, &lp_tail_kernel<float, 0>, tg, dim3(256), fit.bytes, s, tp);
     HIP_TRY(hipGetLastError());
@@ -601,7 +584,7 @@ void stage_lp_tail(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStr
 void stage_burg_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s) {
     const ctu::Design &d = *e->design;
     const int cap = e->vp.ncoef <= 16 ? 16 : 32;
-    if (e->vp.cri == 1 && e->tab.big && x.total_frames > 0) {
+    if (e->tab.big && x.total_frames > 0) {
         const LdsFit fit = bigburg_lds(d.wfft);
         const dim3 g((unsigned)std::min<int64_t>(x.total_frames, (int64_t)e->n_cu * fit.per_cu));
         lift<4, 8, 16>(big_nit(e), [&](auto nit) {
@@ -610,7 +593,7 @@ void stage_burg_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipSt
                            (int64_t)x.total_frames, e->big_tw.p);
             });
         });
-    } else if (e->vp.cri == 1 && !e->tab.sel.vf && !e->tab.big) {
+    } else if (!e->tab.big) {
         const dim3 g((unsigned)std::min<int64_t>((x.total_frames + 3) / 4, (int64_t)e->n_cu * 4));
         const size_t bshm = (512 + (size_t)4 * 2 * (d.wfft / 2 + 4)) * 2 * sizeof(vreal);
         lift<4, 8>(d.window <= 256 ? 4 : 8, [&](auto q) {
@@ -631,13 +614,13 @@ void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
     if (e->tab.trap_bf16) {
         constexpr int NT16 = CTU_TRAP_F16 ? 2 : 3;
         const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16;
-        hipLaunchKernelGGL((trapdct_split16_kernel<CTU_TRAP_F16 != 0>), dim3(std::max(pl->n_trap_chunks128, 1)), dim3(512), shm16, s,
-                           pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->n_trap_chunks128, d.B, nd, d.D);
+        hipLaunchKernelGGL((trapdct_split16_kernel<CTU_TRAP_F16 != 0>), dim3(std::max(pl->hp.n_chunks128, 1)), dim3(512), shm16, s,
+                           pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->hp.n_chunks128, d.B, nd, d.D);
     } else {
         const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float);
         lift<1, 2>(nd <= 16 ? 1 : 2, [&](auto nrb) {
             lift<26, 64>(ns <= 26 ? 26 : 64, [&](auto nsm) {
-                hipLaunchKernelGGL((trapdct_mfma_kernel<decltype(nrb)::value, decltype(nsm)::value>), dim3(pl->n_trap_chunks), dim3(256), shm, s, pl->logmel.p, d_rows,
+                hipLaunchKernelGGL((trapdct_mfma_kernel<decltype(nrb)::value, decltype(nsm)::value>), dim3(pl->hp.n_chunks), dim3(256), shm, s, pl->logmel.p, d_rows,
                                    e->trapG.p, pl->utt_info.p, pl->trap_chunks.p, d.B, tl, nd, d.D);
             });
         });
@@ -680,10 +663,10 @@ void stage_post(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
     const ctu::Design &d = *e->design;
     size_t shm = 0;
     const PostParams pp = post_params(d, &shm);
-    const int pgrid = std::min(pl->n_trap_chunks, e->n_cu * 8);
+    const int pgrid = std::min(pl->hp.n_chunks, e->n_cu * 8);
     const bool std39 = !d.post_stack && d.post_order == 2 && pp.fea_c == 13 && d.Dbase == 13 && d.D == 39 && pp.w[0] == 2 && pp.w[1] == 2;
     lift<0, 1>(std39, [&](auto v) {
-        hipLaunchKernelGGL(post_kernel<decltype(v)::value != 0>, dim3(pgrid), dim3(256), shm, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->trap_chunks.p, pl->n_trap_chunks, pp);
+        hipLaunchKernelGGL(post_kernel<decltype(v)::value != 0>, dim3(pgrid), dim3(256), shm, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->trap_chunks.p, pl->hp.n_chunks, pp);
     });
     HIP_TRY(hipGetLastError());
 }
@@ -699,9 +682,9 @@ CmsParams cms_params(const ctu::Design &d) {
 void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
     const ctu::Design &d = *e->design;
     const CmsParams cp = cms_params(d);
-    if (d.cms == 1) hipLaunchKernelGGL(cms_exp_kernel, dim3((pl->n_utt + 1) / 2), dim3(64), 0, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->n_utt, cp);
+    if (d.cms == 1) hipLaunchKernelGGL(cms_exp_kernel, dim3((pl->hp.n_utt + 1) / 2), dim3(64), 0, s, pl->base_rows.p, d_rows, pl->utt_info.p, pl->hp.n_utt, cp);
     else
-        hipLaunchKernelGGL(cms_block_kernel, dim3(pl->n_trap_chunks), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, pl->base_rows.p, d_rows,
+        hipLaunchKernelGGL(cms_block_kernel, dim3(pl->hp.n_chunks), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, pl->base_rows.p, d_rows,
                            pl->utt_info.p, pl->trap_chunks.p, cp);
     HIP_TRY(hipGetLastError());
 }
@@ -712,7 +695,7 @@ void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipS
     if (CTU_VF_A2C)
         hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((x.total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)x.total_frames);
     if (replay) lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
-        hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((pl->n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->n_live,
+        hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((pl->hp.n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->hp.n_live,
                            pl->d_row_off.p, d_vad, e->vp);
     });
     HIP_TRY(hipGetLastError());
@@ -721,7 +704,7 @@ void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipS
 // After the post passes: the `fea` criterion reads the vector the writer sees (CMS applied), and the energy
 // column is shifted in the finished rows.
 void stage_vad_decide(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows, uint8_t *d_vad) {
-    hipLaunchKernelGGL(vad_decide_kernel, dim3(pl->n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->pnr.p, d_rows, pl->d_row_off.p, pl->n_utt, d_vad, e->vp);
+    hipLaunchKernelGGL(vad_decide_kernel, dim3(pl->hp.n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->pnr.p, d_rows, pl->d_row_off.p, pl->hp.n_utt, d_vad, e->vp);
     HIP_TRY(hipGetLastError());
 }
 
@@ -729,7 +712,7 @@ void stage_vad_decide(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d
 // BATCH::flush_vad's loop does not start (src/vad/vad.cc:742-745, src/io/batch.cc:243-249): the reference writes neither a
 // row nor a decision for it.  Its decision bytes become NUL ("nothing written"); ctu_engine_run_host reports 0 rows.
 void stage_short_files(ctu_engine *e, const ctu_plan *pl, hipStream_t s, uint8_t *d_vad) {
-    hipLaunchKernelGGL(vad_short_files_kernel, dim3((unsigned)((pl->n_utt + 255) / 256)), dim3(256), 0, s, d_vad, pl->d_row_off.p, pl->n_utt,
+    hipLaunchKernelGGL(vad_short_files_kernel, dim3((unsigned)((pl->hp.n_utt + 255) / 256)), dim3(256), 0, s, d_vad, pl->d_row_off.p, pl->hp.n_utt,
                        (e->design->o.vad_filter_order - 1) / 2);
     HIP_TRY(hipGetLastError());
 }
@@ -751,7 +734,7 @@ void launch_bigsynth(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipS
     const LdsFit fit = bigsynth_lds(d.wfft);
     const int g = (int)std::min<int64_t>(x.total_frames, (int64_t)e->n_cu * fit.per_cu);
     lift<4, 8, 16>(big_nit(e), [&](auto nit) {
-        launch_lds(e, &bigsynth_kernel<decltype(nit)::value>, dim3(g), dim3(256), fit.bytes, s, pl->xri.p, synth_reads_pss(e) ? pl->pss.p : pl->pnr.p, pl->ybuf.p,
+        launch_lds(e, &bigsynth_kernel<decltype(nit)::value>, dim3(g), dim3(256), fit.bytes, s, pl->xri.p, e->geom.pss ? pl->pss.p : pl->pnr.p, pl->ybuf.p,
                    (long long)x.total_frames, d.wfft, d.window, inv_n, e->big_tw.p);
     });
     HIP_TRY(hipGetLastError());
@@ -897,16 +880,14 @@ int ctu_engine_create(int argc, const char *const *argv, int device, ctu_engine 
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         e->device = device;
         e->n_cu = prop.multiProcessorCount;
-        e->rows_in = e->design->rows_in;
-        if (e->rows_in) e->kname = "rows_ingest_kernel";  // no front end: no tables, no parameter blocks
+        if (e->design->rows_in) e->kname = "rows_ingest_kernel";  // no front end: no tables, no parameter blocks
         else {
             e->tab = build_engine_tables(*e->design);
             build_tables(e.get());
         }
-        e->do_vad = e->design->o.do_vad();
-        e->per_wave = e->design->o.nr_mode == "exten" || e->tab.ss;  // state along an utterance (exten, the *ss modes): a wave per chain
+        e->geom = plan_geom(*e->design, e->tab, e->sp, e->n_cu);
         e->vp = vad_params(*e->design, e->sp);
-        if (!e->rows_in) e->kp0 = engine_kparams(e.get());
+        if (!e->geom.rows_in) e->kp0 = engine_kparams(e.get());
         if (e->tab.big) e->bp0 = engine_bigparams(e.get());
         HIP_TRY(hipEventCreate(&e->ev0));
         HIP_TRY(hipEventCreate(&e->ev1));
@@ -936,355 +917,91 @@ int ctu_engine_dims(const ctu_engine *e, ctu_dims *out) {
     return CTU_OK;
 }
 
-int64_t ctu_num_frames(const ctu_engine *e, int64_t n) {
-    if (e->rows_in) return n < 0 ? -1 : n;  // the "samples" of a feature file are its rows
-    const int pre = e->design->window - e->design->wshift;
-    if (n < pre) return -1;
-    return (n - pre) / e->design->wshift;
-}
-
-int64_t ctu_arena_layout(const int64_t *utt_nsamples, int32_t n_utt, int64_t *sample_off) {
-    if (n_utt < 0 || (n_utt && !utt_nsamples)) return CTU_ERR_INPUT;
-    int64_t so = PCM_HEAD;
-    for (int i = 0; i < n_utt; i++) {
-        if (utt_nsamples[i] < 0) return CTU_ERR_INPUT;
-        if (sample_off) sample_off[i] = so;
-        so += (utt_nsamples[i] + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN;
-    }
-    if (sample_off) sample_off[n_utt] = so;
-    return so + PCM_TAIL;  // loads run to the end of the last 32-sample row of a frame
-}
-
-int64_t ctu_rows_arena_layout(const int64_t *utt_rows, int32_t n_utt, int32_t width, int64_t *word_off) {
-    if (n_utt < 0 || width < 1 || (n_utt && !utt_rows)) return CTU_ERR_INPUT;
-    int64_t wo = 0;
-    for (int i = 0; i < n_utt; i++) {
-        if (utt_rows[i] < 0) return CTU_ERR_INPUT;
-        if (word_off) word_off[i] = wo;
-        wo += (utt_rows[i] * width + ROWS_ALIGN - 1) / ROWS_ALIGN * ROWS_ALIGN;
-    }
-    if (word_off) word_off[n_utt] = wo;
-    return wo;  // rows_ingest_kernel reads an utterance's own words only: no padding around the arena
-}
+int64_t ctu_num_frames(const ctu_engine *e, int64_t n) { return plan_num_frames(e->geom, n); }
+int64_t ctu_arena_layout(const int64_t *utt_nsamples, int32_t n_utt, int64_t *sample_off) { return arena_layout(utt_nsamples, n_utt, sample_off); }
+int64_t ctu_rows_arena_layout(const int64_t *utt_rows, int32_t n_utt, int32_t width, int64_t *word_off) { return rows_arena_layout(utt_rows, n_utt, width, word_off); }
 
 namespace {
-// The host side of a plan between the three steps of ctu_plan_create: plan_layout fills it, plan_chains links the tiles, plan_alloc uploads it.
-struct PlanHost {
-    std::vector<TileRec> tiles;
-    std::vector<int> uts;       // first tile of every utterance, n_tiles at the end
-    std::vector<int4> uinfo;    // (first row: low, high word; frames; 0) of every utterance
-    std::vector<int> chunks;    // (utterance, first frame) of every 64-frame chunk
-    std::vector<int> wg_first;  // first tile of every chain (plan_chains)
-};
-
-// Step 1, host only, for both kinds of plan: where every utterance sits in the arena and in the rows, the refusals, its tiles and
-// 64-frame chunks, the totals.  The two kinds differ in the arena's layout rule, in what a length counts (ctu_num_frames: samples
-// against the rows themselves, -format_in htk), in the arena elements between two frames, and in a refusal each.
-int plan_layout(ctu_engine *e, ctu_plan *pl, const int64_t *utt_n, int32_t n_utt, PlanHost &h) {
-    static_assert(TILE == 64, "the chunk list of the TRAP / delta / CMS / CMVN passes (64 frames per workgroup) is the tile list");
-    const ctu::Design &d = *e->design;
-    const bool rows = e->rows_in;
-    pl->eng = e;
-    pl->n_utt = n_utt;
-    pl->nsamples.assign(utt_n, utt_n + n_utt);
-    pl->sample_off.resize(n_utt + 1);
-    pl->row_off.resize(n_utt + 1);
-    pl->frames.resize(n_utt);
-    pl->total_samples = rows ? ctu_rows_arena_layout(utt_n, n_utt, d.Dbase, pl->sample_off.data()) : ctu_arena_layout(utt_n, n_utt, pl->sample_off.data());
-    if (pl->total_samples < 0) {
-        set_error(e, "ENGINE: negative utterance length");
-        return CTU_ERR_INPUT;
-    }
-    const int64_t stride = rows ? d.Dbase : d.wshift;  // arena elements from one frame to the next
-    int wmax = 0;
-    for (int j = 0; j < d.post_order; j++) wmax = std::max(wmax, d.post_w[j]);
-    h.uts.assign(n_utt + 1, 0);
-    h.uinfo.resize(n_utt);
-    std::vector<TileRec> tiles;  // local, moved into `h` behind the loop: pushing through `h` measured 3 % on plan creation (profiles/host_pipeline_ab.txt)
-    std::vector<int> chunks;
-    int64_t ro = 0;
-    for (int i = 0; i < n_utt; i++) {
-        const int64_t T = ctu_num_frames(e, utt_n[i]);
-        if (T < 0) {
-            set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277
-            return CTU_ERR_INPUT;
-        }
-        if (rows && T > 0x7fffffff / 2) {
-            set_error(e, "ENGINE: feature file too long");
-            return CTU_ERR_INPUT;
-        }
-        // With exactly window+1 frames a stage never takes its steady-state branch, so its flush starts from ring
-        // slot 0 instead of the oldest slot and the emitted rows mix frames (src/fea/fea_delta.cc:118,183-186);
-        // with fewer it reads slots that were never written.  Neither is a feature worth reproducing.
-        if (d.post_order > 0 && T > 0 && T < wmax + 2) {
-            set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
-            return CTU_ERR_INPUT;
-        }
-        if (!rows && d.kind == ctu::FeaKind::TrapDct && T > 0 && T < (d.o.fea_trapdct_traplen + 1) / 2) {
-            set_error(e, "ENGINE: trapdct on fewer than (traplen+1)/2 frames is undefined in the reference (src/fea/fea_trap.cc:64-70)");
-            return CTU_ERR_INPUT;
-        }
-        const int64_t so = pl->sample_off[i];
-        pl->row_off[i] = ro;
-        pl->frames[i] = T;
-        h.uts[i] = (int)tiles.size();
-        for (int64_t t0 = 0; t0 < T; t0 += TILE) {
-            TileRec r;
-            r.sbase = so + t0 * stride;
-            r.rbase = ro + t0;
-            r.nvalid = (int)std::min<int64_t>(TILE, T - t0);
-            r.t0 = (int)t0;
-            r.next = -1;
-            r.T = (int)T;
-            tiles.push_back(r);
-            chunks.push_back(i);
-            chunks.push_back((int)t0);
-        }
-        h.uinfo[i] = make_int4((int)(ro & 0xffffffff), (int)(ro >> 32), (int)T, 0);
-        pl->max_frames = std::max<int>(pl->max_frames, (int)T);
-        ro += T;
-    }
-    h.uts[n_utt] = (int)tiles.size();
-    pl->row_off[n_utt] = ro;
-    pl->ext.total_frames = ro;
-    pl->ext.n_tiles = (int)tiles.size();
-    h.tiles = std::move(tiles);
-    h.chunks = std::move(chunks);
-    return CTU_OK;
-}
-
-// Front-end workgroups the chip holds at once: two per CU when the instantiation keeps to 128 VGPRs (four waves per SIMD) and 80 KB of LDS; the
-// synthesis and the 512-point detector instantiations take 256 VGPRs.  What plan_chains and a stream set's pushes build their chains for.
-int fe_max_wg(const ctu_engine *e) {
-    const FeSel &k = e->tab.sel;
-    return e->n_cu * ((fe_waves_per_simd(k.mode, k.vf, k.ss, k.sy) >= 4 && e->tab.lds_bytes <= (size_t)LDS_2WG) ? 2 : 1);
-}
-
-// Step 2, host only, for plans over samples: the chains the front end walks and the grid they are built for.  (A plan over rows has
-// no chains: rows_ingest_kernel strides over the tile list.)
-// Each workgroup walks a chain of tiles.  Stateless chains stride over the tile list; with a
-// per-utterance recurrence (exten) a workgroup takes whole utterances, tile after tile.
-void plan_chains(const ctu_engine *e, ctu_plan *pl, PlanHost &h) {
-    std::vector<TileRec> &tiles = h.tiles;
-    const std::vector<int> &uts = h.uts;
-    std::vector<int> &wg_first = h.wg_first;
-    const int n_utt = pl->n_utt;
-    const int max_wg = fe_max_wg(e);
-    if (e->per_wave) {
-        // chains per wave: whole utterances, longest first onto the least loaded chain (LPT), tile after tile
-        std::vector<int> live;  // utterances that have at least one frame
-        for (int i = 0; i < n_utt; i++)
-            if (uts[i + 1] > uts[i]) live.push_back(i);
-        std::stable_sort(live.begin(), live.end(), [&](int a, int b) { return pl->frames[a] > pl->frames[b]; });
-        // (bigfft_kernel walks a chain with a whole workgroup of 256 threads: eight of them fit a CU at once)
-        const int slots = (e->tab.big && e->tab.path != BIG_WAVE1K) ? e->n_cu * 8 : max_wg * NWAVE;
-        const ChainDeal deal = chain_deal((int)live.size(), slots);  // (stream_plan.h: where chain c sits among the heads)
-        const int C = deal.C, G = deal.G;
-        wg_first.assign((size_t)deal.heads(), -1);
-        std::vector<int> tail(C, -1);  // last tile of each chain so far
-        std::priority_queue<std::pair<int64_t, int>, std::vector<std::pair<int64_t, int>>, std::greater<std::pair<int64_t, int>>> load;
-        // (the chains of one workgroup are spread over the length ranks)
-        for (int c = 0; c < C; c++) load.push({0, c});
-        for (int u : live) {
-            const auto top = load.top();
-            load.pop();
-            const int c = top.second, slot = deal.slot(c);
-            for (int t = uts[u]; t + 1 < uts[u + 1]; t++) tiles[t].next = t + 1;
-            tiles[uts[u + 1] - 1].next = -1;
-            if (tail[c] < 0) wg_first[slot] = uts[u];
-            else tiles[tail[c]].next = uts[u];
-            tail[c] = uts[u + 1] - 1;
-            load.push({top.first + pl->frames[u], c});
-        }
-        pl->ext.grid = G;
-    } else {
-        const int G = std::max(1, std::min(pl->ext.n_tiles, max_wg));
-        wg_first.assign(G, -1);
-        for (int t = 0; t < pl->ext.n_tiles; t++) tiles[t].next = (t + G < pl->ext.n_tiles) ? t + G : -1;
-        for (int g = 0; g < G && g < pl->ext.n_tiles; g++) wg_first[g] = g;
-        pl->ext.grid = G;
-    }
-}
-
-// Step 3, the device side: the uploads and the scratch of every stage the engine's runs have.  Throws (ctu_plan_create's frame).
-void plan_alloc(ctu_engine *e, ctu_plan *pl, const PlanHost &h) {
-    const ctu::Design &d = *e->design;
-    const int n_utt = pl->n_utt;
-    const int64_t ro = pl->ext.total_frames;
+// The device side of a plan: the images of the HostPlan's lists, and the scratch of every stage by its PlanScratch.  No arithmetic and
+// no decision here: a list or a count that is empty or zero is not there (DevBuf).  Throws (ctu_plan_create's frame).
+void plan_upload(ctu_engine *e, ctu_plan *pl) {
+    static_assert(sizeof(UttInfo) == sizeof(int4), "the utterance info is read as int4 records");
+    const HostPlan &h = pl->hp;
+    const PlanScratch &n = h.scratch;
     HIP_TRY(hipSetDevice(e->device));
     pl->tiles.upload(h.tiles);
-    // the passes that run a workgroup per 64-frame chunk (TRAP, delta / stacking, CMS, CMVN); a plan over rows has the list in any case
-    const bool chunked = e->rows_in || d.kind == ctu::FeaKind::TrapDct || d.post_order > 0 || d.cms || d.o.stat_cmvn || d.o.apply_cmvn;
-    const bool per_utt = !e->rows_in && (d.signal_out || d.o.remove_dc1);  // the overlap-add and the -remove_dc1 recurrence go by utterance
-    if (chunked || per_utt) pl->utt_info.upload(h.uinfo);
-    if (chunked) {
-        pl->trap_chunks.upload(h.chunks);
-        pl->n_trap_chunks = (int)h.chunks.size() / 2;
-    }
-    if (d.post_order > 0 || d.cms) pl->base_rows.alloc((size_t)ro * d.Dbase);
-    if (e->rows_in) return;  // what follows serves the front end and the stages that read its scratch
-    pl->wg_first.upload(h.wg_first);
-    pl->ext.heads = pl->wg_first.p;
-    if (per_utt) pl->d_sample_off.upload(std::vector<long long>(pl->sample_off.begin(), pl->sample_off.end()));
-    if (e->do_vad || (e->tab.ss && e->tab.big && !e->tab.ss_file)) pl->d_row_off.upload(pl->row_off);
-    if (e->tab.ss) {
-        std::vector<int> tu(h.tiles.size());
-        for (int i = 0; i < n_utt; i++)
-            for (int t = h.uts[i]; t < h.uts[i + 1]; t++) tu[t] = i;
-        pl->tile_utt.upload(tu);
-        pl->ss_seed.alloc((size_t)std::max(n_utt, 1) * d.K);
-        pl->ss_last.alloc((size_t)std::max(n_utt, 1) * d.K);
-        pl->ss_dirty.alloc((size_t)std::max(n_utt, 1));
-        pl->ss_vbits.alloc((size_t)std::max<int64_t>(ro, 1));
-        if (e->tab.big) {  // bigss_kernel.h: the exported spectra, the detector's cepstra, on the speech path the subtracted magnitudes
-            pl->xri.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-            pl->pnr.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-            if (synth_reads_pss(e)) pl->pss.alloc((size_t)std::max<int64_t>(ro, 1) * d.K);
-            if (!e->tab.ss_file) pl->vad_ci.alloc((size_t)std::max<int64_t>(ro, 1) * d.o.fea_ncepcoefs);
-        }
-    }
-    if (e->do_vad) {
-        if (e->vp.cri == 1) {
-            if (!e->tab.sel.vf) {
-                pl->xri.alloc((size_t)ro * d.K);
-                pl->pnr.alloc((size_t)ro * d.K);
-            }
-            if (!e->tab.sel.vf) pl->vad_ci.alloc((size_t)ro * e->vp.ncoef);
-            else {
-                pl->vad_cf.alloc((size_t)std::max<int64_t>(ro, 1) * VFC_STRIDE);
-                std::vector<int> ord;
-                for (int i = 0; i < n_utt; i++)
-                    if (pl->frames[i] > 0) ord.push_back(i);
-                std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return pl->frames[a] > pl->frames[b]; });
-                pl->n_live = (int)ord.size();
-                if (ord.empty()) ord.push_back(0);
-                pl->vf_order.upload(ord);
-            }
-        } else if (e->vp.cri == 0) pl->pnr.alloc((size_t)ro);
-    }
-    if (d.signal_out) {
-        if (!e->tab.sel.sy && !synth_reads_pss(e)) {  // (with pss the *ss block above has allocated the exported spectra)
-            pl->xri.alloc((size_t)ro * d.K);
-            pl->pnr.alloc((size_t)ro * d.K);
-        }
-        pl->out_samples.resize(n_utt);
-        for (int i = 0; i < n_utt; i++) pl->out_samples[i] = pl->frames[i] * d.wshift + (d.window - d.wshift);
-        pl->ybuf.alloc((size_t)ro * d.window);
-    }
-    if (d.o.remove_dc1) {
-        pl->dc1m.alloc((size_t)std::max<int64_t>(ro, 1));
-        pl->dc1.alloc((size_t)std::max<int64_t>(ro, 1));
-    }
-    if (chunked) {  // the 128-frame chunks (trapdct_split16_kernel): every other 64-frame one
-        std::vector<int> c128;
-        for (size_t k = 0; k + 1 < h.chunks.size(); k += 2)
-            if (!(h.chunks[k + 1] & 64)) {
-                c128.push_back(h.chunks[k]);
-                c128.push_back(h.chunks[k + 1]);
-            }
-        pl->n_trap_chunks128 = (int)c128.size() / 2;
-        if (c128.empty()) c128.assign(2, 0);
-        pl->trap_chunks128.upload(c128);
-    }
-    if (d.kind == ctu::FeaKind::TrapDct || e->tab.dctw) pl->logmel.alloc((size_t)ro * d.B);
-    if (lp_tail_runs(e)) pl->lp_r.alloc(((size_t)std::max<int64_t>(ro, 1) * (d.o.fea_lporder + 1) * (lags_double(e) ? 8 : 4) + 7) / 8);
+    pl->wg_first.upload(h.heads);
+    pl->utt_info.upload(h.uinfo);
+    pl->trap_chunks.upload(h.chunks);
+    pl->trap_chunks128.upload(h.chunks128);
+    pl->tile_utt.upload(h.tile_utt);
+    pl->vf_order.upload(h.vf_order);
+    if (n.d_sample_off) pl->d_sample_off.upload(h.sample_off);
+    if (n.d_row_off) pl->d_row_off.upload(h.row_off);
+    pl->base_rows.alloc((size_t)n.base_rows);
+    pl->ss_seed.alloc((size_t)n.ss_seed);
+    pl->ss_last.alloc((size_t)n.ss_last);
+    pl->ss_dirty.alloc((size_t)n.ss_dirty);
+    pl->ss_vbits.alloc((size_t)n.ss_vbits);
+    pl->xri.alloc((size_t)n.xri);
+    pl->pnr.alloc((size_t)n.pnr);
+    pl->pss.alloc((size_t)n.pss);
+    pl->vad_ci.alloc((size_t)n.vad_ci);
+    pl->vad_cf.alloc((size_t)n.vad_cf);
+    pl->ybuf.alloc((size_t)n.ybuf);
+    pl->dc1m.alloc((size_t)n.dc1m);
+    pl->dc1.alloc((size_t)n.dc1);
+    pl->logmel.alloc((size_t)n.logmel);
+    pl->lp_r.alloc((size_t)n.lp_r);
 }
 }  // namespace
 
-// The plan of an engine that starts from rows (-format_in htk) takes row counts as lengths and lays its arena out by
-// ctu_rows_arena_layout; its tiles are what rows_ingest_kernel strides over, four (one per wave) to a workgroup pass.
+// The plan of the engine's geometry (built at create) over the batch, on the host (plan.cc: layout, refusals, chains, lists, scratch
+// sizes); then its images and its scratch on the device.
 int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, ctu_plan **out) {
     if (!e || !out || n_utt < 0 || (n_utt && !utt_nsamples)) return CTU_ERR_INPUT;
     *out = nullptr;
     std::unique_ptr<ctu_plan> pl(new ctu_plan);
-    PlanHost h;
-    if (const int rc = plan_layout(e, pl.get(), utt_nsamples, n_utt, h); rc != CTU_OK) return rc;
-    if (e->rows_in) pl->ext.grid = std::max(1, std::min((pl->ext.n_tiles + 3) / 4, e->n_cu * ROWS_WG_PER_CU));
-    else plan_chains(e, pl.get(), h);
+    pl->eng = e;
+    std::string why;
+    if (const int rc = build_host_plan(e->geom, utt_nsamples, n_utt, pl->hp, why); rc != CTU_OK) {
+        set_error(e, why);
+        return rc;
+    }
     const int rc = guarded(e, [&]() -> int {
-        plan_alloc(e, pl.get(), h);
+        plan_upload(e, pl.get());
         return CTU_OK;
     });
     if (rc != CTU_OK) return rc;
+    pl->ext.n_tiles = (int)pl->hp.tiles.size();
+    pl->ext.grid = pl->hp.grid;
+    pl->ext.total_frames = pl->hp.total_frames;
+    pl->ext.heads = pl->wg_first.p;
     *out = pl.release();
     return CTU_OK;
 }
 
 void ctu_plan_destroy(ctu_plan *p) { delete p; }
-const int64_t *ctu_plan_sample_offsets(const ctu_plan *p) { return p->sample_off.data(); }
-const int64_t *ctu_plan_row_offsets(const ctu_plan *p) { return p->row_off.data(); }
-int64_t ctu_plan_total_samples(const ctu_plan *p) { return p->total_samples; }
-int64_t ctu_plan_total_frames(const ctu_plan *p) { return p->ext.total_frames; }
+const int64_t *ctu_plan_sample_offsets(const ctu_plan *p) { return p->hp.sample_off.data(); }
+const int64_t *ctu_plan_row_offsets(const ctu_plan *p) { return p->hp.row_off.data(); }
+int64_t ctu_plan_total_samples(const ctu_plan *p) { return p->hp.total_samples; }
+int64_t ctu_plan_total_frames(const ctu_plan *p) { return p->hp.total_frames; }
 
-void ctu_vad_ring_step(int32_t order, int64_t frames, int32_t *hidx, int32_t *hsize) {
-    // medianFilter::push / flush_frame / cleanFilter as VAD::process_frame, BATCH::flush_vad and VAD::clean drive them over one file
-    // (src/vad/vad.h:110-175, src/vad/vad.cc:692-699,705-708,742-745): cleanFilter resets neither historyIdx nor historySize
-    if (order < 1 || !hidx || !hsize) return;
-    const int delay = (order - 1) / 2;
-    int hi = ((*hidx % order) + order) % order, hs = *hsize;
-    bool ready = false;
-    for (int64_t t = 0; t < frames; t++) {
-        hi = (hi + 1) % order;
-        if (hs < delay) hs++;
-        else ready = true;
-    }
-    for (;;) {
-        if (hs > 0) {
-            hi = (hi + 1) % order;
-            hs--;
-        } else
-            ready = false;
-        if (!ready) break;
-    }
-    *hidx = hi;
-    *hsize = hs;
-}
-
-int64_t ctu_vad_ring_rows(int32_t order, int64_t frames, int32_t hidx0, int32_t *src) {
-    // the ring of one file: push t writes slot (hidx0 + t) % order; the k-th written row reads slot k % order - at push k + delay, or after
-    // the last push for the rows of the flush (src/vad/vad.h:126-175 with `start` reset by cleanFilter, historyIdx not)
-    if (order < 1 || frames < 0) return CTU_ERR_INPUT;
-    const int delay = (order - 1) / 2;
-    if (frames <= delay) return 0;  // the filter never gets ready: nothing is written
-    if (!src) return frames;
-    const int h0 = ((hidx0 % order) + order) % order;
-    std::vector<int32_t> slot((size_t)order, -1);
-    int64_t k = 0;
-    for (int64_t t = 0; t < frames; t++) {
-        slot[(size_t)((h0 + t) % order)] = (int32_t)t;
-        if (t >= delay) {
-            src[k] = slot[(size_t)(k % order)];
-            k++;
-        }
-    }
-    for (; k < frames; k++) src[k] = slot[(size_t)(k % order)];
-    return frames;
-}
+void ctu_vad_ring_step(int32_t order, int64_t frames, int32_t *hidx, int32_t *hsize) { vad_ring_step(order, frames, hidx, hsize); }
+int64_t ctu_vad_ring_rows(int32_t order, int64_t frames, int32_t hidx0, int32_t *src) { return vad_ring_rows(order, frames, hidx0, src); }
 
 int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
     if (!pl) return CTU_ERR_INPUT;
     ctu_engine *e = pl->eng;
-    const ctu::Design &d = *e->design;
     pl->ring_hidx.clear();
-    if (!hidx || !e->do_vad || d.o.vad_filter_order <= 1) return CTU_OK;
-    const int order = d.o.vad_filter_order, delay = (order - 1) / 2;
-    bool any = false;
-    for (int i = 0; i < pl->n_utt; i++) any = any || (hidx[i] % order) != 0;
-    if (!any) return CTU_OK;
+    if (!hidx || !e->geom.do_vad) return CTU_OK;
+    const std::vector<int> src = plan_ring_src(pl->hp, e->design->o.vad_filter_order, hidx);
+    if (src.empty()) return CTU_OK;  // every utterance is in phase
     const int rc = guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
-        pl->ring_hidx.assign(hidx, hidx + pl->n_utt);
-        std::vector<int> src((size_t)std::max<int64_t>(pl->ext.total_frames, 1), -1);
-        std::vector<int32_t> rel;
-        for (int i = 0; i < pl->n_utt; i++) {
-            const int64_t T = pl->frames[i], r0 = pl->row_off[i];
-            if (T <= delay) continue;  // nothing is written for it
-            rel.assign((size_t)T, -1);
-            ctu_vad_ring_rows(order, T, hidx[i], rel.data());
-            for (int64_t k = 0; k < T; k++) src[(size_t)(r0 + k)] = rel[(size_t)k] < 0 ? -1 : (int)(r0 + rel[(size_t)k]);
-        }
+        pl->ring_hidx.assign(hidx, hidx + pl->hp.n_utt);
         pl->ring_src.upload(src);
-        pl->ring_tmp.reserve((size_t)std::max<int64_t>(pl->ext.total_frames, 1) * d.D);
+        pl->ring_tmp.reserve(src.size() * e->design->D);
         return CTU_OK;
     });
     if (rc != CTU_OK) pl->ring_hidx.clear();  // a plan without its ring is in phase
@@ -1299,7 +1016,7 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
 static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages,
                      bool vad_stages = true) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
-    if (e->rows_in) {
+    if (e->geom.rows_in) {
         set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows");
         return CTU_ERR_INPUT;
     }
@@ -1310,7 +1027,7 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
         set_error(e, "ENGINE: this configuration writes speech (-format_out raw|wave): use ctu_engine_run_signal");
         return CTU_ERR_INPUT;
     }
-    if (!d_pcm || (!signal && !d_rows) || (e->do_vad && vad_stages && !d_vad)) {
+    if (!d_pcm || (!signal && !d_rows) || (e->geom.do_vad && vad_stages && !d_vad)) {
         set_error(e, "ENGINE: null device buffer");
         return CTU_ERR_INPUT;
     }
@@ -1347,15 +1064,15 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
 #if CTU_STAMP
         if (const char *sf = getenv("CTU_STAMP_FILE")) dump_stamps(e, grid, s, sf);
 #endif
-        if (lp_tail_runs(e)) stage_lp_tail(e, pl, x, s, kp);
-        if (e->do_vad) stage_burg_vad(e, pl, x, s);
+        if (e->geom.lp_tail) stage_lp_tail(e, pl, x, s, kp);
+        if (e->geom.vad_burg) stage_burg_vad(e, pl, x, s);
         if (d.kind == ctu::FeaKind::TrapDct) stage_trap(e, pl, s, d_rows);
         if (d.post_order > 0 && row_stages) stage_post(e, pl, s, d_rows);
         if (d.cms && row_stages) stage_cms(e, pl, s, d_rows);
-        if (e->do_vad && e->tab.sel.vf && pl->n_live > 0) stage_fused_vad(e, pl, x, s, d_vad, vad_stages);
-        if (e->do_vad && !e->tab.sel.vf && vad_stages) stage_vad_decide(e, pl, s, d_rows, d_vad);
-        if (e->do_vad && d.o.vad_filter_order > 1 && vad_stages) stage_short_files(e, pl, s, d_vad);
-        if (e->do_vad && !pl->ring_hidx.empty() && x.total_frames > 0 && vad_stages) stage_ring_gather(e, pl, x, s, d_rows);
+        if (e->geom.vad_fused && pl->hp.n_live > 0) stage_fused_vad(e, pl, x, s, d_vad, vad_stages);
+        if (e->geom.do_vad && !e->geom.vad_fused && vad_stages) stage_vad_decide(e, pl, s, d_rows, d_vad);
+        if (e->geom.do_vad && d.o.vad_filter_order > 1 && vad_stages) stage_short_files(e, pl, s, d_vad);
+        if (e->geom.do_vad && !pl->ring_hidx.empty() && x.total_frames > 0 && vad_stages) stage_ring_gather(e, pl, x, s, d_rows);
         return CTU_OK;
     });
 }
@@ -1391,19 +1108,11 @@ int split_host_parts(ctu_engine *e, ctu_plan *pl, int nparts) {
     if (nparts <= 1 || pl->parts_for == nparts) return CTU_OK;
     pl->parts.clear();
     pl->parts_for = 0;
-    pl->part_first.assign(1, 0);
-    const int64_t per = (pl->sample_off[pl->n_utt] - pl->sample_off[0] + nparts - 1) / nparts;
-    for (int k = 1; k < nparts; k++) {
-        int u = pl->part_first.back();
-        const int64_t goal = pl->sample_off[0] + per * k;
-        while (u < pl->n_utt && pl->sample_off[u] < goal) u++;
-        if (u > pl->part_first.back() && u < pl->n_utt) pl->part_first.push_back(u);
-    }
-    pl->part_first.push_back(pl->n_utt);
+    pl->part_first = plan_part_first(pl->hp, nparts);
     for (size_t k = 0; k + 1 < pl->part_first.size(); k++) {
         ctu_plan *sub = nullptr;
         const int u0 = pl->part_first[k], u1 = pl->part_first[k + 1];
-        const int rc = ctu_plan_create(e, pl->nsamples.data() + u0, u1 - u0, &sub);
+        const int rc = ctu_plan_create(e, pl->hp.nsamples.data() + u0, u1 - u0, &sub);
         if (rc != CTU_OK) {
             pl->parts.clear();
             return rc;
@@ -1422,9 +1131,9 @@ int split_host_parts(ctu_engine *e, ctu_plan *pl, int nparts) {
 int host_chunks(const ctu_engine *e, const ctu_plan *pl, int64_t input_bytes, bool pinned) {
     if (e->tab.ss) return 1;
     // pageable buffers go through blocking staged copies: cutting those up only adds calls (measured 1.04e8 -> 0.96e8 frames/s)
-    int k = (pinned && pl->n_utt >= 16 && input_bytes >= (int64_t)32 << 20) ? 8 : 1;
+    int k = (pinned && pl->hp.n_utt >= 16 && input_bytes >= (int64_t)32 << 20) ? 8 : 1;
     if (const char *v = getenv("CTU_HOST_CHUNKS")) k = std::max(1, atoi(v));
-    return std::min(k, std::max(1, pl->n_utt));
+    return std::min(k, std::max(1, pl->hp.n_utt));
 }
 
 // What a host-buffer run feeds run_host_ranges: the caller's arena and how a (sub)plan stages and runs its share of it.
@@ -1471,7 +1180,7 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
     const int D = e->design->D;
     HIP_TRY(hipSetDevice(e->device));
     const bool pin_in = is_pinned(in.base), pin_out = is_pinned(h_rows);
-    const int nparts = host_chunks(e, pl, pl->total_samples * (int64_t)in.elem, pin_in && pin_out);
+    const int nparts = host_chunks(e, pl, pl->hp.total_samples * (int64_t)in.elem, pin_in && pin_out);
     if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
     const bool ranges = nparts > 1 && pl->parts.size() > 1;
     const int np = ranges ? (int)pl->parts.size() : 1;
@@ -1482,7 +1191,7 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
     auto download = [&](int k) {
         ctu_plan *sp = part(k);
         if (sp->ext.total_frames == 0) return;
-        float *dst = h_rows + pl->row_off[first(k)] * D;
+        float *dst = h_rows + pl->hp.row_off[first(k)] * D;
         if (pin_out) HIP_TRY(hipMemcpyAsync(dst, sp->h_rows.p, (size_t)sp->ext.total_frames * D * 4, hipMemcpyDeviceToHost, st[k & 1]));
         else {
             HIP_TRY(hipStreamSynchronize(st[k & 1]));
@@ -1499,9 +1208,9 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
             void *d_in = in.stage(sp);
             sp->h_rows.reserve((size_t)sp->ext.total_frames * D);
             // a part's arena is the slice of the caller's that starts `head` elements ahead of its first utterance (split_host_parts)
-            const char *src = static_cast<const char *>(in.base) + (pl->sample_off[first(k)] - in.head) * (int64_t)in.elem;
-            if (pin_in) HIP_TRY(hipMemcpyAsync(d_in, src, (size_t)sp->total_samples * in.elem, hipMemcpyHostToDevice, st[k & 1]));
-            else HIP_TRY(hipMemcpy(d_in, src, (size_t)sp->total_samples * in.elem, hipMemcpyHostToDevice));
+            const char *src = static_cast<const char *>(in.base) + (pl->hp.sample_off[first(k)] - in.head) * (int64_t)in.elem;
+            if (pin_in) HIP_TRY(hipMemcpyAsync(d_in, src, (size_t)sp->hp.total_samples * in.elem, hipMemcpyHostToDevice, st[k & 1]));
+            else HIP_TRY(hipMemcpy(d_in, src, (size_t)sp->hp.total_samples * in.elem, hipMemcpyHostToDevice));
             const int rc = in.run(sp, st[k & 1]);
             if (rc != CTU_OK) {  // earlier ranges are still in flight on the two streams: drain them before the caller reuses its buffers
                 if (ranges) {
@@ -1523,7 +1232,7 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
     }
     if (in.vad)
         for (int k = 0; k < np; k++)
-            if (part(k)->ext.total_frames) in.vad(part(k), pl->row_off[first(k)]);
+            if (part(k)->ext.total_frames) in.vad(part(k), pl->hp.row_off[first(k)]);
     return CTU_OK;
 }
 }  // namespace
@@ -1531,39 +1240,39 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
 int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm, float *h_rows, uint8_t *h_vad,
                         int64_t *rows_per_utt) {
     if (!e || !pl_ || pl_->eng != e) return CTU_ERR_INPUT;
-    if (e->rows_in) {
+    if (e->geom.rows_in) {
         set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows_host");
         return CTU_ERR_INPUT;
     }
     ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
     const ctu::Design &d = *e->design;
     if (rows_per_utt)
-        for (int i = 0; i < pl->n_utt; i++) rows_per_utt[i] = pl->frames[i];
+        for (int i = 0; i < pl->hp.n_utt; i++) rows_per_utt[i] = pl->hp.frames[i];
     if (pl->ext.total_frames == 0) return CTU_OK;
     if (!h_pcm || !h_rows) {
         set_error(e, "ENGINE: null host buffer");
         return CTU_ERR_INPUT;
     }
     return guarded(e, [&]() -> int {
-        std::vector<uint8_t> v(e->do_vad ? (size_t)pl->ext.total_frames : 0);
+        std::vector<uint8_t> v(e->geom.do_vad ? (size_t)pl->ext.total_frames : 0);
         HostInput in{h_pcm, sizeof(int16_t), PCM_HEAD};
         in.stage = [&](ctu_plan *p) {
-            p->h_pcm.reserve((size_t)p->total_samples);
-            if (e->do_vad) p->h_vad.reserve((size_t)p->ext.total_frames);
+            p->h_pcm.reserve((size_t)p->hp.total_samples);
+            if (e->geom.do_vad) p->h_vad.reserve((size_t)p->ext.total_frames);
             return p->h_pcm.p;
         };
         in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run(e, p, p->h_pcm.p, p->h_rows.p, p->h_vad.p, s); };
-        if (e->do_vad) {
+        if (e->geom.do_vad) {
             in.ring = [&](ctu_plan *sub, int first) { return ctu_plan_set_vad_ring(sub, pl->ring_hidx.empty() ? nullptr : pl->ring_hidx.data() + first); };
             in.vad = [&](const ctu_plan *p, int64_t row0) { HIP_TRY(hipMemcpy(v.data() + row0, p->h_vad.p, (size_t)p->ext.total_frames, hipMemcpyDeviceToHost)); };
         }
         if (const int rc = run_host_ranges(e, pl, in, h_rows); rc != CTU_OK) return rc;
-        if (e->do_vad) {
+        if (e->geom.do_vad) {
             if (h_vad) std::memcpy(h_vad, v.data(), v.size());
             if (d.o.vad_apply_mode == "drop") {
                 // rows of non-speech frames are dropped (src/io/batch.cc:237-238): compact each utterance in place
-                for (int i = 0; i < pl->n_utt; i++) {
-                    const int64_t r0 = pl->row_off[i], T = pl->frames[i];
+                for (int i = 0; i < pl->hp.n_utt; i++) {
+                    const int64_t r0 = pl->hp.row_off[i], T = pl->hp.frames[i];
                     int64_t keep = 0;
                     for (int64_t t = 0; t < T; t++)
                         if (v[r0 + t] == '1') {
@@ -1575,8 +1284,8 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
             } else if (rows_per_utt) {
                 // a file the majority filter never got ready on (no more frames than its delay) writes no row (ctu_engine_run)
                 const int64_t delay = (d.o.vad_filter_order - 1) / 2;
-                for (int i = 0; i < pl->n_utt; i++)
-                    if (pl->frames[i] <= delay) rows_per_utt[i] = 0;
+                for (int i = 0; i < pl->hp.n_utt; i++)
+                    if (pl->hp.frames[i] <= delay) rows_per_utt[i] = 0;
             }
         }
         return CTU_OK;
@@ -1587,7 +1296,7 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
 // Stages: ingest (rows_in_kernels.h) -> 7 delta chain / stacking -> 8 CMS; CMVN is the caller's, over the resulting rows.
 int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in, float *d_rows, void *stream) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
-    if (!e->rows_in) {
+    if (!e->geom.rows_in) {
         set_error(e, "ENGINE: this configuration starts from samples: use ctu_engine_run (ctu_engine_run_rows needs -format_in htk)");
         return CTU_ERR_INPUT;
     }
@@ -1600,8 +1309,8 @@ int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in
     hipStream_t s = (hipStream_t)stream;
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
-        const bool staged = d.post_order > 0 || d.cms;  // the passes behind read the plan's base rows, else the ingest writes the caller's
-        uint32_t *dst = reinterpret_cast<uint32_t *>(staged ? pl->base_rows.p : d_rows);
+        // (staged: the passes behind read the plan's base rows, else the ingest writes the caller's)
+        uint32_t *dst = reinterpret_cast<uint32_t *>(e->geom.staged ? pl->base_rows.p : d_rows);
         HIP_TRY(hipEventRecord(e->ev0, s));
         lift<0, 1>(d.o.swap_in, [&](auto sw) {
             lift<0, 1>(d.post_stack, [&](auto rot) {
@@ -1621,7 +1330,7 @@ int ctu_engine_run_rows(ctu_engine *e, const ctu_plan *pl, const void *d_rows_in
 
 int ctu_engine_run_rows_host(ctu_engine *e, const ctu_plan *pl_, const void *h_rows_in, float *h_rows) {
     if (!e || !pl_ || pl_->eng != e) return CTU_ERR_INPUT;
-    if (!e->rows_in) {
+    if (!e->geom.rows_in) {
         set_error(e, "ENGINE: this configuration starts from samples: use ctu_engine_run_host (ctu_engine_run_rows_host needs -format_in htk)");
         return CTU_ERR_INPUT;
     }
@@ -1634,7 +1343,7 @@ int ctu_engine_run_rows_host(ctu_engine *e, const ctu_plan *pl_, const void *h_r
     return guarded(e, [&]() -> int {
         HostInput in{h_rows_in, sizeof(uint32_t), 0};
         in.stage = [](ctu_plan *p) {
-            p->h_words.reserve((size_t)p->total_samples);
+            p->h_words.reserve((size_t)p->hp.total_samples);
             return p->h_words.p;
         };
         in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run_rows(e, p, p->h_words.p, p->h_rows.p, s); };
@@ -1649,7 +1358,7 @@ static void cmvn_maps(ctu_engine *e) {
     e->col_of_slot.assign(X, 0);
     e->slot_of_col.assign(d.D, -1);
     for (int k = 0; k < X; k++) {
-        if (e->rows_in) {  // feature files: slot k is vector entry k, written to column k (src/fea/post_impl.cc:55-57, src/io/out.cc:177-179)
+        if (e->geom.rows_in) {  // feature files: slot k is vector entry k, written to column k (src/fea/post_impl.cc:55-57, src/io/out.cc:177-179)
             e->col_of_slot[k] = k;
             e->slot_of_col[k] = k;
             continue;
@@ -1671,11 +1380,11 @@ static int cmvn_check(ctu_engine *e, const ctu_plan *pl, const int32_t *spk_of_u
         set_error(e, "ENGINE: engine was not created with -stat_cmvn / -apply_cmvn");
         return CTU_ERR_INPUT;
     }
-    if (n_spk < 1 || (pl->n_utt && !spk_of_utt)) {
+    if (n_spk < 1 || (pl->hp.n_utt && !spk_of_utt)) {
         set_error(e, "ENGINE: speaker table missing");
         return CTU_ERR_INPUT;
     }
-    for (int i = 0; i < pl->n_utt; i++)
+    for (int i = 0; i < pl->hp.n_utt; i++)
         if (spk_of_utt[i] < 0 || spk_of_utt[i] >= n_spk) {
             set_error(e, "ENGINE: speaker index out of range");
             return CTU_ERR_INPUT;
@@ -1700,12 +1409,12 @@ int ctu_cmvn_accumulate(ctu_engine *e, const ctu_plan *pl, const float *d_rows, 
         HIP_TRY(hipSetDevice(e->device));
         cmvn_maps(e);
         const int cols = ctu_cmvn_cols(e);
-        std::vector<int> spk(spk_of_utt, spk_of_utt + pl->n_utt);
+        std::vector<int> spk(spk_of_utt, spk_of_utt + pl->hp.n_utt);
         e->d_spk.upload(spk);
         std::vector<double> zero((size_t)n_spk * (cols + 1), 0.0);
         e->d_stat_a.upload(zero);
         if (mean) e->d_stat_b.upload(std::vector<double>(mean, mean + (size_t)n_spk * cols));
-        hipLaunchKernelGGL(cmvn_accumulate_kernel, dim3(pl->n_trap_chunks), dim3(256), 0, s, d_rows, pl->utt_info.p,
+        hipLaunchKernelGGL(cmvn_accumulate_kernel, dim3(pl->hp.n_chunks), dim3(256), 0, s, d_rows, pl->utt_info.p,
                            pl->trap_chunks.p, e->d_spk.p, e->d_col_of_slot.p, mean ? e->d_stat_b.p : nullptr, e->d_stat_a.p,
                            cols, e->design->D);
         HIP_TRY(hipGetLastError());
@@ -1727,18 +1436,18 @@ int ctu_cmvn_apply(ctu_engine *e, const ctu_plan *pl, float *d_rows, const int32
         HIP_TRY(hipSetDevice(e->device));
         cmvn_maps(e);
         const int cols = ctu_cmvn_cols(e);
-        std::vector<int> spk(spk_of_utt, spk_of_utt + pl->n_utt);
+        std::vector<int> spk(spk_of_utt, spk_of_utt + pl->hp.n_utt);
         e->d_spk.upload(spk);
         e->d_stat_a.upload(std::vector<double>(mean, mean + (size_t)n_spk * cols));
         e->d_stat_b.upload(std::vector<double>(var, var + (size_t)n_spk * cols));
-        hipLaunchKernelGGL(cmvn_apply_kernel, dim3(pl->n_trap_chunks), dim3(256), 0, s, d_rows, pl->utt_info.p,
+        hipLaunchKernelGGL(cmvn_apply_kernel, dim3(pl->hp.n_chunks), dim3(256), 0, s, d_rows, pl->utt_info.p,
                            pl->trap_chunks.p, e->d_spk.p, e->d_slot_of_col.p, e->d_stat_a.p, e->d_stat_b.p, cols, e->design->D);
         HIP_TRY(hipGetLastError());
         return CTU_OK;
     });
 }
 
-const int64_t *ctu_plan_out_samples(const ctu_plan *p) { return p->out_samples.empty() ? nullptr : p->out_samples.data(); }
+const int64_t *ctu_plan_out_samples(const ctu_plan *p) { return p->hp.out_samples.empty() ? nullptr : p->hp.out_samples.data(); }
 
 int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pcm, int16_t *d_out, void *stream) {
     if (!e || !pl || pl->eng != e) return CTU_ERR_INPUT;
@@ -1747,7 +1456,7 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
         set_error(e, "ENGINE: ctu_engine_run_signal needs -format_out raw|wave");
         return CTU_ERR_INPUT;
     }
-    if (pl->n_utt == 0) return CTU_OK;
+    if (pl->hp.n_utt == 0) return CTU_OK;
     if (!d_pcm || !d_out) {
         set_error(e, "ENGINE: null device buffer");
         return CTU_ERR_INPUT;
@@ -1770,10 +1479,10 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
             HIP_TRY(hipGetLastError());
         }
         int64_t longest = 0;
-        for (int64_t n : pl->out_samples) longest = std::max(longest, n);
+        for (int64_t n : pl->hp.out_samples) longest = std::max(longest, n);
         const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((longest + 255) / 256, 64));
-        hipLaunchKernelGGL(ola_kernel, dim3(gx, pl->n_utt), dim3(256), 0, s, pl->ybuf.p, d_out, pl->utt_info.p, pl->d_sample_off.p,
-                           pl->n_utt, sp);
+        hipLaunchKernelGGL(ola_kernel, dim3(gx, pl->hp.n_utt), dim3(256), 0, s, pl->ybuf.p, d_out, pl->utt_info.p, pl->d_sample_off.p,
+                           pl->hp.n_utt, sp);
         HIP_TRY(hipGetLastError());
         return CTU_OK;
     });
@@ -1784,14 +1493,14 @@ int ctu_engine_run_signal_host(ctu_engine *e, const ctu_plan *pl, const int16_t 
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         DevBuf<int16_t> pcm, out;
-        pcm.alloc((size_t)pl->total_samples);
-        out.alloc((size_t)pl->total_samples);
-        HIP_TRY(hipMemcpy(pcm.p, h_pcm, (size_t)pl->total_samples * 2, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(out.p, 0, (size_t)pl->total_samples * 2));
+        pcm.alloc((size_t)pl->hp.total_samples);
+        out.alloc((size_t)pl->hp.total_samples);
+        HIP_TRY(hipMemcpy(pcm.p, h_pcm, (size_t)pl->hp.total_samples * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(out.p, 0, (size_t)pl->hp.total_samples * 2));
         const int rc = ctu_engine_run_signal(e, pl, pcm.p, out.p, nullptr);
         if (rc != CTU_OK) return rc;
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(h_out, out.p, (size_t)pl->total_samples * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_out, out.p, (size_t)pl->hp.total_samples * 2, hipMemcpyDeviceToHost));
         return CTU_OK;
     });
 }

@@ -8,9 +8,6 @@ namespace {
 
 // NZ = number of 32-sample rows that can hold non-zero input (ceil(window/32)); rows >= NZ are
 // literal zeros so the compiler prunes the first butterflies.
-#ifndef CTU_LB
-#define CTU_LB 4        // waves per SIMD the register allocator must leave room for (2 workgroups x 8 waves / 4 SIMDs)
-#endif
 #ifndef CTU_STAMP
 #define CTU_STAMP 0     // diagnostic build: per-wave s_memtime sums per code segment (never in production)
 #endif
@@ -83,17 +80,7 @@ namespace {
 // XS:     a stream set with noise state (CTU_STREAMS_NR_STATE): the per-wave chains are chains of whole streams, and exten's state comes
 //         from, and goes back to, the stream's slot in HBM at the edges of a push (see xs_slot below).  A switch at compile time, not a
 //         pointer at run time: the offline instantiations keep their registers (see the note on 97 -> 96 VGPRs below).
-// The fused detector paths of the 512-point mode (VF / SS with MODE 0) keep both passes' transform outputs and a 25-sample
-// lattice per lane alive: 256 VGPRs, one workgroup per CU (their staging area takes the LDS of the second one anyway).
-#ifndef CTU_SY_LB
-#define CTU_SY_LB 2  // register budget of the synthesis instantiations (SY): 256 VGPRs, one workgroup per CU.  Measured (profiles/r03_ab_sy_register_budget.txt): at 128 VGPRs they spill 200 bytes per lane; 2 -> -25 % kernel time, 3 -> -21 %
-#endif
-#ifndef CTU_VF1_LB
-#define CTU_VF1_LB CTU_LB  // experiment: register budget of the fused-detector instantiations of the 256-point mode
-#endif
-constexpr int fe_waves_per_simd(int mode, bool vf, bool ss, bool sy = false) {
-    return ((vf || ss) && mode == 0) ? 2 : (sy ? CTU_SY_LB : ((vf || ss) ? CTU_VF1_LB : CTU_LB));
-}
+// (fe_waves_per_simd, the waves per SIMD an instantiation is compiled for, and its switches CTU_LB / CTU_SY_LB / CTU_VF1_LB: layout_constants.h)
 // (fe_dual, the DUAL instantiations of phase 1 below, and its switch CTU_DUAL: layout_constants.h - tables.cc halves their window table)
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order

@@ -6,8 +6,6 @@
 
 namespace {
 
-constexpr int LDS_2WG = 80 * 1024;  // two workgroups per CU fit when a workgroup's LDS stays at or under this
-
 // Host side: the dynamic LDS of a launch and the workgroups of it that share a CU's 160 KiB (at most `cap`).  Each kernel's header has the
 // function that sizes it, beside the carve-up it must match.
 struct LdsFit {
@@ -400,14 +398,8 @@ __device__ __forceinline__ void cells_reduce(float (&c)[NCW]) {
     for (int i = 0; i < NCW; i++) c[i] = lanes8_allreduce_add(c[i]);
 }
 
-// Tile record (32 bytes, read with one scalar load): where the tile's first frame starts in the PCM
-// arena, where its first output row goes, how many of its 64 frame slots are real, the frame index of
-// slot 0 inside its utterance, the next tile this workgroup / wave walks (-1 = done), the utterance's frame count.
-struct TileRec {
-    int64_t sbase, rbase;
-    int nvalid, t0, next, T;  // T = frames of the tile's utterance
-};
-
+// A tile record (TileRec, layout_constants.h) through one scalar load of its eight words
+static_assert(sizeof(TileRec) == 32, "load_rec reads a tile record as eight 32-bit words");
 __device__ __forceinline__ TileRec load_rec(const TileRec *tiles, int tile) {
     ci32 *w = as_const(reinterpret_cast<const int *>(tiles)) + 8 * tile;
     TileRec r;

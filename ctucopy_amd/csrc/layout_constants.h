@@ -1,8 +1,11 @@
 // Every constant, enum and build switch that host-only code shares with the kernels: plain C++, no HIP.
 // Included by kernel_common.h (the kernels), by accept.cc / tables.cc (what is accepted, which instantiation runs, what the tables
-// hold) and by stream_plan.h (the push planner); all of these but the kernels compile without hipcc.  The kernel headers define none
+// hold), by plan_host.h / plan.cc (the plan of an offline run) and by stream_plan.h (the push planner); all of these but the kernels
+// compile without hipcc.  The kernel headers define none
 // of these themselves, and every #ifndef CTU_... switch below is defined here only, so the host units and engine.hip see one value.
 #pragma once
+
+#include <cstdint>
 
 // ---- build switches (A/B and diagnostic builds pass -DCTU_...=0)
 #ifndef CTU_MD
@@ -23,6 +26,15 @@
 #ifndef CTU_DUAL
 #define CTU_DUAL 1      // the two passes of the 512-point mode side by side in the headline instantiation (frontend_kernel.h: DUAL)
 #endif
+#ifndef CTU_LB
+#define CTU_LB 4        // waves per SIMD the front end's register allocator must leave room for (2 workgroups x 8 waves / 4 SIMDs)
+#endif
+#ifndef CTU_SY_LB
+#define CTU_SY_LB 2     // register budget of the synthesis instantiations (SY): 256 VGPRs, one workgroup per CU.  Measured (profiles/r03_ab_sy_register_budget.txt): at 128 VGPRs they spill 200 bytes per lane; 2 -> -25 % kernel time, 3 -> -21 %
+#endif
+#ifndef CTU_VF1_LB
+#define CTU_VF1_LB CTU_LB  // experiment: register budget of the fused-detector instantiations of the 256-point mode
+#endif
 #ifndef CTU_TRAP_BF16
 #define CTU_TRAP_BF16 1  // 0: TRAP-DCT on the fp32 matrix pipe only (trapdct_mfma_kernel)
 #endif
@@ -39,6 +51,29 @@ constexpr int PCM_ALIGN = 8;   // utterance starts are multiples of this many sa
 constexpr int PCM_HEAD = 8;    // samples of padding before the first utterance (x[-2..-1] of frame 0 is loaded)
 constexpr int PCM_TAIL = 512;  // padding after the last one: the generic instantiation loads 16 rows of 32 samples whatever the window
 constexpr int ROWS_ALIGN = 4;  // HTK feature input: utterance starts in the arena are multiples of this many 32-bit words (16 bytes)
+// What an utterance of n samples takes of the PCM arena, and one of n words of the arena of feature files: the one statement of the
+// two layout rules (plan.cc: arena_layout, rows_arena_layout; stream_plan.h: the slot of a pushed stream)
+constexpr int64_t pcm_slot(int64_t n) { return (n + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN; }
+constexpr int64_t rows_slot(int64_t n) { return (n + ROWS_ALIGN - 1) / ROWS_ALIGN * ROWS_ALIGN; }
+
+// Tile record (32 bytes, read with one scalar load: load_rec, kernel_common.h): where the tile's first frame starts in the PCM
+// arena, where its first output row goes, how many of its 64 frame slots are real, the frame index of
+// slot 0 inside its utterance, the next tile this workgroup / wave walks (-1 = done), the utterance's frame count.
+// Filled by the planner of an offline run (plan.cc) and, push after push, by stream_stitch_kernel.
+struct TileRec {
+    int64_t sbase, rbase;
+    int nvalid, t0, next, T;  // T = frames of the tile's utterance
+};
+
+constexpr int LDS_2WG = 80 * 1024;     // two workgroups per CU fit when a workgroup's LDS stays at or under this
+constexpr int ROWS_WG_PER_CU = 8;      // rows_ingest_kernel: workgroups of four waves per CU: 32 waves, each with a tile of 64 rows in flight
+constexpr int VFC_STRIDE = 16;         // vad_kernels.h: floats per frame in the cepstra scratch: the fused path's 14 coefficients, 64-byte rows
+// Waves per SIMD a front-end instantiation is compiled for (frontend_kernel's launch bounds; PlanGeom sizes the chains by it).
+// The fused detector paths of the 512-point mode (VF / SS with MODE 0) keep both passes' transform outputs and a 25-sample
+// lattice per lane alive: 256 VGPRs, one workgroup per CU (their staging area takes the LDS of the second one anyway).
+constexpr int fe_waves_per_simd(int mode, bool vf, bool ss, bool sy = false) {
+    return ((vf || ss) && mode == 0) ? 2 : (sy ? CTU_SY_LB : ((vf || ss) ? CTU_VF1_LB : CTU_LB));
+}
 
 constexpr int PSTRIDE = 260;   // floats per P-tile row: 257 bins padded so rows stay 16-byte aligned (b128 reads in phase 2)
 constexpr int MAX_LP = 23;     // LP order / cepstral order limit: the front end accumulates MAXC = 24 lags (R[0..23]) per frame, lp_tail_kernel keeps one frame's recursion in a lane's registers

@@ -17,7 +17,7 @@ namespace {
 // count alone.  Straight copy: 16 bytes per lane, stores aligned on the destination (row offsets are sums of frame counts, so at
 // odd widths a tile's rows start at any 4-byte phase), contiguous over the wave.  No LDS; the next tile's record is fetched ahead
 // of the copy.
-constexpr int ROWS_WG_PER_CU = 8;   // workgroups of four waves per CU: 32 waves, each with a tile of 64 rows in flight
+// (ROWS_WG_PER_CU, layout_constants.h: workgroups of four waves per CU, 32 waves, each with a tile of 64 rows in flight)
 
 struct __attribute__((aligned(4))) RowsWord4 {
     uint32_t x, y, z, w;

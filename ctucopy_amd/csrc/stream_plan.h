@@ -3,7 +3,7 @@
 //
 //   StreamPush, RowPush   the descriptors the stream kernels read, one per pushed stream
 //   stream_frames, stream_halo, stream_rows_out   frames of a file after so many samples, rows that have gone out after so many frames
-//   chain_deal            where chain c of C sits among the chain heads of a launch (plan_chains deals utterances by it, a push streams)
+//   chain_deal            where chain c of C sits among the chain heads of a launch (plan.cc deals the utterances of an offline run by it, a push streams)
 //   stream_plan_push      a whole push from the set's geometry and mirrors: slots, prefix sums, chains, row descriptors, the launch's
 //                         sizes, the mirrors' next values.  It writes its output only; ctu_streams_push commits and launches from it
 //   stream_plan_finish    the same for ctu_streams_finish: the rows held back, the refusal of a file too short for its chain
@@ -137,7 +137,7 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
     for (int i = 0; i < n; i++) {
         const int64_t c = consumed[ids[i]];
         const int64_t F = stream_frames(c, g.window, g.wshift), T = stream_frames(c + n_samples[i], g.window, g.wshift) - F;
-        const int64_t len = STREAM_LEAD + (c - F * g.wshift) + n_samples[i];  // the stitched utterance, laid out by ctu_arena_layout's rule
+        const int64_t len = STREAM_LEAD + (c - F * g.wshift) + n_samples[i];  // the stitched utterance: an utterance of the arena (pcm_slot)
         StreamPush &p = L.push[i];
         p.src = n_samples[i] ? sample_off[i] : 0;
         p.slot = so;
@@ -153,7 +153,7 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
             else L.push[tail].pad = tiles;
             tail = i;
         }
-        so += (len + PCM_ALIGN - 1) / PCM_ALIGN * PCM_ALIGN;
+        so += pcm_slot(len);
         ro += T;
         tiles += (int)((T + TILE - 1) / TILE);
         slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));

@@ -13,8 +13,8 @@
 #pragma once
 
 // A stream set (ctu_streams_create): per-stream state in HBM, and what a push needs that does not change from push to push - a plan over
-// n_streams utterances of the longest stitched length, whose tile list, chain heads (workgroup g starts at tile g), arena size and scratch a
-// push uses the front of.  The tile records themselves are written by stream_stitch_kernel, push after push.
+// n_streams utterances of the longest stitched length (its HostPlan, plan_host.h, is where the set reads the arena size, the tile and row
+// totals from), whose tile list, chain heads (workgroup g starts at tile g), arena and scratch a push uses the front of.  The tile records themselves are written by stream_stitch_kernel, push after push.
 struct ctu_streams {
     ctu_engine *eng = nullptr;
     int n_streams = 0, cstride = 0;
@@ -159,7 +159,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
-    if ((e->per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->tab.ss || (e->per_wave && e->tab.big) || (e->do_vad && e->tab.big)) {
+    if ((e->geom.per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->geom.do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->tab.ss || (e->geom.per_wave && e->tab.big) || (e->geom.do_vad && e->tab.big)) {
         set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
         return CTU_ERR_UNSUPPORTED;
     }
@@ -171,7 +171,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
     PushGeom &g = st->g;
     g.window = d.window;
     g.wshift = d.wshift;
-    g.max_wg = fe_max_wg(e);
+    g.max_wg = e->geom.max_wg;
     g.held = d.post_order > 0 || d.cms;  // (only with CTU_STREAMS_ROW_STATE: refused above without)
     design_halo(d, &g.H, &g.wmax);
     st->vad = g.vad = streams_vad(d, flags);
@@ -179,7 +179,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         stream_vad_halo(d.o.vad_filter_order, &g.H, &g.wmax);
         g.held = g.H > 0;
     }
-    g.chained = e->per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
+    g.chained = e->geom.per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
     g.max_chains = g.max_wg * NWAVE;
     st->C = st->vad ? g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
     st->consumed.assign((size_t)n_streams, 0);
@@ -199,11 +199,11 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
     ctu_plan *pl = nullptr;
     if (const int rc = ctu_plan_create(e, longest.data(), n_streams, &pl); rc != CTU_OK) return rc;
     st->plan.reset(pl);
-    g.arena_samples = pl->total_samples;
-    g.tile_cap = (int64_t)pl->tiles.n;
+    g.arena_samples = pl->hp.total_samples;
+    g.tile_cap = (int64_t)pl->hp.tiles.size();
     const int rc = guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
-        st->arena.alloc((size_t)pl->total_samples);
+        st->arena.alloc((size_t)pl->hp.total_samples);
         st->carry.alloc((size_t)n_streams * st->cstride);
         st->state.alloc((size_t)n_streams);
         HIP_TRY(hipMemset(st->arena.p, 0, st->arena.n * sizeof(int16_t)));
@@ -233,7 +233,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             }
         }
         if (st->vad) {
-            const int64_t ro = pl->row_off[pl->n_utt];
+            const int64_t ro = pl->hp.total_frames;
             st->vstate.alloc((size_t)n_streams * VST_DOUBLES);
             HIP_TRY(hipMemset(st->vstate.p, 0, st->vstate.n * sizeof(double)));  // (never read ahead of a store: a file's first push resets)
             st->vsink.alloc((size_t)std::max<int64_t>(ro + (int64_t)n_streams * g.H, 1));
@@ -314,7 +314,7 @@ void launch_stream_vad(ctu_streams *st, int k, int n, const PushLayout &L, float
     vp.push = st->d_rdesc[k].p; vp.replay = st->d_replay[k].p; vp.n_replay = L.n_replay;
     vp.cf = pl->vad_cf.p; vp.ci = pl->vad_ci.p; vp.energy = pl->pnr.p;
     vp.vstate = st->vstate.p; vp.vad = d_vad ? d_vad : st->vsink.p;
-    if (e->tab.sel.vf)
+    if (e->geom.vad_fused)
         lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
             hipLaunchKernelGGL((stream_vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((unsigned)((L.n_replay + 15) / 16)), dim3(64), 0, s, vp, e->vp);
         });
@@ -459,7 +459,7 @@ int ctu_streams_push_vad_host(ctu_streams *st, int32_t n, const int32_t *ids, co
             if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
             st->d_stage.alloc(cap);
             // (a push that brings a stream's frame wmax + 2 also delivers the rows of the wmax + 1 frames before it)
-            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->row_off[st->plan->n_utt] + (int64_t)st->n_streams * (st->g.wmax + 1), 1) * D);
+            st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->hp.total_frames + (int64_t)st->n_streams * (st->g.wmax + 1), 1) * D);
         }
         int64_t at = 0;
         for (int i = 0; i < n; i++) {
@@ -539,7 +539,7 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
         set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
         return CTU_ERR_INPUT;
     }
-    if (too_short) {  // plan_layout's words; the stream is reset all the same
+    if (too_short) {  // the words of an offline plan's refusal (plan.cc); the stream is reset all the same
         set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
         return CTU_ERR_INPUT;
     }

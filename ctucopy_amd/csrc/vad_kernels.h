@@ -364,7 +364,7 @@ __device__ __forceinline__ void vad_flush(VadRun &r, const VadParams &vp, int T,
 // brackets: with the step written out in the kernel and the state in loose locals): 66 / 72 / 77 / 74 VGPRs (70 / 75 / 78 / 90), 40 / 38 /
 // 42 / 52 SGPRs (43 / 42 / 45 / 53), 1023 / 1132 / 1202 / 1293 instructions (1053 / 1155 / 1244 / 1312), no scratch; vad_decide_kernel 99
 // VGPRs, 106 SGPRs, 3462 instructions (3403), 16 KB of LDS, no scratch.  Times of the two forms: profiles/vad_step_ab.txt.
-constexpr int VFC_STRIDE = 16;  // floats per frame in the cepstra scratch: the fused path's 14 coefficients, 64-byte rows
+// (VFC_STRIDE, layout_constants.h: floats per frame in the cepstra scratch)
 
 // The detector's state of one utterance in a quad of lanes; an utterance starts from zeros ({})
 struct VadQuad {
