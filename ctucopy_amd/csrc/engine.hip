@@ -19,6 +19,7 @@
 //   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
 //   stream_kernels.h   streaming input: carry | new samples into the slots of a push arena, the tile records of the push, the next carry
 //   stream_rows_kernels.h  streaming input with row state: delta chain / stacking and CMS by absolute frame index, the base-row history
+//   stream_signal_kernels.h  streaming input with signal state: the overlap-add of a push from the stream's tail, the flush at a file's end
 //   stream_plan.h      streaming input, host only and HIP-free: the descriptors of a push and the planner that fills them (slots, chains, rows)
 //   streams_host.h     streaming input, host side: the stream set, create / push (check, plan, commit, launch) / finish
 //
@@ -111,6 +112,7 @@ using namespace ctu;  // accept.h, tables.h: what is accepted, FeSel and fe_comp
 #include "stream_rows_kernels.h"
 #include "stream_vad_kernels.h"
 #include "signal_kernels.h"
+#include "stream_signal_kernels.h"
 
 struct ctu_engine {
     std::unique_ptr<ctu::Design> design;
@@ -271,7 +273,11 @@ void lift(int v, F &&f) {
 // The front-end launch of an engine: its FeSel lifted to template arguments, one at a time; fe_compiled decides which leaves exist.
 // `xs`: the launch of a stream set with noise state (frontend_kernel<..., XS>; the generic walk: the same rows bit for bit).
 // (with detector state as well: the fused Burg-cepstral criterion behind exten, C4's front end - its cepstra go to the scratch by frame, nothing of it runs along a file)
-constexpr bool fe_streamed(const FeSel &k) { return !k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf)); }
+// (with signal state: the one instantiation per (NZ, MODE) a speech-output design runs on - FEAT_BANDS, 16 coefficient rows, GEN_FULL,
+// with SY, or in a build without it (CTU_SY=0) with VX ahead of synth_kernel.  VX stays out otherwise: the VAD's export is not carried
+// behind exten's state, and streams_unsupported_reason refuses those configurations)
+constexpr bool fe_streamed_signal(const FeSel &k) { return k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL && !k.vf && !k.ss && (CTU_SY ? k.sy && !k.vx : k.vx && !k.sy); }
+constexpr bool fe_streamed(const FeSel &k) { return fe_streamed_signal(k) || (!k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf))); }
 void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp, bool xs = false) {
     const FeSel &k = e->tab.sel;
 #define V(x) decltype(x)::value

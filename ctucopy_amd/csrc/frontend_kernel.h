@@ -80,6 +80,12 @@ namespace {
 // XS:     a stream set with noise state (CTU_STREAMS_NR_STATE): the per-wave chains are chains of whole streams, and exten's state comes
 //         from, and goes back to, the stream's slot in HBM at the edges of a push (see xs_slot below).  A switch at compile time, not a
 //         pointer at run time: the offline instantiations keep their registers (see the note on 97 -> 96 VGPRs below).
+//         With SY (a set with signal state as well, CTU_STREAMS_SIGNAL_STATE): speech output behind exten on a stream set - the one
+//         instantiation per (NZ, MODE) a speech-output design runs on, <NZ, FEAT_BANDS, MODE, no VX, 16, GEN_FULL, SY, XS>.  The frames
+//         leave by frame for the set's overlap-add (stream_signal_kernels.h); what runs along the file inside the kernel is exten's
+//         state alone.  gfx950, hipcc -O3, from the code object's metadata: MODE 1 (NZ 13 and 16) 137 VGPRs, 106 SGPRs, MODE 0 (NZ 13
+//         and 16) 177 VGPRs, 106 SGPRs - the VGPRs of the offline SY instantiations; 48 / 60 SGPRs are kept in VGPR lanes (offline:
+//         36 / 52); no VGPR spills, no scratch.  (A build with CTU_SY=0 takes the VX form of the same instantiation ahead of synth_kernel.)
 // (fe_waves_per_simd, the waves per SIMD an instantiation is compiled for, and its switches CTU_LB / CTU_SY_LB / CTU_VF1_LB: layout_constants.h)
 // (fe_dual, the DUAL instantiations of phase 1 below, and its switch CTU_DUAL: layout_constants.h - tables.cc halves their window table)
 
@@ -108,7 +114,8 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
     static_assert(!SS || (!VX && !VF && (GEN == GEN_PLAIN || GEN == GEN_FULL)), "SS: the plain chain, or run-time flags (signal output, energy columns, -fb_inld, LP kinds, magnitude spectra)");
     static_assert(!((VF || SS) && MODE == 0) || NZ == 13, "VF / SS in the 512-point mode: 400-sample windows (16 lanes x 25 samples)");
     static_assert(!SY || (!VX && !VF && (GEN == GEN_FULL || GEN == GEN_DC1)), "SY: run-time flags, no export");
-    static_assert(!XS || (!VX && !SS && !SY && (GEN == GEN_EXTEN || (GEN == GEN_FULL && !VF))), "XS: exten on the spectrum, nothing else that runs along a file (VF stores a frame's cepstra and keeps nothing)");
+    static_assert(!XS || (!SS && (GEN == GEN_EXTEN || (GEN == GEN_FULL && !VF))), "XS: exten on the spectrum, nothing else that runs along a file (VF stores a frame's cepstra and keeps nothing)");
+    static_assert(!XS || !(VX || SY) || (FEAT == FEAT_BANDS && NC == 16 && GEN == GEN_FULL), "XS with SY (or VX): speech output on a stream set with signal state, the one instantiation per (NZ, MODE) - frames and spectra leave by frame, the overlap-add's state is the set's");
     const int o_e_mode = FULL ? p.e_mode : 0, o_dbg = FULL ? p.dbg : 0;
     const bool o_fb_inld = FULL ? p.fb_inld != 0 : GEN == GEN_INLD, o_nr_exten = FULL ? p.nr_exten != 0 : GEN == GEN_EXTEN;
     const bool o_fb_power = FULL ? p.fb_power != 0 : true, o_remove_dc = FULL ? p.remove_dc != 0 : true;

@@ -119,6 +119,13 @@ __global__ __launch_bounds__(256) void synth_kernel(const float2 *__restrict__ x
     }
 }
 
+// The rounding rule of sigOUT (out.cc:436-451), stated once for ola_kernel and the stream kernels (stream_signal_kernels.h): the sum of
+// the frames over a sample, divided by the window's overlap-add gain, floor, +-32767 clip.
+__device__ __forceinline__ int16_t ola_round(double acc, double corr) {
+    const int value = (int)floor(acc / corr);
+    return fabsf((float)value) > 32767.f ? (int16_t)(value < 0 ? -32767 : 32767) : (int16_t)value;
+}
+
 __global__ __launch_bounds__(256) void ola_kernel(const float *__restrict__ ybuf, int16_t *__restrict__ out,
                                                   const int4 *__restrict__ utt_info, const long long *__restrict__ sample_off,
                                                   int n_utt, const SynthParams sp) {
@@ -147,10 +154,7 @@ __global__ __launch_bounds__(256) void ola_kernel(const float *__restrict__ ybuf
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const long long n = n0 + (long long)q * stride;
-            if (n < nout) {
-                const int value = (int)floor(acc[q] / sp.corr);
-                o[n] = fabsf((float)value) > 32767.f ? (value < 0 ? -32767 : 32767) : (int16_t)value;
-            }
+            if (n < nout) o[n] = ola_round(acc[q], sp.corr);
         }
     }
 }

@@ -7,6 +7,8 @@
 //   stream_plan_push      a whole push from the set's geometry and mirrors: slots, prefix sums, chains, row descriptors, the launch's
 //                         sizes, the mirrors' next values.  It writes its output only; ctu_streams_push commits and launches from it
 //   stream_plan_finish    the same for ctu_streams_finish: the rows held back, the refusal of a file too short for its chain
+//   SignalPush            signal state (CTU_STREAMS_SIGNAL_STATE, stream_signal_kernels.h): where the samples of a pushed stream go and which
+//                         time-domain frames of the push they are made of; PushGeom::signal turns a push's counts into samples
 //   stream_vad_halo       detector state (CTU_STREAMS_VAD_STATE): the majority filter's delay h as the halo of the row arithmetic, so that
 //                         a frame's row and its decision leave together; PushGeom::vad then adds the list of the streams that run the replay
 #pragma once
@@ -73,6 +75,16 @@ struct RowPush {
     int hsel;        // which of the stream's two histories holds frames F0 - C .. F0 - 1
 };
 
+// One stream of a push on a set with signal state, or the stream that finishes (host-built): the overlap-add of stream_ola_kernel.
+// The stream goes from F0 to F0 + T frames and delivers T * wshift samples, file samples F0 * wshift on; the sums its later frames
+// still add to - window - wshift of them - stay in the stream's tail.  Samples of a push lie stream after stream, as rows do.
+struct SignalPush {
+    long long out0;  // first sample of the caller's buffer it writes
+    long long row0;  // first of its time-domain frames among the push's
+    long long F0;    // frames of the file ahead of this push
+    int id, T;       // stream; frames this push completes
+};
+
 // Chains per wave: `live` files dealt onto C chains, at most `slots` of them, in G workgroups of NWAVE waves.  Chain c lives in wave
 // c / G of workgroup c % G, so the chains of one workgroup are spread over the ranks of whatever order the files are dealt in.
 struct ChainDeal {
@@ -92,6 +104,7 @@ struct PushGeom {
     bool held;               // row state: RowPush descriptors, the history flip
     bool vad = false;        // detector state: RowPush descriptors (whether rows are held or not), the list of the streams that run the replay
     bool chained;            // noise state: chains of whole streams, a wave each
+    bool signal = false;     // signal state: SignalPush descriptors; a push's counts, prefix sums and capacity are samples, wshift per frame
     int max_chains, max_wg;  // the most chains, and without chains the most workgroups, the front end is launched with
     int64_t arena_samples;   // the push arena, PCM_TAIL included
     int64_t tile_cap;        // tile records the set has room for
@@ -105,6 +118,9 @@ struct PushLayout {
     int *replay = nullptr;           // (vad only) positions in the push of the streams that complete a frame, in push order: the detector's
                                      // replay runs over these alone (16 to a wave); a stream that completes none is not touched
     int n_replay = 0;                // entries of `replay`
+    SignalPush *sig = nullptr;       // (signal only)
+    int64_t capacity = -1;           // (signal only) what the caller's buffer holds; -1: not checked
+    bool over_capacity = false;      // (signal only) the push delivers more than that: the plan fails and nothing of L may be used
     int *heads = nullptr;            // (chained only) first tile of every chain, by ChainDeal::slot
     int *tail = nullptr;             // (chained only) scratch: the stream at the end of every chain so far
     int64_t *row_counts = nullptr;   // rows every pushed stream delivers now
@@ -116,7 +132,8 @@ struct PushLayout {
 };
 
 // Plans the push of n_samples[i] new samples to stream ids[i], i < n (ids in range and distinct, counts >= 0: the caller has checked).
-// false, with nothing the caller may use in L, when the push does not fit the arena or the tile list.
+// false, with nothing the caller may use in L, when the push does not fit the arena or the tile list - or, on a set with signal state,
+// delivers more samples than L.capacity (L.over_capacity says which).
 inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const uint8_t *hsel, int n, const int32_t *ids, const int64_t *n_samples,
                              const int64_t *sample_off, PushLayout &L) {
     int live = 0;
@@ -157,7 +174,8 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
         ro += T;
         tiles += (int)((T + TILE - 1) / TILE);
         slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
-        const int64_t r0 = stream_rows_out(g.H, g.wmax, F), nr = stream_rows_out(g.H, g.wmax, F + T) - r0;
+        // what goes out now: rows - or, with signal state, the samples no later frame adds to: wshift for every frame
+        const int64_t r0 = stream_rows_out(g.H, g.wmax, F), nr = g.signal ? T * g.wshift : stream_rows_out(g.H, g.wmax, F + T) - r0;
         if (g.vad && T > 0) L.replay[n_replay++] = i;
         if (g.held || g.vad) {  // (vad: decision byte k of the push belongs to row k, so out0 serves both; F0 is the replay's absolute frame index)
             RowPush &r = L.rows[i];
@@ -165,13 +183,19 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
             r.id = ids[i]; r.Tn = (int)T; r.nr = (int)nr;
             r.hsel = hsel[ids[i]];
         }
+        if (g.signal) {
+            SignalPush &q = L.sig[i];
+            q.out0 = oo; q.row0 = p.row0; q.F0 = F;
+            q.id = ids[i]; q.T = (int)T;
+        }
         oo += nr;
         most = std::max(most, nr);
         L.row_counts[i] = nr;
         L.consumed[i] = c + n_samples[i];
         L.hsel[i] = (uint8_t)(hsel[ids[i]] ^ (g.held && T > 0 ? 1 : 0));  // stream_rows_carry_kernel writes the other history
     }
-    if (so + PCM_TAIL > g.arena_samples || tiles > g.tile_cap) return false;
+    L.over_capacity = g.signal && L.capacity >= 0 && oo > L.capacity;
+    if (so + PCM_TAIL > g.arena_samples || tiles > g.tile_cap || L.over_capacity) return false;
     L.tiles = tiles;
     L.slices = slices;
     L.grid = g.chained ? deal.G : std::max(1, std::min(tiles, g.max_wg));
@@ -186,13 +210,17 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
 // pending > 0), or none from a file too short for its chain (the plan's refusal: such a file has no defined rows).
 // vad: H, wmax are stream_vad_halo's; a file of 1 .. h frames is no refusal there - the reference writes nothing for it - and the
 // pending min(F, h) rows come with as many decisions, which the majority filter's flush makes (row.F0 = the file's frames).
+// signal: H = wmax = 0; pending counts samples - the window - wshift sums of the stream's tail, which the reference's close() writes,
+// once the file has a frame - and `sig` says whose tail (T = 0: no frame is added).
 struct FinishLayout {
     int64_t frames, pending;
     bool too_short;
     RowPush row;
+    SignalPush sig;
 };
-inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel, bool vad = false) {
+inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel, bool vad = false, bool signal = false) {
     FinishLayout f;
+    f.sig.out0 = 0; f.sig.row0 = 0; f.sig.F0 = 0; f.sig.id = id; f.sig.T = 0;
     f.frames = stream_frames(consumed, window, wshift);
     const int64_t r0 = stream_rows_out(H, wmax, f.frames);
     f.too_short = H > 0 && f.frames > 0 && f.frames < wmax + 2;
@@ -201,6 +229,11 @@ inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, 
     f.row.F0 = f.frames; f.row.r0 = r0; f.row.out0 = 0; f.row.row0 = 0;  // rows r0 .. F - 1 with the file's length known
     f.row.id = id; f.row.Tn = 0; f.row.nr = (int)f.pending;
     f.row.hsel = hsel;
+    if (signal) {
+        f.too_short = false;
+        f.pending = f.frames > 0 ? window - wshift : 0;
+        f.sig.F0 = f.frames;
+    }
     return f;
 }
 

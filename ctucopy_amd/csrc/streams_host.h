@@ -8,6 +8,8 @@
 // set's ctu_plan with the extent of the push (RunExtent), so the plan itself is not written after ctu_streams_create_ex.
 // On a set with detector state the run stops ahead of the VAD's sequential stages (run_chain: vad_stages off) and launch_stream_vad
 // replays them from the set's own state, by the plan's RowPush descriptors and its list of the streams that complete a frame.
+// On a set with signal state (speech output) the run leaves the time-domain frames of the push in the plan's ybuf and stream_ola_kernel
+// adds them onto every stream's tail of the overlap-add (stream_signal_kernels.h): ctu_streams_push_signal / ctu_streams_finish_signal.
 // A HIP call that fails behind the commit (CTU_ERR_DEVICE) leaves mirrors and device state out of step: include/ctu_engine.h says what
 // the caller may still do with the set.
 #pragma once
@@ -57,14 +59,23 @@ struct ctu_streams {
     DevBuf<uint8_t> vsink;
     int *h_replay[2] = {nullptr, nullptr};
     DevBuf<int> d_replay[2];
-    // the host form: page-locked staging of the new samples, their device copy, the rows ahead of the download
+    // CTU_STREAMS_SIGNAL_STATE on a configuration with speech output (stream_signal_kernels.h; g.signal): the overlap-add's tail of every
+    // stream - tstride doubles each, window - wshift of them in use - and the descriptors of stream_ola_kernel
+    bool signal = false;
+    int tstride = 0;
+    DevBuf<double> otail;
+    SignalPush *h_sdesc[2] = {nullptr, nullptr};
+    DevBuf<SignalPush> d_sdesc[2];
+    // the host form: page-locked staging of the new samples, their device copy, the rows (the samples) ahead of the download
     int16_t *h_stage = nullptr;
     DevBuf<int16_t> d_stage;
     DevBuf<float> d_rows;
+    DevBuf<int16_t> d_sig;
     std::vector<int64_t> offs;
     ~ctu_streams() {
         for (StreamPush *h : h_desc) ctu_host_free(h);
         for (RowPush *h : h_rdesc) ctu_host_free(h);
+        for (SignalPush *h : h_sdesc) ctu_host_free(h);
         for (int *h : h_heads) ctu_host_free(h);
         for (int *h : h_replay) ctu_host_free(h);
         ctu_host_free(h_stage);
@@ -80,6 +91,10 @@ void design_halo(const ctu::Design &d, int *H, int *wmax) { stream_halo(d.post_o
 int64_t stream_rows_of(const ctu_streams *st, int64_t F) { return stream_rows_out(st->g.H, st->g.wmax, F); }
 // a set with detector state on a configuration with the VAD module: the majority filter's delay is the halo (nothing else holds rows there)
 bool streams_vad(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STREAMS_VAD_STATE) && d.o.do_vad(); }
+// a set with signal state on a configuration with speech output: samples go out, by the *_signal calls
+bool streams_signal(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STREAMS_SIGNAL_STATE) && d.signal_out; }
+// the samples the finish of a stream with F frames delivers: the overlap-add's tail, once there is a frame
+int64_t signal_pending(const ctu::Design &d, int64_t F) { return F > 0 ? d.window - d.wshift : 0; }
 }  // namespace
 
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
@@ -179,6 +194,16 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         stream_vad_halo(d.o.vad_filter_order, &g.H, &g.wmax);
         g.held = g.H > 0;
     }
+    st->signal = g.signal = streams_signal(d, flags);
+    if (st->signal) {  // (speech output writes no rows: whatever the command line says of a delta chain or CMS, nothing is held)
+        g.held = false;
+        g.H = g.wmax = 0;
+        st->tstride = (std::max(d.window - d.wshift, 1) + 1) / 2 * 2;
+        if (d.window - d.wshift > OLA_TAIL_MAX || e->tab.big) {
+            set_error(e, "ENGINE: internal: a signal set beyond the 512-point front end");
+            return CTU_ERR_UNSUPPORTED;
+        }
+    }
     g.chained = e->geom.per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
     g.max_chains = g.max_wg * NWAVE;
     st->C = st->vad ? g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
@@ -244,6 +269,15 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
                 st->d_replay[k].alloc((size_t)n_streams);
             }
         }
+        if (st->signal) {
+            st->otail.alloc((size_t)n_streams * st->tstride);
+            HIP_TRY(hipMemset(st->otail.p, 0, st->otail.n * sizeof(double)));  // (+0.0: a file's first frames add to nothing)
+            for (int k = 0; k < 2; k++) {
+                st->h_sdesc[k] = static_cast<SignalPush *>(ctu_host_alloc((size_t)n_streams * sizeof(SignalPush)));
+                if (!st->h_sdesc[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_sdesc[k].alloc((size_t)n_streams);
+            }
+        }
         if (g.held) {
             st->hist.alloc(std::max<size_t>((size_t)2 * n_streams * st->C * d.Dbase, 1));
             st->means.alloc((size_t)n_streams * STREAM_MEANS);
@@ -275,7 +309,15 @@ int64_t ctu_streams_pending(const ctu_streams *st, int32_t id) {
     if (!st || id < 0 || id >= st->n_streams) return CTU_ERR_INPUT;
     const ctu::Design &d = *st->eng->design;
     const int64_t F = stream_frames(st->consumed[(size_t)id], d.window, d.wshift);
+    if (st->signal) return signal_pending(d, F);
     return F - stream_rows_of(st, F);
+}
+
+int64_t ctu_streams_signal_step(int32_t window, int32_t wshift, int64_t total, int64_t *pending) {
+    if (window < 1 || wshift < 1 || wshift > window || total < 0) return CTU_ERR_INPUT;
+    const int64_t F = stream_frames(total, window, wshift);
+    if (pending) *pending = F > 0 ? window - wshift : 0;
+    return F * wshift;
 }
 
 namespace {
@@ -328,6 +370,9 @@ void launch_stream_vad(ctu_streams *st, int k, int n, const PushLayout &L, float
     }
     HIP_TRY(hipGetLastError());
 }
+// The wrong call for the set, refused before anything changes
+constexpr const char *SIGNAL_SET_ROW_CALL = "a set with signal state (CTU_STREAMS_SIGNAL_STATE) delivers samples, not rows: use ctu_streams_push_signal / ctu_streams_finish_signal";
+constexpr const char *ROW_SET_SIGNAL_CALL = "ctu_streams_push_signal / ctu_streams_finish_signal need a set with signal state (CTU_STREAMS_SIGNAL_STATE on a configuration with -format_out raw | wave): use ctu_streams_push / ctu_streams_finish";
 // The argument checks the device and the host form of a push share (each refuses in its own words)
 bool push_args_ok(const ctu_streams *st, int32_t n, const int32_t *ids, const int64_t *n_samples) { return n >= 0 && n <= st->n_streams && (!n || (ids && n_samples)); }
 bool push_count_ok(const ctu_streams *st, int64_t n_samples) { return n_samples >= 0 && n_samples <= st->max_push; }
@@ -349,6 +394,7 @@ int ctu_streams_push_vad(ctu_streams *st, int32_t n, const int32_t *ids, const i
         return CTU_ERR_INPUT;
     };
     // ---- everything that can be refused is refused here, ahead of the first launch and of any change to the set
+    if (st->signal) return refuse(SIGNAL_SET_ROW_CALL);
     if (d_vad && !st->vad) return refuse("push: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
     if (!push_args_ok(st, n, ids, n_samples)) return refuse("push: bad stream count or null argument");
     if (n == 0) return CTU_OK;
@@ -434,6 +480,10 @@ int ctu_streams_push_vad_host(ctu_streams *st, int32_t n, const int32_t *ids, co
                               int64_t rows_capacity, int64_t *row_counts, uint8_t *h_vad) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
+    if (st->signal) {
+        set_error(e, std::string("ENGINE: ") + SIGNAL_SET_ROW_CALL);
+        return CTU_ERR_INPUT;
+    }
     if (h_vad && !st->vad) {
         set_error(e, "ENGINE: push: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
         return CTU_ERR_INPUT;
@@ -493,6 +543,10 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
     const ctu::Design &d = *e->design;
+    if (st->signal) {
+        set_error(e, std::string("ENGINE: ") + SIGNAL_SET_ROW_CALL);
+        return CTU_ERR_INPUT;
+    }
     if (d_vad && !st->vad) {
         set_error(e, "ENGINE: finish: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
         return CTU_ERR_INPUT;
@@ -554,6 +608,10 @@ int ctu_streams_finish_host(ctu_streams *st, int32_t id, float *h_rows, int64_t 
 int ctu_streams_finish_vad_host(ctu_streams *st, int32_t id, float *h_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *h_vad) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
+    if (st->signal) {
+        set_error(e, std::string("ENGINE: ") + SIGNAL_SET_ROW_CALL);
+        return CTU_ERR_INPUT;
+    }
     if (h_vad && !st->vad) {
         set_error(e, "ENGINE: finish: decisions asked of a set without detector state (CTU_STREAMS_VAD_STATE on a configuration with the VAD module)");
         return CTU_ERR_INPUT;
@@ -574,6 +632,228 @@ int ctu_streams_finish_vad_host(ctu_streams *st, int32_t id, float *h_rows, int6
         return CTU_OK;
     });
     if (rc == CTU_OK && row_count) *row_count = cnt;
+    return rc;
+}
+
+// ---- signal state: the same push - check, plan, commit, launch - with samples out.  The front end leaves the time-domain frames of the
+// push in the plan's ybuf, a row per frame (its SY instantiations; in a build without them synth_kernel from the exported spectra), and
+// stream_ola_kernel adds them onto every stream's tail.
+namespace {
+SignalParams signal_params(const ctu_streams *st, const SignalPush *push, int16_t *d_out) {
+    const ctu::Design &d = *st->eng->design;
+    SignalParams gp;
+    gp.push = push; gp.ybuf = st->plan->ybuf.p; gp.tail = st->otail.p; gp.out = d_out;
+    gp.tstride = st->tstride; gp.window = d.window; gp.wshift = d.wshift;
+    gp.corr = d.ola_corr;
+    return gp;
+}
+}  // namespace
+
+int ctu_streams_push_signal(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
+                            int16_t *d_out, int64_t out_capacity, int64_t *out_counts, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
+    const ctu_plan *pl = st->plan.get();
+    auto refuse = [&](const char *m) {
+        set_error(e, std::string("ENGINE: ") + m);
+        return CTU_ERR_INPUT;
+    };
+    // ---- everything that can be refused is refused here or by the plan, ahead of the first launch and of any change to the set
+    if (!st->signal) return refuse(ROW_SET_SIGNAL_CALL);
+    if (!push_args_ok(st, n, ids, n_samples)) return refuse("push: bad stream count or null argument");
+    if (n == 0) return CTU_OK;
+    if (++st->push_no == 0) {  // (the counter wrapped: forget the marks)
+        std::fill(st->seen.begin(), st->seen.end(), 0u);
+        st->push_no = 1;
+    }
+    int64_t fresh = 0, out = 0;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= st->n_streams) return refuse("push: stream id out of range");
+        if (st->seen[(size_t)ids[i]] == st->push_no) return refuse("push: a stream id appears twice");
+        st->seen[(size_t)ids[i]] = st->push_no;
+        if (!push_count_ok(st, n_samples[i])) return refuse("push: more samples than the set's max_push_samples (or fewer than none)");
+        if (n_samples[i] && (!sample_off || sample_off[i] < 0)) return refuse("push: null or negative sample offsets");
+        const int64_t c = st->consumed[(size_t)ids[i]];
+        out += (stream_frames(c + n_samples[i], d.window, d.wshift) - stream_frames(c, d.window, d.wshift)) * d.wshift;
+        fresh += n_samples[i];
+    }
+    if (fresh && !d_pcm) return refuse("push: null sample buffer");
+    if (out_capacity < 0 || (out && !d_out)) return refuse("push: the samples of this push do not fit out_capacity");
+    hipStream_t s = (hipStream_t)stream;
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const int k = st->turn;
+        HIP_TRY(hipEventSynchronize(st->desc_free[k]));  // (the push before last has read them; immediate before the first record)
+        // ---- plan: as ctu_streams_push plans, with the samples' prefix sums and the capacity check (stream_plan.h)
+        PushLayout L;
+        L.push = st->h_desc[k]; L.sig = st->h_sdesc[k]; L.heads = st->h_heads[k]; L.tail = st->chain_tail.data();
+        L.row_counts = out_counts ? out_counts : st->counts.data();
+        L.consumed = st->next_consumed.data(); L.hsel = st->next_hsel.data();
+        L.capacity = out_capacity;
+        if (!stream_plan_push(st->g, st->consumed.data(), st->hsel.data(), n, ids, n_samples, sample_off, L)) {
+            if (L.over_capacity) return refuse("push: the samples of this push do not fit out_capacity");
+            throw std::runtime_error("internal: a push beyond the set's arena");
+        }
+        // ---- commit
+        st->turn ^= 1;
+        for (int i = 0; i < n; i++) st->consumed[(size_t)ids[i]] = L.consumed[i];
+        // ---- launch
+        HIP_TRY(hipMemcpyAsync(st->d_desc[k].p, L.push, (size_t)n * sizeof(StreamPush), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st->d_sdesc[k].p, L.sig, (size_t)n * sizeof(SignalPush), hipMemcpyHostToDevice, s));
+        RunExtent x;
+        x.n_tiles = L.tiles; x.grid = L.grid; x.total_frames = L.base_rows;
+        x.heads = L.n_heads ? st->d_heads[k].p : pl->ext.heads;
+        x.xstate = st->xstate.p;
+        StreamParams sp;
+        sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
+        sp.cstride = st->cstride; sp.window = d.window; sp.wshift = d.wshift;
+        sp.n_tiles = L.tiles; sp.grid = L.grid;
+        sp.tile_stream = L.n_heads ? pl->tile_utt.p : nullptr;
+        if (L.n_heads) HIP_TRY(hipMemcpyAsync(st->d_heads[k].p, L.heads, (size_t)L.n_heads * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(st->ev[0], s));
+        hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)L.slices), dim3(256), 0, s, sp);
+        HIP_TRY(hipEventRecord(st->ev[1], s));
+        HIP_TRY(hipGetLastError());
+        int rc = CTU_OK;
+        if (L.tiles) {
+            e->in_signal_call = true;
+            rc = run_chain(e, pl, x, st->arena.p, nullptr, nullptr, s, true);
+            e->in_signal_call = false;
+        }
+        if (L.tiles && rc == CTU_OK) {
+            if (!e->tab.sel.sy) {  // the spectra of the push's frames back to the time domain (ctu_engine_run_signal's launch, over this extent)
+                SynthParams yp;
+                yp.K = d.K; yp.wfft = d.wfft; yp.window = d.window; yp.wshift = d.wshift;
+                yp.inv_n = 1.0f / (float)d.wfft;
+                yp.corr = d.ola_corr;
+                const int g = (int)std::min<int64_t>((L.base_rows + 7) / 8, (int64_t)e->n_cu * 8);
+                hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)L.base_rows, yp);
+            }
+            const unsigned slices = (unsigned)((L.most + OLA_SLICE - 1) / OLA_SLICE);
+            hipLaunchKernelGGL(stream_ola_kernel, dim3((unsigned)n, slices), dim3(256), 0, s, signal_params(st, st->d_sdesc[k].p, d_out));
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(st->ev[2], s));
+        hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
+        HIP_TRY(hipEventRecord(st->ev[3], s));
+        HIP_TRY(hipEventRecord(st->desc_free[k], s));
+        HIP_TRY(hipGetLastError());
+        st->timed = true;
+        return rc;
+    });
+}
+
+int ctu_streams_push_signal_host(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples, int16_t *h_out,
+                                 int64_t out_capacity, int64_t *out_counts) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    if (!st->signal) {
+        set_error(e, std::string("ENGINE: ") + ROW_SET_SIGNAL_CALL);
+        return CTU_ERR_INPUT;
+    }
+    if (!push_args_ok(st, n, ids, n_samples) || (n && !h_pcm)) {
+        set_error(e, "ENGINE: push: bad stream count or null argument");
+        return CTU_ERR_INPUT;
+    }
+    int64_t fresh = 0;
+    for (int i = 0; i < n; i++) {
+        if (!push_count_ok(st, n_samples[i]) || (n_samples[i] && !h_pcm[i])) {
+            set_error(e, "ENGINE: push: more samples than the set's max_push_samples (or fewer than none), or a null sample buffer");
+            return CTU_ERR_INPUT;
+        }
+        fresh += n_samples[i];
+    }
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const size_t cap = (size_t)st->n_streams * (size_t)st->max_push;
+        if (!st->h_stage) {
+            st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
+            if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
+            st->d_stage.alloc(cap);
+            // (a stream delivers wshift samples per frame, and a push completes frames out of its own samples and fewer than `window` carried ones)
+            st->d_sig.alloc((size_t)st->n_streams * ((size_t)st->max_push + (size_t)e->design->window));
+        }
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            st->offs[(size_t)i] = at;
+            if (n_samples[i]) std::memcpy(st->h_stage + at, h_pcm[i], (size_t)n_samples[i] * sizeof(int16_t));
+            at += n_samples[i];
+        }
+        if (fresh) HIP_TRY(hipMemcpyAsync(st->d_stage.p, st->h_stage, (size_t)fresh * sizeof(int16_t), hipMemcpyHostToDevice, nullptr));
+        // the device samples hold any push of the set; what the caller's buffer holds is the device form's check
+        const int rc = ctu_streams_push_signal(st, n, ids, st->d_stage.p, st->offs.data(), n_samples, h_out ? st->d_sig.p : nullptr, h_out ? out_capacity : 0,
+                                               out_counts, nullptr);
+        if (rc != CTU_OK) return rc;
+        const int64_t *counts = out_counts ? out_counts : st->counts.data();  // (where the push planned them)
+        int64_t out = 0;
+        for (int i = 0; i < n; i++) out += counts[i];
+        if (out) HIP_TRY(hipMemcpyAsync(h_out, st->d_sig.p, (size_t)out * sizeof(int16_t), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return CTU_OK;
+    });
+}
+
+int ctu_streams_finish_signal(ctu_streams *st, int32_t id, int16_t *d_out, int64_t out_capacity, int64_t *out_count, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    const ctu::Design &d = *e->design;
+    if (!st->signal) {
+        set_error(e, std::string("ENGINE: ") + ROW_SET_SIGNAL_CALL);
+        return CTU_ERR_INPUT;
+    }
+    if (id < 0 || id >= st->n_streams) {
+        set_error(e, "ENGINE: finish: stream id out of range");
+        return CTU_ERR_INPUT;
+    }
+    if (out_count) *out_count = 0;
+    const int64_t total = st->consumed[(size_t)id];
+    const FinishLayout fin = stream_plan_finish(d.window, d.wshift, 0, 0, total, id, 0, false, true);
+    if (fin.pending > out_capacity || (fin.pending && !d_out)) {  // ahead of any launch or change: the stream stays as it was
+        set_error(e, "ENGINE: finish: the samples of this stream's tail do not fit out_capacity");
+        return CTU_ERR_INPUT;
+    }
+    st->consumed[(size_t)id] = 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        // the tail rounded and cleared (a file without a frame has added nothing to it); the noise estimate needs no clearing: the first
+        // tile of a file starts from the reference's initial one (frontend_kernel: rec.t0 == 0), as behind ctu_streams_finish
+        if (fin.pending) hipLaunchKernelGGL(stream_ola_flush_kernel, dim3(1), dim3(256), 0, s, signal_params(st, nullptr, d_out), fin.sig);
+        HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
+        HIP_TRY(hipGetLastError());
+        return CTU_OK;
+    });
+    if (rc != CTU_OK) return rc;
+    if (total > 0 && total < d.window - d.wshift) {
+        set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
+        return CTU_ERR_INPUT;
+    }
+    if (out_count) *out_count = fin.pending;
+    return CTU_OK;
+}
+
+int ctu_streams_finish_signal_host(ctu_streams *st, int32_t id, int16_t *h_out, int64_t out_capacity, int64_t *out_count) {
+    if (!st) return CTU_ERR_INPUT;
+    ctu_engine *e = st->eng;
+    if (!st->signal) {
+        set_error(e, std::string("ENGINE: ") + ROW_SET_SIGNAL_CALL);
+        return CTU_ERR_INPUT;
+    }
+    if (out_count) *out_count = 0;
+    const int64_t pending = ctu_streams_pending(st, id);  // (an id outside the set is ctu_streams_finish_signal's to refuse)
+    DevBuf<int16_t> out;
+    int64_t cnt = 0;
+    const int rc = guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        if (pending > 0) out.alloc((size_t)pending);
+        const int rc = ctu_streams_finish_signal(st, id, h_out ? out.p : nullptr, h_out ? out_capacity : 0, &cnt, nullptr);
+        if (rc != CTU_OK) return rc;
+        if (cnt) HIP_TRY(hipMemcpy(h_out, out.p, (size_t)cnt * sizeof(int16_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return CTU_OK;
+    });
+    if (rc == CTU_OK && out_count) *out_count = cnt;
     return rc;
 }
 

@@ -15,6 +15,7 @@ CTU_OK, CTU_ERR_OPTS, CTU_ERR_UNSUPPORTED, CTU_ERR_DEVICE, CTU_ERR_INPUT = 0, -1
 STREAMS_ROW_STATE = 1  # CTU_STREAMS_ROW_STATE
 STREAMS_NR_STATE = 4   # CTU_STREAMS_NR_STATE
 STREAMS_VAD_STATE = 8  # CTU_STREAMS_VAD_STATE
+STREAMS_SIGNAL_STATE = 32  # CTU_STREAMS_SIGNAL_STATE (2 and 16 are no flags)
 
 
 class CtuError(RuntimeError):
@@ -42,7 +43,8 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_streams_create", "ctu_streams_destroy", "ctu_streams_config_check", "ctu_streams_push", "ctu_streams_push_host",
            "ctu_streams_finish", "ctu_streams_frames", "ctu_streams_step", "ctu_streams_last_push_ms",
            "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step",
-           "ctu_streams_push_vad", "ctu_streams_push_vad_host", "ctu_streams_finish_vad", "ctu_streams_finish_vad_host", "ctu_streams_vad_step"]
+           "ctu_streams_push_vad", "ctu_streams_push_vad_host", "ctu_streams_finish_vad", "ctu_streams_finish_vad_host", "ctu_streams_vad_step",
+           "ctu_streams_push_signal", "ctu_streams_push_signal_host", "ctu_streams_finish_signal", "ctu_streams_finish_signal_host", "ctu_streams_signal_step"]
 
 _lib = None
 
@@ -143,6 +145,13 @@ def load_library():
         L.ctu_streams_finish_vad_host.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64), vp]
         L.ctu_streams_vad_step.restype = i64
         L.ctu_streams_vad_step.argtypes = [i32, i32, i32, i64, ctypes.POINTER(i64)]
+    if hasattr(L, "ctu_streams_signal_step"):  # (likewise: stream sets with signal state)
+        L.ctu_streams_push_signal.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]
+        L.ctu_streams_push_signal_host.argtypes = [vp, i32, vp, vp, vp, vp, i64, vp]
+        L.ctu_streams_finish_signal.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64), vp]
+        L.ctu_streams_finish_signal_host.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64)]
+        L.ctu_streams_signal_step.restype = i64
+        L.ctu_streams_signal_step.argtypes = [i32, i32, i64, ctypes.POINTER(i64)]
     _lib = L
     return L
 
@@ -190,23 +199,25 @@ def config_table(args, name):
     return out
 
 
-def _stream_flags(row_state, nr_state, vad_state):
-    return (STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0) | (STREAMS_VAD_STATE if vad_state else 0)
+def _stream_flags(row_state, nr_state, vad_state, signal_state=False):
+    return ((STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0) | (STREAMS_VAD_STATE if vad_state else 0) |
+            (STREAMS_SIGNAL_STATE if signal_state else 0))
 
 
-def streams_config_check(args, row_state=False, nr_state=False, vad_state=False):
+def streams_config_check(args, row_state=False, nr_state=False, vad_state=False, signal_state=False):
     """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
     CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give.  With row_state (a set that
     may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo).  With nr_state the set keeps the noise
-    estimate of -nr_mode exten too, with vad_state the VAD module's detector state."""
+    estimate of -nr_mode exten too, with vad_state the VAD module's detector state, with signal_state the overlap-add's tail of
+    speech output (-format_out raw | wave)."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
-    if not row_state and not nr_state and not vad_state:
+    if not row_state and not nr_state and not vad_state and not signal_state:
         rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
         return int(rc), buf.value.decode()
     halo = ctypes.c_int32(0)
-    flags = _stream_flags(row_state, nr_state, vad_state)
+    flags = _stream_flags(row_state, nr_state, vad_state, signal_state)
     rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
     return (int(rc), buf.value.decode(), int(halo.value)) if row_state else (int(rc), buf.value.decode())
 
@@ -240,19 +251,30 @@ def streams_vad_step(window, wshift, filter_order, total):
     return int(r), int(pending.value)
 
 
+def streams_signal_step(window, wshift, total):
+    """(samples delivered, samples a finish adds) of a stream with signal state after `total` input samples (ctu_streams_signal_step)."""
+    pending = ctypes.c_int64(0)
+    r = load_library().ctu_streams_signal_step(int(window), int(wshift), int(total), ctypes.byref(pending))
+    if r < 0:
+        raise CtuError(int(r), "ctu_streams_signal_step: bad argument")
+    return int(r), int(pending.value)
+
+
 class Streams:
     """A set of `n` streams on an engine (Engine.streams): PCM in per stream as it arrives, the rows of the frames it completes out.
     With row_state the set takes delta chains, stacking and CMS too, and may deliver a frame's row with a later push or with finish.
     With nr_state it takes -nr_mode exten (on the spectrum, 256- and 512-point front end): the noise estimate is kept per stream.
     With vad_state it takes the VAD module (energy and Burg-cepstral criteria): the detector's state is kept per stream, and a frame's
-    row leaves with its decision, (vad_filter_order - 1) / 2 frames late."""
+    row leaves with its decision, (vad_filter_order - 1) / 2 frames late.
+    With signal_state it takes speech output (-format_out raw | wave; with nr_state as well behind -nr_mode exten): push_signal and
+    finish_signal deliver the enhanced samples, wshift per completed frame and the window - wshift behind them at the file's end."""
 
-    def __init__(self, engine, n, max_push, row_state=False, nr_state=False, vad_state=False):
+    def __init__(self, engine, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        if row_state or nr_state or vad_state:
-            flags = _stream_flags(row_state, nr_state, vad_state)
+        if row_state or nr_state or vad_state or signal_state:
+            flags = _stream_flags(row_state, nr_state, vad_state, signal_state)
             rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))
         else:
             rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
@@ -333,6 +355,49 @@ class Streams:
             return rows[:int(cnt.value)], vad[:int(cnt.value)]
         self.engine._check(load_library().ctu_streams_finish_host(self._h, int(sid), rows.ctypes.data if cap else None, cap, ctypes.byref(cnt)))
         return rows[:int(cnt.value)]
+
+    def push_signal(self, chunks, capacity=None):
+        """{stream id: int16 array} -> {stream id: int16 array}: the enhanced samples the new input completes, wshift for every frame
+        (a set with signal_state; host buffers).  `capacity`: the room offered for them (default: enough for any such push)."""
+        ids = np.array(list(chunks.keys()), dtype=np.int32)
+        arrs = [np.ascontiguousarray(chunks[k], dtype=np.int16).reshape(-1) for k in chunks]
+        ns = np.array([a.size for a in arrs], dtype=np.int64)
+        ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        sh = self.engine.dims.wshift
+        cap = int(sum((int(a) // sh + 1) * sh for a in ns)) if capacity is None else int(capacity)  # at most one frame more than whole hops per stream
+        out = np.empty(max(cap, 1), dtype=np.int16)
+        counts = np.zeros(max(len(arrs), 1), dtype=np.int64)
+        self.engine._check(load_library().ctu_streams_push_signal_host(self._h, len(arrs), ids.ctypes.data, ptrs, ns.ctypes.data, out.ctypes.data, cap,
+                                                                       counts.ctypes.data))
+        res, at = {}, 0
+        for k, c in zip(chunks, counts):
+            res[k] = out[at:at + int(c)]
+            at += int(c)
+        return res
+
+    def push_signal_device(self, ids, pcm, sample_off, n_samples, out, stream=None):
+        """Device form: pcm as in push_device; out a torch int16 CUDA tensor for the samples.  Returns the sample counts per stream
+        (numpy int64); asynchronous on `stream`."""
+        import torch
+        assert pcm.is_cuda and pcm.dtype == torch.int16 and out.is_cuda and out.dtype == torch.int16
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int64)
+        assert ids.size == off.size == ns.size and (ns.size == 0 or int((off + ns).max()) <= pcm.numel())
+        counts = np.zeros(max(ids.size, 1), dtype=np.int64)
+        s = stream if stream is not None else torch.cuda.current_stream(pcm.device)
+        self.engine._check(load_library().ctu_streams_push_signal(self._h, int(ids.size), ids.ctypes.data, pcm.data_ptr(), off.ctypes.data, ns.ctypes.data,
+                                                                  out.data_ptr(), out.numel(), counts.ctypes.data, s.cuda_stream))
+        return counts[:ids.size]
+
+    def finish_signal(self, sid):
+        """Ends stream `sid`'s file on a set with signal_state: the window - wshift samples behind the ones delivered (none for a file
+        without a frame); the stream then starts a new file."""
+        cnt = ctypes.c_int64(0)
+        cap = max(self.pending(sid), 0)
+        out = np.empty(max(cap, 1), dtype=np.int16)
+        self.engine._check(load_library().ctu_streams_finish_signal_host(self._h, int(sid), out.ctypes.data if cap else None, cap, ctypes.byref(cnt)))
+        return out[:int(cnt.value)]
 
     def frames(self, sid):
         """Rows of the current file delivered so far."""
@@ -428,9 +493,9 @@ class Engine:
     def plan(self, nsamples):
         return Plan(self, nsamples)
 
-    def streams(self, n, max_push, row_state=False, nr_state=False, vad_state=False):
+    def streams(self, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
-        return Streams(self, n, max_push, row_state, nr_state, vad_state)
+        return Streams(self, n, max_push, row_state, nr_state, vad_state, signal_state)
 
     def _check(self, rc):
         if rc != CTU_OK:

@@ -204,8 +204,8 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * kinds, and with row state the delta chains, stacking and CMS behind them.  Exten is causal - frame t reads frames 0 .. t - so a row
  * still goes out with the push that completes its frame, R(F) is unchanged and ctu_streams_finish has nothing to add; a stream's next
  * file starts from the reference's initial estimate.  Still refused, by name, whatever the flags: -nr_when afterFB, exten on 1024 ..
- * 4096 points, hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct, CMVN, speech output, HTK feature
- * input.  On a chain without -nr_mode exten the flag changes nothing.
+ * 4096 points, hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct, CMVN, speech output (without its
+ * flag, below), HTK feature input.  On a chain without -nr_mode exten the flag changes nothing.
  *
  * Detector state (CTU_STREAMS_VAD_STATE; combines with the other two): the set also keeps, per stream, the state of the VAD module's
  * sequential part - the threshold recurrences, the background cepstrum, the majority filter's ring (src/vad/vad.cc:220-625,
@@ -223,8 +223,23 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * deliver the rows only.  On a set without detector state a non-NULL vad buffer is CTU_ERR_INPUT before anything changes.  Refused by
  * name whatever the flags: -vad_apply_mode drop, -vad_cepdist_mode fea, the VAD module with -fea_delta / -fea_trap / -fea_Z_exp /
  * -fea_Z_block, -fea_E where the offline run shifts the energy column (filter orders above 2), the VAD on 1024-point and larger
- * frames, -nr_mode exten with a criterion outside the fused shapes.  On a configuration without the VAD module the flag changes nothing. */
-enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8 };   /* (2 is no flag: sets refuse it as unknown, and callers may rely on that) */
+ * frames, -nr_mode exten with a criterion outside the fused shapes.  On a configuration without the VAD module the flag changes nothing.
+ *
+ * Signal state (CTU_STREAMS_SIGNAL_STATE): the set streams the speech-enhancement output (-format_out raw | wave, row N3; what the
+ * reference's -online_in / -online_out pair is for).  It also keeps, per stream, the tail of the overlap-add: the window - wshift
+ * partial sums of the samples that later frames still add to (src/io/out.cc:436-451), in double.  A sample is final once frame
+ * floor(n / wshift) is in, so after F frames a stream has delivered F * wshift samples, and ctu_streams_finish_signal delivers the
+ * window - wshift behind them - what close() writes - once the file has a frame.  The samples are those of ctu_engine_run_signal on
+ * the whole file: the partial sum of a sample is continued in frame order, the offline run's own sequence of additions, so the two
+ * differ only where the front end's frames do (bit-equal when every push ends a multiple of eight frames into the file, else within
+ * 1 LSB).  Taken: the configurations ctu_engine_create accepts for speech output on the 256- and 512-point front end (even windows
+ * of 32 samples or more) - the plain chain, and with CTU_STREAMS_NR_STATE as well -nr_mode exten, whose noise estimate then travels
+ * with the stream as above.  Still refused by name: hwss / fwss / 2fwss, -remove_dc1, speech output on 1024 .. 4096-point frames.
+ * Without the flag speech output is refused as before; on a configuration without speech output the flag changes nothing, and the
+ * row and detector flags change nothing on one with it.  A set with signal state takes the *_signal calls below and refuses the row
+ * calls (ctu_streams_push*, ctu_streams_finish*) with CTU_ERR_INPUT before anything changes; a set without it refuses the *_signal
+ * calls likewise.  A stream delivers samples: wave headers are the caller's. */
+enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32 };   /* (2 and 16 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
@@ -254,9 +269,26 @@ int ctu_streams_push_vad_host(ctu_streams *, int32_t n, const int32_t *stream_id
                               float *h_rows, int64_t rows_capacity, int64_t *row_counts, uint8_t *h_vad);
 int ctu_streams_finish_vad(ctu_streams *, int32_t stream_id, float *d_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *d_vad, void *stream);
 int ctu_streams_finish_vad_host(ctu_streams *, int32_t stream_id, float *h_rows, int64_t rows_capacity, int64_t *row_count, uint8_t *h_vad);
-/* Rows the stream's current file has produced so far. */
+/* The calls of a set with signal state.  They mirror the row calls: the samples of a push are written to d_out one stream after the
+ * other in the order of stream_ids, out_counts[i] of them for stream i (host memory, filled on return; may be NULL); fewer than that
+ * in out_capacity, a repeated or foreign id, or more than max_push_samples for one stream is CTU_ERR_INPUT before anything is launched
+ * or changed.  Asynchronous on `stream`; the host forms are synchronised on return.  ctu_streams_finish_signal writes the window -
+ * wshift samples of the stream's tail (none, with CTU_OK, for a file without a frame; 1 .. window - wshift - 1 samples are the
+ * reference's "IO: Signal shorter than one frame!": CTU_ERR_INPUT and no samples), clears the tail, and the stream starts a new file -
+ * with the reference's initial noise estimate - with its next push; room for fewer samples is CTU_ERR_INPUT and the stream stays as it was. */
+int ctu_streams_push_signal(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *d_pcm, const int64_t *sample_off,
+                            const int64_t *n_samples, int16_t *d_out, int64_t out_capacity, int64_t *out_counts, void *stream);
+int ctu_streams_push_signal_host(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *const *h_pcm, const int64_t *n_samples,
+                                 int16_t *h_out, int64_t out_capacity, int64_t *out_counts);
+int ctu_streams_finish_signal(ctu_streams *, int32_t stream_id, int16_t *d_out, int64_t out_capacity, int64_t *out_count, void *stream);
+int ctu_streams_finish_signal_host(ctu_streams *, int32_t stream_id, int16_t *h_out, int64_t out_capacity, int64_t *out_count);
+/* The arithmetic of such a stream on its own (pure): the samples delivered after `total` input samples, F * wshift, and in *pending
+ * (may be NULL) what a finish adds: window - wshift if F > 0, else 0. */
+int64_t ctu_streams_signal_step(int32_t window, int32_t wshift, int64_t total, int64_t *pending);
+/* Rows the stream's current file has produced so far (signal state: its frames). */
 int64_t ctu_streams_frames(const ctu_streams *, int32_t stream_id);
-/* Rows a finish would deliver now: the frames of the current file whose rows are held back (0 without row state). */
+/* Rows a finish would deliver now: the frames of the current file whose rows are held back (0 without row state).  Signal state: the
+ * samples ctu_streams_finish_signal would deliver now. */
 int64_t ctu_streams_pending(const ctu_streams *, int32_t stream_id);
 /* The arithmetic of a stream on its own (pure): the frames a file has produced after `total` samples - the frame count of
  * ctu_num_frames, 0 while it has none - and in *carry (may be NULL) the samples the next frame already has. */
