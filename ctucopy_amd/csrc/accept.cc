@@ -217,7 +217,7 @@ int streams_check(const Design &d, uint32_t flags, std::string &err) {
         err = "ENGINE: configuration not on the accelerated path: " + why;
         return CTU_ERR_UNSUPPORTED;
     }
-    if (flags & ~STREAMS_FLAGS) {
+    if (streams_flags_unknown(flags)) {
         err = "ENGINE: unknown stream set flags";
         return CTU_ERR_INPUT;
     }
@@ -234,22 +234,24 @@ int streams_check(const Design &d, uint32_t flags, std::string &err) {
 // With CTU_STREAMS_NR_STATE it keeps the noise estimate of -nr_mode exten on the spectrum (256- and 512-point front end): that passes too.
 // With CTU_STREAMS_SIGNAL_STATE it keeps the overlap-add's tail of speech output (stream_signal_kernels.h): -format_out raw | wave passes on
 // the 256- and 512-point front end, the plain chain and - with the noise state as well - exten.  Without the flag every answer is the one it was.
+// With CTU_STREAMS_LARGE_STATE the noise state and the signal state reach 1024 .. 4096-point frames (wave1k_kernel / bigfft_kernel<..., XS>,
+// stream_ola_big_kernel): the two refusals by size below fall away, everything else stands.  Without the flag every answer is the one it was.
 std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
     const Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
     if (d.signal_out && !(flags & CTU_STREAMS_SIGNAL_STATE)) return "-format_out raw | wave (speech output: the overlap-add runs across a file's frames)";
-    const bool nr_state = (flags & CTU_STREAMS_NR_STATE) != 0;
+    const bool nr_state = (flags & CTU_STREAMS_NR_STATE) != 0, large_state = (flags & CTU_STREAMS_LARGE_STATE) != 0;
     if (d.signal_out) {  // the overlap-add's tail travels with the stream (stream_signal_kernels.h), exten's state as on the feature path
         if (o.nr_mode != "none" && !(o.nr_mode == "exten" && nr_state)) return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
         if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
-        if (d.wfft >= 1024)
+        if (d.wfft >= 1024 && !large_state)
             return "-format_out raw | wave on " + std::to_string(d.wfft) + "-point frames (-w: a stream set carries the overlap-add behind the 256- and 512-point front end; the large transforms' synthesis is not streamed)";
         if (d.wshift > d.window) return "-s above -w (frames that leave samples out)";
         return "";  // (nothing else of a speech-output configuration runs along a file: no rows, no detector - unsupported_reason)
     }
     if (o.nr_mode == "exten" && nr_state) {  // the state of exten on the spectrum travels with the stream (frontend_kernel<..., XS>)
         if (o.nr_when_afterFB) return "-nr_when afterFB (exten behind the filter bank keeps its noise estimate per band, inside the filter-bank walk: a stream set carries the estimate per bin)";
-        if (d.wfft >= 1024) return "-nr_mode exten on " + std::to_string(d.wfft) + "-point frames (-w: the noise estimate of the large transforms lives in their own kernels, a stream set carries the one of the 256- and 512-point front end)";
+        if (d.wfft >= 1024 && !large_state) return "-nr_mode exten on " + std::to_string(d.wfft) + "-point frames (-w: the noise estimate of the large transforms lives in their own kernels, a stream set carries the one of the 256- and 512-point front end)";
     } else if (o.nr_mode != "none") return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
     if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
     if (o.do_vad() && !(flags & CTU_STREAMS_VAD_STATE)) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";

@@ -51,6 +51,9 @@ struct BigParams {
     const unsigned char *ss_dirty, *ss_vbits;  // [n_utt] utterances this pass recomputes; [total_frames] the detector's decisions
     const int *tile_utt;     // utterance of every tile
     float *pss;              // speech output: the subtracted magnitudes [total_frames][K] for bigsynth_kernel (pnr stays as exported), or NULL
+    float *xstate;           // XS instantiations (a stream set with noise and large-transform state): exten's Navg | Yavg of every stream as the
+                             // kernel that runs holds them - bigfft_kernel [n_streams][2][256 NB], wave1k_kernel [n_streams][2][64 * 9]; tile_utt
+                             // is then the stream of every tile
 };
 
 __device__ __forceinline__ double block_sum(double v, double *red) {  // 256 threads; red: 4 doubles of LDS
@@ -200,7 +203,21 @@ LdsFit bigfft_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
 
 // EXTEN: -nr_mode exten (src/nr/nr.cc:86-140) - the recurrence runs along an utterance, so a WORKGROUP walks one of the plan's chains of
 // whole utterances (chain_first / TileRec::next, as wave1k_kernel's waves do) with Navg / Yavg of its bins k = tid + 256 i in registers.
-template <int NIT, bool EXTEN = false>  // NIT = wfft / 256: 4, 8 or 16 samples per lane
+// XS: a stream set with noise state and large-transform state (CTU_STREAMS_NR_STATE | CTU_STREAMS_LARGE_STATE), frontend_kernel's XS at
+// this size: the chains are chains of whole streams, and the estimate comes from the stream's slot of p.xstate - 2 * 256 * NB floats,
+// Navg then Yavg of bin tid + 256 r at [256 r + tid] - when the workgroup enters the first tile the stream has in this launch, unless
+// that tile starts a file (rec.t0 == 0: the reset below), and goes back behind the stream's last tile of the push (rec.t0 + nvalid ==
+// rec.T, stream_stitch_kernel's rule); between a stream's tiles it stays in registers.  Thread = bin: every access is a dword per lane,
+// 1 KiB contiguous per workgroup; floats travel as they stand, so a store and reload is exact.  A stream is named once in a push, so
+// no two workgroups touch one slot in a launch.  A switch at compile time: the offline instantiations keep their code and registers.
+// gfx950, hipcc -O3, from the code object's metadata, offline instantiation -> XS (VGPRs, AGPRs included | SGPRs | SGPRs kept in VGPR lanes):
+//   <4, true>  109 | 106 | 270  ->  <4, true, XS>  111 | 106 | 274
+//   <8, true>  125 | 106 | 412  ->  <8, true, XS>  127 | 106 | 415
+//   <16, true> 182 (10 AGPRs) | 108 | 690  ->  <16, true, XS> 186 (10 AGPRs) | 108 | 695
+// No VGPR goes to scratch in any of them: the 784 bytes of scratch per lane every instantiation has are big_project's LP arrays.  The
+// metadata's VGPR spill count is 0 at <4> and <8>; at <16> it counts the VGPRs of SGPR lanes parked in an AGPR, a register copy: 1 with
+// XS, 2 offline (1 in the plain <16>).
+template <int NIT, bool EXTEN = false, bool XS = false>  // NIT = wfft / 256: 4, 8 or 16 samples per lane
 __global__ __launch_bounds__(256) void bigfft_kernel(const BigParams p) {
     extern __shared__ __align__(16) float smem[];
     const int N = p.wfft, Nc = N >> 1, K = p.K;
@@ -235,10 +252,24 @@ __global__ __launch_bounds__(256) void bigfft_kernel(const BigParams p) {
         navg[r] = 0.95f;
         yavg[r] = 0.05f;
     }
+    static_assert(!XS || EXTEN, "XS: exten's state, nothing else runs along a file here");
+    bool xs_first = true;  // XS: the tile at hand is the first its stream has in this launch
     int tile = EXTEN ? ((int)blockIdx.x < p.n_chains ? p.chain_first[blockIdx.x] : -1) : ((int)blockIdx.x < p.n_tiles ? (int)blockIdx.x : -1);
     while (tile >= 0) {
         const TileRec rec = load_rec(p.tiles, tile);
+        float *const xs = XS ? p.xstate + (size_t)p.tile_utt[tile] * (2 * 256 * NB) : nullptr;
         tile = EXTEN ? rec.next : (tile + (int)gridDim.x < p.n_tiles ? tile + (int)gridDim.x : -1);
+        if constexpr (XS) {
+            if (xs_first && rec.t0 != 0) {  // the file goes on: where the stream's last push left off (a file's first frame resets below)
+#pragma unroll
+                for (int r = 0; r < NB; r++) {
+                    navg[r] = xs[256 * r + tid];
+                    yavg[r] = xs[256 * (NB + r) + tid];
+                }
+            }
+            xs_first = rec.t0 + rec.nvalid == rec.T;  // the stream's last tile of this push (stream_stitch_kernel: T = the file's frames once
+                                                      // the push is through): the next tile, if any, is another stream's first
+        }
         // the samples of a frame are fetched one frame ahead (registers): the loads fly under the previous frame's passes
         int16_t cur[NIT], prv[NIT];
         auto fetch = [&](int f) {
@@ -385,6 +416,15 @@ __global__ __launch_bounds__(256) void bigfft_kernel(const BigParams p) {
             }
             big_project(p, P, Y, Ylog, red, lfb, lcoef, lcoef_d, lrange, rec.rbase + f, e_raw, tid);
             lds_barrier();  // P, Y and the FFT buffers are rewritten by the next frame
+        }
+        if constexpr (XS) {
+            if (xs_first) {  // behind the stream's last tile of this push
+#pragma unroll
+                for (int r = 0; r < NB; r++) {
+                    xs[256 * r + tid] = navg[r];
+                    xs[256 * (NB + r) + tid] = yavg[r];
+                }
+            }
         }
     }
 }

@@ -160,6 +160,7 @@ struct RunExtent {
     int grid = 0;                  // workgroups of the front-end launch (tile chains are built for it)
     int64_t total_frames = 0;
     const int *heads = nullptr;    // first tile of every chain: a plan's wg_first, or the heads a push was dealt onto (null: a plan over rows)
+    int n_heads = 0;               // entries of `heads`: the chains wave1k_kernel / bigfft_kernel are launched for with exten
     void *xstate = nullptr;        // a stream set with noise state: exten's state of every stream (null: none, every file starts afresh)
 };
 
@@ -406,7 +407,8 @@ KParams run_kparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent &x,
 BigParams run_bigparams(const ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const KParams &kp) {
     BigParams bp = e->bp0;
     bp.pcm = kp.pcm; bp.rows = kp.rows; bp.logmel = kp.logmel; bp.tiles = pl->tiles.p; bp.n_tiles = x.n_tiles;
-    bp.chain_first = x.heads; bp.n_chains = (int)pl->wg_first.n;  // (the count is the plan's: no stream set runs chains on the large-FFT kernels)
+    bp.chain_first = x.heads; bp.n_chains = x.n_heads;  // (the plan's own, or those of a push: a stream set with large-transform state)
+    bp.xstate = static_cast<float *>(x.xstate);
     bp.vad_en = e->geom.vad_energy ? pl->pnr.p : nullptr;
     bp.dc1 = pl->dc1.p;
     // the spectra leave bigfft_kernel for bigsynth_kernel, bigburg_kernel (which reads them; the rows are projected as well) or bigss_kernel
@@ -435,7 +437,8 @@ void launch_bigfft(ctu_engine *e, const RunExtent &x, hipStream_t s, const BigPa
     const dim3 g((unsigned)std::max(1, bp.nr_exten ? bp.n_chains : std::min(x.n_tiles, e->n_cu * fit.per_cu)));
     lift<4, 8, 16>(big_nit(e), [&](auto nit) {
         constexpr int NIT = decltype(nit)::value;
-        if (bp.nr_exten) launch_lds(e, &bigfft_kernel<NIT, true>, g, dim3(256), fit.bytes, s, bp);
+        if (bp.nr_exten && x.xstate) launch_lds(e, &bigfft_kernel<NIT, true, true>, g, dim3(256), fit.bytes, s, bp);
+        else if (bp.nr_exten) launch_lds(e, &bigfft_kernel<NIT, true>, g, dim3(256), fit.bytes, s, bp);
         else launch_lds(e, &bigfft_kernel<NIT>, g, dim3(256), fit.bytes, s, bp);
     });
 }
@@ -448,9 +451,11 @@ void stage_wave1k(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStre
     // exten: one wave per chain of utterances, every chain gets its wave whatever fits the chip at once
     const int wg = bp.nr_exten ? std::max(1, (bp.n_chains + W1K_WAVES - 1) / W1K_WAVES)
                                : std::max(1, std::min((x.n_tiles + W1K_WAVES - 1) / W1K_WAVES, e->n_cu * fit.per_cu));
-    lift<0, 1>(bp.nr_exten, [&](auto ex) {
-        launch_lds(e, &wave1k_kernel<decltype(ex)::value != 0>, dim3(wg), dim3(64 * W1K_WAVES), fit.bytes, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
-    });
+    if (bp.nr_exten && x.xstate) launch_lds(e, &wave1k_kernel<true, true>, dim3(wg), dim3(64 * W1K_WAVES), fit.bytes, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
+    else
+        lift<0, 1>(bp.nr_exten, [&](auto ex) {
+            launch_lds(e, &wave1k_kernel<decltype(ex)::value != 0>, dim3(wg), dim3(64 * W1K_WAVES), fit.bytes, s, bp, (void *)pl->lp_r.p, d.o.fea_lporder + 1);
+        });
 }
 // hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h): the spectra once (bigfft_kernel with the export on and the projection off),
 // the detector's cepstra and decisions once; returns the launch of bigss_kernel, one pass of the seed iteration (run_ss_chain)
@@ -983,6 +988,7 @@ int ctu_plan_create(ctu_engine *e, const int64_t *utt_nsamples, int32_t n_utt, c
     pl->ext.grid = pl->hp.grid;
     pl->ext.total_frames = pl->hp.total_frames;
     pl->ext.heads = pl->wg_first.p;
+    pl->ext.n_heads = (int)pl->wg_first.n;
     *out = pl.release();
     return CTU_OK;
 }

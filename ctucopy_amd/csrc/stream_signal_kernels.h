@@ -20,7 +20,27 @@
 // and touch only ybuf and their own samples.  A stream that completes no frame returns at once: tail and output stay as they are.
 // Plain C++ stores throughout (global_store_short / _dwordx2); no atomics: a stream id appears once in a push.
 //
-// gfx950, hipcc -O3: stream_ola_kernel 24 VGPRs, 54 SGPRs; stream_ola_flush_kernel 20 VGPRs, 22 SGPRs; no spills, no scratch, no LDS.
+//
+//   stream_ola_big_kernel    the same overlap-add for tails of 513 .. 4096 entries (CTU_STREAMS_LARGE_STATE: windows of up to 4096 samples
+//                            behind the large transforms).  There the tail can be longer than a slice, so a workgroup of slice >= 1 of
+//                            the kernel above would read old entries that slice 0's workgroup replaces in the same launch: a race
+//                            between workgroups, which no barrier closes.  Of the two forms that cannot race - the tail's owner
+//                            produces everything below w - s, or two tails flipped per push - this is the first: it needs no second
+//                            tail per stream (32 KiB at 4096 points), no flip bit mirrored on the host that a refused push would have
+//                            to leave alone, and nothing new in the plan of a push or a finish; its price, one workgroup's walk over
+//                            up to 4095 positions, is small beside the transforms of the same frames.
+//                            Position x of a push, counted from the first sample it delivers, is the old entry x (0.0 past the tail)
+//                            plus the push's frames over x in ascending order; it is output sample x while x < T s and the new tail's
+//                            entry x - T s from there to T s + w - s.  So every old entry is read exactly once, by position x < w - s.
+//                            Workgroup 0 of a stream, the owner, reads all of them into registers - sixteen per lane - ahead of a
+//                            barrier, and behind it writes every position below w - s, output or tail, and every other entry of the
+//                            new tail.  The workgroups y >= 1 take the output positions w - s + 2048 (y - 1) on: they touch ybuf and
+//                            their own samples, never the tail.  No tail entry is read outside the owner, none is written outside
+//                            it, and inside it the barrier stands between the last read and the first store: nothing can race.
+//                            Sums are ola_cover's, rounding ola_round's: the samples of the small kernel, and of ola_kernel, bit for bit.
+//
+// gfx950, hipcc -O3: stream_ola_kernel 24 VGPRs, 54 SGPRs; stream_ola_flush_kernel 20 VGPRs, 22 SGPRs; stream_ola_big_kernel 74 VGPRs, 75 SGPRs;
+// no spills, no scratch, no LDS.
 #pragma once
 
 #include "stream_plan.h"  // SignalPush: the host plans a push by it
@@ -28,7 +48,9 @@
 namespace {
 
 constexpr int OLA_SLICE = 2048;  // samples per workgroup of stream_ola_kernel: 256 lanes x 8
-constexpr int OLA_TAIL_MAX = 512;  // the longest tail a workgroup's lanes hold two entries each of
+constexpr int OLA_TAIL_MAX = 512;  // the longest tail a workgroup's lanes hold two entries each of (stream_ola_kernel)
+constexpr int OLA_BIG_Q = 16;      // stream_ola_big_kernel: old entries per lane of the owner
+constexpr int OLA_BIG_TAIL_MAX = 256 * OLA_BIG_Q;  // ... and so the longest tail it holds: window - wshift <= 4095 at 4096 points
 
 struct SignalParams {
     const SignalPush *push;
@@ -78,6 +100,43 @@ __global__ __launch_bounds__(256) void stream_ola_kernel(const SignalParams p) {
         const long long x = (long long)blockIdx.y * OLA_SLICE + threadIdx.x + 256 * i;
         if (x < n) o[x] = ola_round(ola_cover(i < 2 ? lead[i] : 0.0, y, x, d.T, w, s), p.corr);
     }
+}
+
+// grid (pushed streams, 1 + slices of OLA_SLICE output samples past the tail), 256 lanes
+__global__ __launch_bounds__(256) void stream_ola_big_kernel(const SignalParams p) {
+    const SignalPush d = p.push[blockIdx.x];
+    const int w = p.window, s = p.wshift, L = w - s;
+    const long long n = (long long)d.T * s;
+    if (n == 0) return;  // (no frame: tail and output stay as they are; the whole workgroup leaves ahead of the barrier)
+    const float *y = p.ybuf + d.row0 * w;
+    int16_t *o = p.out + d.out0;
+    if (blockIdx.y > 0) {  // output past the tail: nothing old under it
+        const long long x0 = L + (long long)(blockIdx.y - 1) * OLA_SLICE;
+#pragma unroll
+        for (int i = 0; i < OLA_SLICE / 256; i++) {
+            const long long x = x0 + threadIdx.x + 256 * i;
+            if (x < n) o[x] = ola_round(ola_cover(0.0, y, x, d.T, w, s), p.corr);
+        }
+        return;
+    }
+    double *tl = p.tail + (size_t)d.id * p.tstride;
+    double old[OLA_BIG_Q];
+#pragma unroll
+    for (int q = 0; q < OLA_BIG_Q; q++) {
+        const int x = threadIdx.x + 256 * q;
+        old[q] = x < L ? tl[x] : 0.0;
+    }
+    __syncthreads();  // every old entry is in a register
+#pragma unroll
+    for (int q = 0; q < OLA_BIG_Q; q++) {
+        const int x = threadIdx.x + 256 * q;
+        if (x < L) {
+            const double v = ola_cover(old[q], y, x, d.T, w, s);
+            if (x < n) o[x] = ola_round(v, p.corr);
+            else tl[x - n] = v;
+        }
+    }
+    for (long long x = (n > L ? n : L) + threadIdx.x; x < n + L; x += 256) tl[x - n] = ola_cover(0.0, y, x, d.T, w, s);  // the new tail past the old one
 }
 
 // one workgroup of 256 lanes: the stream d.id finishes its file

@@ -44,7 +44,8 @@ struct ctu_streams {
     std::vector<uint8_t> hsel, next_hsel;
     RowPush *h_rdesc[2] = {nullptr, nullptr};
     DevBuf<RowPush> d_rdesc[2];
-    // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten (g.chained, g.max_chains): Navg | Yavg of every stream (frontend_kernel<..., XS>),
+    // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten (g.chained, g.max_chains): Navg | Yavg of every stream (frontend_kernel<..., XS>;
+    // with CTU_STREAMS_LARGE_STATE on 1024 .. 4096 points wave1k_kernel<true, XS> / bigfft_kernel<NIT, true, XS>: sized by the kernel that runs),
     // the heads of the chains a push is dealt onto, which travel as the descriptors do, and the stream of every tile
     DevBuf<float> xstate;
     int *h_heads[2] = {nullptr, nullptr};
@@ -60,8 +61,9 @@ struct ctu_streams {
     int *h_replay[2] = {nullptr, nullptr};
     DevBuf<int> d_replay[2];
     // CTU_STREAMS_SIGNAL_STATE on a configuration with speech output (stream_signal_kernels.h; g.signal): the overlap-add's tail of every
-    // stream - tstride doubles each, window - wshift of them in use - and the descriptors of stream_ola_kernel
-    bool signal = false;
+    // stream - tstride doubles each, window - wshift of them in use - and the descriptors of stream_ola_kernel; ola_big: a tail beyond
+    // OLA_TAIL_MAX entries (CTU_STREAMS_LARGE_STATE), which stream_ola_big_kernel carries
+    bool signal = false, ola_big = false;
     int tstride = 0;
     DevBuf<double> otail;
     SignalPush *h_sdesc[2] = {nullptr, nullptr};
@@ -161,7 +163,7 @@ int ctu_streams_create(ctu_engine *e, int32_t n_streams, int64_t max_push_sample
 int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out) {
     if (!e || !out) return CTU_ERR_INPUT;
     *out = nullptr;
-    if (flags & ~STREAMS_FLAGS) {
+    if (ctu::streams_flags_unknown(flags)) {
         set_error(e, "ENGINE: unknown stream set flags");
         return CTU_ERR_INPUT;
     }
@@ -174,7 +176,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
-    if ((e->geom.per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->geom.do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->tab.ss || (e->geom.per_wave && e->tab.big) || (e->geom.do_vad && e->tab.big)) {
+    if ((e->geom.per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->geom.do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->tab.ss || (e->geom.per_wave && e->tab.big && !(flags & CTU_STREAMS_LARGE_STATE)) || (e->geom.do_vad && e->tab.big)) {
         set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
         return CTU_ERR_UNSUPPORTED;
     }
@@ -199,13 +201,14 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         g.held = false;
         g.H = g.wmax = 0;
         st->tstride = (std::max(d.window - d.wshift, 1) + 1) / 2 * 2;
-        if (d.window - d.wshift > OLA_TAIL_MAX || e->tab.big) {
+        st->ola_big = d.window - d.wshift > OLA_TAIL_MAX;
+        if (((st->ola_big || e->tab.big) && !(flags & CTU_STREAMS_LARGE_STATE)) || d.window - d.wshift > OLA_BIG_TAIL_MAX) {
             set_error(e, "ENGINE: internal: a signal set beyond the 512-point front end");
             return CTU_ERR_UNSUPPORTED;
         }
     }
     g.chained = e->geom.per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
-    g.max_chains = g.max_wg * NWAVE;
+    g.max_chains = e->geom.chain_slots;  // (the plan geometry's: max_wg * NWAVE wave chains, or n_cu * 8 workgroup chains of bigfft_kernel)
     st->C = st->vad ? g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
     st->consumed.assign((size_t)n_streams, 0);
     st->seen.assign((size_t)n_streams, 0);
@@ -246,7 +249,9 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             }
         }
         if (g.chained) {
-            const size_t per_stream = (size_t)2 * 64 * (e->tab.sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1);  // [2][64 NJ] of xstate_t (frontend_kernel.h)
+            // by the kernel that runs: [2][64 NJ] of xstate_t (frontend_kernel.h), [2][64 * 9] floats (wave1k_kernel.h), [2][256 NB] floats (bigfft_kernel.h)
+            const size_t per_stream = !e->tab.big ? (size_t)2 * 64 * (e->tab.sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1)
+                                      : e->tab.path == BIG_WAVE1K ? (size_t)2 * 64 * 9 : (size_t)2 * 256 * (big_nit(e) / 2 + 1);
             st->xstate.alloc((size_t)n_streams * per_stream);
             HIP_TRY(hipMemset(st->xstate.p, 0, st->xstate.n * sizeof(float)));  // (never read ahead of a store: a file's first tile resets)
             pl->tile_utt.alloc(pl->tiles.n);
@@ -438,6 +443,7 @@ int ctu_streams_push_vad(ctu_streams *st, int32_t n, const int32_t *ids, const i
         RunExtent x;  // the front end and its tails run over the front of the set's plan: this push
         x.n_tiles = L.tiles; x.grid = L.grid; x.total_frames = L.base_rows;
         x.heads = L.n_heads ? st->d_heads[k].p : pl->ext.heads;
+        x.n_heads = L.n_heads ? L.n_heads : pl->ext.n_heads;
         x.xstate = st->xstate.p;
         StreamParams sp;
         sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
@@ -637,7 +643,8 @@ int ctu_streams_finish_vad_host(ctu_streams *st, int32_t id, float *h_rows, int6
 
 // ---- signal state: the same push - check, plan, commit, launch - with samples out.  The front end leaves the time-domain frames of the
 // push in the plan's ybuf, a row per frame (its SY instantiations; in a build without them synth_kernel from the exported spectra), and
-// stream_ola_kernel adds them onto every stream's tail.
+// stream_ola_kernel adds them onto every stream's tail.  With CTU_STREAMS_LARGE_STATE on 1024 .. 4096-point frames the frames come from
+// bigfft_kernel's exported spectra through bigsynth_kernel, and a tail of more than OLA_TAIL_MAX entries is stream_ola_big_kernel's.
 namespace {
 SignalParams signal_params(const ctu_streams *st, const SignalPush *push, int16_t *d_out) {
     const ctu::Design &d = *st->eng->design;
@@ -704,6 +711,7 @@ int ctu_streams_push_signal(ctu_streams *st, int32_t n, const int32_t *ids, cons
         RunExtent x;
         x.n_tiles = L.tiles; x.grid = L.grid; x.total_frames = L.base_rows;
         x.heads = L.n_heads ? st->d_heads[k].p : pl->ext.heads;
+        x.n_heads = L.n_heads ? L.n_heads : pl->ext.n_heads;
         x.xstate = st->xstate.p;
         StreamParams sp;
         sp.push = st->d_desc[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
@@ -722,7 +730,8 @@ int ctu_streams_push_signal(ctu_streams *st, int32_t n, const int32_t *ids, cons
             e->in_signal_call = false;
         }
         if (L.tiles && rc == CTU_OK) {
-            if (!e->tab.sel.sy) {  // the spectra of the push's frames back to the time domain (ctu_engine_run_signal's launch, over this extent)
+            if (e->tab.big) launch_bigsynth(e, pl, x, s, 1.0f / (float)d.wfft);  // (large transforms: bigfft_kernel exported the spectra)
+            else if (!e->tab.sel.sy) {  // the spectra of the push's frames back to the time domain (ctu_engine_run_signal's launch, over this extent)
                 SynthParams yp;
                 yp.K = d.K; yp.wfft = d.wfft; yp.window = d.window; yp.wshift = d.wshift;
                 yp.inv_n = 1.0f / (float)d.wfft;
@@ -730,8 +739,14 @@ int ctu_streams_push_signal(ctu_streams *st, int32_t n, const int32_t *ids, cons
                 const int g = (int)std::min<int64_t>((L.base_rows + 7) / 8, (int64_t)e->n_cu * 8);
                 hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)L.base_rows, yp);
             }
-            const unsigned slices = (unsigned)((L.most + OLA_SLICE - 1) / OLA_SLICE);
-            hipLaunchKernelGGL(stream_ola_kernel, dim3((unsigned)n, slices), dim3(256), 0, s, signal_params(st, st->d_sdesc[k].p, d_out));
+            if (st->ola_big) {  // the owner of every tail, then the slices of the samples past it
+                const int64_t past = std::max<int64_t>(L.most - (d.window - d.wshift), 0);
+                hipLaunchKernelGGL(stream_ola_big_kernel, dim3((unsigned)n, 1u + (unsigned)((past + OLA_SLICE - 1) / OLA_SLICE)), dim3(256), 0, s,
+                                   signal_params(st, st->d_sdesc[k].p, d_out));
+            } else {
+                const unsigned slices = (unsigned)((L.most + OLA_SLICE - 1) / OLA_SLICE);
+                hipLaunchKernelGGL(stream_ola_kernel, dim3((unsigned)n, slices), dim3(256), 0, s, signal_params(st, st->d_sdesc[k].p, d_out));
+            }
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(st->ev[2], s));

@@ -72,7 +72,14 @@ LdsFit wave1k_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
 // per SIMD - twiddles come from one shared W1024 table instead of 48 registers per lane, samples are not fetched a frame ahead.
 // EXTEN: -nr_mode exten (the recurrence's eighteen state registers and the chain walk) as an instantiation of its own, one wave per SIMD
 // fewer: the plain kernel keeps its registers.
-template <bool EXTEN>
+// XS: a stream set with noise state and large-transform state (bigfft_kernel.h has the rule; frontend_kernel's XS at this size): a wave's
+// chain is one of whole streams, and the estimate comes from, and goes back to, the stream's slot of p.xstate - 2 * 64 * 9 floats, Navg
+// then Yavg of bin lane + 64 r at [64 r + lane] - at the edges of a push.  Lane = bin: a dword per lane, 256 contiguous bytes per access.
+// A base per half, since the last two of eighteen accesses from one base would lie 4096 bytes and more from it, past the instruction's
+// offset field: the 64-bit lane address kept for them across the frame loop was what spilled under this kernel's 128 VGPRs.
+// gfx950, hipcc -O3, from the code object's metadata: <true> 128 VGPRs, 106 SGPRs, 85 SGPRs kept in VGPR lanes; <true, XS> 128 VGPRs,
+// 106 SGPRs, 100 kept in VGPR lanes; no VGPR spills and no scratch in either.
+template <bool EXTEN, bool XS = false>
 __global__ __launch_bounds__(64 * W1K_WAVES, EXTEN ? CTU_W1K_LB - 1 : CTU_W1K_LB) void wave1k_kernel(const BigParams p, void *lp_r, int lp_stride) {
     extern __shared__ __align__(16) float smem[];
     constexpr int Nc = 512;
@@ -135,10 +142,28 @@ __global__ __launch_bounds__(64 * W1K_WAVES, EXTEN ? CTU_W1K_LB - 1 : CTU_W1K_LB
         navg[r] = 0.95f;
         yavg[r] = 0.05f;
     }
+    static_assert(!XS || EXTEN, "XS: exten's state, nothing else runs along a file here");
+    bool xs_first = true;  // XS: the tile at hand is the first its stream has in this launch
     int tile = EXTEN ? (gw < p.n_chains ? p.chain_first[gw] : -1) : (gw < p.n_tiles ? gw : -1);
     while (tile >= 0) {
         const TileRec rec = load_rec(p.tiles, tile);
+        const int xs_stream = XS ? as_const(p.tile_utt)[tile] : 0;
+        // (a wave-uniform base for each half and a 32-bit lane offset: every access keeps its distance from the base in the instruction's
+        // 12-bit offset field, no 64-bit address per lane)
+        auto xs_slot = [&](int half) { return uniform_ptr(p.xstate + (size_t)xs_stream * (2 * 64 * 9) + half * (64 * 9)); };
         tile = EXTEN ? rec.next : (tile + nw < p.n_tiles ? tile + nw : -1);
+        if constexpr (XS) {
+            if (xs_first && rec.t0 != 0) {  // the file goes on: where the stream's last push left off (a file's first frame resets below)
+                const auto xn = xs_slot(0), xy = xs_slot(1);
+#pragma unroll
+                for (int r = 0; r < 9; r++) {
+                    navg[r] = xn[(unsigned)(lane + 64 * r)];
+                    yavg[r] = xy[(unsigned)(lane + 64 * r)];
+                }
+            }
+            xs_first = rec.t0 + rec.nvalid == rec.T;  // the stream's last tile of this push (stream_stitch_kernel: T = the file's frames once
+                                                      // the push is through): the next tile, if any, is another stream's first
+        }
         for (int f = 0; f < rec.nvalid; f++) {
             pcm4 q[8];  // samples x[i-2 .. i+1], i = 2 lane + 128 n2
             {
@@ -381,6 +406,16 @@ __global__ __launch_bounds__(64 * W1K_WAVES, EXTEN ? CTU_W1K_LB - 1 : CTU_W1K_LB
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();  // P, Y and the planes are rewritten by the next frame
+        }
+        if constexpr (XS) {
+            if (xs_first) {  // behind the stream's last tile of this push
+                const auto xn = xs_slot(0), xy = xs_slot(1);
+#pragma unroll
+                for (int r = 0; r < 9; r++) {
+                    xn[(unsigned)(lane + 64 * r)] = navg[r];
+                    xy[(unsigned)(lane + 64 * r)] = yavg[r];
+                }
+            }
         }
     }
 }

@@ -204,7 +204,7 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * kinds, and with row state the delta chains, stacking and CMS behind them.  Exten is causal - frame t reads frames 0 .. t - so a row
  * still goes out with the push that completes its frame, R(F) is unchanged and ctu_streams_finish has nothing to add; a stream's next
  * file starts from the reference's initial estimate.  Still refused, by name, whatever the flags: -nr_when afterFB, exten on 1024 ..
- * 4096 points, hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct, CMVN, speech output (without its
+ * 4096 points (without CTU_STREAMS_LARGE_STATE, below), hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct, CMVN, speech output (without its
  * flag, below), HTK feature input.  On a chain without -nr_mode exten the flag changes nothing.
  *
  * Detector state (CTU_STREAMS_VAD_STATE; combines with the other two): the set also keeps, per stream, the state of the VAD module's
@@ -234,12 +234,27 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * differ only where the front end's frames do (bit-equal when every push ends a multiple of eight frames into the file, else within
  * 1 LSB).  Taken: the configurations ctu_engine_create accepts for speech output on the 256- and 512-point front end (even windows
  * of 32 samples or more) - the plain chain, and with CTU_STREAMS_NR_STATE as well -nr_mode exten, whose noise estimate then travels
- * with the stream as above.  Still refused by name: hwss / fwss / 2fwss, -remove_dc1, speech output on 1024 .. 4096-point frames.
+ * with the stream as above.  Still refused by name: hwss / fwss / 2fwss, -remove_dc1, speech output on 1024 .. 4096-point frames
+ * (without CTU_STREAMS_LARGE_STATE, below).
  * Without the flag speech output is refused as before; on a configuration without speech output the flag changes nothing, and the
  * row and detector flags change nothing on one with it.  A set with signal state takes the *_signal calls below and refuses the row
  * calls (ctu_streams_push*, ctu_streams_finish*) with CTU_ERR_INPUT before anything changes; a set without it refuses the *_signal
- * calls likewise.  A stream delivers samples: wave headers are the caller's. */
-enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32 };   /* (2 and 16 are no flags: sets refuse them as unknown, and callers may rely on that) */
+ * calls likewise.  A stream delivers samples: wave headers are the caller's.
+ *
+ * Large-transform state (CTU_STREAMS_LARGE_STATE; combines with all of the above): the noise state and the signal state reach the
+ * configurations whose FFT size is 1024, 2048 or 4096 points - 25 ms at 44.1 or 48 kHz, 40 ms at 16 kHz.  The flag keeps nothing of its
+ * own, so it is a flag only beside CTU_STREAMS_NR_STATE or CTU_STREAMS_SIGNAL_STATE: without either, 64 is refused as an unknown flag,
+ * as it always was.  Kept per stream: with
+ * CTU_STREAMS_NR_STATE, Navg and Yavg of every bin as the large-transform kernels hold them in registers (floats, stored and reloaded
+ * as they stand); with CTU_STREAMS_SIGNAL_STATE, an overlap-add tail of window - wshift doubles, up to 4095 of them.  Taken with the
+ * noise state: -nr_mode exten on the spectrum (-nr_when beforeFB) with every feature tail ctu_engine_create accepts at these sizes,
+ * and with row state the delta chains, stacking and CMS behind it.  Taken with the signal state: speech output of the plain chain,
+ * and with the noise state as well behind exten; windows of odd length are fine here, as offline.  Rows and samples relate to the
+ * offline run as above (bit-equal when every push ends a multiple of eight frames into the file).  Still
+ * refused by name, whatever the flags: -nr_when afterFB, hwss / fwss / 2fwss, -remove_dc1, the VAD module on 1024-point and larger
+ * frames, trapdct, CMVN, HTK feature input.  On a configuration of 512 points or fewer the flag changes nothing, and without it
+ * every answer - exten and speech output on 1024 .. 4096-point frames refused by name - is the one it was. */
+enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64 };   /* (2 and 16 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
