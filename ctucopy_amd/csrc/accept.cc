@@ -236,6 +236,8 @@ int streams_check(const Design &d, uint32_t flags, std::string &err) {
 // the 256- and 512-point front end, the plain chain and - with the noise state as well - exten.  Without the flag every answer is the one it was.
 // With CTU_STREAMS_LARGE_STATE the noise state and the signal state reach 1024 .. 4096-point frames (wave1k_kernel / bigfft_kernel<..., XS>,
 // stream_ola_big_kernel): the two refusals by size below fall away, everything else stands.  Without the flag every answer is the one it was.
+// With CTU_STREAMS_TRAP_STATE it keeps the last traplen - 1 log-mel rows of every stream (stream_trap_kernels.h): -fea_kind trapdct passes
+// on the plain chain and behind exten's state; beside the VAD module it stays refused.  Without the flag every answer is the one it was.
 std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
     const Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
@@ -268,7 +270,8 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
         if (o.nr_mode == "exten" && !(burg && vf_eligible(d)))
             return "-nr_mode exten with a VAD criterion outside the fused shapes (25 ms frames at 8 or 16 kHz, the lpc criterion with 14 coefficients: the exported spectra are not carried behind exten's state)";
     }
-    if (d.kind == FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
+    // with CTU_STREAMS_TRAP_STATE the last traplen - 1 log-mel rows travel with the stream (stream_trap_kernels.h)
+    if (d.kind == FeaKind::TrapDct && !(flags & CTU_STREAMS_TRAP_STATE)) return "-fea_kind trapdct (a vector spans traplen frames)";
     const bool row_state = (flags & CTU_STREAMS_ROW_STATE) != 0;
     if (d.post_order > 0 && !row_state) return d.post_stack ? "-fea_trap (stacking spans 2 * trap_win + 1 frames)" : "-fea_delta (the delta chain spans the frames of its windows)";
     if (d.cms && !row_state) return d.cms == 1 ? "-fea_Z_exp (CMS: the running mean runs along the file)" : "-fea_Z_block (CMS: the block mean spans its window of frames)";

@@ -19,6 +19,7 @@
 //   bigss_kernel.h     hwss / fwss / 2fwss on 2048 / 4096-point frames along chains of whole utterances
 //   stream_kernels.h   streaming input: carry | new samples into the slots of a push arena, the tile records of the push, the next carry
 //   stream_rows_kernels.h  streaming input with row state: delta chain / stacking and CMS by absolute frame index, the base-row history
+//   stream_trap_kernels.h  streaming input with trap state: TRAP-DCT over the rows a push completes, sixteen (stream, row) columns per MFMA
 //   stream_signal_kernels.h  streaming input with signal state: the overlap-add of a push from the stream's tail, the flush at a file's end
 //   stream_plan.h      streaming input, host only and HIP-free: the descriptors of a push and the planner that fills them (slots, chains, rows)
 //   streams_host.h     streaming input, host side: the stream set, create / push (check, plan, commit, launch) / finish
@@ -110,6 +111,7 @@ using namespace ctu;  // accept.h, tables.h: what is accepted, FeSel and fe_comp
 
 #include "post_kernels.h"
 #include "stream_rows_kernels.h"
+#include "stream_trap_kernels.h"
 #include "stream_vad_kernels.h"
 #include "signal_kernels.h"
 #include "stream_signal_kernels.h"
@@ -1022,7 +1024,8 @@ int ctu_plan_set_vad_ring(ctu_plan *pl, const int32_t *hidx) {
 
 // A run of a plan over the extent `x`: the plan's own, or the front of it a push of a stream set covers.  `row_stages` off stops ahead of
 // stage_post and stage_cms with the base rows in the plan's scratch: a stream set with row state runs its own forms of the two
-// (stream_rows_kernels.h) over them and its history.  `vad_stages` off likewise leaves the VAD's sequential stages out - the detector's
+// (stream_rows_kernels.h) over them and its history.  It stops ahead of stage_trap likewise, with the log-mel rows in the plan's scratch: a
+// stream set with trap state contracts them with its history (stream_trap_kernels.h); an offline run always has row_stages on.  `vad_stages` off likewise leaves the VAD's sequential stages out - the detector's
 // replay, the short files' bytes, the ring - with the criterion's input of every frame in the plan's scratch (vad_cf / vad_ci / the
 // energy): a stream set with detector state replays them from its own state (stream_vad_kernels.h) and needs no d_vad here.
 static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, const int16_t *d_pcm, float *d_rows, uint8_t *d_vad, void *stream, bool row_stages,
@@ -1078,7 +1081,7 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
 #endif
         if (e->geom.lp_tail) stage_lp_tail(e, pl, x, s, kp);
         if (e->geom.vad_burg) stage_burg_vad(e, pl, x, s);
-        if (d.kind == ctu::FeaKind::TrapDct) stage_trap(e, pl, s, d_rows);
+        if (d.kind == ctu::FeaKind::TrapDct && row_stages) stage_trap(e, pl, s, d_rows);
         if (d.post_order > 0 && row_stages) stage_post(e, pl, s, d_rows);
         if (d.cms && row_stages) stage_cms(e, pl, s, d_rows);
         if (e->geom.vad_fused && pl->hp.n_live > 0) stage_fused_vad(e, pl, x, s, d_vad, vad_stages);

@@ -11,6 +11,8 @@
 //                         time-domain frames of the push they are made of; PushGeom::signal turns a push's counts into samples
 //   stream_vad_halo       detector state (CTU_STREAMS_VAD_STATE): the majority filter's delay h as the halo of the row arithmetic, so that
 //                         a frame's row and its decision leave together; PushGeom::vad then adds the list of the streams that run the replay
+//   stream_trap_halo, stream_trap_columns   trap state (CTU_STREAMS_TRAP_STATE): half a context as the halo of the row arithmetic, and
+//                         the stream of every output row of a push, which stream_trap_kernel takes sixteen at a time
 #pragma once
 
 #include <algorithm>
@@ -204,6 +206,24 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
     L.rows_out = oo;
     L.most = most;
     return true;
+}
+
+// Trap state (CTU_STREAMS_TRAP_STATE, stream_trap_kernels.h): the halo of trapdct's context.  Row t reads log-mel frames t - half ..
+// t + half, half = (traplen - 1) / 2 (traplen is odd, at least 3), so R(F) = F - half once F >= half + 1 and none before - a file of
+// 1 .. half frames is the offline plan's refusal (plan.cc: trap_min = (traplen + 1) / 2).  That is stream_rows_out with H = half and
+// wmax = half - 1.
+inline void stream_trap_halo(int traplen, int *H, int *wmax) {
+    *H = (traplen - 1) / 2;
+    *wmax = *H - 1;
+}
+// The columns of stream_trap_kernel: the rows that go out with a push are its columns, in the order of the caller's buffer (RowPush::out0
+// is the prefix sum of nr over the push), sixteen to a wave whatever streams they belong to.  col[c] = the position in the push of the
+// stream column c belongs to, c < sum of nr; `col` has room for that many.  Returns the sum.
+inline int64_t stream_trap_columns(const RowPush *rows, int n, int *col) {
+    int64_t c = 0;
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < rows[i].nr; k++) col[c++] = i;
+    return c;
 }
 
 // A stream that finishes after `consumed` samples: the rows held back for it, which go out now (RowPush `row`, meaningful while

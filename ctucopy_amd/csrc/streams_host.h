@@ -68,6 +68,13 @@ struct ctu_streams {
     DevBuf<double> otail;
     SignalPush *h_sdesc[2] = {nullptr, nullptr};
     DevBuf<SignalPush> d_sdesc[2];
+    // CTU_STREAMS_TRAP_STATE on a configuration with -fea_kind trapdct (stream_trap_kernels.h; g.held, g.H = half, g.wmax = half - 1):
+    // the histories above hold the last C = 2 half log-mel rows of every stream, hw = B floats each; the stream of every column of
+    // stream_trap_kernel, which travels as the descriptors do
+    bool trap = false;
+    int hw = 0;                      // floats of a history row: Dbase, or B with trap state
+    int *h_cols[2] = {nullptr, nullptr};
+    DevBuf<int> d_cols[2];
     // the host form: page-locked staging of the new samples, their device copy, the rows (the samples) ahead of the download
     int16_t *h_stage = nullptr;
     DevBuf<int16_t> d_stage;
@@ -80,6 +87,7 @@ struct ctu_streams {
         for (SignalPush *h : h_sdesc) ctu_host_free(h);
         for (int *h : h_heads) ctu_host_free(h);
         for (int *h : h_replay) ctu_host_free(h);
+        for (int *h : h_cols) ctu_host_free(h);
         ctu_host_free(h_stage);
         for (hipEvent_t v : desc_free)
             if (v) (void)hipEventDestroy(v);
@@ -97,6 +105,9 @@ bool streams_vad(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STR
 bool streams_signal(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STREAMS_SIGNAL_STATE) && d.signal_out; }
 // the samples the finish of a stream with F frames delivers: the overlap-add's tail, once there is a frame
 int64_t signal_pending(const ctu::Design &d, int64_t F) { return F > 0 ? d.window - d.wshift : 0; }
+// a set with trap state on a configuration with -fea_kind trapdct: half a context is the halo (nothing else holds rows there: delta
+// chains, stacking and CMS are refused on trapdct at create)
+bool streams_trap(const ctu::Design &d, uint32_t flags) { return (flags & CTU_STREAMS_TRAP_STATE) && d.kind == ctu::FeaKind::TrapDct; }
 }  // namespace
 
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap) {
@@ -125,6 +136,7 @@ int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flag
         int H = 0, wmax = 0;
         design_halo(d, &H, &wmax);
         if (streams_vad(d, flags)) stream_vad_halo(d.o.vad_filter_order, &H, &wmax);
+        if (streams_trap(d, flags)) stream_trap_halo(d.o.fea_trapdct_traplen, &H, &wmax);
         if (halo) *halo = H;
         return CTU_OK;
     } catch (const std::exception &ex) {
@@ -141,7 +153,8 @@ int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t 
 }
 
 int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending) {
-    if (window < 1 || wshift < 1 || wshift > window || total < 0 || halo < 0 || wmax < 0 || wmax > halo || (halo > 0 && wmax < 1)) return CTU_ERR_INPUT;
+    // (a chain's largest window is at least 1; trapdct's rule is wmax = halo - 1, which is 0 for a context of three frames)
+    if (window < 1 || wshift < 1 || wshift > window || total < 0 || halo < 0 || wmax < 0 || wmax > halo || (halo > 0 && wmax < 1 && wmax != halo - 1)) return CTU_ERR_INPUT;
     const int64_t F = stream_frames(total, window, wshift), R = stream_rows_out(halo, wmax, F);
     if (pending) *pending = F - R;
     return R;
@@ -196,6 +209,11 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         stream_vad_halo(d.o.vad_filter_order, &g.H, &g.wmax);
         g.held = g.H > 0;
     }
+    st->trap = streams_trap(d, flags);
+    if (st->trap) {  // (no chain, no CMS, no detector beside trapdct: refused above) half a context holds the rows back
+        stream_trap_halo(d.o.fea_trapdct_traplen, &g.H, &g.wmax);
+        g.held = true;
+    }
     st->signal = g.signal = streams_signal(d, flags);
     if (st->signal) {  // (speech output writes no rows: whatever the command line says of a delta chain or CMS, nothing is held)
         g.held = false;
@@ -209,7 +227,8 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
     }
     g.chained = e->geom.per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
     g.max_chains = e->geom.chain_slots;  // (the plan geometry's: max_wg * NWAVE wave chains, or n_cu * 8 workgroup chains of bigfft_kernel)
-    st->C = st->vad ? g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
+    st->hw = st->trap ? d.B : d.Dbase;
+    st->C = st->vad ? g.H : st->trap ? 2 * g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
     st->consumed.assign((size_t)n_streams, 0);
     st->seen.assign((size_t)n_streams, 0);
     st->hsel.assign((size_t)n_streams, 0);
@@ -284,10 +303,18 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             }
         }
         if (g.held) {
-            st->hist.alloc(std::max<size_t>((size_t)2 * n_streams * st->C * d.Dbase, 1));
+            st->hist.alloc(std::max<size_t>((size_t)2 * n_streams * st->C * st->hw, 1));
             st->means.alloc((size_t)n_streams * STREAM_MEANS);
             HIP_TRY(hipMemset(st->hist.p, 0, st->hist.n * sizeof(float)));
             HIP_TRY(hipMemset(st->means.p, 0, st->means.n * sizeof(float)));
+        }
+        if (st->trap) {  // a column per row that goes out: no more than the frames of a push, or the half a finish delivers
+            const size_t n_cols = (size_t)std::max<int64_t>(pl->hp.total_frames, g.H);
+            for (int k = 0; k < 2; k++) {
+                st->h_cols[k] = static_cast<int *>(ctu_host_alloc(n_cols * sizeof(int)));
+                if (!st->h_cols[k]) throw std::runtime_error("page-locked descriptors of a stream set");
+                st->d_cols[k].alloc(n_cols);
+            }
         }
         for (hipEvent_t &v : st->ev) HIP_TRY(hipEventCreate(&v));
         return CTU_OK;
@@ -346,6 +373,26 @@ void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finish
         if (d.cms == 1) hipLaunchKernelGGL(stream_cms_exp_kernel, dim3((unsigned)n), dim3(64), 0, s, rp, cp);
         else hipLaunchKernelGGL(stream_cms_block_kernel, dim3(chunks, (unsigned)n), dim3(256), (size_t)(64 + cp.L - 1) * cp.ncols * sizeof(float), s, rp, cp);
     }
+    HIP_TRY(hipGetLastError());
+}
+// stream_trap_kernel over the rows that go out with a push, or with a finish, of the n streams h_rdesc[k] describes (uploaded here, with
+// the stream of every column)
+void launch_stream_trap(ctu_streams *st, int k, int n, float *d_rows, hipStream_t s) {
+    const ctu::Design &d = *st->eng->design;
+    HIP_TRY(hipMemcpyAsync(st->d_rdesc[k].p, st->h_rdesc[k], (size_t)n * sizeof(RowPush), hipMemcpyHostToDevice, s));
+    const int64_t n_cols = stream_trap_columns(st->h_rdesc[k], n, st->h_cols[k]);
+    if (n_cols == 0) return;
+    HIP_TRY(hipMemcpyAsync(st->d_cols[k].p, st->h_cols[k], (size_t)n_cols * sizeof(int), hipMemcpyHostToDevice, s));
+    StreamTrapParams tp;
+    tp.push = st->d_rdesc[k].p; tp.col = st->d_cols[k].p; tp.fresh = st->plan->logmel.p; tp.hist = st->hist.p; tp.G = st->eng->trapG.p; tp.rows = d_rows;
+    tp.n_cols = n_cols; tp.n_streams = st->n_streams; tp.C = st->C; tp.B = d.B;
+    tp.traplen = d.o.fea_trapdct_traplen; tp.ndct = d.o.fea_trapdct_ndct; tp.D = d.D;
+    const int nrb = tp.ndct <= 16 ? 1 : 2, bb = nrb == 1 ? 8 : 4;
+    const dim3 grid((unsigned)((n_cols + 15) / 16), (unsigned)((d.B + bb - 1) / bb));
+    const bool comp = (tp.traplen + 3) / 4 > TRAP_COMP_STEPS;  // (contexts of more than 104 frames: stream_trap_kernels.h)
+    lift<1, 2>(nrb, [&](auto v) {
+        lift<0, 1>(comp, [&](auto c) { hipLaunchKernelGGL((stream_trap_kernel<decltype(v)::value, decltype(c)::value != 0>), grid, dim3(64), 0, s, tp); });
+    });
     HIP_TRY(hipGetLastError());
 }
 // The detector's kernels of a push over the n streams h_rdesc[k] describes and the L.n_replay of them h_replay[k] lists (both uploaded
@@ -456,9 +503,11 @@ int ctu_streams_push_vad(ctu_streams *st, int32_t n, const int32_t *ids, const i
         HIP_TRY(hipEventRecord(st->ev[1], s));
         HIP_TRY(hipGetLastError());
         int rc = CTU_OK;
-        float *const base = st->vad ? st->vbase.p : pl->base_rows.p;  // (held) where the front end leaves the push's rows
+        // (held) where the front end leaves the push's rows - with trap state its log-mel rows, and no kernel of the run writes rows
+        float *const base = st->trap ? pl->logmel.p : st->vad ? st->vbase.p : pl->base_rows.p;
         if (L.tiles) rc = run_chain(e, pl, x, st->arena.p, held ? base : d_rows, nullptr, s, !held, !st->vad);
         if (st->vad && L.tiles && rc == CTU_OK) launch_stream_vad(st, k, n, L, d_rows, d_vad, s);
+        else if (st->trap && L.tiles && rc == CTU_OK) launch_stream_trap(st, k, n, d_rows, s);
         else if (held && L.tiles && rc == CTU_OK) launch_stream_rows(st, k, n, L.most, false, d_rows, s);
         HIP_TRY(hipEventRecord(st->ev[2], s));
         hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
@@ -466,8 +515,8 @@ int ctu_streams_push_vad(ctu_streams *st, int32_t n, const int32_t *ids, const i
             RowParams rp;
             std::memset(&rp, 0, sizeof rp);
             rp.push = st->d_rdesc[k].p; rp.fresh = base; rp.hist = st->hist.p;
-            rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase;
-            hipLaunchKernelGGL(stream_rows_carry_kernel, dim3((unsigned)n, (unsigned)((st->C * d.Dbase + 255) / 256)), dim3(256), 0, s, rp);
+            rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = st->hw;
+            hipLaunchKernelGGL(stream_rows_carry_kernel, dim3((unsigned)n, (unsigned)((st->C * st->hw + 255) / 256)), dim3(256), 0, s, rp);
         }
         HIP_TRY(hipEventRecord(st->ev[3], s));
         HIP_TRY(hipEventRecord(st->desc_free[k], s));
@@ -587,11 +636,15 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
                 rp.n_streams = st->n_streams; rp.C = st->C; rp.Dbase = d.Dbase; rp.finishing = 1;
                 hipLaunchKernelGGL(stream_vad_finish_kernel, dim3(1), dim3(256), 0, s, rp, d.D, st->vstate.p, d_vad, d.o.vad_filter_order);
                 HIP_TRY(hipGetLastError());
-            } else launch_stream_rows(st, k, 1, pending, true, d_rows, s);
+            } else if (st->trap) launch_stream_trap(st, k, 1, d_rows, s);  // (Tn = 0: the newest frame is the file's last)
+            else launch_stream_rows(st, k, 1, pending, true, d_rows, s);
             HIP_TRY(hipEventRecord(st->desc_free[k], s));
         }
         HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
         if (st->g.held && !st->vad) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
+        if (st->trap)  // both histories of the stream (a new file reads neither ahead of its own rows: the left clamp is frame 0)
+            for (int h = 0; h < 2; h++)
+                HIP_TRY(hipMemsetAsync(st->hist.p + ((size_t)h * st->n_streams + id) * st->C * st->hw, 0, (size_t)st->C * st->hw * sizeof(float), s));
         return CTU_OK;
     });
     if (rc != CTU_OK) return rc;
@@ -599,7 +652,11 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
         set_error(e, "IO: Signal shorter than one frame!");  // src/io/in.cc:277; the stream is reset all the same
         return CTU_ERR_INPUT;
     }
-    if (too_short) {  // the words of an offline plan's refusal (plan.cc); the stream is reset all the same
+    if (too_short && st->trap) {  // the words of an offline plan's refusal (plan.cc); the stream is reset all the same
+        set_error(e, "ENGINE: trapdct on fewer than (traplen+1)/2 frames is undefined in the reference (src/fea/fea_trap.cc:64-70)");
+        return CTU_ERR_INPUT;
+    }
+    if (too_short) {  // the same for a delta chain or a stacking
         set_error(e, "ENGINE: delta / stacking on fewer than window+2 frames is ill-defined in the reference (src/fea/fea_delta.cc:74-130,178-206)");
         return CTU_ERR_INPUT;
     }

@@ -175,8 +175,8 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  *
  * Streamed are the chains whose frames share nothing but samples: every feature kind, filter bank, FFT size and energy
  * column ctu_engine_create accepts, without -nr_mode, -remove_dc1, the VAD module, -fea_delta / -fea_trap / trapdct, CMS,
- * CMVN, speech output or HTK feature input (the flags of ctu_streams_create_ex below add the delta chains, stacking, CMS and
- * -nr_mode exten).  ctu_streams_create refuses those with CTU_ERR_UNSUPPORTED and the option's name in
+ * CMVN, speech output or HTK feature input (the flags of ctu_streams_create_ex below add the delta chains, stacking, CMS,
+ * -nr_mode exten, the VAD module, speech output and trapdct).  ctu_streams_create refuses those with CTU_ERR_UNSUPPORTED and the option's name in
  * ctu_last_error; ctu_streams_config_check says the same from the command line alone (no device; `reason` receives the text).
  *
  * A push names n different streams (a repeat, an id outside the set, more than max_push_samples for one stream or more rows
@@ -204,7 +204,7 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * kinds, and with row state the delta chains, stacking and CMS behind them.  Exten is causal - frame t reads frames 0 .. t - so a row
  * still goes out with the push that completes its frame, R(F) is unchanged and ctu_streams_finish has nothing to add; a stream's next
  * file starts from the reference's initial estimate.  Still refused, by name, whatever the flags: -nr_when afterFB, exten on 1024 ..
- * 4096 points (without CTU_STREAMS_LARGE_STATE, below), hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct, CMVN, speech output (without its
+ * 4096 points (without CTU_STREAMS_LARGE_STATE, below), hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct (without CTU_STREAMS_TRAP_STATE, below), CMVN, speech output (without its
  * flag, below), HTK feature input.  On a chain without -nr_mode exten the flag changes nothing.
  *
  * Detector state (CTU_STREAMS_VAD_STATE; combines with the other two): the set also keeps, per stream, the state of the VAD module's
@@ -252,9 +252,30 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * and with the noise state as well behind exten; windows of odd length are fine here, as offline.  Rows and samples relate to the
  * offline run as above (bit-equal when every push ends a multiple of eight frames into the file).  Still
  * refused by name, whatever the flags: -nr_when afterFB, hwss / fwss / 2fwss, -remove_dc1, the VAD module on 1024-point and larger
- * frames, trapdct, CMVN, HTK feature input.  On a configuration of 512 points or fewer the flag changes nothing, and without it
- * every answer - exten and speech output on 1024 .. 4096-point frames refused by name - is the one it was. */
-enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64 };   /* (2 and 16 are no flags: sets refuse them as unknown, and callers may rely on that) */
+ * frames, trapdct (without CTU_STREAMS_TRAP_STATE, below), CMVN, HTK feature input.  On a configuration of 512 points or fewer the flag changes nothing, and without it
+ * every answer - exten and speech output on 1024 .. 4096-point frames refused by name - is the one it was.
+ *
+ * Trap state (CTU_STREAMS_TRAP_STATE = 256; 128 is no flag; combines with the noise and large-transform flags): the set also keeps, per
+ * stream, the last traplen - 1 log-mel rows of the file ([bands] floats each), and so takes -fea_kind trapdct,<traplen>,<ndct>: C5.
+ * TRAP-DCT is a pure function of a window of log-mel rows - out[t][b * ndct + k] = sum_j G[k][j] logmel[clamp(t - half + j, 0, T - 1)][b],
+ * half = (traplen - 1) / 2 - so row t is final once frame t + half exists: with H = half and wmax = half - 1 in the arithmetic of the
+ * row state, after F frames a stream has delivered R(F) = F - half rows once F >= half + 1, none before (a push delivers at most as
+ * many rows as it completes frames), and ctu_streams_finish delivers the last half with the file's length known.  A file that ends with
+ * 1 .. half frames is the offline plan's "trapdct on fewer than (traplen+1)/2 frames": CTU_ERR_INPUT and no rows at finish, and the stream
+ * starts over clean; a file without a frame finishes with nothing.  ctu_streams_config_check_ex reports halo = half, and the counting
+ * function is ctu_streams_rows_step(window, wshift, half, half - 1, total, &pending): no entry point is new.  The contraction is the
+ * offline fp32 one (v_mfma_f32_16x16x4_f32 over the operand minus the column's own centre value), so a row depends on nothing but its
+ * own traplen log-mel rows - not on the cut into pushes, not on the other streams - and is the row of ctu_engine_run bit for bit
+ * wherever the log-mel rows are (every push a multiple of eight frames into the file) and the offline run launches its fp32 kernel
+ * (more than 24 bands or more than 16 coefficients; elsewhere offline splits into fp16 terms and the two agree to rounding) on a context
+ * of at most 104 frames.  Longer contexts (traplen 105 .. 255) are summed in compensated runs of 16 taps: a single fp32 chain over them
+ * leaves the engine's parity bound (1.9e-4 of the reference at 255 taps, against 1e-4), so there a stream's rows are closer to the
+ * reference than ctu_engine_run's and agree with them to that rounding; the independence of pushes and streams holds at every size.  Taken: the plain chain at every FFT size ctu_engine_create takes trapdct at, 1024 .. 4096 points included; with
+ * CTU_STREAMS_NR_STATE as well -nr_mode exten on the spectrum, and with CTU_STREAMS_LARGE_STATE beside that on 1024 .. 4096-point
+ * frames.  Still refused by name with the flag: the VAD module beside trapdct (whatever the detector flag), -remove_dc1,
+ * -nr_when afterFB behind exten, -s above -w; hwss / fwss / 2fwss and CMVN on trapdct are outside ctu_engine_create.  Without the flag
+ * every answer is the one it was, and on a configuration of another feature kind the flag changes no answer and no row. */
+enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64, CTU_STREAMS_TRAP_STATE = 256 };   /* (2, 16 and 128 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
@@ -272,7 +293,7 @@ int ctu_streams_push_host(ctu_streams *, int32_t n, const int32_t *stream_ids, c
  * writes the rows it held back (ctu_streams_pending of them) to d_rows, asynchronously on `stream`; room for fewer is CTU_ERR_INPUT
  * ahead of any launch, and the stream stays as it was.  A file of 1 .. window - wshift - 1 samples is the reference's "IO: Signal
  * shorter than one frame!", and a delta chain or stacking on a file of 1 .. wmax + 1 frames the offline plan's "fewer than window+2
- * frames": CTU_ERR_INPUT and no rows.  In every case but the lack of room the stream starts a new file with its next push. */
+ * frames", and trapdct (trap state) on a file of 1 .. (traplen - 1) / 2 frames its "fewer than (traplen+1)/2 frames": CTU_ERR_INPUT and no rows.  In every case but the lack of room the stream starts a new file with its next push. */
 int ctu_streams_finish(ctu_streams *, int32_t stream_id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream);
 /* Host-buffer form of the above.  Synchronised on return. */
 int ctu_streams_finish_host(ctu_streams *, int32_t stream_id, float *h_rows, int64_t rows_capacity, int64_t *row_count);
@@ -309,12 +330,12 @@ int64_t ctu_streams_pending(const ctu_streams *, int32_t stream_id);
  * ctu_num_frames, 0 while it has none - and in *carry (may be NULL) the samples the next frame already has. */
 int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry);
 /* The same for the rows (pure): R(F) of a file after `total` samples for a chain of halo H >= wmax >= 0 (0, 0: no chain), and in
- * *pending (may be NULL) F - R(F). */
+ * *pending (may be NULL) F - R(F).  Trap state: halo = (traplen - 1) / 2, wmax = halo - 1 (0 for a context of three frames). */
 int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending);
 /* The same for a set with detector state (pure): R(F) for the majority filter of order filter_order (1 .. 31), F - R(F) in *pending. */
 int64_t ctu_streams_vad_step(int32_t window, int32_t wshift, int32_t filter_order, int64_t total, int64_t *pending);
 /* Times of the last push on the set, measured with HIP events on its stream: ms3[0] stream_stitch_kernel, ms3[1] the front end
- * and its tails (with row state: and the row kernels behind them; with detector state: and the replay), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel).  Blocks until that push has finished. */
+ * and its tails (with row state: and the row kernels behind them; with detector state: and the replay), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel; trap state: stream_trap_kernel is in ms3[1]).  Blocks until that push has finished. */
 int ctu_streams_last_push_ms(ctu_streams *, float *ms3);
 
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53
