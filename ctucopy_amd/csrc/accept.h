@@ -18,7 +18,7 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags = 0);
 int create_check(const Design &d, std::string &err);
 // ... and ctu_streams_config_check_ex, for a design after spread_small_fft
 constexpr uint32_t STREAMS_FLAGS = CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE | CTU_STREAMS_VAD_STATE | CTU_STREAMS_SIGNAL_STATE | CTU_STREAMS_LARGE_STATE |
-                                   CTU_STREAMS_TRAP_STATE;
+                                   CTU_STREAMS_TRAP_STATE | CTU_STREAMS_SS_STATE;
 // CTU_STREAMS_LARGE_STATE keeps nothing of its own: it says how far the noise state and the signal state reach.  Without either it names
 // no state, and a set answers what it always answered to 64: unknown flags.
 inline bool streams_flags_unknown(uint32_t flags) {

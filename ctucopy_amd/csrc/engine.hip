@@ -274,13 +274,15 @@ void lift(int v, F &&f) {
     (void)((v == C && (f(std::integral_constant<int, C>{}), true)) || ...);
 }
 // The front-end launch of an engine: its FeSel lifted to template arguments, one at a time; fe_compiled decides which leaves exist.
-// `xs`: the launch of a stream set with noise state (frontend_kernel<..., XS>; the generic walk: the same rows bit for bit).
+// `xs`: the launch of a stream set with noise or subtraction state (frontend_kernel<..., XS>; the generic walk: the same rows bit for bit).
 // (with detector state as well: the fused Burg-cepstral criterion behind exten, C4's front end - its cepstra go to the scratch by frame, nothing of it runs along a file)
 // (with signal state: the one instantiation per (NZ, MODE) a speech-output design runs on - FEAT_BANDS, 16 coefficient rows, GEN_FULL,
 // with SY, or in a build without it (CTU_SY=0) with VX ahead of synth_kernel.  VX stays out otherwise: the VAD's export is not carried
 // behind exten's state, and streams_unsupported_reason refuses those configurations)
 constexpr bool fe_streamed_signal(const FeSel &k) { return k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL && !k.vf && !k.ss && (CTU_SY ? k.sy && !k.vx : k.vx && !k.sy); }
-constexpr bool fe_streamed(const FeSel &k) { return fe_streamed_signal(k) || (!k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf))); }
+// (with subtraction state: the twin of every feature-path *ss instantiation - a set runs the engine's own instantiation plus the state traffic)
+constexpr bool fe_streamed_ss(const FeSel &k) { return k.ss && !k.sy && !k.vx && !k.vf; }
+constexpr bool fe_streamed(const FeSel &k) { return fe_streamed_signal(k) || fe_streamed_ss(k) || (!k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf))); }
 void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp, bool xs = false) {
     const FeSel &k = e->tab.sel;
 #define V(x) decltype(x)::value
@@ -1061,13 +1063,23 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
         HIP_TRY(hipEventRecord(e->ev0, s));
         // the front end; with hwss / fwss / 2fwss `pass` is one pass of the seed iteration, which launches it
         std::function<void()> pass = [&] { launch_frontend(e, dim3(grid), s, kp, x.xstate != nullptr); };
+        // a stream set with subtraction state: every file of a stream is a first file, so the seed is zero and there is nothing to iterate -
+        // one pass from the streams' own state, no read-back, and the engine's offline chain (ss_stale, vad_pos) is neither read nor written
+        const bool ss_streamed = e->tab.ss && x.xstate != nullptr;
+        if (ss_streamed) {
+            if (e->tab.path != BIG_NONE || e->tab.ss_file) throw std::runtime_error("internal: a streamed *ss configuration outside the 256- / 512-point detector path");
+            kp.ss_cached = 0;
+            kp.ss_dirty = nullptr;
+            kp.ss_seed = nullptr;
+            kp.ss_last = nullptr;
+        }
         switch (e->tab.path) {
-            case BIG_NONE: if (!e->tab.ss) pass(); break;
+            case BIG_NONE: if (!e->tab.ss || ss_streamed) pass(); break;
             case BIG_WAVE1K: stage_wave1k(e, pl, x, s, bp); break;
             case BIG_SS: pass = stage_bigss_front(e, pl, x, s, bp); break;
             case BIG_FFT: launch_bigfft(e, x, s, bp); break;
         }
-        if (e->tab.ss) {
+        if (e->tab.ss && !ss_streamed) {
             const int rc = run_ss_chain(e, pl, x, s, kp, pass);
             if (rc != CTU_OK) return rc;
         }

@@ -86,6 +86,11 @@ namespace {
 //         state alone.  gfx950, hipcc -O3, from the code object's metadata: MODE 1 (NZ 13 and 16) 137 VGPRs, 106 SGPRs, MODE 0 (NZ 13
 //         and 16) 177 VGPRs, 106 SGPRs - the VGPRs of the offline SY instantiations; 48 / 60 SGPRs are kept in VGPR lanes (offline:
 //         36 / 52); no VGPR spills, no scratch.  (A build with CTU_SY=0 takes the VX form of the same instantiation ahead of synth_kernel.)
+//         With SS (a set with subtraction state, CTU_STREAMS_SS_STATE): the twin of every feature-path SS instantiation (no SY) - the noise
+//         estimate(s) and the detector's record of hwss / fwss / 2fwss travel as exten's state does (xss_slot below; the slot's layout:
+//         xs_ss_floats, layout_constants.h), every file starts from the zero seed, and neither ss_seed, ss_last nor ss_dirty is touched.
+//         gfx950, hipcc -O3, from the code object's metadata: each twin sits at its parent's cap (128 VGPRs in MODE 1, 256 in MODE 0; 104 / 106
+//         SGPRs) and has no more scratch than the parent (20 .. 528 B per lane against 28 .. 544); the table is in DESIGN.md section 4.10.
 // (fe_waves_per_simd, the waves per SIMD an instantiation is compiled for, and its switches CTU_LB / CTU_SY_LB / CTU_VF1_LB: layout_constants.h)
 // (fe_dual, the DUAL instantiations of phase 1 below, and its switch CTU_DUAL: layout_constants.h - tables.cc halves their window table)
 
@@ -114,7 +119,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
     static_assert(!SS || (!VX && !VF && (GEN == GEN_PLAIN || GEN == GEN_FULL)), "SS: the plain chain, or run-time flags (signal output, energy columns, -fb_inld, LP kinds, magnitude spectra)");
     static_assert(!((VF || SS) && MODE == 0) || NZ == 13, "VF / SS in the 512-point mode: 400-sample windows (16 lanes x 25 samples)");
     static_assert(!SY || (!VX && !VF && (GEN == GEN_FULL || GEN == GEN_DC1)), "SY: run-time flags, no export");
-    static_assert(!XS || (!SS && (GEN == GEN_EXTEN || (GEN == GEN_FULL && !VF))), "XS: exten on the spectrum, nothing else that runs along a file (VF stores a frame's cepstra and keeps nothing)");
+    static_assert(!XS || (SS ? !SY : (GEN == GEN_EXTEN || (GEN == GEN_FULL && !VF))), "XS: exten on the spectrum, or the *ss modes on the feature path; nothing else that runs along a file (VF stores a frame's cepstra and keeps nothing)");
     static_assert(!XS || !(VX || SY) || (FEAT == FEAT_BANDS && NC == 16 && GEN == GEN_FULL), "XS with SY (or VX): speech output on a stream set with signal state, the one instantiation per (NZ, MODE) - frames and spectra leave by frame, the overlap-add's state is the set's");
     const int o_e_mode = FULL ? p.e_mode : 0, o_dbg = FULL ? p.dbg : 0;
     const bool o_fb_inld = FULL ? p.fb_inld != 0 : GEN == GEN_INLD, o_nr_exten = FULL ? p.nr_exten != 0 : GEN == GEN_EXTEN;
@@ -201,6 +206,13 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
 #pragma unroll
     for (int j = 0; j < NJ; j++) snavg[j] = snrav[j] = 0.f;
     if constexpr (SS) cepdet_reset(sdet);
+    // XS with SS (a set with subtraction state, CTU_STREAMS_SS_STATE): what hwss / fwss / 2fwss keep along a file travels as exten's state
+    // does - in from the stream's slot at the first tile the stream has in this launch unless that tile starts a file, out behind its last
+    // one, registers in between.  A slot is xs_ss_floats(NJ) floats (layout_constants.h): Navg[64 NJ] | Nravg[64 NJ], element 64 j + lane, then
+    // the detector's record as doubles - c0 of every lane [64], dMean, dMean2, threshold - and nseg in the first word of an eighth float
+    // pair.  Floats and doubles as they stand; the wave-uniform values are read by every lane from one address and written by lane 0.
+    auto xss_slot = [&](int t) { return uniform_ptr(reinterpret_cast<float *>(p.xstate) + (size_t)as_const(p.tile_utt)[t] * xs_ss_floats(NJ)); };
+    auto xss_det = [&](int t) { return uniform_ptr(reinterpret_cast<double *>(reinterpret_cast<float *>(p.xstate) + (size_t)as_const(p.tile_utt)[t] * xs_ss_floats(NJ) + 2 * 64 * NJ)); };
 
     while (true) {
         const int nvalid = rec.nvalid;
@@ -209,7 +221,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         TileRec nrec = rec;
         if (next >= 0) nrec = load_rec(p.tiles, next);
         // SS, second and later passes of the seed iteration (engine.hip): an utterance whose seed did not change keeps its rows
-        const bool skip_tile = SS && p.ss_dirty && !reinterpret_cast<const unsigned char *>(p.ss_dirty)[as_const(p.tile_utt)[tile]];
+        const bool skip_tile = SS && !XS && p.ss_dirty &&!reinterpret_cast<const unsigned char *>(p.ss_dirty)[as_const(p.tile_utt)[tile]];
         const int nsub = skip_tile ? 0 : (per_wave ? (nvalid + 7) >> 3 : 1);
         for (int sub = 0; sub < nsub; sub++) {
         // this step's frame slots are [slot0, slot0 + 8) of the tile; their spectra live in the wave's P rows 0..7
@@ -856,9 +868,27 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     cepdet_reset(sdet);
 #pragma unroll
                     for (int j = 0; j < NJ; j++) {
-                        const float sd = (lane + 64 * j < p.K) ? p.ss_seed[(int64_t)utt * p.K + lane + 64 * j] : 0.f;
+                        // (XS: every file of a stream is the first file of a process, whose seed is the zero vector)
+                        const float sd = (!XS && lane + 64 * j < p.K) ? p.ss_seed[(int64_t)utt * p.K + lane + 64 * j] : 0.f;
                         snavg[j] = two ? sd : ss_pow(sd, p.nr_a);
                         snrav[j] = 0.f;
+                    }
+                } else {
+                    if constexpr (XS) {
+                        if (xs_first && slot0 == 0) {  // the file goes on: where the stream's last push left off
+                            const auto xs = xss_slot(tile);  // (a wave-uniform base and a 32-bit lane offset: no 64-bit address per lane)
+                            const auto xd = xss_det(tile);
+#pragma unroll
+                            for (int j = 0; j < NJ; j++) {
+                                snavg[j] = xs[(unsigned)(lane + 64 * j)];
+                                snrav[j] = xs[(unsigned)(lane + 64 * (NJ + j))];
+                            }
+                            sdet.c0 = xd[(unsigned)lane];
+                            sdet.dMean = xd[64];
+                            sdet.dMean2 = xd[65];
+                            sdet.threshold = xd[66];
+                            sdet.nseg = __builtin_amdgcn_readfirstlane(reinterpret_cast<const __attribute__((address_space(1))) int *>(xd + 67)[0]);
+                        }
                     }
                 }
                 unsigned vbits = 0;
@@ -923,7 +953,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                                 X = ss_root(X, p.nr_a);
                             }
                             row[64 * j] = X;
-                            if (t == rec.T - 1) {
+                            if (!XS && t == rec.T - 1) {  // (XS: T is the frames so far - and no file of a stream is seeded from another)
                                 // what the next file's noise estimate starts from (nr.cc:212-221).  With signal output sigOUT has flipped the
                                 // Nyquist entry's sign by then if that bin's phase was pi (src/io/out.cc:419): phase 1 left the bin's signed
                                 // real part behind the row's last bin
@@ -1447,11 +1477,28 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         if constexpr (XS) {
             xs_first = rec.t0 + nvalid == rec.T;  // (stream_stitch_kernel: T = the frames of the file once this push is through)
             if (xs_first) {  // the stream's last tile of this push: the next tile, if any, is another stream's first
-                const auto xs = xs_slot(tile);
+                if constexpr (SS) {
+                    const auto xs = xss_slot(tile);
+                    const auto xd = xss_det(tile);
 #pragma unroll
-                for (int j = 0; j < NJ; j++) {
-                    xs[(unsigned)(lane + 64 * j)] = navg[j];
-                    xs[(unsigned)(lane + 64 * (NJ + j))] = yavg[j];
+                    for (int j = 0; j < NJ; j++) {
+                        xs[(unsigned)(lane + 64 * j)] = snavg[j];
+                        xs[(unsigned)(lane + 64 * (NJ + j))] = snrav[j];
+                    }
+                    xd[(unsigned)lane] = sdet.c0;
+                    if (lane == 0) {  // the wave-uniform part of the record: one lane, ordinary stores
+                        xd[64] = sdet.dMean;
+                        xd[65] = sdet.dMean2;
+                        xd[66] = sdet.threshold;
+                        reinterpret_cast<__attribute__((address_space(1))) int *>(xd + 67)[0] = sdet.nseg;
+                    }
+                } else {
+                    const auto xs = xs_slot(tile);
+#pragma unroll
+                    for (int j = 0; j < NJ; j++) {
+                        xs[(unsigned)(lane + 64 * j)] = navg[j];
+                        xs[(unsigned)(lane + 64 * (NJ + j))] = yavg[j];
+                    }
                 }
             }
         }

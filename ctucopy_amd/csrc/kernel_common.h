@@ -70,7 +70,7 @@ struct KParams {
     void *lp_r;       // LP kinds: autocorrelation lags of every frame [total_frames][lp_stride] (float; double for FEAT_LPD), finished by lp_tail_kernel
     int lp_stride;
     int dbg;  // diagnostic ablation (CTU_DEBUG_MODE): 1 = phase 1 only, 2 = phase 2 only; 0 in production
-    void *xstate;  // XS instantiations (a stream set with noise state): exten's Navg | Yavg of every stream, [n_streams][2][64 NJ]; tile_utt is then the stream of every tile
+    void *xstate;  // XS instantiations (a stream set with noise state): exten's Navg | Yavg of every stream, [n_streams][2][64 NJ]; tile_utt is then the stream of every tile.  With SS (a set with subtraction state): [n_streams][xs_ss_floats(NJ)], Navg | Nravg | the detector's record
 };
 
 #ifndef CTU_VF_A2C

@@ -98,6 +98,10 @@ enum FeatMode { FEAT_BANDS = 0, FEAT_DCTC = 2, FEAT_LP = 3, FEAT_LPD = 4 };  // 
 constexpr int VF_NC = 14;         // cepstral coefficients of the fused path (-vad_lpc_coefs default: Burg order 13)
 constexpr int SS_NC = 16;         // the *ss modes' detector uses -fea_ncepcoefs coefficients (src/nr/nr.cc:266-268: 12 in the presets): the lattice is
                                   // unrolled for up to 16 (one coefficient per lane of a frame's 16) and stops at the run-time count (KParams::ss_nc)
+// A stream's slot of subtraction state (a set with CTU_STREAMS_SS_STATE; frontend_kernel<..., SS, ..., XS>), in floats, nj = ceil(K / 64):
+// Navg[64 nj] | Nravg[64 nj] (element 64 j + lane), then on an 8-byte boundary the detector's record as doubles - c0[64] (one per lane),
+// dMean, dMean2, threshold - and nseg as the int in the first word of the last pair
+constexpr int xs_ss_floats(int nj) { return 2 * 64 * nj + 2 * 64 + 2 * 3 + 2; }
 constexpr int VF_WINDOW = 200;    // the window the fused path is built for (8 kHz, 25 ms); other windows take the separate kernels
 constexpr int VF_SPL = 13;        // samples per lane of a frame: 16 lanes x 13 = 208 >= window
 // The 512-point mode (16 kHz, 25 ms): one frame per 16-lane group, four frames per half step

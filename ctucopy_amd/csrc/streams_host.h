@@ -46,7 +46,9 @@ struct ctu_streams {
     DevBuf<RowPush> d_rdesc[2];
     // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten (g.chained, g.max_chains): Navg | Yavg of every stream (frontend_kernel<..., XS>;
     // with CTU_STREAMS_LARGE_STATE on 1024 .. 4096 points wave1k_kernel<true, XS> / bigfft_kernel<NIT, true, XS>: sized by the kernel that runs),
-    // the heads of the chains a push is dealt onto, which travel as the descriptors do, and the stream of every tile
+    // the heads of the chains a push is dealt onto, which travel as the descriptors do, and the stream of every tile.
+    // CTU_STREAMS_SS_STATE on a chain with -nr_mode hwss | fwss | 2fwss: the same buffer and the same chains, a slot of xs_ss_floats
+    // (layout_constants.h) per stream - Navg | Nravg and the detector's record (frontend_kernel<..., SS, ..., XS>)
     DevBuf<float> xstate;
     int *h_heads[2] = {nullptr, nullptr};
     DevBuf<int> d_heads[2];
@@ -189,7 +191,9 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         set_error(e, "ENGINE: configuration cannot be streamed: " + why);
         return CTU_ERR_UNSUPPORTED;
     }
-    if ((e->geom.per_wave && !(flags & CTU_STREAMS_NR_STATE)) || (e->geom.do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || e->tab.ss || (e->geom.per_wave && e->tab.big && !(flags & CTU_STREAMS_LARGE_STATE)) || (e->geom.do_vad && e->tab.big)) {
+    // (per-wave chains are exten's with the noise state, or those of hwss / fwss / 2fwss with the subtraction state, on the 256- / 512-point front end)
+    const bool ss_set = e->tab.ss && (flags & CTU_STREAMS_SS_STATE) && !e->tab.big && !e->tab.ss_file && !d.signal_out;
+    if ((e->geom.per_wave && !e->tab.ss && !(flags & CTU_STREAMS_NR_STATE)) || (e->geom.do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || (e->tab.ss && !ss_set) || (e->geom.per_wave && e->tab.big && !(flags & CTU_STREAMS_LARGE_STATE)) || (e->geom.do_vad && e->tab.big)) {
         set_error(e, "ENGINE: internal: a streamed configuration with chains of whole utterances");
         return CTU_ERR_UNSUPPORTED;
     }
@@ -225,7 +229,7 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             return CTU_ERR_UNSUPPORTED;
         }
     }
-    g.chained = e->geom.per_wave;  // (exten with CTU_STREAMS_NR_STATE: everything else with chains of whole files is refused above)
+    g.chained = e->geom.per_wave;  // (exten with CTU_STREAMS_NR_STATE, hwss / fwss / 2fwss with CTU_STREAMS_SS_STATE: everything else with chains of whole files is refused above)
     g.max_chains = e->geom.chain_slots;  // (the plan geometry's: max_wg * NWAVE wave chains, or n_cu * 8 workgroup chains of bigfft_kernel)
     st->hw = st->trap ? d.B : d.Dbase;
     st->C = st->vad ? g.H : st->trap ? 2 * g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;  // (detector state: a row is copied h frames late, nothing more)
@@ -269,7 +273,9 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
         }
         if (g.chained) {
             // by the kernel that runs: [2][64 NJ] of xstate_t (frontend_kernel.h), [2][64 * 9] floats (wave1k_kernel.h), [2][256 NB] floats (bigfft_kernel.h)
-            const size_t per_stream = !e->tab.big ? (size_t)2 * 64 * (e->tab.sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1)
+            // (subtraction state: the slot of layout_constants.h - both noise estimates and the detector's record)
+            const size_t per_stream = ss_set ? (size_t)xs_ss_floats(e->tab.sel.mode == 1 ? 3 : 5)
+                                      : !e->tab.big ? (size_t)2 * 64 * (e->tab.sel.mode == 1 ? 3 : 5) * (CTU_EXTEN_F64 ? 2 : 1)
                                       : e->tab.path == BIG_WAVE1K ? (size_t)2 * 64 * 9 : (size_t)2 * 256 * (big_nit(e) / 2 + 1);
             st->xstate.alloc((size_t)n_streams * per_stream);
             HIP_TRY(hipMemset(st->xstate.p, 0, st->xstate.n * sizeof(float)));  // (never read ahead of a store: a file's first tile resets)

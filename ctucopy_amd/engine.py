@@ -18,6 +18,7 @@ STREAMS_VAD_STATE = 8  # CTU_STREAMS_VAD_STATE
 STREAMS_SIGNAL_STATE = 32  # CTU_STREAMS_SIGNAL_STATE (2 and 16 are no flags)
 STREAMS_LARGE_STATE = 64   # CTU_STREAMS_LARGE_STATE
 STREAMS_TRAP_STATE = 256   # CTU_STREAMS_TRAP_STATE (128 is no flag either)
+STREAMS_SS_STATE = 1024    # CTU_STREAMS_SS_STATE (nor is 512)
 
 
 class CtuError(RuntimeError):
@@ -201,28 +202,30 @@ def config_table(args, name):
     return out
 
 
-def _stream_flags(row_state, nr_state, vad_state, signal_state=False, large_state=False, trap_state=False):
+def _stream_flags(row_state, nr_state, vad_state, signal_state=False, large_state=False, trap_state=False, ss_state=False):
     return ((STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0) | (STREAMS_VAD_STATE if vad_state else 0) |
             (STREAMS_SIGNAL_STATE if signal_state else 0) | (STREAMS_LARGE_STATE if large_state else 0) |
-            (STREAMS_TRAP_STATE if trap_state else 0))
+            (STREAMS_TRAP_STATE if trap_state else 0) | (STREAMS_SS_STATE if ss_state else 0))
 
 
-def streams_config_check(args, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False):
+def streams_config_check(args, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False,
+                         ss_state=False):
     """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
     CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give.  With row_state (a set that
     may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo).  With nr_state the set keeps the noise
     estimate of -nr_mode exten too, with vad_state the VAD module's detector state, with signal_state the overlap-add's tail of
     speech output (-format_out raw | wave), with large_state exten's estimate and the overlap-add's tail on 1024 .. 4096-point frames.
     With trap_state (a set that keeps the log-mel context of -fea_kind trapdct) the answer is (code, reason, halo) as with row_state:
-    the halo is (traplen - 1) / 2."""
+    the halo is (traplen - 1) / 2.  With ss_state the set keeps what -nr_mode hwss | fwss | 2fwss carry along a file (noise estimates and
+    the Burg-cepstral detector's record)."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
-    if not row_state and not nr_state and not vad_state and not signal_state and not large_state and not trap_state:
+    if not row_state and not nr_state and not vad_state and not signal_state and not large_state and not trap_state and not ss_state:
         rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
         return int(rc), buf.value.decode()
     halo = ctypes.c_int32(0)
-    flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state)
+    flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state)
     rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
     return (int(rc), buf.value.decode(), int(halo.value)) if row_state or trap_state else (int(rc), buf.value.decode())
 
@@ -276,15 +279,17 @@ class Streams:
     With large_state, nr_state and signal_state reach 1024 .. 4096-point frames too (exten on the spectrum, speech output); it is a
     flag beside one of the two only.
     With trap_state it takes -fea_kind trapdct (the plain chain, and with nr_state behind -nr_mode exten): the last traplen - 1 log-mel
-    rows are kept per stream, a frame's row leaves (traplen - 1) / 2 frames late and finish delivers the last (traplen - 1) / 2."""
+    rows are kept per stream, a frame's row leaves (traplen - 1) / 2 frames late and finish delivers the last (traplen - 1) / 2.
+    With ss_state it takes -nr_mode hwss | fwss | 2fwss with -vad burg on the feature path of the 256- and 512-point front end: the noise
+    estimates and the detector's record are kept per stream, and every file of a stream gives the rows of a fresh engine's extract of it."""
 
     def __init__(self, engine, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False,
-                 trap_state=False):
+                 trap_state=False, ss_state=False):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        if row_state or nr_state or vad_state or signal_state or large_state or trap_state:
-            flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state)
+        if row_state or nr_state or vad_state or signal_state or large_state or trap_state or ss_state:
+            flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state)
             rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))
         else:
             rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
@@ -503,9 +508,10 @@ class Engine:
     def plan(self, nsamples):
         return Plan(self, nsamples)
 
-    def streams(self, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False):
+    def streams(self, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False,
+                ss_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
-        return Streams(self, n, max_push, row_state, nr_state, vad_state, signal_state, large_state, trap_state)
+        return Streams(self, n, max_push, row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state)
 
     def _check(self, rc):
         if rc != CTU_OK:

@@ -204,7 +204,7 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * kinds, and with row state the delta chains, stacking and CMS behind them.  Exten is causal - frame t reads frames 0 .. t - so a row
  * still goes out with the push that completes its frame, R(F) is unchanged and ctu_streams_finish has nothing to add; a stream's next
  * file starts from the reference's initial estimate.  Still refused, by name, whatever the flags: -nr_when afterFB, exten on 1024 ..
- * 4096 points (without CTU_STREAMS_LARGE_STATE, below), hwss / fwss / 2fwss, the VAD module (without the flag below), -remove_dc1, trapdct (without CTU_STREAMS_TRAP_STATE, below), CMVN, speech output (without its
+ * 4096 points (without CTU_STREAMS_LARGE_STATE, below), hwss / fwss / 2fwss (without CTU_STREAMS_SS_STATE, below), the VAD module (without the flag below), -remove_dc1, trapdct (without CTU_STREAMS_TRAP_STATE, below), CMVN, speech output (without its
  * flag, below), HTK feature input.  On a chain without -nr_mode exten the flag changes nothing.
  *
  * Detector state (CTU_STREAMS_VAD_STATE; combines with the other two): the set also keeps, per stream, the state of the VAD module's
@@ -251,7 +251,7 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * and with row state the delta chains, stacking and CMS behind it.  Taken with the signal state: speech output of the plain chain,
  * and with the noise state as well behind exten; windows of odd length are fine here, as offline.  Rows and samples relate to the
  * offline run as above (bit-equal when every push ends a multiple of eight frames into the file).  Still
- * refused by name, whatever the flags: -nr_when afterFB, hwss / fwss / 2fwss, -remove_dc1, the VAD module on 1024-point and larger
+ * refused by name, whatever the flags: -nr_when afterFB, hwss / fwss / 2fwss on 2048- / 4096-point frames, -remove_dc1, the VAD module on 1024-point and larger
  * frames, trapdct (without CTU_STREAMS_TRAP_STATE, below), CMVN, HTK feature input.  On a configuration of 512 points or fewer the flag changes nothing, and without it
  * every answer - exten and speech output on 1024 .. 4096-point frames refused by name - is the one it was.
  *
@@ -274,8 +274,24 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * CTU_STREAMS_NR_STATE as well -nr_mode exten on the spectrum, and with CTU_STREAMS_LARGE_STATE beside that on 1024 .. 4096-point
  * frames.  Still refused by name with the flag: the VAD module beside trapdct (whatever the detector flag), -remove_dc1,
  * -nr_when afterFB behind exten, -s above -w; hwss / fwss / 2fwss and CMVN on trapdct are outside ctu_engine_create.  Without the flag
- * every answer is the one it was, and on a configuration of another feature kind the flag changes no answer and no row. */
-enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64, CTU_STREAMS_TRAP_STATE = 256 };   /* (2, 16 and 128 are no flags: sets refuse them as unknown, and callers may rely on that) */
+ * every answer is the one it was, and on a configuration of another feature kind the flag changes no answer and no row.
+ *
+ * Subtraction state (CTU_STREAMS_SS_STATE = 1024; 512 is no flag; combines with the row state): the set also keeps, per stream, what
+ * -nr_mode hwss | fwss | 2fwss carry along a file (src/nr/nr.cc:181-442, src/vdet/CepstralDet.h:140-194) - the noise estimate Navg of
+ * every bin (and Nravg in 2fwss), the Burg-cepstral detector's record (background cepstrum, dMean, dMean2, threshold, segment count) -
+ * while the file's frame index, which -nr_initsegs counts, is the stream's own.  Taken: what ctu_engine_create accepts of these modes on
+ * the feature path of the 256- and 512-point front end with -vad burg - cepstra, band outputs, -fea_E, -fb_inld and the LP kinds - and
+ * with row state the delta chains, stacking and CMS behind them.  All of it is causal, so a row leaves with the push that completes its
+ * frame, R(F) is the chain's, and ctu_streams_finish has nothing of the subtraction to add.  Every file of a stream is the first file
+ * of a process: its noise estimate starts from zero and its detector afresh, so a file's rows are those of a fresh engine's
+ * ctu_engine_run on that file alone - bit for bit when every push ends a multiple of eight frames into the file, else to the rounding
+ * of the front end's steps - and a push neither reads nor writes what the engine's offline runs carry from
+ * list to list (ctu_engine_reset_chain).  Refused by name with the flag: -vad file=... beside these modes (one byte stream per
+ * process), the modes with speech output (whatever the signal flag), the modes on 2048- / 4096-point frames, and what stands for every
+ * set (-remove_dc1, -s above -w, ...).  Without the flag every answer is the one it was, and on a configuration without one of the
+ * three modes the flag changes no answer and no row. */
+enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64, CTU_STREAMS_TRAP_STATE = 256,
+       CTU_STREAMS_SS_STATE = 1024 };   /* (2, 16, 128 and 512 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
