@@ -22,7 +22,8 @@
 //   stream_trap_kernels.h  streaming input with trap state: TRAP-DCT over the rows a push completes, sixteen (stream, row) columns per MFMA
 //   stream_signal_kernels.h  streaming input with signal state: the overlap-add of a push from the stream's tail, the flush at a file's end
 //   stream_plan.h      streaming input, host only and HIP-free: the descriptors of a push and the planner that fills them (slots, chains, rows)
-//   streams_host.h     streaming input, host side: the stream set, create / push (check, plan, commit, launch) / finish
+//   stream_set_shape.h streaming input, host only and HIP-free: what a stream set is - its kinds of state, halo, strides, the size of every buffer
+//   streams_host.h     streaming input, host side: the stream set, create by the shape / one push body (check, plan, commit, launch) / finish
 //
 // Data layout in HBM
 //   pcm   : one packed int16 arena; utterance i starts at sample_off[i] (multiple of 8 samples)
@@ -63,6 +64,7 @@
 #include "bigburg_kernel.h"
 #include "bigss_kernel.h"
 #include "stream_kernels.h"
+#include "stream_set_shape.h"
 
 namespace {
 

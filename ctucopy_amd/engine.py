@@ -202,7 +202,7 @@ def config_table(args, name):
     return out
 
 
-def _stream_flags(row_state, nr_state, vad_state, signal_state=False, large_state=False, trap_state=False, ss_state=False):
+def _stream_flags(row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False, ss_state=False):
     return ((STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0) | (STREAMS_VAD_STATE if vad_state else 0) |
             (STREAMS_SIGNAL_STATE if signal_state else 0) | (STREAMS_LARGE_STATE if large_state else 0) |
             (STREAMS_TRAP_STATE if trap_state else 0) | (STREAMS_SS_STATE if ss_state else 0))
@@ -221,10 +221,7 @@ def streams_config_check(args, row_state=False, nr_state=False, vad_state=False,
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
-    if not row_state and not nr_state and not vad_state and not signal_state and not large_state and not trap_state and not ss_state:
-        rc = L.ctu_streams_config_check(n, arr, buf, len(buf))
-        return int(rc), buf.value.decode()
-    halo = ctypes.c_int32(0)
+    halo = ctypes.c_int32(0)  # (no flag set: flags 0, which is all the plain ctu_streams_config_check passes on)
     flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state)
     rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
     return (int(rc), buf.value.decode(), int(halo.value)) if row_state or trap_state else (int(rc), buf.value.decode())
@@ -288,11 +285,8 @@ class Streams:
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        if row_state or nr_state or vad_state or signal_state or large_state or trap_state or ss_state:
-            flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state)
-            rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))
-        else:
-            rc = L.ctu_streams_create(engine._h, self.n, self.max_push, ctypes.byref(h))
+        flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state)
+        rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))  # (flags 0: what the plain ctu_streams_create passes on)
         if rc != CTU_OK:
             raise CtuError(rc, L.ctu_last_error(engine._h).decode())
         self._h = h

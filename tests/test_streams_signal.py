@@ -256,6 +256,49 @@ def test_refusals_come_before_anything_changes(Engine):
     assert np.array_equal(rest, off[8 * s:16 * s])
 
 
+def test_a_refused_row_call_between_signal_pushes_and_a_finish_changes_nothing(Engine):
+    """Turn and descriptor reuse across call kinds on one set: pushes of one to three hops on a set of three streams at 256 points,
+    a finish between two pushes, and a row call, which is refused and must leave the turn, the push counter and the mirrors alone."""
+    eng = _case(Engine, "B")[0]
+    w, s = eng.dims.window, eng.dims.wshift
+    assert (w, s) == (256, 128)
+    hops = {0: [3, 0, 1, 2, 0, 3], 1: [0, 2, 3, 0, 1, 2], 2: [0, 3, 0, 2, 1, 3]}   # per push (stream 1: its second file)
+    first1 = _signal(eng, 4, seed=5)[:3 * s].copy()                                         # stream 1's first file: three hops, two frames
+    xs = {k: _signal(eng, 16, seed=11 + k)[:sum(hops[k]) * s].copy() for k in hops}
+    st = _set(eng, "B", 3, 3 * s)
+    got, at = {k: [] for k in hops}, {k: 0 for k in hops}
+
+    def push(i):
+        p = {k: xs[k][at[k]:at[k] + hops[k][i] * s] for k in hops if hops[k][i]}
+        for k, r in st.push_signal(p).items():
+            got[k].append(r.copy())
+            at[k] += p[k].size
+
+    out = st.push_signal({0: xs[0][:3 * s], 1: first1})
+    got[0].append(out[0].copy())
+    at[0] = 3 * s
+    file1 = np.concatenate([out[1], st.finish_signal(1)])
+    assert st.frames(1) == 0 and st.pending(1) == 0
+    push(1)                                                  # streams 1 and 2: stream 1 starts its second file
+    before = [(st.frames(k), st.pending(k)) for k in hops]
+    with pytest.raises(CtuError) as ei:
+        st.push({0: xs[0][at[0]:at[0] + s]})
+    assert ei.value.code == ceng.CTU_ERR_INPUT
+    assert "a set with signal state (CTU_STREAMS_SIGNAL_STATE) delivers samples, not rows: use ctu_streams_push_signal / ctu_streams_finish_signal" in str(ei.value)
+    assert [(st.frames(k), st.pending(k)) for k in hops] == before
+    for i in range(2, 6):                                    # four more
+        push(i)
+    assert np.array_equal(file1, eng.enhance([first1])[0])
+    off = eng.enhance([xs[k] for k in hops])
+    for k in hops:
+        assert at[k] == xs[k].size
+        got[k].append(st.finish_signal(k).copy())
+        mine = np.concatenate(got[k])
+        d = _lsb(mine, off[k]) if mine.shape == off[k].shape else None
+        print("stream %d: %d samples, %s differ from the offline run" % (k, mine.size, "?" if d is None else int((d > 0).sum())))
+        assert mine.shape == off[k].shape and np.array_equal(mine, off[k]), k
+
+
 def test_a_file_shorter_than_one_frame(Engine):
     eng, x, off = _case(Engine, "C")
     w, s = eng.dims.window, eng.dims.wshift

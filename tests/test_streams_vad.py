@@ -286,3 +286,55 @@ def test_calls_on_the_wrong_kind_of_set(Engine):
             ps.finish(0, want_vad=True)
         assert ei.value.code == ceng.CTU_ERR_INPUT and ps.frames(0) == 8
         assert ps.finish(0).shape[0] == 0 and ps.frames(0) == 0
+
+
+def test_a_refused_signal_call_between_pushes_with_decisions_changes_nothing(Engine):
+    """Turn and descriptor reuse across call kinds on one set, the mirror of tests/test_streams_signal.py's: pushes of one to three hops
+    on a set of three streams with detector state (512 points: every chunking gives the offline rows bit for bit), a finish between two
+    pushes, and a signal call, which is refused and must leave the turn, the push counter and the mirrors alone."""
+    cfg = C2 + BURG + ["-vad_thr_mode", "adapt"]
+    eng = Engine(cfg)
+    w, s = eng.dims.window, eng.dims.wshift
+    assert eng.dims.wfft == 512
+    hops = {0: [3, 0, 1, 2, 0, 3], 1: [0, 2, 3, 0, 1, 2], 2: [0, 3, 0, 2, 1, 3]}   # per push (stream 1: its second file)
+    lead = w - s                                                                  # (behind it a push of k hops completes k frames)
+    first1 = _signal(eng, 4)[:lead + 3 * s].copy()                                # stream 1's first file: three frames
+    xs = {k: _signal(eng, 40)[100 * k:100 * k + lead + sum(hops[k]) * s].copy() for k in hops}
+    st = _set(eng, cfg, 3, lead + 3 * s)
+    rows, vads, at = {k: [] for k in hops}, {k: [] for k in hops}, {k: 0 for k in hops}
+
+    def take(out):
+        for k, (r, v) in out.items():
+            rows[k].append(r.copy())
+            vads[k].append(v.copy())
+
+    def push(i):
+        p = {k: xs[k][at[k]:at[k] + hops[k][i] * s + (0 if at[k] else lead)] for k in hops if hops[k][i]}
+        take(st.push(p, want_vad=True))
+        for k in p:
+            at[k] += p[k].size
+
+    out = st.push({0: xs[0][:lead + 3 * s], 1: first1}, want_vad=True)
+    take({0: out[0]})
+    at[0] = lead + 3 * s
+    fin = st.finish(1, want_vad=True)
+    file1 = (np.concatenate([out[1][0], fin[0]]), np.concatenate([out[1][1], fin[1]]))
+    assert st.frames(1) == 0 and st.pending(1) == 0
+    push(1)                                                  # streams 1 and 2: stream 1 starts its second file
+    before = [(st.frames(k), st.pending(k)) for k in hops]
+    with pytest.raises(CtuError) as ei:
+        st.push_signal({0: xs[0][at[0]:at[0] + s]})
+    assert ei.value.code == ceng.CTU_ERR_INPUT
+    assert "ctu_streams_push_signal / ctu_streams_finish_signal need a set with signal state" in str(ei.value)
+    assert [(st.frames(k), st.pending(k)) for k in hops] == before
+    for i in range(2, 6):                                    # four more
+        push(i)
+    off1, vad1, _ = _offline(eng, cfg, first1, both=False)
+    assert np.array_equal(file1[0], off1) and np.array_equal(file1[1], vad1)
+    for k in hops:
+        assert at[k] == xs[k].size
+        take({k: st.finish(k, want_vad=True)})
+        off, vad, _ = _offline(eng, cfg, xs[k], both=False)
+        assert off.shape[0] == sum(hops[k])
+        assert np.array_equal(np.concatenate(vads[k]), vad), k
+        assert np.array_equal(np.concatenate(rows[k]), off), k
