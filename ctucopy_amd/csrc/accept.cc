@@ -241,10 +241,29 @@ int streams_check(const Design &d, uint32_t flags, std::string &err) {
 // With CTU_STREAMS_SS_STATE it keeps what hwss / fwss / 2fwss carry along a file - the noise estimate(s) per bin and the Burg-cepstral detector's
 // record (frontend_kernel<..., SS, ..., XS>): the modes pass on the feature path of the 256- and 512-point front end with -vad burg; -vad file=,
 // speech output and 2048- / 4096-point frames are refused by name.  Without the flag every answer is the one it was.
+// With CTU_STREAMS_SS_SIGNAL_STATE beside the subtraction state and the signal state the two meet in one set (frontend_kernel<..., SS, SY, ..., XS>
+// ahead of stream_ola_kernel): the modes pass with speech output where ss_eligible holds; -vad file=, 2048- / 4096-point frames and -s above -w
+// are refused by name.  Without the flag every answer is the one it was.
 std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
     const Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
     const bool ss_state = (flags & CTU_STREAMS_SS_STATE) != 0 && ss_mode_of(o) != 0;  // (beside another -nr_mode the flag changes no answer)
+    // what no set with subtraction state carries, on the feature path or ahead of speech output
+    auto ss_refused = [&]() -> std::string {
+        if (o.vadmode == "file") return "-vad file=... with -nr_mode " + o.nr_mode + " (the decision bytes are one stream per process, read on from file to file: a stream set has no place in it)";
+        if (!ss_eligible(d))  // (what ctu_engine_create takes beside ss_eligible: ss_big_eligible)
+            return "-nr_mode " + o.nr_mode + " on " + std::to_string(d.wfft) + "-point frames (-w: the passes of the large transforms' subtraction are not streamed, a stream set carries the one of the 256- and 512-point front end)";
+        return "";
+    };
+    // (CTU_STREAMS_SS_SIGNAL_STATE is a flag only beside the subtraction state and the signal state: streams_flags_unknown)
+    constexpr uint32_t ss_signal_flags = CTU_STREAMS_SS_STATE | CTU_STREAMS_SIGNAL_STATE | CTU_STREAMS_SS_SIGNAL_STATE;
+    if (d.signal_out && ss_state && (flags & ss_signal_flags) == ss_signal_flags) {
+        // both kinds of state in one set (frontend_kernel<..., SS, SY, ..., XS> ahead of stream_ola_kernel): what neither carries alone is
+        // refused in the words of the subtraction state and of the signal state
+        if (const std::string why = ss_refused(); !why.empty()) return why;
+        if (d.wshift > d.window) return "-s above -w (frames that leave samples out)";
+        return "";  // (-remove_dc1, the VAD module, longer windows: unsupported_reason, ahead of anything a set is asked)
+    }
     if (d.signal_out && ss_state)
         return "-nr_mode " + o.nr_mode + " with -format_out raw | wave (speech output behind hwss / fwss / 2fwss is not streamed, whatever the signal flag: the subtraction state serves the feature path)";
     if (d.signal_out && !(flags & CTU_STREAMS_SIGNAL_STATE)) return "-format_out raw | wave (speech output: the overlap-add runs across a file's frames)";
@@ -261,9 +280,7 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
         if (o.nr_when_afterFB) return "-nr_when afterFB (exten behind the filter bank keeps its noise estimate per band, inside the filter-bank walk: a stream set carries the estimate per bin)";
         if (d.wfft >= 1024 && !large_state) return "-nr_mode exten on " + std::to_string(d.wfft) + "-point frames (-w: the noise estimate of the large transforms lives in their own kernels, a stream set carries the one of the 256- and 512-point front end)";
     } else if (ss_state) {  // the noise estimate(s) and the detector's record travel with the stream (frontend_kernel<..., SS, ..., XS>)
-        if (o.vadmode == "file") return "-vad file=... with -nr_mode " + o.nr_mode + " (the decision bytes are one stream per process, read on from file to file: a stream set has no place in it)";
-        if (!ss_eligible(d))  // (what ctu_engine_create takes beside ss_eligible: ss_big_eligible)
-            return "-nr_mode " + o.nr_mode + " on " + std::to_string(d.wfft) + "-point frames (-w: the passes of the large transforms' subtraction are not streamed, a stream set carries the one of the 256- and 512-point front end)";
+        if (const std::string why = ss_refused(); !why.empty()) return why;
     } else if (o.nr_mode != "none") return "-nr_mode " + o.nr_mode + " (the noise estimate runs from frame to frame of a file)";
     if (o.remove_dc1) return "-remove_dc1 (a frame's offset stays subtracted from the samples the later frames share with it)";
     if (o.do_vad() && !(flags & CTU_STREAMS_VAD_STATE)) return "the VAD module (-vad_apply_mode / -vad_out_mode: thresholds and the majority filter run along the file)";

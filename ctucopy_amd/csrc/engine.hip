@@ -283,7 +283,8 @@ void lift(int v, F &&f) {
 // behind exten's state, and streams_unsupported_reason refuses those configurations)
 constexpr bool fe_streamed_signal(const FeSel &k) { return k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL && !k.vf && !k.ss && (CTU_SY ? k.sy && !k.vx : k.vx && !k.sy); }
 // (with subtraction state: the twin of every feature-path *ss instantiation - a set runs the engine's own instantiation plus the state traffic)
-constexpr bool fe_streamed_ss(const FeSel &k) { return k.ss && !k.sy && !k.vx && !k.vf; }
+// (with signal state as well: the twin of the one speech-output *ss instantiation per mode, FEAT_BANDS, 16 coefficient rows, GEN_FULL)
+constexpr bool fe_streamed_ss(const FeSel &k) { return k.ss && !k.vx && !k.vf && (!k.sy || (CTU_SY && k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL)); }
 constexpr bool fe_streamed(const FeSel &k) { return fe_streamed_signal(k) || fe_streamed_ss(k) || (!k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf))); }
 void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp, bool xs = false) {
     const FeSel &k = e->tab.sel;

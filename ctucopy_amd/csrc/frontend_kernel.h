@@ -91,6 +91,9 @@ namespace {
 //         xs_ss_floats, layout_constants.h), every file starts from the zero seed, and neither ss_seed, ss_last nor ss_dirty is touched.
 //         gfx950, hipcc -O3, from the code object's metadata: each twin sits at its parent's cap (128 VGPRs in MODE 1, 256 in MODE 0; 104 / 106
 //         SGPRs) and has no more scratch than the parent (20 .. 528 B per lane against 28 .. 544); the table is in DESIGN.md section 4.10.
+//         With SS and SY (a set with both, CTU_STREAMS_SS_SIGNAL_STATE): the twin of the one speech-output SS instantiation per MODE,
+//         <13, FEAT_BANDS, MODE, no VX, 16, GEN_FULL, SS, SY, XS>.  Nothing of its own: the slot traffic is the feature path's, the frames
+//         leave by frame as behind exten, and ss_last with its Nyquist sign flip - the next file's seed - is compiled out.
 // (fe_waves_per_simd, the waves per SIMD an instantiation is compiled for, and its switches CTU_LB / CTU_SY_LB / CTU_VF1_LB: layout_constants.h)
 // (fe_dual, the DUAL instantiations of phase 1 below, and its switch CTU_DUAL: layout_constants.h - tables.cc halves their window table)
 
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
     static_assert(!SS || (!VX && !VF && (GEN == GEN_PLAIN || GEN == GEN_FULL)), "SS: the plain chain, or run-time flags (signal output, energy columns, -fb_inld, LP kinds, magnitude spectra)");
     static_assert(!((VF || SS) && MODE == 0) || NZ == 13, "VF / SS in the 512-point mode: 400-sample windows (16 lanes x 25 samples)");
     static_assert(!SY || (!VX && !VF && (GEN == GEN_FULL || GEN == GEN_DC1)), "SY: run-time flags, no export");
-    static_assert(!XS || (SS ? !SY : (GEN == GEN_EXTEN || (GEN == GEN_FULL && !VF))), "XS: exten on the spectrum, or the *ss modes on the feature path; nothing else that runs along a file (VF stores a frame's cepstra and keeps nothing)");
+    static_assert(!XS || SS || GEN == GEN_EXTEN || (GEN == GEN_FULL && !VF), "XS: exten on the spectrum, or the *ss modes (with SY: ahead of speech output, the assertion below); nothing else that runs along a file (VF stores a frame's cepstra and keeps nothing)");
     static_assert(!XS || !(VX || SY) || (FEAT == FEAT_BANDS && NC == 16 && GEN == GEN_FULL), "XS with SY (or VX): speech output on a stream set with signal state, the one instantiation per (NZ, MODE) - frames and spectra leave by frame, the overlap-add's state is the set's");
     const int o_e_mode = FULL ? p.e_mode : 0, o_dbg = FULL ? p.dbg : 0;
     const bool o_fb_inld = FULL ? p.fb_inld != 0 : GEN == GEN_INLD, o_nr_exten = FULL ? p.nr_exten != 0 : GEN == GEN_EXTEN;

@@ -83,7 +83,9 @@ inline StreamSetShape stream_set_shape(const ctu::Design &d, uint32_t flags, con
     StreamSetShape s;
     const bool do_vad = d.o.do_vad();
     // (per-wave chains are exten's with the noise state, or those of hwss / fwss / 2fwss with the subtraction state, on the 256- / 512-point front end)
-    s.ss = f.ss && (flags & CTU_STREAMS_SS_STATE) && !f.big && !f.ss_file && !d.signal_out;
+    // (with speech output the subtraction state and the signal state meet in one set: CTU_STREAMS_SS_SIGNAL_STATE beside the two)
+    constexpr uint32_t ss_signal_flags = CTU_STREAMS_SS_STATE | CTU_STREAMS_SIGNAL_STATE | CTU_STREAMS_SS_SIGNAL_STATE;
+    s.ss = f.ss && (flags & CTU_STREAMS_SS_STATE) && !f.big && !f.ss_file && (!d.signal_out || (flags & ss_signal_flags) == ss_signal_flags);
     if ((f.per_wave && !f.ss && !(flags & CTU_STREAMS_NR_STATE)) || (do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || (f.ss && !s.ss) ||
         (f.per_wave && f.big && !(flags & CTU_STREAMS_LARGE_STATE)) || (do_vad && f.big)) {
         s.refusal = "internal: a streamed configuration with chains of whole utterances";
@@ -114,7 +116,7 @@ inline StreamSetShape stream_set_shape(const ctu::Design &d, uint32_t flags, con
             return s;
         }
     }
-    s.chained = g.chained = f.per_wave;  // (exten with CTU_STREAMS_NR_STATE, hwss / fwss / 2fwss with CTU_STREAMS_SS_STATE)
+    s.chained = g.chained = f.per_wave;  // (exten with CTU_STREAMS_NR_STATE, hwss / fwss / 2fwss with CTU_STREAMS_SS_STATE - a signal set as well where s.signal)
     g.max_chains = f.chain_slots;        // (max_wg * NWAVE wave chains, or n_cu * 8 workgroup chains of bigfft_kernel)
     s.hw = s.trap ? d.B : d.Dbase;
     // (detector state: a row is copied h frames late, nothing more; trap state: the last 2 half log-mel rows)

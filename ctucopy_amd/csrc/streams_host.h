@@ -69,7 +69,8 @@ struct ctu_streams {
     // CTU_STREAMS_NR_STATE on a chain with -nr_mode exten (sh.chained): Navg | Yavg of every stream (frontend_kernel<..., XS>; with
     // CTU_STREAMS_LARGE_STATE on 1024 .. 4096 points wave1k_kernel<true, XS> / bigfft_kernel<NIT, true, XS>), the heads of the chains a push is
     // dealt onto, and the stream of every tile.  CTU_STREAMS_SS_STATE on a chain with -nr_mode hwss | fwss | 2fwss: the same buffer and the
-    // same chains, a slot of xs_ss_floats per stream - Navg | Nravg and the detector's record (frontend_kernel<..., SS, ..., XS>)
+    // same chains, a slot of xs_ss_floats per stream - Navg | Nravg and the detector's record (frontend_kernel<..., SS, ..., XS>); with
+    // CTU_STREAMS_SS_SIGNAL_STATE on speech output the same slots beside the tails below (frontend_kernel<..., SS, SY, ..., XS>)
     DevBuf<float> xstate;
     TurnBuf<int> heads;
     std::vector<int> chain_tail;     // (scratch of stream_plan_push)
@@ -388,8 +389,9 @@ int push_rows(ctu_streams *st, int k, int n, const PushLayout &L, const RunExten
     return CTU_OK;
 }
 // ... on a set with signal state: the front end leaves the time-domain frames of the push in the plan's ybuf, a row per frame (its SY
-// instantiations; in a build without them synth_kernel from the exported spectra; on 1024 .. 4096-point frames bigsynth_kernel from
-// bigfft_kernel's), and stream_ola_kernel adds them onto every stream's tail - stream_ola_big_kernel a tail of more than OLA_TAIL_MAX entries
+// instantiations - behind hwss / fwss / 2fwss run_chain's one streamed pass from the streams' slots; in a build without them
+// synth_kernel from the exported spectra; on 1024 .. 4096-point frames bigsynth_kernel from bigfft_kernel's), and stream_ola_kernel adds
+// them onto every stream's tail - stream_ola_big_kernel a tail of more than OLA_TAIL_MAX entries
 int push_signal(ctu_streams *st, int k, int n, const PushLayout &L, const RunExtent &x, const PushOutput &o, hipStream_t s) {
     ctu_engine *e = st->eng;
     const ctu::Design &d = *e->design;

@@ -287,11 +287,26 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * ctu_engine_run on that file alone - bit for bit when every push ends a multiple of eight frames into the file, else to the rounding
  * of the front end's steps - and a push neither reads nor writes what the engine's offline runs carry from
  * list to list (ctu_engine_reset_chain).  Refused by name with the flag: -vad file=... beside these modes (one byte stream per
- * process), the modes with speech output (whatever the signal flag), the modes on 2048- / 4096-point frames, and what stands for every
+ * process), the modes with speech output (without CTU_STREAMS_SS_SIGNAL_STATE, below), the modes on 2048- / 4096-point frames, and what stands for every
  * set (-remove_dc1, -s above -w, ...).  Without the flag every answer is the one it was, and on a configuration without one of the
- * three modes the flag changes no answer and no row. */
+ * three modes the flag changes no answer and no row.
+ *
+ * Subtraction state with signal state (CTU_STREAMS_SS_SIGNAL_STATE = 2048): like CTU_STREAMS_LARGE_STATE the flag keeps nothing of its
+ * own - it says that the subtraction state and the signal state meet in one set, so it is a flag only beside both
+ * CTU_STREAMS_SS_STATE and CTU_STREAMS_SIGNAL_STATE: without either, 2048 is refused as an unknown flag, as it always was.  With the three
+ * flags the set streams the speech-enhancement output behind -nr_mode hwss | fwss | 2fwss with -vad burg on the 256- and 512-point
+ * front end (frontend_kernel<..., SS, SY, ..., XS>): windows of 129 .. 208 samples on 256 points and 257 .. 400 on 512, detectors of 2
+ * to 16 coefficients, any -nr_a / -nr_b / -nr_p / -nr_q / -nr_initsegs.  Per stream the set keeps the slot of the subtraction state
+ * and the overlap-add's tail of the signal state; ctu_streams_push_signal delivers wshift samples per frame a push completes,
+ * ctu_streams_finish_signal the window - wshift behind them.  Every file of a stream is the first file of a process (zero seed,
+ * detector afresh, tail zero), so its samples are those of a fresh engine's ctu_engine_run_signal on that file alone - bit for bit when
+ * every push ends a multiple of eight frames into the file, else to the rounding of the front end's steps -
+ * and a push neither reads nor writes what the engine's offline runs carry from list to list.  Refused by name with the flags:
+ * -vad file=... (one byte stream per process), the modes on 2048- / 4096-point frames, -s above -w; what ctu_engine_create refuses
+ * (-remove_dc1, the VAD module with speech output, longer windows) keeps the engine's words.  Without the flag every answer is the one
+ * it was, and beside a configuration that is not one of the three modes with speech output the flag changes no answer and no sample. */
 enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64, CTU_STREAMS_TRAP_STATE = 256,
-       CTU_STREAMS_SS_STATE = 1024 };   /* (2, 16, 128 and 512 are no flags: sets refuse them as unknown, and callers may rely on that) */
+       CTU_STREAMS_SS_STATE = 1024, CTU_STREAMS_SS_SIGNAL_STATE = 2048 };   /* (2, 16, 128 and 512 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
