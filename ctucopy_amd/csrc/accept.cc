@@ -244,15 +244,24 @@ int streams_check(const Design &d, uint32_t flags, std::string &err) {
 // With CTU_STREAMS_SS_SIGNAL_STATE beside the subtraction state and the signal state the two meet in one set (frontend_kernel<..., SS, SY, ..., XS>
 // ahead of stream_ola_kernel): the modes pass with speech output where ss_eligible holds; -vad file=, 2048- / 4096-point frames and -s above -w
 // are refused by name.  Without the flag every answer is the one it was.
+// With CTU_STREAMS_SS_LARGE_STATE beside the subtraction state the latter reaches 2048- / 4096-point frames (bigss_kernel<NIT, true> behind
+// ss_decide_stream_kernel): the modes pass on the feature path where ss_big_eligible holds; -vad file=, speech output at these sizes and
+// -s above -w are refused by name.  Without the flag every answer is the one it was.
 std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
     const Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
     const bool ss_state = (flags & CTU_STREAMS_SS_STATE) != 0 && ss_mode_of(o) != 0;  // (beside another -nr_mode the flag changes no answer)
+    const bool ss_large = ss_state && (flags & CTU_STREAMS_SS_LARGE_STATE) != 0;  // (the subtraction state reaches 2048- / 4096-point frames)
     // what no set with subtraction state carries, on the feature path or ahead of speech output
     auto ss_refused = [&]() -> std::string {
         if (o.vadmode == "file") return "-vad file=... with -nr_mode " + o.nr_mode + " (the decision bytes are one stream per process, read on from file to file: a stream set has no place in it)";
-        if (!ss_eligible(d))  // (what ctu_engine_create takes beside ss_eligible: ss_big_eligible)
-            return "-nr_mode " + o.nr_mode + " on " + std::to_string(d.wfft) + "-point frames (-w: the passes of the large transforms' subtraction are not streamed, a stream set carries the one of the 256- and 512-point front end)";
+        if (!ss_eligible(d)) {  // (what ctu_engine_create takes beside ss_eligible: ss_big_eligible)
+            if (!ss_large)
+                return "-nr_mode " + o.nr_mode + " on " + std::to_string(d.wfft) + "-point frames (-w: the passes of the large transforms' subtraction are not streamed, a stream set carries the one of the 256- and 512-point front end)";
+            // the large transforms' state travels with the stream (bigss_kernel<NIT, true>, ss_decide_stream_kernel): the feature path
+            if (d.signal_out)
+                return "-nr_mode " + o.nr_mode + " with -format_out raw | wave on " + std::to_string(d.wfft) + "-point frames (speech output behind the large transforms' subtraction is not streamed, whatever the other flags: CTU_STREAMS_SS_LARGE_STATE serves the feature path)";
+        }
         return "";
     };
     // (CTU_STREAMS_SS_SIGNAL_STATE is a flag only beside the subtraction state and the signal state: streams_flags_unknown)
@@ -264,6 +273,8 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
         if (d.wshift > d.window) return "-s above -w (frames that leave samples out)";
         return "";  // (-remove_dc1, the VAD module, longer windows: unsupported_reason, ahead of anything a set is asked)
     }
+    if (d.signal_out && ss_large)  // (on 2048- / 4096-point frames the refusal names the size, whatever other flags come with it)
+        if (const std::string why = ss_refused(); !why.empty()) return why;
     if (d.signal_out && ss_state)
         return "-nr_mode " + o.nr_mode + " with -format_out raw | wave (speech output behind hwss / fwss / 2fwss is not streamed, whatever the signal flag: the subtraction state serves the feature path)";
     if (d.signal_out && !(flags & CTU_STREAMS_SIGNAL_STATE)) return "-format_out raw | wave (speech output: the overlap-add runs across a file's frames)";

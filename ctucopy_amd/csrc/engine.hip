@@ -465,10 +465,15 @@ void stage_wave1k(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStre
         });
 }
 // hwss / fwss / 2fwss at 2048 / 4096 points (bigss_kernel.h): the spectra once (bigfft_kernel with the export on and the projection off),
-// the detector's cepstra and decisions once; returns the launch of bigss_kernel, one pass of the seed iteration (run_ss_chain)
+// the detector's cepstra and decisions once; returns the launch of bigss_kernel, one pass of the seed iteration (run_ss_chain).
+// With the extent of a push of a stream set with subtraction state (x.xstate): the export and the detector's cepstra are per frame and run
+// as they are over the push's frames; the decisions come from ss_decide_stream_kernel and the returned launch is bigss_kernel<NIT, true>,
+// both along the push's chains from the streams' slots - run_chain launches it once.
 std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, const BigParams &bp) {
     const ctu::Design &d = *e->design;
     if (d.wfft != 2048 && d.wfft != 4096) throw std::runtime_error("internal: SS engine without an SS instantiation");
+    const bool streamed = x.xstate != nullptr;
+    if (streamed && e->tab.ss_file) throw std::runtime_error("internal: -vad file= on a stream set");
     BigParams xp = bp;
     xp.xri_only = 1;
     launch_bigfft(e, x, s, xp);
@@ -484,16 +489,25 @@ std::function<void()> stage_bigss_front(ctu_engine *e, const ctu_plan *pl, const
             });
         });
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->hp.n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->hp.n_utt, nc, d.o.nr_initsegs,
-                           (double)d.o.nr_p, (double)d.o.nr_q, pl->ss_vbits.p);
+        if (streamed) {  // the chains of the push, the detector's record in every stream's slot
+            SsDecideStreamParams sp;
+            sp.ci = pl->vad_ci.p; sp.tiles = pl->tiles.p; sp.tile_stream = pl->tile_utt.p; sp.heads = x.heads; sp.n_heads = x.n_heads;
+            sp.xstate = static_cast<float *>(x.xstate); sp.slot_floats = xs_ss_big_floats(big_nit(e)); sp.det_doubles = xs_ss_big_doubles(big_nit(e));
+            sp.nc = nc; sp.ninit = d.o.nr_initsegs; sp.pcoef = d.o.nr_p; sp.qcoef = d.o.nr_q; sp.vbits = pl->ss_vbits.p;
+            hipLaunchKernelGGL(ss_decide_stream_kernel, dim3((unsigned)std::max(1, x.n_heads)), dim3(64), 0, s, sp);
+        } else
+            hipLaunchKernelGGL(ss_decide_kernel, dim3((unsigned)pl->hp.n_utt), dim3(64), 0, s, pl->vad_ci.p, pl->d_row_off.p, pl->hp.n_utt, nc, d.o.nr_initsegs,
+                               (double)d.o.nr_p, (double)d.o.nr_q, pl->ss_vbits.p);
         HIP_TRY(hipGetLastError());
     }
     const LdsFit fit = bigss_lds(d, e->tab.feat, e->tab.p2.ncoef_out, e->tab.big_fb_total);
     if (fit.bytes > 160 * 1024) throw std::runtime_error("filter bank too wide for the LDS tables of the large-FFT kernel");
     if (!e->geom.per_wave) throw std::runtime_error("internal: hwss / fwss / 2fwss without chains");
-    return [e, s, &bp, shm = fit.bytes] {
+    return [e, s, &bp, streamed, shm = fit.bytes] {
         lift<8, 16>(big_nit(e), [&](auto nit) {
-            launch_lds(e, &bigss_kernel<decltype(nit)::value>, dim3((unsigned)std::max(1, bp.n_chains)), dim3(256), shm, s, bp);
+            constexpr int NIT = decltype(nit)::value;
+            if (streamed) launch_lds(e, &bigss_kernel<NIT, true>, dim3((unsigned)std::max(1, bp.n_chains)), dim3(256), shm, s, bp);
+            else launch_lds(e, &bigss_kernel<NIT>, dim3((unsigned)std::max(1, bp.n_chains)), dim3(256), shm, s, bp);
         });
     };
 }
@@ -852,6 +866,7 @@ int64_t ctu_config_table(int argc, const char *const *argv, const char *name, do
                  (double)k.ss, (double)k.sy, (double)k.walk};
         }
         else if (n == "host_tables") v = host_tables_report(d);  // EngineTables and VadParams as ctu_engine_create builds them (include/ctu_engine.h)
+        else if (n == "tile_frames") v = {(double)TILE};  // frames per tile record of a plan (offline, and of a stream set's pushes)
         else {
             g_create_error = "unknown table name";
             return CTU_ERR_INPUT;
@@ -1055,7 +1070,7 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
         KParams kp = run_kparams(e, pl, x, d_pcm, d_rows);
-        const BigParams bp = e->tab.big ? run_bigparams(e, pl, x, kp) : BigParams{};
+        BigParams bp = e->tab.big ? run_bigparams(e, pl, x, kp) : BigParams{};
         const int grid = x.grid;
 #if CTU_STAMP
         e->stamps.reserve((size_t)grid * NWAVE * 16);
@@ -1070,16 +1085,22 @@ static int run_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, cons
         // one pass from the streams' own state, no read-back, and the engine's offline chain (ss_stale, vad_pos) is neither read nor written
         const bool ss_streamed = e->tab.ss && x.xstate != nullptr;
         if (ss_streamed) {
-            if (e->tab.path != BIG_NONE || e->tab.ss_file) throw std::runtime_error("internal: a streamed *ss configuration outside the 256- / 512-point detector path");
+            if ((e->tab.path != BIG_NONE && e->tab.path != BIG_SS) || e->tab.ss_file) throw std::runtime_error("internal: a streamed *ss configuration outside the detector paths");
             kp.ss_cached = 0;
             kp.ss_dirty = nullptr;
             kp.ss_seed = nullptr;
             kp.ss_last = nullptr;
+            bp.ss_dirty = nullptr;
+            bp.ss_seed = nullptr;
+            bp.ss_last = nullptr;
         }
         switch (e->tab.path) {
             case BIG_NONE: if (!e->tab.ss || ss_streamed) pass(); break;
             case BIG_WAVE1K: stage_wave1k(e, pl, x, s, bp); break;
-            case BIG_SS: pass = stage_bigss_front(e, pl, x, s, bp); break;
+            case BIG_SS:  // (streamed: export, detector, streamed decide, then bigss_kernel<NIT, true> once)
+                pass = stage_bigss_front(e, pl, x, s, bp);
+                if (ss_streamed) pass();
+                break;
             case BIG_FFT: launch_bigfft(e, x, s, bp); break;
         }
         if (e->tab.ss && !ss_streamed) {

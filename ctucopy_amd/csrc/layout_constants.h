@@ -102,6 +102,14 @@ constexpr int SS_NC = 16;         // the *ss modes' detector uses -fea_ncepcoefs
 // Navg[64 nj] | Nravg[64 nj] (element 64 j + lane), then on an 8-byte boundary the detector's record as doubles - c0[64] (one per lane),
 // dMean, dMean2, threshold - and nseg as the int in the first word of the last pair
 constexpr int xs_ss_floats(int nj) { return 2 * 64 * nj + 2 * 64 + 2 * 3 + 2; }
+// ... and on 2048- / 4096-point frames (CTU_STREAMS_SS_LARGE_STATE beside it; bigss_kernel<NIT, true>, ss_decide_stream_kernel), nit = wfft / 256,
+// NB = nit / 2 + 1 bins per thread: everything in 8-byte cells - Navg[NB][256] | Nravg[NB][256] as doubles, bin tid + 256 r at [r][tid]
+// (a workgroup's loads and stores are 2 KiB contiguous), then the detector's record - c0[64] (one per lane), dMean, dMean2, threshold as
+// doubles and nseg as a 64-bit integer.  The set's buffer is one of floats: the count is even, so every slot starts on an 8-byte boundary.
+constexpr int xs_ss_big_doubles(int nit) { return 2 * 256 * (nit / 2 + 1); }  // (where the detector's record starts, in doubles)
+constexpr int xs_ss_big_floats(int nit) { return 2 * (xs_ss_big_doubles(nit) + 64 + 4); }
+static_assert(xs_ss_big_floats(8) % 2 == 0 && xs_ss_big_floats(16) % 2 == 0 && xs_ss_big_floats(8) == 5256 && xs_ss_big_floats(16) == 9352,
+              "a slot of doubles in a buffer of floats: an even count keeps every slot base 8-byte aligned");
 constexpr int VF_WINDOW = 200;    // the window the fused path is built for (8 kHz, 25 ms); other windows take the separate kernels
 constexpr int VF_SPL = 13;        // samples per lane of a frame: 16 lanes x 13 = 208 >= window
 // The 512-point mode (16 kHz, 25 ms): one frame per 16-lane group, four frames per half step

@@ -85,9 +85,11 @@ inline StreamSetShape stream_set_shape(const ctu::Design &d, uint32_t flags, con
     // (per-wave chains are exten's with the noise state, or those of hwss / fwss / 2fwss with the subtraction state, on the 256- / 512-point front end)
     // (with speech output the subtraction state and the signal state meet in one set: CTU_STREAMS_SS_SIGNAL_STATE beside the two)
     constexpr uint32_t ss_signal_flags = CTU_STREAMS_SS_STATE | CTU_STREAMS_SIGNAL_STATE | CTU_STREAMS_SS_SIGNAL_STATE;
-    s.ss = f.ss && (flags & CTU_STREAMS_SS_STATE) && !f.big && !f.ss_file && (!d.signal_out || (flags & ss_signal_flags) == ss_signal_flags);
+    // (on 2048- / 4096-point frames the subtraction state reaches the feature path with CTU_STREAMS_SS_LARGE_STATE beside it: bigss_kernel<NIT, true>)
+    s.ss = f.ss && (flags & CTU_STREAMS_SS_STATE) && !f.ss_file &&
+           (f.big ? !d.signal_out && (flags & CTU_STREAMS_SS_LARGE_STATE) : !d.signal_out || (flags & ss_signal_flags) == ss_signal_flags);
     if ((f.per_wave && !f.ss && !(flags & CTU_STREAMS_NR_STATE)) || (do_vad && !(flags & CTU_STREAMS_VAD_STATE)) || (f.ss && !s.ss) ||
-        (f.per_wave && f.big && !(flags & CTU_STREAMS_LARGE_STATE)) || (do_vad && f.big)) {
+        (f.per_wave && f.big && !f.ss && !(flags & CTU_STREAMS_LARGE_STATE)) || (do_vad && f.big)) {
         s.refusal = "internal: a streamed configuration with chains of whole utterances";
         return s;
     }
@@ -123,9 +125,9 @@ inline StreamSetShape stream_set_shape(const ctu::Design &d, uint32_t flags, con
     s.C = s.vad ? g.H : s.trap ? 2 * g.H : g.held ? std::max(2 * g.H, g.H + (d.cms == 2 ? d.o.length_b : 1) - 1) : 0;
     if (s.chained) {
         // [2][64 NJ] of xstate_t (frontend_kernel.h), [2][64 * 9] floats (wave1k_kernel.h), [2][256 NB] floats (bigfft_kernel.h); with
-        // subtraction state the slot of layout_constants.h - both noise estimates and the detector's record
+        // subtraction state the slot of layout_constants.h - both noise estimates and the detector's record, on large transforms in doubles
         const int nj = f.mode == 1 ? 3 : 5;
-        s.xstate_floats = s.ss ? xs_ss_floats(nj) : !f.big ? 2 * 64 * nj * (f.exten_f64 ? 2 : 1) : f.wave1k ? 2 * 64 * 9 : 2 * 256 * (d.wfft / 256 / 2 + 1);
+        s.xstate_floats = s.ss ? (f.big ? xs_ss_big_floats(d.wfft / 256) : xs_ss_floats(nj)) : !f.big ? 2 * 64 * nj * (f.exten_f64 ? 2 : 1) : f.wave1k ? 2 * 64 * 9 : 2 * 256 * (d.wfft / 256 / 2 + 1);
     }
     s.n_heads = chain_deal(n_streams, g.max_chains).heads();
     // the lead, a full carry, a full push (and no shorter than the shortest file a delta chain is defined on: the plan of a set whose

@@ -70,7 +70,9 @@ struct ctu_streams {
     // CTU_STREAMS_LARGE_STATE on 1024 .. 4096 points wave1k_kernel<true, XS> / bigfft_kernel<NIT, true, XS>), the heads of the chains a push is
     // dealt onto, and the stream of every tile.  CTU_STREAMS_SS_STATE on a chain with -nr_mode hwss | fwss | 2fwss: the same buffer and the
     // same chains, a slot of xs_ss_floats per stream - Navg | Nravg and the detector's record (frontend_kernel<..., SS, ..., XS>); with
-    // CTU_STREAMS_SS_SIGNAL_STATE on speech output the same slots beside the tails below (frontend_kernel<..., SS, SY, ..., XS>)
+    // CTU_STREAMS_SS_SIGNAL_STATE on speech output the same slots beside the tails below (frontend_kernel<..., SS, SY, ..., XS>); with
+    // CTU_STREAMS_SS_LARGE_STATE on 2048- / 4096-point frames a slot of xs_ss_big_floats per stream, all in 8-byte cells - Navg | Nravg as
+    // doubles and the detector's record (bigss_kernel<NIT, true>, ss_decide_stream_kernel), on workgroup chains as bigfft_kernel's
     DevBuf<float> xstate;
     TurnBuf<int> heads;
     std::vector<int> chain_tail;     // (scratch of stream_plan_push)

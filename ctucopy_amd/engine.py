@@ -20,6 +20,7 @@ STREAMS_LARGE_STATE = 64   # CTU_STREAMS_LARGE_STATE
 STREAMS_TRAP_STATE = 256   # CTU_STREAMS_TRAP_STATE (128 is no flag either)
 STREAMS_SS_STATE = 1024    # CTU_STREAMS_SS_STATE (nor is 512)
 STREAMS_SS_SIGNAL_STATE = 2048  # CTU_STREAMS_SS_SIGNAL_STATE (a flag beside STREAMS_SS_STATE and STREAMS_SIGNAL_STATE only)
+STREAMS_SS_LARGE_STATE = 8192   # CTU_STREAMS_SS_LARGE_STATE (a flag beside STREAMS_SS_STATE only; 4096 is no flag)
 
 
 class CtuError(RuntimeError):
@@ -204,15 +205,15 @@ def config_table(args, name):
 
 
 def _stream_flags(row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False, ss_state=False,
-                  ss_signal_state=False):
+                  ss_signal_state=False, ss_large_state=False):
     return ((STREAMS_ROW_STATE if row_state else 0) | (STREAMS_NR_STATE if nr_state else 0) | (STREAMS_VAD_STATE if vad_state else 0) |
             (STREAMS_SIGNAL_STATE if signal_state else 0) | (STREAMS_LARGE_STATE if large_state else 0) |
             (STREAMS_TRAP_STATE if trap_state else 0) | (STREAMS_SS_STATE if ss_state else 0) |
-            (STREAMS_SS_SIGNAL_STATE if ss_signal_state else 0))
+            (STREAMS_SS_SIGNAL_STATE if ss_signal_state else 0) | (STREAMS_SS_LARGE_STATE if ss_large_state else 0))
 
 
 def streams_config_check(args, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False,
-                         ss_state=False, ss_signal_state=False):
+                         ss_state=False, ss_signal_state=False, ss_large_state=False):
     """(code, reason): whether a command line can be streamed (Engine.streams), without touching a GPU.  CTU_OK and "", or
     CTU_ERR_UNSUPPORTED / CTU_ERR_OPTS and the text ctu_streams_create / ctu_engine_create would give.  With row_state (a set that
     may hold rows back: delta chains, stacking, CMS) the answer is (code, reason, halo).  With nr_state the set keeps the noise
@@ -221,12 +222,12 @@ def streams_config_check(args, row_state=False, nr_state=False, vad_state=False,
     With trap_state (a set that keeps the log-mel context of -fea_kind trapdct) the answer is (code, reason, halo) as with row_state:
     the halo is (traplen - 1) / 2.  With ss_state the set keeps what -nr_mode hwss | fwss | 2fwss carry along a file (noise estimates and
     the Burg-cepstral detector's record); with ss_signal_state beside ss_state and signal_state, the set streams the speech output of
-    those modes."""
+    those modes; with ss_large_state beside ss_state the feature path of those modes reaches 2048- and 4096-point frames."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
     halo = ctypes.c_int32(0)  # (no flag set: flags 0, which is all the plain ctu_streams_config_check passes on)
-    flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state)
+    flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state, ss_large_state)
     rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
     return (int(rc), buf.value.decode(), int(halo.value)) if row_state or trap_state else (int(rc), buf.value.decode())
 
@@ -284,14 +285,16 @@ class Streams:
     With ss_state it takes -nr_mode hwss | fwss | 2fwss with -vad burg on the feature path of the 256- and 512-point front end: the noise
     estimates and the detector's record are kept per stream, and every file of a stream gives the rows of a fresh engine's extract of it.
     With ss_signal_state beside ss_state and signal_state it takes those modes with speech output (-format_out raw | wave): push_signal
-    and finish_signal deliver the samples of a fresh engine's enhance of the file."""
+    and finish_signal deliver the samples of a fresh engine's enhance of the file.
+    With ss_large_state beside ss_state it takes those modes with -vad burg on the feature path of 2048- and 4096-point frames (44.1 /
+    48 kHz audio): both estimates and the detector's record are kept per stream in double, as the large transforms' kernels hold them."""
 
     def __init__(self, engine, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False,
-                 trap_state=False, ss_state=False, ss_signal_state=False):
+                 trap_state=False, ss_state=False, ss_signal_state=False, ss_large_state=False):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state)
+        flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state, ss_large_state)
         rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))  # (flags 0: what the plain ctu_streams_create passes on)
         if rc != CTU_OK:
             raise CtuError(rc, L.ctu_last_error(engine._h).decode())
@@ -509,9 +512,9 @@ class Engine:
         return Plan(self, nsamples)
 
     def streams(self, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False, trap_state=False,
-                ss_state=False, ss_signal_state=False):
+                ss_state=False, ss_signal_state=False, ss_large_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
-        return Streams(self, n, max_push, row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state)
+        return Streams(self, n, max_push, row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state, ss_large_state)
 
     def _check(self, rc):
         if rc != CTU_OK:

@@ -94,7 +94,9 @@ int ctu_config_dims(int argc, const char *const *argv, ctu_dims *out);
  *            carry ints whose bit patterns are NaNs; a double is two words, low then high): lanec, ftab, itab, trapG, trapG16,
  *            dctw_tab, big_win, big_tw, big_fbw, big_range, big_seg, big_coef, big_coef_d, big_slot, big_lifter, big_han;
  *          the 32 fields of the kernels' VAD parameter block (VadParams, layout_constants.h) in declaration order, as values.
- *        Not for HTK feature input, which has no tables.  tests/golden/host_tables.json pins it].
+ *        Not for HTK feature input, which has no tables.  tests/golden/host_tables.json pins it] |
+ *        "tile_frames" [1: frames per tile record of a plan - an offline run's and a stream set's alike: a push that completes more
+ *        frames of a stream than this spans two tiles].
  * Returns the number of values (written up to cap), or a negative error code. */
 int64_t ctu_config_table(int argc, const char *const *argv, const char *name, double *out, int64_t cap);
 
@@ -287,7 +289,7 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * ctu_engine_run on that file alone - bit for bit when every push ends a multiple of eight frames into the file, else to the rounding
  * of the front end's steps - and a push neither reads nor writes what the engine's offline runs carry from
  * list to list (ctu_engine_reset_chain).  Refused by name with the flag: -vad file=... beside these modes (one byte stream per
- * process), the modes with speech output (without CTU_STREAMS_SS_SIGNAL_STATE, below), the modes on 2048- / 4096-point frames, and what stands for every
+ * process), the modes with speech output (without CTU_STREAMS_SS_SIGNAL_STATE, below), the modes on 2048- / 4096-point frames (without CTU_STREAMS_SS_LARGE_STATE, below), and what stands for every
  * set (-remove_dc1, -s above -w, ...).  Without the flag every answer is the one it was, and on a configuration without one of the
  * three modes the flag changes no answer and no row.
  *
@@ -304,9 +306,23 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * and a push neither reads nor writes what the engine's offline runs carry from list to list.  Refused by name with the flags:
  * -vad file=... (one byte stream per process), the modes on 2048- / 4096-point frames, -s above -w; what ctu_engine_create refuses
  * (-remove_dc1, the VAD module with speech output, longer windows) keeps the engine's words.  Without the flag every answer is the one
- * it was, and beside a configuration that is not one of the three modes with speech output the flag changes no answer and no sample. */
+ * it was, and beside a configuration that is not one of the three modes with speech output the flag changes no answer and no sample.
+ *
+ * Subtraction state on large transforms (CTU_STREAMS_SS_LARGE_STATE = 8192; 4096 is no flag): a flag only beside CTU_STREAMS_SS_STATE -
+ * without it 8192 is refused as an unknown flag, as it always was - and it does not involve CTU_STREAMS_LARGE_STATE.  With the two flags
+ * the set runs -nr_mode hwss | fwss | 2fwss with -vad burg on the feature path of 2048- and 4096-point frames (44.1 / 48 kHz audio at
+ * the presets' 25 ms, or long windows): whatever ctu_engine_create takes of these modes there - detectors of 2 to 32 coefficients,
+ * cepstra, band outputs, the LP kinds, -fea_E, any -nr_a / -nr_b / -nr_p / -nr_q / -nr_initsegs - and with row state the delta chains,
+ * stacking and CMS behind them.  Per stream the set keeps, as the large transforms' kernels hold them, Navg and Nravg of every bin and the
+ * detector's record, all as doubles (bigss_kernel<NIT, true>, ss_decide_stream_kernel).  Every file of a stream is the first file of a
+ * process, and none of these kernels works in steps of several frames: a file's rows are those of a fresh engine's ctu_engine_run on
+ * that file alone bit for bit, however the file is cut into pushes.  A push neither reads nor writes what the
+ * engine's offline runs carry from list to list.  Still refused by name with the flag: -vad file=..., the speech output of these modes
+ * on 2048- / 4096-point frames (whatever other flags come with it), -s above -w, and what stands for every set; 1024-point frames,
+ * more than 32 detector coefficients, trapdct, -nr_when afterFB and the VAD module beside these modes are outside ctu_engine_create.
+ * Without the flag every answer is the one it was, and beside another configuration the flag changes no answer and no row. */
 enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64, CTU_STREAMS_TRAP_STATE = 256,
-       CTU_STREAMS_SS_STATE = 1024, CTU_STREAMS_SS_SIGNAL_STATE = 2048 };   /* (2, 16, 128 and 512 are no flags: sets refuse them as unknown, and callers may rely on that) */
+       CTU_STREAMS_SS_STATE = 1024, CTU_STREAMS_SS_SIGNAL_STATE = 2048, CTU_STREAMS_SS_LARGE_STATE = 8192 };   /* (2, 16, 128, 512 and 4096 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
