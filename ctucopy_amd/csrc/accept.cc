@@ -247,6 +247,10 @@ int streams_check(const Design &d, uint32_t flags, std::string &err) {
 // With CTU_STREAMS_SS_LARGE_STATE beside the subtraction state the latter reaches 2048- / 4096-point frames (bigss_kernel<NIT, true> behind
 // ss_decide_stream_kernel): the modes pass on the feature path where ss_big_eligible holds; -vad file=, speech output at these sizes and
 // -s above -w are refused by name.  Without the flag every answer is the one it was.
+// With CTU_STREAMS_VAD_ROW_STATE beside the row state and the detector state the VAD module passes with a delta chain, stacking or CMS behind
+// it (the delayed calls of stream_vad_decide_kernel<true>, the criterion record, h more history rows); drop, the `fea` criterion, trapdct,
+// -fea_E behind the majority filter, large frames and exten outside the fused shapes stay refused by name.  Without the flag every answer
+// is the one it was.
 std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
     const Opts &o = d.o;
     if (d.rows_in) return "-format_in htk (HTK feature input: there are no samples to stream)";
@@ -300,9 +304,12 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
         if (o.vad_apply_mode == "drop") return "-vad_apply_mode drop (the row count of a push would depend on the data)";
         if (o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "fea") return "-vad_cepdist_mode fea (the criterion reads finished rows)";
         if (d.kind == FeaKind::TrapDct) return "-fea_kind trapdct (a vector spans traplen frames)";
-        if (d.post_order > 0)
+        // with CTU_STREAMS_VAD_ROW_STATE beside the row and the detector state the calls run behind the chain's delay (stream_vad_kernels.h:
+        // stream_vad_decide_kernel<true>), and the rows leave h calls behind theirs
+        const bool vad_rows = (flags & STREAMS_VAD_ROW_FLAGS) == STREAMS_VAD_ROW_FLAGS;
+        if (d.post_order > 0 && !vad_rows)
             return std::string(d.post_stack ? "-fea_trap" : "-fea_delta") + " together with the VAD module (the detector is called when a vector reaches the writer, on frame min(t + H, T - 1))";
-        if (d.cms) return std::string(d.cms == 1 ? "-fea_Z_exp" : "-fea_Z_block") + " together with the VAD module (CMS behind the detector's delayed rows is not carried by a stream set)";
+        if (d.cms && !vad_rows) return std::string(d.cms == 1 ? "-fea_Z_exp" : "-fea_Z_block") + " together with the VAD module (CMS behind the detector's delayed rows is not carried by a stream set)";
         if (o.fea_E && (o.vad_filter_order - 1) / 2 > 0) return "-fea_E with the VAD module's majority filter (the offline run shifts the energy column along the file)";
         if (d.wfft >= 1024) return "the VAD module on 1024-point and larger frames (-w: a stream set carries the detector behind the 256- and 512-point front end)";
         if (o.nr_mode == "exten" && !(burg && vf_eligible(d)))

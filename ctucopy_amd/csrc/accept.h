@@ -18,13 +18,17 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags = 0);
 int create_check(const Design &d, std::string &err);
 // ... and ctu_streams_config_check_ex, for a design after spread_small_fft
 constexpr uint32_t STREAMS_FLAGS = CTU_STREAMS_ROW_STATE | CTU_STREAMS_NR_STATE | CTU_STREAMS_VAD_STATE | CTU_STREAMS_SIGNAL_STATE | CTU_STREAMS_LARGE_STATE |
-                                   CTU_STREAMS_TRAP_STATE | CTU_STREAMS_SS_STATE | CTU_STREAMS_SS_SIGNAL_STATE | CTU_STREAMS_SS_LARGE_STATE;
+                                   CTU_STREAMS_TRAP_STATE | CTU_STREAMS_SS_STATE | CTU_STREAMS_SS_SIGNAL_STATE | CTU_STREAMS_SS_LARGE_STATE |
+                                   CTU_STREAMS_VAD_ROW_STATE;
 // CTU_STREAMS_LARGE_STATE keeps nothing of its own: it says how far the noise state and the signal state reach.  Without either it names
 // no state, and a set answers what it always answered to 64: unknown flags.  CTU_STREAMS_SS_SIGNAL_STATE likewise: it says that the
 // subtraction state and the signal state meet in one set, and without both of them 2048 is the unknown flag it always was.
 // CTU_STREAMS_SS_LARGE_STATE says how far the subtraction state reaches (2048- / 4096-point frames): without it 8192 is the unknown flag it always was.
+// CTU_STREAMS_VAD_ROW_STATE says that the row state and the detector state meet in one set: without both of them 16384 is the unknown flag it always was.
+constexpr uint32_t STREAMS_VAD_ROW_FLAGS = CTU_STREAMS_ROW_STATE | CTU_STREAMS_VAD_STATE | CTU_STREAMS_VAD_ROW_STATE;
 inline bool streams_flags_unknown(uint32_t flags) {
     constexpr uint32_t both = CTU_STREAMS_SS_STATE | CTU_STREAMS_SIGNAL_STATE;
+    if ((flags & CTU_STREAMS_VAD_ROW_STATE) && (flags & STREAMS_VAD_ROW_FLAGS) != STREAMS_VAD_ROW_FLAGS) return true;
     return (flags & ~STREAMS_FLAGS) || ((flags & CTU_STREAMS_LARGE_STATE) && !(flags & (CTU_STREAMS_NR_STATE | CTU_STREAMS_SIGNAL_STATE))) ||
            ((flags & CTU_STREAMS_SS_SIGNAL_STATE) && (flags & both) != both) || ((flags & CTU_STREAMS_SS_LARGE_STATE) && !(flags & CTU_STREAMS_SS_STATE));
 }

@@ -11,6 +11,9 @@
 //                         time-domain frames of the push they are made of; PushGeom::signal turns a push's counts into samples
 //   stream_vad_halo       detector state (CTU_STREAMS_VAD_STATE): the majority filter's delay h as the halo of the row arithmetic, so that
 //                         a frame's row and its decision leave together; PushGeom::vad then adds the list of the streams that run the replay
+//   stream_vad_rows_out, VadCalls   detector state behind row state (CTU_STREAMS_VAD_ROW_STATE): the detector is called when a chain row is
+//                         complete, C(F) = stream_rows_out(H, wmax, F) calls after F frames, and a row leaves h calls behind its own:
+//                         R(F) = max(C(F) - h, 0).  PushGeom::vh is h; VadCalls says which calls a pushed stream makes
 //   stream_trap_halo, stream_trap_columns   trap state (CTU_STREAMS_TRAP_STATE): half a context as the halo of the row arithmetic, and
 //                         the stream of every output row of a push, which stream_trap_kernel takes sixteen at a time
 #pragma once
@@ -57,6 +60,10 @@ inline void stream_vad_halo(int order, int *H, int *wmax) {
     *wmax = *H > 0 ? *H - 1 : 0;
 }
 
+// Detector state behind row state: the rows (and decisions) that have gone out after F frames of a file whose chain has halo H and
+// largest window wmax and whose majority filter delays by h calls.  h = 0 is stream_rows_out.
+inline int64_t stream_vad_rows_out(int H, int wmax, int h, int64_t F) { return std::max<int64_t>(stream_rows_out(H, wmax, F) - h, 0); }
+
 // One stream of a push (host-built: the prefix sums over the push are the host's, which mirrors the counts)
 struct StreamPush {
     long long src;    // where its new samples start in the caller's arena (samples)
@@ -75,6 +82,13 @@ struct RowPush {
     int id, Tn;      // stream; frames this push completes
     int nr;          // rows that go out now
     int hsel;        // which of the stream's two histories holds frames F0 - C .. F0 - 1
+};
+
+// One stream of a push on a set with detector state behind row state: the detector's calls c0 .. c0 + nc - 1 of the file, made now
+// (call j reads the criterion of frame j + H, which is a frame of this push or - one push of a file at most - the one before it)
+struct VadCalls {
+    long long c0;  // calls of the file made ahead of this push: C(F0)
+    int nc, pad;   // calls this push makes: C(F0 + Tn) - C(F0)
 };
 
 // One stream of a push on a set with signal state, or the stream that finishes (host-built): the overlap-add of stream_ola_kernel.
@@ -104,6 +118,7 @@ struct PushGeom {
     int window, wshift;
     int H, wmax;             // halo and largest window of the set's delta chain or stacking (0, 0: a frame's row goes out with it)
     bool held;               // row state: RowPush descriptors, the history flip
+    int vh = 0;              // detector state behind row state: the majority filter's delay h, behind the chain's H (0: no such set)
     bool vad = false;        // detector state: RowPush descriptors (whether rows are held or not), the list of the streams that run the replay
     bool chained;            // noise state: chains of whole streams, a wave each
     bool signal = false;     // signal state: SignalPush descriptors; a push's counts, prefix sums and capacity are samples, wshift per frame
@@ -120,6 +135,8 @@ struct PushLayout {
     int *replay = nullptr;           // (vad only) positions in the push of the streams that complete a frame, in push order: the detector's
                                      // replay runs over these alone (16 to a wave); a stream that completes none is not touched
     int n_replay = 0;                // entries of `replay`
+    VadCalls *calls = nullptr;       // (vh > 0 or a chain behind the detector: PushGeom::vad with H of a chain) the calls of every pushed stream;
+                                     // null on every other set
     SignalPush *sig = nullptr;       // (signal only)
     int64_t capacity = -1;           // (signal only) what the caller's buffer holds; -1: not checked
     bool over_capacity = false;      // (signal only) the push delivers more than that: the plan fails and nothing of L may be used
@@ -177,7 +194,11 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
         tiles += (int)((T + TILE - 1) / TILE);
         slices = std::max(slices, (int)((len + STREAM_SLICE - 1) / STREAM_SLICE));
         // what goes out now: rows - or, with signal state, the samples no later frame adds to: wshift for every frame
-        const int64_t r0 = stream_rows_out(g.H, g.wmax, F), nr = g.signal ? T * g.wshift : stream_rows_out(g.H, g.wmax, F + T) - r0;
+        const int64_t r0 = stream_vad_rows_out(g.H, g.wmax, g.vh, F), nr = g.signal ? T * g.wshift : stream_vad_rows_out(g.H, g.wmax, g.vh, F + T) - r0;
+        if (L.calls) {
+            const int64_t c0 = stream_rows_out(g.H, g.wmax, F);
+            L.calls[i].c0 = c0; L.calls[i].nc = (int)(stream_rows_out(g.H, g.wmax, F + T) - c0); L.calls[i].pad = 0;
+        }
         if (g.vad && T > 0) L.replay[n_replay++] = i;
         if (g.held || g.vad) {  // (vad: decision byte k of the push belongs to row k, so out0 serves both; F0 is the replay's absolute frame index)
             RowPush &r = L.rows[i];
@@ -232,19 +253,25 @@ inline int64_t stream_trap_columns(const RowPush *rows, int n, int *col) {
 // pending min(F, h) rows come with as many decisions, which the majority filter's flush makes (row.F0 = the file's frames).
 // signal: H = wmax = 0; pending counts samples - the window - wshift sums of the stream's tail, which the reference's close() writes,
 // once the file has a frame - and `sig` says whose tail (T = 0: no frame is added).
+// vh (detector state behind row state; vad is false there and H, wmax are the chain's): the rows leave h calls behind theirs, so
+// pending = F - max(C(F) - h, 0) - none from a file of no more than h frames, which writes nothing - and `calls` are those the finish
+// still makes, C(F) .. F - 1, each on the criterion of the file's last frame; a file too short for its chain is refused as ever.
 struct FinishLayout {
     int64_t frames, pending;
     bool too_short;
+    VadCalls calls;
     RowPush row;
     SignalPush sig;
 };
-inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel, bool vad = false, bool signal = false) {
+inline FinishLayout stream_plan_finish(int window, int wshift, int H, int wmax, int64_t consumed, int id, int hsel, bool vad = false, bool signal = false,
+                                       int vh = 0) {
     FinishLayout f;
     f.sig.out0 = 0; f.sig.row0 = 0; f.sig.F0 = 0; f.sig.id = id; f.sig.T = 0;
     f.frames = stream_frames(consumed, window, wshift);
-    const int64_t r0 = stream_rows_out(H, wmax, f.frames);
+    const int64_t r0 = stream_vad_rows_out(H, wmax, vh, f.frames);
     f.too_short = H > 0 && f.frames > 0 && f.frames < wmax + 2;
-    f.pending = f.too_short ? 0 : f.frames - r0;
+    f.pending = f.too_short || f.frames <= vh ? 0 : f.frames - r0;
+    f.calls.c0 = stream_rows_out(H, wmax, f.frames); f.calls.nc = f.pending ? (int)(f.frames - f.calls.c0) : 0; f.calls.pad = 0;
     if (vad) f.too_short = false;  // (pending stays 0: neither rows nor decisions)
     f.row.F0 = f.frames; f.row.r0 = r0; f.row.out0 = 0; f.row.row0 = 0;  // rows r0 .. F - 1 with the file's length known
     f.row.id = id; f.row.Tn = 0; f.row.nr = (int)f.pending;

@@ -24,6 +24,18 @@
 //   stream_vad_rows_kernel             rows r0 .. r0 + nr - 1 of every pushed stream, copied h frames late (stream_base_row's two sources)
 //   stream_vad_finish_kernel           the end of a file: vad_flush's zeros through the filter, the last min(F, h) bytes and rows
 //
+// Behind row state (CTU_STREAMS_VAD_ROW_STATE beside the two: a delta chain, a stacking or CMS behind the detector) the reference calls the
+// detector when a vector reaches the writer (src/io/batch.cc:172-192,230-241,251-291): call j - the index every branch of the recurrences
+// takes - reads the criterion of frame min(j + delay, T - 1), delay the chain's halo H.  After F frames C(F) = stream_rows_out(H, wmax, F)
+// calls are made and R(F) = max(C(F) - h, 0) rows and bytes are out; the host says which calls a push makes (VadCalls, stream_plan.h).  Once
+// F >= wmax + 2 the calls of a push read the push's own frames; the push in which F crosses wmax + 2 may read frame F0 - 1 (a stacking,
+// H = wmax, with the boundary between frames wmax and wmax + 1), and the end of a file repeats frame T - 1's criterion for the calls
+// C(T) .. T - 1.  Both are served by one record per stream, in a buffer of its own (crec: the newest frame's criterion input, one energy or
+// ncoef <= 32 Burg cepstra, doubles stored and reloaded as they stand); vstate and the fused kernel's layout are untouched - the fused
+// criterion only ever runs here with delay 0, as it stands.  The rows are the row kernels' (stream_rows_kernels.h), over histories h rows deeper.
+//   stream_vad_delayed_kernel          stream_vad_decide_kernel's twin: the calls of a push, then the push's newest frame into the record
+//   stream_vad_delayed_finish_kernel   stream_vad_finish_kernel's twin: the calls the file still owes on the record, then vad_flush
+//
 // State (vstate): one record of VST_DOUBLES doubles per stream, 384 bytes, 128-byte aligned when the array is:
 //   [0..6]   crimin, crimax, crimean, crimean2, crivar, dmin, dmax          (VadThr's seven doubles)
 //   [7]      hist: the majority filter's ring of raw decisions, bit k = slot k   (64 bits, stored as they stand)
@@ -43,6 +55,9 @@
 // 422 instructions (358 / 376 / 390 / 442); stream_vad_decide_kernel 78 VGPRs (75), 99 SGPRs, 875 instructions (730: the replay loop now comes
 // in two versions, with and without the energy criterion), 16 KB of LDS; stream_vad_rows_kernel 20 VGPRs, 33 SGPRs; stream_vad_finish_kernel
 // 24 VGPRs, 43 SGPRs, 161 instructions (the same); no spills, no scratch.  Times against the restated step: profiles/vad_step_ab.txt.
+// stream_vad_delayed_kernel 79 VGPRs, 106 SGPRs, 978 instructions, 16 KB of LDS (stream_vad_decide_kernel beside it: 78 / 99 / 875, the
+// code it had before the twin existed); stream_vad_delayed_finish_kernel 59 VGPRs, 76 SGPRs, 766 instructions, no LDS; no spills, no
+// scratch.  Like stream_vad_decide_kernel the two are coverage, not tuned paths, and no time is claimed for them.
 #pragma once
 
 namespace {
@@ -150,6 +165,14 @@ __device__ __forceinline__ void vst_store(const VadRun &r, double *vs, int lane)
     if (lane < 32) vs[VST_C0 + lane] = r.c0r;
 }
 
+// Detector state behind row state (CTU_STREAMS_VAD_ROW_STATE): what the delayed replay reads beside StreamVadParams
+struct StreamVadDelay {
+    const VadCalls *calls;  // by position in the push: the calls every pushed stream makes now (stream_plan.h)
+    double *crec;           // [n_streams][stride]: the criterion input of every stream's newest frame - the energy (as a double: exact), or
+                            // the frame's ncoef Burg cepstra.  Stored and reloaded as they stand
+    int stride, delay;      // doubles of a record; the chain's halo H
+};
+
 // grid (pushed streams), 64 lanes: vad_decide_kernel's replay of the energy (vp.cri 0) and Burg (vp.cri 1) criteria over the frames of
 // the push - 64 of them staged in LDS with coalesced loads, then vad_frame one at a time
 __global__ __launch_bounds__(64) void stream_vad_decide_kernel(const StreamVadParams p, const VadParams vp) {
@@ -182,6 +205,53 @@ __global__ __launch_bounds__(64) void stream_vad_decide_kernel(const StreamVadPa
         }
     }
     vst_store(run, vs, lane);
+}
+
+// Its delayed twin, behind a delta chain, a stacking or CMS (the same grid): instead of a call per frame the calls c0 .. c0 + nc - 1 of
+// q.calls, call j on the criterion of frame j + q.delay - a frame of this push, or (one push of a file at most) the frame ahead of it,
+// which is the stream's record - with j the index every branch of the recurrences takes.  A file's first call (c0 == 0) starts from the
+// zero state, whichever push makes it; behind the calls the push's newest frame becomes the record.
+__global__ __launch_bounds__(64) void stream_vad_delayed_kernel(const StreamVadParams p, const VadParams vp, const StreamVadDelay q) {
+    __shared__ double stage[64 * 32];
+    const RowPush d = p.push[blockIdx.x];
+    const int lane = threadIdx.x;
+    const int T = d.Tn;
+    if (T == 0) return;  // completes no frame: neither a call nor a newer record
+    const int nc = vp.cri == 0 ? 1 : vp.ncoef;
+    double *vs = p.vstate + (size_t)d.id * VST_DOUBLES, *rec = q.crec + (size_t)d.id * q.stride;
+    const VadCalls c = q.calls[blockIdx.x];
+    const int first = (int)(c.c0 + q.delay - d.F0);  // the push's frame call c0 reads (-1: the one ahead of it); the last call reads frame T - 1
+    VadRun run = {};
+    if (c.c0 > 0) vst_load(run, vs, lane);
+    run.nout = (int)min(d.r0, (long long)0x40000000);  // (as above; R(F0) = max(c0 - h, 0) is the host's)
+    uint8_t *out = p.vad + d.out0 - run.nout;
+    for (int tb = 0; tb < c.nc; tb += 64) {
+        const int nt = min(64, c.nc - tb);
+        __syncthreads();
+        if (vp.cri == 0) {
+            if (lane < nt) {
+                const int f = first + tb + lane;
+                stage[lane] = f < 0 ? rec[0] : (double)p.energy[d.row0 + f];
+            }
+        } else {
+            for (int e = lane; e < nt * nc; e += 64) {
+                const int k = e / nc, i = e - k * nc, f = first + tb + k;
+                stage[e] = f < 0 ? rec[i] : p.ci[(d.row0 + f) * nc + i];
+            }
+        }
+        __syncthreads();
+        for (int tt = 0; tt < nt; tt++) {
+            const double en = vp.cri == 0 ? stage[tt] : 0.0;
+            const double cil = (vp.cri != 0 && lane < nc) ? stage[tt * nc + lane] : 0.0;
+            const int t = (int)min(c.c0 + tb + tt, (long long)0x40000000);
+            vad_frame(run, vp, t, en, cil, lane, out);
+        }
+    }
+    if (c.nc > 0) vst_store(run, vs, lane);
+    // frame F0 + T - 1 is the file's newest (the record was read ahead of the first barrier above, by this wave)
+    if (vp.cri == 0) {
+        if (lane == 0) rec[0] = (double)p.energy[d.row0 + T - 1];
+    } else if (lane < nc) rec[lane] = p.ci[(d.row0 + T - 1) * nc + lane];
 }
 
 // grid (64-row chunks of the stream with the most rows, pushed streams), 256 lanes
@@ -221,6 +291,29 @@ __global__ __launch_bounds__(256) void stream_vad_finish_kernel(const RowParams 
             vad[d.out0 + k] = vad_byte(f, order);
         }
     }
+}
+
+// Its twin behind row state.  One wave: the stream that finishes (p.push[0]: F0 = the file's frames T, Tn = 0, r0 = R(T), nr = T - r0 > 0,
+// so T > h) makes the calls the file still owes, c.c0 = C(T) .. T - 1 - all of them where T <= delay - each on the criterion of frame
+// T - 1, which is the stream's record (vad_decide_kernel's min(j + delay, T - 1)); then vad_flush's zeros.  Bytes r0 .. T - 1 of the file
+// are bytes 0 .. nr - 1 of the call.  The rows are the row kernels' (finishing); record and state are left as they stand.
+__global__ __launch_bounds__(64) void stream_vad_delayed_finish_kernel(const StreamVadParams p, const VadParams vp, const StreamVadDelay q, const VadCalls c) {
+    const RowPush d = p.push[0];
+    const int lane = threadIdx.x;
+    const int nc = vp.cri == 0 ? 1 : vp.ncoef;
+    VadRun run = {};
+    if (c.c0 > 0) vst_load(run, p.vstate + (size_t)d.id * VST_DOUBLES, lane);
+    run.nout = (int)min(d.r0, (long long)0x40000000);
+    uint8_t *out = p.vad + d.out0 - run.nout;
+    const int end = run.nout + d.nr;  // (the file's length, but for the clamp of nout)
+    const double *rec = q.crec + (size_t)d.id * q.stride;
+    const double en = vp.cri == 0 ? rec[0] : 0.0;
+    const double cil = (vp.cri != 0 && lane < nc) ? rec[lane] : 0.0;
+    for (int k = 0; k < c.nc; k++) {
+        const int t = (int)min(c.c0 + k, (long long)0x40000000);
+        vad_frame(run, vp, t, en, cil, lane, out);
+    }
+    vad_flush(run, vp, end, lane, out);
 }
 
 }  // namespace

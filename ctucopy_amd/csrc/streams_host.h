@@ -11,7 +11,9 @@
 // run goes over the front of the set's ctu_plan with the extent of the push (RunExtent), so the plan itself is not written after create.
 // Between the stitch and the carry a set with rows out runs push_rows: on a set with detector state the run stops ahead of the VAD's
 // sequential stages (run_chain: vad_stages off) and launch_stream_vad replays them from the set's own state, by the plan's RowPush
-// descriptors and its list of the streams that complete a frame.  A set with signal state (speech output) runs push_signal: the run leaves
+// descriptors and its list of the streams that complete a frame.  With CTU_STREAMS_VAD_ROW_STATE beside the row and the detector state
+// (sh.vad_rows) launch_stream_vad_rows makes the calls of the push behind the chain's delay (the plan's VadCalls, the criterion record)
+// and the row kernels deliver the rows that leave h calls behind theirs.  A set with signal state (speech output) runs push_signal: the run leaves
 // the time-domain frames of the push in the plan's ybuf and stream_ola_kernel adds them onto every stream's tail of the overlap-add
 // (stream_signal_kernels.h).
 // A HIP call that fails behind the commit (CTU_ERR_DEVICE) leaves mirrors and device state out of step: include/ctu_engine.h says what
@@ -83,6 +85,11 @@ struct ctu_streams {
     DevBuf<float> vbase;
     DevBuf<uint8_t> vsink;
     TurnBuf<int> replay;
+    // CTU_STREAMS_VAD_ROW_STATE beside the row and the detector state, the VAD module with a chain, a stacking or CMS behind it (sh.vad_rows;
+    // sh.g.H, wmax the chain's, sh.g.vh = h): the histories hold h more base rows, from which the rows held back are rebuilt (vbase is not
+    // used); the criterion input of every stream's newest frame, and the calls of a push's streams (stream_vad_delayed_kernel)
+    DevBuf<double> crec;
+    TurnBuf<VadCalls> vcalls;
     // CTU_STREAMS_SIGNAL_STATE on a configuration with speech output (stream_signal_kernels.h; sh.signal): the overlap-add's tail of every
     // stream - sh.tstride doubles each, window - wshift of them in use - and the descriptors of stream_ola_kernel / stream_ola_big_kernel
     DevBuf<double> otail;
@@ -156,6 +163,12 @@ int64_t ctu_streams_vad_step(int32_t window, int32_t wshift, int32_t filter_orde
     int H = 0, wmax = 0;
     stream_vad_halo(filter_order, &H, &wmax);
     return stream_rows_step(window, wshift, H, wmax, total, pending);
+}
+
+int64_t ctu_streams_vad_rows_step(int32_t window, int32_t wshift, int32_t filter_order, int32_t halo, int32_t wmax, int64_t total, int64_t *pending) {
+    // (the arguments of the two calls above, each with its own rule)
+    if (ctu_streams_rows_step(window, wshift, halo, wmax, total, nullptr) < 0 || filter_order < 1 || filter_order > 31) return CTU_ERR_INPUT;
+    return stream_vad_rows_step(window, wshift, (filter_order - 1) / 2, halo, wmax, total, pending);
 }
 
 int64_t ctu_streams_signal_step(int32_t window, int32_t wshift, int64_t total, int64_t *pending) {
@@ -233,6 +246,10 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
             st->vsink.alloc((size_t)sh.vsink_n(tf));
             st->vbase.alloc((size_t)sh.vbase_n(tf));
             st->replay.alloc((size_t)n_streams);
+            if (sh.vad_rows) {
+                zeroed(st->crec, (size_t)sh.crec_n());  // (never read ahead of a store: a call reads frames of the file)
+                st->vcalls.alloc((size_t)n_streams);
+            }
         }
         if (sh.signal) {
             zeroed(st->otail, (size_t)sh.otail_n());  // (+0.0: a file's first frames add to nothing)
@@ -260,7 +277,7 @@ void ctu_streams_destroy(ctu_streams *st) {
 
 int64_t ctu_streams_frames(const ctu_streams *st, int32_t id) {
     if (!st || id < 0 || id >= st->sh.n_streams) return CTU_ERR_INPUT;
-    return stream_rows_step(st->sh.g.window, st->sh.g.wshift, st->sh.g.H, st->sh.g.wmax, st->consumed[(size_t)id], nullptr);
+    return stream_vad_rows_step(st->sh.g.window, st->sh.g.wshift, st->sh.g.vh, st->sh.g.H, st->sh.g.wmax, st->consumed[(size_t)id], nullptr);
 }
 
 int64_t ctu_streams_pending(const ctu_streams *st, int32_t id) {
@@ -272,9 +289,9 @@ int64_t ctu_streams_pending(const ctu_streams *st, int32_t id) {
 
 namespace {
 // The row kernels of a push, or of a finish, over the n streams rdesc.h[k] describes (uploaded here); `most` is the largest row count among them
-void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finishing, float *d_rows, hipStream_t s) {
+void launch_stream_rows(ctu_streams *st, int k, int n, int64_t most, bool finishing, float *d_rows, hipStream_t s, bool upload = true) {
     const ctu::Design &d = *st->eng->design;
-    st->rdesc.upload(k, (size_t)n, s);
+    if (upload) st->rdesc.upload(k, (size_t)n, s);
     if (most == 0) return;
     RowParams rp;
     rp.push = st->rdesc.d[k].p; rp.fresh = st->plan->base_rows.p; rp.hist = st->hist.p; rp.means = st->means.p; rp.rows = d_rows;
@@ -340,6 +357,37 @@ void launch_stream_vad(ctu_streams *st, int k, int n, const PushLayout &L, float
     }
     HIP_TRY(hipGetLastError());
 }
+// ... on a set with detector state behind row state: the calls of the push - the delayed replay, by the plan's VadCalls (uploaded here)
+// and every stream's criterion record (with CMS alone the delay is 0 and a call reads its own frame); the fused criterion's replay as it
+// stands, which only ever has CMS behind it - then the row kernels over the rows that leave h calls behind theirs
+StreamVadDelay stream_vad_delay(const ctu_streams *st, const VadCalls *calls) {
+    StreamVadDelay q;
+    q.calls = calls; q.crec = st->crec.p; q.stride = st->sh.crec; q.delay = st->sh.g.H;
+    return q;
+}
+void launch_stream_vad_rows(ctu_streams *st, int k, int n, const PushLayout &L, float *d_rows, uint8_t *d_vad, hipStream_t s) {
+    ctu_engine *e = st->eng;
+    const ctu_plan *pl = st->plan.get();
+    st->rdesc.upload(k, (size_t)n, s);
+    if (L.n_replay > 0) {
+        StreamVadParams vp;
+        vp.push = st->rdesc.d[k].p; vp.replay = st->replay.d[k].p; vp.n_replay = L.n_replay;
+        vp.cf = pl->vad_cf.p; vp.ci = pl->vad_ci.p; vp.energy = pl->pnr.p;
+        vp.vstate = st->vstate.p; vp.vad = d_vad ? d_vad : st->vsink.p;
+        if (e->geom.vad_fused) {  // (vf_eligible: no chain, no stacking - the delay is 0)
+            if (st->sh.g.H != 0) throw std::runtime_error("internal: the fused detector behind a delayed chain");
+            st->replay.upload(k, (size_t)L.n_replay, s);
+            lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
+                hipLaunchKernelGGL((stream_vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((unsigned)((L.n_replay + 15) / 16)), dim3(64), 0, s, vp, e->vp);
+            });
+        } else {
+            st->vcalls.upload(k, (size_t)n, s);
+            hipLaunchKernelGGL(stream_vad_delayed_kernel, dim3((unsigned)n), dim3(64), 0, s, vp, e->vp, stream_vad_delay(st, st->vcalls.d[k].p));
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    launch_stream_rows(st, k, n, L.most, false, d_rows, s, false);
+}
 SignalParams signal_params(const ctu_streams *st, const SignalPush *push, int16_t *d_out) {
     const ctu::Design &d = *st->eng->design;
     SignalParams gp;
@@ -369,7 +417,7 @@ bool push_args_ok(const ctu_streams *st, int32_t n, const int32_t *ids, const in
 bool push_count_ok(const ctu_streams *st, int64_t n_samples) { return n_samples >= 0 && n_samples <= st->max_push; }
 
 // where the front end leaves the rows of a push on a set that holds rows - with trap state its log-mel rows, and no kernel of the run writes rows
-float *held_base(const ctu_streams *st) { return st->sh.trap ? st->plan->logmel.p : st->sh.vad ? st->vbase.p : st->plan->base_rows.p; }
+float *held_base(const ctu_streams *st) { return st->sh.trap ? st->plan->logmel.p : st->sh.vad && !st->sh.vad_rows ? st->vbase.p : st->plan->base_rows.p; }
 
 // Where a push delivers: rows (with decisions, if asked) or, on a set with signal state, samples; `capacity` and `counts` are of either
 struct PushOutput {
@@ -385,7 +433,8 @@ int push_rows(ctu_streams *st, int k, int n, const PushLayout &L, const RunExten
     const bool held = st->sh.g.held;
     const int rc = run_chain(st->eng, st->plan.get(), x, st->arena.p, held ? held_base(st) : o.d_rows, nullptr, s, !held, !st->sh.vad);
     if (rc != CTU_OK) return rc;
-    if (st->sh.vad) launch_stream_vad(st, k, n, L, o.d_rows, o.d_vad, s);
+    if (st->sh.vad_rows) launch_stream_vad_rows(st, k, n, L, o.d_rows, o.d_vad, s);
+    else if (st->sh.vad) launch_stream_vad(st, k, n, L, o.d_rows, o.d_vad, s);
     else if (st->sh.trap) launch_stream_trap(st, k, n, o.d_rows, s);
     else if (held) launch_stream_rows(st, k, n, L.most, false, o.d_rows, s);
     return CTU_OK;
@@ -465,6 +514,7 @@ int push_common(ctu_streams *st, bool want_signal, int32_t n, const int32_t *ids
         L.row_counts = o.counts ? o.counts : st->counts.data();  // (the caller's array is output of the call: planned in place)
         L.consumed = st->next_consumed.data(); L.hsel = st->next_hsel.data(); L.replay = st->replay.h[k];
         if (sh.signal) L.capacity = o.capacity;
+        if (sh.vad_rows) L.calls = st->vcalls.h[k];
         if (!stream_plan_push(sh.g, st->consumed.data(), st->hsel.data(), n, ids, n_samples, sample_off, L)) {
             if (L.over_capacity) return refuse(e, no_room);
             throw std::runtime_error("internal: a push beyond the set's arena");
@@ -622,7 +672,7 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
     if (id < 0 || id >= sh.n_streams) return refuse(e, "finish: stream id out of range");
     if (row_count) *row_count = 0;  // fread() comes up short on a trailing partial window and the file ends there (src/io/in.cc:314,438)
     const int64_t total = st->consumed[(size_t)id];
-    const FinishLayout fin = stream_plan_finish(d.window, d.wshift, sh.g.H, sh.g.wmax, total, id, st->hsel[(size_t)id], sh.vad);
+    const FinishLayout fin = stream_plan_finish(d.window, d.wshift, sh.g.H, sh.g.wmax, total, id, st->hsel[(size_t)id], sh.vad && !sh.vad_rows, false, sh.g.vh);
     const int64_t pending = fin.pending;
     const bool too_short = fin.too_short;
     // ahead of any launch or change: the stream stays as it was
@@ -636,7 +686,16 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
             st->turn ^= 1;
             HIP_TRY(hipEventSynchronize(st->desc_free[k]));
             st->rdesc.h[k][0] = fin.row;
-            if (sh.vad) {  // the filter's flush and the h rows it releases, with the file's length known
+            if (sh.vad_rows) {  // the calls the file still owes and the filter's flush, then the rows with the file's length known
+                launch_stream_rows(st, k, 1, pending, true, d_rows, s);
+                if (d_vad) {
+                    StreamVadParams vp;
+                    std::memset(&vp, 0, sizeof vp);
+                    vp.push = st->rdesc.d[k].p; vp.vstate = st->vstate.p; vp.vad = d_vad;
+                    hipLaunchKernelGGL(stream_vad_delayed_finish_kernel, dim3(1), dim3(64), 0, s, vp, e->vp, stream_vad_delay(st, nullptr), fin.calls);
+                    HIP_TRY(hipGetLastError());
+                }
+            } else if (sh.vad) {  // the filter's flush and the h rows it releases, with the file's length known
                 st->rdesc.upload(k, 1, s);
                 RowParams rp;
                 std::memset(&rp, 0, sizeof rp);
@@ -649,7 +708,7 @@ int ctu_streams_finish_vad(ctu_streams *st, int32_t id, float *d_rows, int64_t r
             HIP_TRY(hipEventRecord(st->desc_free[k], s));
         }
         HIP_TRY(hipMemsetAsync(st->state.p + id, 0, sizeof(StreamState), s));
-        if (sh.g.held && !sh.vad) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
+        if (sh.g.held && (!sh.vad || sh.vad_rows)) HIP_TRY(hipMemsetAsync(st->means.p + (size_t)id * STREAM_MEANS, 0, STREAM_MEANS * sizeof(float), s));
         if (sh.trap)  // both histories of the stream (a new file reads neither ahead of its own rows: the left clamp is frame 0)
             for (int h = 0; h < 2; h++)
                 HIP_TRY(hipMemsetAsync(st->hist.p + ((size_t)h * sh.n_streams + id) * sh.C * sh.hw, 0, (size_t)sh.C * sh.hw * sizeof(float), s));

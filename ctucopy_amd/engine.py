@@ -21,6 +21,7 @@ STREAMS_TRAP_STATE = 256   # CTU_STREAMS_TRAP_STATE (128 is no flag either)
 STREAMS_SS_STATE = 1024    # CTU_STREAMS_SS_STATE (nor is 512)
 STREAMS_SS_SIGNAL_STATE = 2048  # CTU_STREAMS_SS_SIGNAL_STATE (a flag beside STREAMS_SS_STATE and STREAMS_SIGNAL_STATE only)
 STREAMS_SS_LARGE_STATE = 8192   # CTU_STREAMS_SS_LARGE_STATE (a flag beside STREAMS_SS_STATE only; 4096 is no flag)
+STREAMS_VAD_ROW_STATE = 16384   # CTU_STREAMS_VAD_ROW_STATE (a flag beside STREAMS_ROW_STATE and STREAMS_VAD_STATE only)
 
 
 class CtuError(RuntimeError):
@@ -49,7 +50,8 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_streams_finish", "ctu_streams_frames", "ctu_streams_step", "ctu_streams_last_push_ms",
            "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step",
            "ctu_streams_push_vad", "ctu_streams_push_vad_host", "ctu_streams_finish_vad", "ctu_streams_finish_vad_host", "ctu_streams_vad_step",
-           "ctu_streams_push_signal", "ctu_streams_push_signal_host", "ctu_streams_finish_signal", "ctu_streams_finish_signal_host", "ctu_streams_signal_step"]
+           "ctu_streams_push_signal", "ctu_streams_push_signal_host", "ctu_streams_finish_signal", "ctu_streams_finish_signal_host", "ctu_streams_signal_step",
+           "ctu_streams_vad_rows_step"]
 
 _lib = None
 
@@ -157,6 +159,9 @@ def load_library():
         L.ctu_streams_finish_signal_host.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64)]
         L.ctu_streams_signal_step.restype = i64
         L.ctu_streams_signal_step.argtypes = [i32, i32, i64, ctypes.POINTER(i64)]
+    if hasattr(L, "ctu_streams_vad_rows_step"):  # (likewise: stream sets with detector state behind row state)
+        L.ctu_streams_vad_rows_step.restype = i64
+        L.ctu_streams_vad_rows_step.argtypes = [i32, i32, i32, i32, i32, i64, ctypes.POINTER(i64)]
     _lib = L
     return L
 
@@ -222,7 +227,8 @@ def streams_config_check(args, row_state=False, nr_state=False, vad_state=False,
     With trap_state (a set that keeps the log-mel context of -fea_kind trapdct) the answer is (code, reason, halo) as with row_state:
     the halo is (traplen - 1) / 2.  With ss_state the set keeps what -nr_mode hwss | fwss | 2fwss carry along a file (noise estimates and
     the Burg-cepstral detector's record); with ss_signal_state beside ss_state and signal_state, the set streams the speech output of
-    those modes; with ss_large_state beside ss_state the feature path of those modes reaches 2048- and 4096-point frames."""
+    those modes; with ss_large_state beside ss_state the feature path of those modes reaches 2048- and 4096-point frames.
+    The flag that has no keyword here, STREAMS_VAD_ROW_STATE, is asked with streams_config_check_ex."""
     L = load_library()
     n, arr = _argv(args)
     buf = ctypes.create_string_buffer(1024)
@@ -230,6 +236,19 @@ def streams_config_check(args, row_state=False, nr_state=False, vad_state=False,
     flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state, ss_large_state)
     rc = L.ctu_streams_config_check_ex(n, arr, flags, buf, len(buf), ctypes.byref(halo))
     return (int(rc), buf.value.decode(), int(halo.value)) if row_state or trap_state else (int(rc), buf.value.decode())
+
+
+def streams_config_check_ex(args, flags):
+    """(code, reason, halo) of a command line for a stream set created with the STREAMS_* bits `flags` (Engine.streams_ex), without
+    touching a GPU: ctu_streams_config_check_ex as it stands.  The keywords of streams_config_check are the bits up to
+    STREAMS_SS_LARGE_STATE; STREAMS_VAD_ROW_STATE - beside STREAMS_ROW_STATE and STREAMS_VAD_STATE the VAD module with delta chains,
+    stacking and CMS behind it, the halo the chain's plus (vad_filter_order - 1) / 2 - is given here."""
+    L = load_library()
+    n, arr = _argv(args)
+    buf = ctypes.create_string_buffer(1024)
+    halo = ctypes.c_int32(0)
+    rc = L.ctu_streams_config_check_ex(n, arr, int(flags), buf, len(buf), ctypes.byref(halo))
+    return int(rc), buf.value.decode(), int(halo.value)
 
 
 def streams_step(window, wshift, total):
@@ -261,6 +280,16 @@ def streams_vad_step(window, wshift, filter_order, total):
     return int(r), int(pending.value)
 
 
+def streams_vad_rows_step(window, wshift, filter_order, halo, wmax, total):
+    """(rows and decisions delivered, frames held back) of a stream with detector state behind row state after `total` samples: a chain
+    of halo `halo` and largest window `wmax` ahead of a majority filter of order `filter_order` (ctu_streams_vad_rows_step)."""
+    pending = ctypes.c_int64(0)
+    r = load_library().ctu_streams_vad_rows_step(int(window), int(wshift), int(filter_order), int(halo), int(wmax), int(total), ctypes.byref(pending))
+    if r < 0:
+        raise CtuError(int(r), "ctu_streams_vad_rows_step: bad argument")
+    return int(r), int(pending.value)
+
+
 def streams_signal_step(window, wshift, total):
     """(samples delivered, samples a finish adds) of a stream with signal state after `total` input samples (ctu_streams_signal_step)."""
     pending = ctypes.c_int64(0)
@@ -287,14 +316,27 @@ class Streams:
     With ss_signal_state beside ss_state and signal_state it takes those modes with speech output (-format_out raw | wave): push_signal
     and finish_signal deliver the samples of a fresh engine's enhance of the file.
     With ss_large_state beside ss_state it takes those modes with -vad burg on the feature path of 2048- and 4096-point frames (44.1 /
-    48 kHz audio): both estimates and the detector's record are kept per stream in double, as the large transforms' kernels hold them."""
+    48 kHz audio): both estimates and the detector's record are kept per stream in double, as the large transforms' kernels hold them.
+    Streams.with_flags (Engine.streams_ex) creates a set from the STREAMS_* bits themselves.  With STREAMS_VAD_ROW_STATE beside
+    STREAMS_ROW_STATE and STREAMS_VAD_STATE it takes the VAD module with delta chains, stacking and CMS behind it: the detector is called
+    when a chain row is complete, and a row leaves with its decision (vad_filter_order - 1) / 2 calls later or with finish."""
 
     def __init__(self, engine, n, max_push, row_state=False, nr_state=False, vad_state=False, signal_state=False, large_state=False,
                  trap_state=False, ss_state=False, ss_signal_state=False, ss_large_state=False):
+        self._create(engine, n, max_push, _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state,
+                                                        ss_large_state))
+
+    @classmethod
+    def with_flags(cls, engine, n, max_push, flags):
+        """A set created with the STREAMS_* bits `flags` (ctu_streams_create_ex as it stands)."""
+        st = cls.__new__(cls)
+        st._create(engine, n, max_push, int(flags))
+        return st
+
+    def _create(self, engine, n, max_push, flags):
         L = load_library()
         self.engine, self.n, self.max_push = engine, int(n), int(max_push)
         h = ctypes.c_void_p()
-        flags = _stream_flags(row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state, ss_large_state)
         rc = L.ctu_streams_create_ex(engine._h, self.n, self.max_push, flags, ctypes.byref(h))  # (flags 0: what the plain ctu_streams_create passes on)
         if rc != CTU_OK:
             raise CtuError(rc, L.ctu_last_error(engine._h).decode())
@@ -515,6 +557,10 @@ class Engine:
                 ss_state=False, ss_signal_state=False, ss_large_state=False):
         """A set of n streams taking up to max_push samples per stream and push (see Streams)."""
         return Streams(self, n, max_push, row_state, nr_state, vad_state, signal_state, large_state, trap_state, ss_state, ss_signal_state, ss_large_state)
+
+    def streams_ex(self, n, max_push, flags):
+        """The same from the STREAMS_* bits themselves (Streams.with_flags): how a set with STREAMS_VAD_ROW_STATE is created."""
+        return Streams.with_flags(self, n, max_push, flags)
 
     def _check(self, rc):
         if rc != CTU_OK:

@@ -320,9 +320,29 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * engine's offline runs carry from list to list.  Still refused by name with the flag: -vad file=..., the speech output of these modes
  * on 2048- / 4096-point frames (whatever other flags come with it), -s above -w, and what stands for every set; 1024-point frames,
  * more than 32 detector coefficients, trapdct, -nr_when afterFB and the VAD module beside these modes are outside ctu_engine_create.
- * Without the flag every answer is the one it was, and beside another configuration the flag changes no answer and no row. */
+ * Without the flag every answer is the one it was, and beside another configuration the flag changes no answer and no row.
+ *
+ * Detector state behind row state (CTU_STREAMS_VAD_ROW_STATE = 16384): like CTU_STREAMS_SS_SIGNAL_STATE the flag says that two kinds
+ * of state meet in one set, so it is a flag only beside both CTU_STREAMS_ROW_STATE and CTU_STREAMS_VAD_STATE: alone, or beside one of
+ * them, 16384 is refused as an unknown flag, as it always was.  With the three flags the set runs the VAD module with -fea_delta
+ * d | d_a | d_a_t, -fea_trap, -fea_Z_exp or -fea_Z_block behind it - MFCC_0_D_A with CMS and a speech / non-speech byte per row - on
+ * everything a set with detector state takes.  The reference calls the detector when a vector reaches the writer (src/io/batch.cc:172-192,
+ * 230-241,251-291): call j, with the absolute index j in every branch of the recurrences, reads the criterion of input frame
+ * min(j + delay, T - 1), delay the chain's halo (the sum of its windows, or the stacking window; 0 with CMS alone).  With
+ * C(F) = F - delay once F >= wmax + 2 (none before: the R(F) of the row state), after F frames a stream has made C(F) calls and
+ * delivered R(F) = max(C(F) - h, 0) rows and decisions, h = (vad_filter_order - 1) / 2; ctu_streams_finish makes the calls that are left
+ * on the criterion of the file's last frame, pushes h zeros through the filter and delivers the rest: T rows and bytes in all for a
+ * file of T > h frames the chain is defined on, nothing (CTU_OK) for one of no more than h frames, and the offline plan's "fewer than
+ * window+2 frames" (CTU_ERR_INPUT) for one the chain is not defined on.  ctu_streams_config_check_ex reports halo = delay + h; the
+ * counting function is ctu_streams_vad_rows_step below.  Per stream the set keeps the detector's record, the criterion input of the
+ * newest frame (one energy, or up to 32 Burg cepstra, as doubles) and h more base rows than the row state alone, from which the rows
+ * held back are rebuilt.  Decisions are those of ctu_engine_run on the whole file byte for byte however it is cut; rows relate to it
+ * as those of the row state do.  With CTU_STREAMS_NR_STATE as well: -nr_mode exten ahead of the fused detector with CMS behind it
+ * (C4 + -fea_Z_exp; delay 0).  Still refused by name with the flag: -vad_apply_mode drop, -vad_cepdist_mode fea, -fea_kind trapdct,
+ * -remove_dc1, the VAD on 1024-point and larger frames, -fea_E with a filter order above 2, -nr_mode exten with a criterion outside the
+ * fused shapes (so behind every delta chain or stacking).  Without the flag every answer is the one it was. */
 enum { CTU_STREAMS_ROW_STATE = 1, CTU_STREAMS_NR_STATE = 4, CTU_STREAMS_VAD_STATE = 8, CTU_STREAMS_SIGNAL_STATE = 32, CTU_STREAMS_LARGE_STATE = 64, CTU_STREAMS_TRAP_STATE = 256,
-       CTU_STREAMS_SS_STATE = 1024, CTU_STREAMS_SS_SIGNAL_STATE = 2048, CTU_STREAMS_SS_LARGE_STATE = 8192 };   /* (2, 16, 128, 512 and 4096 are no flags: sets refuse them as unknown, and callers may rely on that) */
+       CTU_STREAMS_SS_STATE = 1024, CTU_STREAMS_SS_SIGNAL_STATE = 2048, CTU_STREAMS_SS_LARGE_STATE = 8192, CTU_STREAMS_VAD_ROW_STATE = 16384 };   /* (2, 16, 128, 512 and 4096 are no flags: sets refuse them as unknown, and callers may rely on that) */
 int ctu_streams_create(ctu_engine *, int32_t n_streams, int64_t max_push_samples, ctu_streams **out);
 void ctu_streams_destroy(ctu_streams *);   /* ahead of ctu_engine_destroy of its engine: a set reads its engine to the end */
 int ctu_streams_config_check(int argc, const char *const *argv, char *reason, int64_t cap);
@@ -381,6 +401,9 @@ int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t 
 int64_t ctu_streams_rows_step(int32_t window, int32_t wshift, int32_t halo, int32_t wmax, int64_t total, int64_t *pending);
 /* The same for a set with detector state (pure): R(F) for the majority filter of order filter_order (1 .. 31), F - R(F) in *pending. */
 int64_t ctu_streams_vad_step(int32_t window, int32_t wshift, int32_t filter_order, int64_t total, int64_t *pending);
+/* The same for a set with detector state behind row state (pure): R(F) = max(C(F) - h, 0) with C the rows of a chain of halo
+ * H >= wmax >= 0 (the arguments of ctu_streams_rows_step) and h the delay of the majority filter, F - R(F) in *pending. */
+int64_t ctu_streams_vad_rows_step(int32_t window, int32_t wshift, int32_t filter_order, int32_t halo, int32_t wmax, int64_t total, int64_t *pending);
 /* Times of the last push on the set, measured with HIP events on its stream: ms3[0] stream_stitch_kernel, ms3[1] the front end
  * and its tails (with row state: and the row kernels behind them; with detector state: and the replay), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel; trap state: stream_trap_kernel is in ms3[1]).  Blocks until that push has finished. */
 int ctu_streams_last_push_ms(ctu_streams *, float *ms3);
