@@ -416,6 +416,21 @@ class Streams:
         self.engine._check(load_library().ctu_streams_finish_host(self._h, int(sid), rows.ctypes.data if cap else None, cap, ctypes.byref(cnt)))
         return rows[:int(cnt.value)]
 
+    def finish_device(self, sid, rows, vad=None, stream=None):
+        """Device form of finish: rows a float32 CUDA tensor [capacity, D] for the rows held back, vad (a set with detector state) a uint8
+        CUDA tensor [capacity] for their decisions.  Returns the row count; asynchronous on `stream`."""
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.float32
+        cnt = ctypes.c_int64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+        cap = rows.numel() // self.engine.dims.row_floats
+        if vad is not None:
+            assert vad.is_cuda and vad.dtype == torch.uint8 and vad.numel() >= cap
+            self.engine._check(load_library().ctu_streams_finish_vad(self._h, int(sid), rows.data_ptr(), cap, ctypes.byref(cnt), vad.data_ptr(), s.cuda_stream))
+        else:
+            self.engine._check(load_library().ctu_streams_finish(self._h, int(sid), rows.data_ptr(), cap, ctypes.byref(cnt), s.cuda_stream))
+        return int(cnt.value)
+
     def push_signal(self, chunks, capacity=None):
         """{stream id: int16 array} -> {stream id: int16 array}: the enhanced samples the new input completes, wshift for every frame
         (a set with signal_state; host buffers).  `capacity`: the room offered for them (default: enough for any such push)."""
@@ -458,6 +473,16 @@ class Streams:
         out = np.empty(max(cap, 1), dtype=np.int16)
         self.engine._check(load_library().ctu_streams_finish_signal_host(self._h, int(sid), out.ctypes.data if cap else None, cap, ctypes.byref(cnt)))
         return out[:int(cnt.value)]
+
+    def finish_signal_device(self, sid, out, stream=None):
+        """Device form of finish_signal: out a torch int16 CUDA tensor for the tail's samples.  Returns the sample count; asynchronous on
+        `stream`."""
+        import torch
+        assert out.is_cuda and out.dtype == torch.int16
+        cnt = ctypes.c_int64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        self.engine._check(load_library().ctu_streams_finish_signal(self._h, int(sid), out.data_ptr(), out.numel(), ctypes.byref(cnt), s.cuda_stream))
+        return int(cnt.value)
 
     def frames(self, sid):
         """Rows of the current file delivered so far."""
