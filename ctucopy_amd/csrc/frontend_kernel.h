@@ -2,9 +2,19 @@
 // Included by engine.hip (one translation unit: the kernels and their host launchers share types).
 #pragma once
 
+#include "paircol_map.h"
 #include "phase2_walks.h"
 
 namespace {
+
+// CTU_ADDTID16_PC's literal row offsets (kernel_common.h) are the map's
+constexpr bool paircol_macro_rows_are_the_maps() {
+    constexpr int rows[16] = CTU_PC_ROW_BYTES;
+    for (int k1 = 0; k1 < 16; k1++)
+        if (rows[k1] != paircol::store_byte(k1, 0)) return false;
+    return paircol::store_byte(0, 1) == 4164 && paircol::D == 65 && paircol::AREA == 8 * PSTRIDE;
+}
+static_assert(paircol_macro_rows_are_the_maps(), "CTU_ADDTID16_PC / CTU_READ2_PAIRCOL16 and paircol_map.h state one layout");
 
 // NZ = number of 32-sample rows that can hold non-zero input (ceil(window/32)); rows >= NZ are
 // literal zeros so the compiler prunes the first butterflies.
@@ -297,6 +307,75 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     v[2 * h + 1] = cmul_s(v[2 * h + 1], tw.x, tw.y);
                     if (2 * h + 2 < 16) v[2 * h + 2] = cmul_s(v[2 * h + 2], tw.z, tw.w);
                 }
+#if CTU_PAIRCOL
+                // Stage 2 on column pairs (paircol_map.h): from here on the lane is (frame slot f8 = 4 pass + fg, pair p) and the halves of
+                // every register pair are the frame's mirror columns c_lo(p) | c_hi(p), so the untangle finds Z[256 - k] in its own lane.
+                const int pc_p = paircol::lane_p(lane);
+                {   // both transposes at once through the wave's eight rows (layout: CTU_ADDTID16_PC)
+                    const uint32_t sa = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lvoid_t *)Pw);
+                    const uint32_t rd = (uint32_t)(size_t)(lvoid_t *)(Pw + paircol::read_dword(lane));
+#define CTU_E_XA(i) v[i].x.x
+#define CTU_E_XB(i) v[i].x.y
+#define CTU_E_YA(i) v[i].y.x
+#define CTU_E_YB(i) v[i].y.y
+                    __builtin_amdgcn_wave_barrier();
+                    CTU_ADDTID16_PC(CTU_E_XA, sa, 0);
+                    CTU_ADDTID16_PC(CTU_E_XB, sa, 4164);
+                    v2f re[16], im[16];
+                    CTU_READ2_PAIRCOL16(re, rd);
+                    CTU_ADDTID16_PC(CTU_E_YA, sa, 0);
+                    CTU_ADDTID16_PC(CTU_E_YB, sa, 4164);
+                    CTU_READ2_PAIRCOL16(im, rd);
+#pragma unroll
+                    for (int n2 = 0; n2 < 16; n2++) v[n2] = cx2{re[n2], im[n2]};
+                    __builtin_amdgcn_wave_barrier();
+#undef CTU_E_XA
+#undef CTU_E_XB
+#undef CTU_E_YA
+#undef CTU_E_YB
+                }
+                dft16(v);
+                {
+                    const bool self = pc_p == 0;  // columns 0 and 8 mirror onto themselves: the partner is in the same half
+                    const int clo = paircol::c_lo(pc_p), chi = paircol::c_hi(pc_p);
+                    // W512^k of the two halves' bins: the LC_UT entries of the columns' records
+                    const float4 *ulo = reinterpret_cast<const float4 *>(ltw + clo * LTW_STRIDE + LC_UT);
+                    const float4 *uhi = reinterpret_cast<const float4 *>(ltw + chi * LTW_STRIDE + LC_UT);
+                    float *const prow = Pw + paircol::lane_f8(lane) * PSTRIDE;
+                    // bins c + 16 k2 upwards from the column, bins 256 - c - 16 k2 downwards: 144 = 256 - 16 * 7
+                    float *const pk_lo = prow + clo, *const pk_hi = prow + chi, *const pm_lo = prow + 144 - clo, *const pm_hi = prow + 144 - chi;
+#pragma unroll
+                    for (int k2 = 0; k2 < 8; k2++) {
+                        const float4 qlo = ulo[k2 >> 1], qhi = uhi[k2 >> 1];
+                        const float wr0 = (k2 & 1) ? qlo.z : qlo.x, wi0 = (k2 & 1) ? qlo.w : qlo.y;
+                        const float wr1 = (k2 & 1) ? qhi.z : qhi.x, wi1 = (k2 & 1) ? qhi.w : qhi.y;
+                        // Z[256 - k]: register 15 - k2 of the other half; lane p = 0: of the same half (column 8), register (16 - k2) & 15 (column 0)
+                        const cx2 &m = v[15 - k2], &z = v[(16 - k2) & 15];
+                        const v2f br = {self ? z.x.x : m.x.y, self ? m.x.y : m.x.x};
+                        const v2f bi = {self ? z.y.x : m.y.y, self ? m.y.y : m.y.x};
+                        const v2f ar = v[k2].x, ai = v[k2].y;
+                        const v2f sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
+                        // tr = di * wr + dr * wi, ti = di * wi - dr * wr, |u|^2 and |v|^2 with the one product and the one FMA of each stated:
+                        // which of two products the compiler fuses is its choice, and the block below (CTU_PAIRCOL = 0) compiles in every
+                        // instantiation to these - fma(dr, wi, di wr), fma(di, wi, -(dr wr)), fma(re, re, im im) - so the rows agree to the bit
+                        const v2f tr = {__builtin_fmaf(dr.x, wi0, di.x * wr0), __builtin_fmaf(dr.y, wi1, di.y * wr1)};
+                        const v2f ti = {__builtin_fmaf(di.x, wi0, -(dr.x * wr0)), __builtin_fmaf(di.y, wi1, -(dr.y * wr1))};
+                        const v2f ur = sr + tr, ui = si + ti, vr = sr - tr, vi = si - ti;
+                        // the untangle's 1/4 is in the window (the engine scales this instantiation's table by 1/2: ctu_engine::half_window)
+                        const v2f pk = __builtin_elementwise_fma(ur, ur, ui * ui), pm = __builtin_elementwise_fma(vr, vr, vi * vi);
+                        pk_lo[16 * k2] = pk.x;
+                        pk_hi[16 * k2] = pk.y;
+                        pm_lo[16 * (7 - k2)] = pm.x;
+                        pm_hi[16 * (7 - k2)] = pm.y;
+                    }
+                    if (self) {  // bin 128 is its own mirror (no 1/4 there: the halved window is undone): column 0, register 8; bin 0 floor (src/io/in.cc:390)
+                        const v2f a = v[8].x * 2.f, b = v[8].y * 2.f;
+                        const v2f p128 = __builtin_elementwise_fma(a, a, b * b);  // (the same statement of the FMA)
+                        pk_lo[128] = p128.x;  // (lane p = 0: pk_lo is the row itself - no fifth address register)
+                        pk_lo[0] = 1e-10f;
+                    }
+                }
+#else
                 {   // both transposes at once through the wave's eight rows (layout: CTU_ADDTID16_P)
                     const uint32_t sa = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lvoid_t *)Pw);
                     const uint32_t rd = (uint32_t)(size_t)(lvoid_t *)(Pw + 129 * l16 + 16 * fg);
@@ -352,6 +431,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     pr1[128] = p128.y;
                     pr0[0] = pr1[0] = 1e-10f;
                 }
+#endif  // CTU_PAIRCOL
             }
         } else
         if constexpr (DUAL) {

@@ -195,7 +195,8 @@ __device__ __forceinline__ void dft16(cx2 (&v)[16]) {  // as dft16(float2[16]) a
     } while (0)
 
 // The same for sixteen arbitrary float expressions E(i), i = 0..15 (the halves of packed pairs), rows 516 bytes apart
-// starting OFF bytes behind BASE: the layout of the packed transpose (frontend_kernel.h, CTU_PK) - row k1 of pass A at
+// starting OFF bytes behind BASE: the layout of the packed transpose with the passes in the halves through stage 2 as well
+// (frontend_kernel.h, CTU_PK with CTU_PAIRCOL = 0; the default build compiles CTU_ADDTID16_PC below instead) - row k1 of pass A at
 // dword 129 k1, of pass B at 129 k1 + 64, so that one ds_read2_b32 (offset0 = n2, offset1 = 64 + n2) returns the
 // (pass A, pass B) pair of an element into one register pair, and lane (k1, fg) reading dword 129 k1 + 16 fg + n2 meets
 // bank (k1 + 16 fg + n2) mod 32: distinct over each half wave.  16 x 129 dwords fit the wave's eight P rows (2080).
@@ -228,6 +229,46 @@ __device__ __forceinline__ void dft16(cx2 (&v)[16]) {  // as dft16(float2[16]) a
                  "ds_read2_b32 %10, %16 offset0:10 offset1:74\n\tds_read2_b32 %11, %16 offset0:11 offset1:75\n\t"                    \
                  "ds_read2_b32 %12, %16 offset0:12 offset1:76\n\tds_read2_b32 %13, %16 offset0:13 offset1:77\n\t"                    \
                  "ds_read2_b32 %14, %16 offset0:14 offset1:78\n\tds_read2_b32 %15, %16 offset0:15 offset1:79\n\t"                    \
+                 "s_waitcnt lgkmcnt(0)"                                                                                              \
+                 : "=&v"(R[0]), "=&v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]), "=&v"(R[8]), \
+                   "=&v"(R[9]), "=&v"(R[10]), "=&v"(R[11]), "=&v"(R[12]), "=&v"(R[13]), "=&v"(R[14]), "=&v"(R[15])                       \
+                 : "v"(ADDR)                                                                                                         \
+                 : "memory")
+
+// The pair-column layout of the packed transpose (frontend_kernel.h, CTU_PAIRCOL; every index map: paircol_map.h).  The stores are the
+// same sixteen add-TID stores per component and pass, linear in the stage-1 lane 16 fg + n2; only the row bases differ: rows 65 dwords
+// (260 bytes) apart, row 2 p for column c_lo(p) = p and row 2 p + 1 for its mirror column c_hi(p) = 16 - p (p = 0: columns 0 and 8),
+// pass B 1041 dwords behind pass A (OFF = 4164): 1041 + 15 x 65 + 64 = 2080 dwords, exactly the wave's eight P rows.
+// The row offsets below are paircol::store_byte(k1, 0), k1 = 0..15 (asserted beside the kernel).
+#define CTU_ADDTID16_PC(E, BASE, OFF)                                                                                                \
+    do {                                                                                                                             \
+        uint32_t keep_;                                                                                                              \
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %17\n\ts_nop 0\n\t"                                                         \
+                     "ds_write_addtid_b32 %1 offset:%c18\n\tds_write_addtid_b32 %2 offset:520+%c18\n\tds_write_addtid_b32 %3 offset:1040+%c18\n\t"  \
+                     "ds_write_addtid_b32 %4 offset:1560+%c18\n\tds_write_addtid_b32 %5 offset:2080+%c18\n\tds_write_addtid_b32 %6 offset:2600+%c18\n\t" \
+                     "ds_write_addtid_b32 %7 offset:3120+%c18\n\tds_write_addtid_b32 %8 offset:3640+%c18\n\tds_write_addtid_b32 %9 offset:260+%c18\n\t" \
+                     "ds_write_addtid_b32 %10 offset:3900+%c18\n\tds_write_addtid_b32 %11 offset:3380+%c18\n\tds_write_addtid_b32 %12 offset:2860+%c18\n\t" \
+                     "ds_write_addtid_b32 %13 offset:2340+%c18\n\tds_write_addtid_b32 %14 offset:1820+%c18\n\tds_write_addtid_b32 %15 offset:1300+%c18\n\t" \
+                     "ds_write_addtid_b32 %16 offset:780+%c18\n\ts_mov_b32 m0, %0"                                                         \
+                     : "=&s"(keep_)                                                                                                  \
+                     : "v"(E(0)), "v"(E(1)), "v"(E(2)), "v"(E(3)), "v"(E(4)), "v"(E(5)), "v"(E(6)), "v"(E(7)), "v"(E(8)), "v"(E(9)),   \
+                       "v"(E(10)), "v"(E(11)), "v"(E(12)), "v"(E(13)), "v"(E(14)), "v"(E(15)), "s"(BASE), "n"(OFF)                    \
+                     : "memory");                                                                                                    \
+    } while (0)
+#define CTU_PC_ROW_BYTES {0, 520, 1040, 1560, 2080, 2600, 3120, 3640, 260, 3900, 3380, 2860, 2340, 1820, 1300, 780}  // the offsets above, for the assertion
+
+// The sixteen (column c_lo, column c_hi) pairs of one component back from that layout: the stage-2 lane (frame slot f8, pair p) reads
+// from ADDR = the wave's rows + paircol::read_dword(lane) with offset0 = n2, offset1 = 65 + n2.  Over a half wave (pass, fg & 1, p) the
+// sixteen lanes of pass A start at the even banks 2 p + 16 (fg & 1), those of pass B at the odd banks 17 more; offset1 moves all by one.
+#define CTU_READ2_PAIRCOL16(R, ADDR)                                                                                                 \
+    asm volatile("ds_read2_b32 %0, %16 offset0:0 offset1:65\n\tds_read2_b32 %1, %16 offset0:1 offset1:66\n\t"                        \
+                 "ds_read2_b32 %2, %16 offset0:2 offset1:67\n\tds_read2_b32 %3, %16 offset0:3 offset1:68\n\t"                        \
+                 "ds_read2_b32 %4, %16 offset0:4 offset1:69\n\tds_read2_b32 %5, %16 offset0:5 offset1:70\n\t"                        \
+                 "ds_read2_b32 %6, %16 offset0:6 offset1:71\n\tds_read2_b32 %7, %16 offset0:7 offset1:72\n\t"                        \
+                 "ds_read2_b32 %8, %16 offset0:8 offset1:73\n\tds_read2_b32 %9, %16 offset0:9 offset1:74\n\t"                        \
+                 "ds_read2_b32 %10, %16 offset0:10 offset1:75\n\tds_read2_b32 %11, %16 offset0:11 offset1:76\n\t"                    \
+                 "ds_read2_b32 %12, %16 offset0:12 offset1:77\n\tds_read2_b32 %13, %16 offset0:13 offset1:78\n\t"                    \
+                 "ds_read2_b32 %14, %16 offset0:14 offset1:79\n\tds_read2_b32 %15, %16 offset0:15 offset1:80\n\t"                    \
                  "s_waitcnt lgkmcnt(0)"                                                                                              \
                  : "=&v"(R[0]), "=&v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]), "=&v"(R[8]), \
                    "=&v"(R[9]), "=&v"(R[10]), "=&v"(R[11]), "=&v"(R[12]), "=&v"(R[13]), "=&v"(R[14]), "=&v"(R[15])                       \

@@ -26,6 +26,9 @@
 #ifndef CTU_DUAL
 #define CTU_DUAL 1      // the two passes of the 512-point mode side by side in the headline instantiation (frontend_kernel.h: DUAL)
 #endif
+#ifndef CTU_PAIRCOL
+#define CTU_PAIRCOL 1   // the packed DUAL block's second stage on the two mirror columns of one frame per lane (paircol_map.h): the untangle's partner bin in-lane; 0: the passes stay in the halves and the partner comes by ds_bpermute (A/B)
+#endif
 #ifndef CTU_LB
 #define CTU_LB 4        // waves per SIMD the front end's register allocator must leave room for (2 workgroups x 8 waves / 4 SIMDs)
 #endif
