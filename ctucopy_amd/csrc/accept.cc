@@ -325,6 +325,28 @@ std::string streams_unsupported_reason(const Design &d, uint32_t flags) {
     return "";
 }
 
+// The flag set a configuration needs on a stream set (ctu_streams_flags_for): the union of the kinds of state its options call for, each
+// under the condition streams_unsupported_reason asks for it under - so every bit set is one whose absence is a refusal (or, for the flags
+// that only say how far another reaches, an unknown flag set), and a configuration no set takes gets its refusal for this very set.
+uint32_t streams_flags_for(const Design &d) {
+    const Opts &o = d.o;
+    const bool exten = o.nr_mode == "exten", ss = ss_mode_of(o) != 0;
+    uint32_t f = 0;
+    if (d.signal_out) {  // (the row and the detector flags change nothing beside speech output)
+        f |= CTU_STREAMS_SIGNAL_STATE;
+        if (exten) f |= CTU_STREAMS_NR_STATE;
+        if (ss) f |= CTU_STREAMS_SS_STATE | CTU_STREAMS_SS_SIGNAL_STATE | (d.wfft >= 2048 ? CTU_STREAMS_SS_LARGE_STATE : 0);
+        else if (d.wfft >= 1024) f |= CTU_STREAMS_LARGE_STATE;
+        return f;
+    }
+    if (d.post_order > 0 || d.cms) f |= CTU_STREAMS_ROW_STATE;
+    if (exten) f |= CTU_STREAMS_NR_STATE | (d.wfft >= 1024 ? CTU_STREAMS_LARGE_STATE : 0);
+    if (o.do_vad()) f |= CTU_STREAMS_VAD_STATE | ((f & CTU_STREAMS_ROW_STATE) ? CTU_STREAMS_VAD_ROW_STATE : 0);
+    if (d.kind == FeaKind::TrapDct) f |= CTU_STREAMS_TRAP_STATE;
+    if (ss) f |= CTU_STREAMS_SS_STATE | (d.wfft >= 2048 ? CTU_STREAMS_SS_LARGE_STATE : 0);
+    return f;
+}
+
 // the plain cepstral chain: what the specialised instantiations (GEN_PLAIN / GEN_EXTEN with MD) cover
 static bool plain_cepstral(const Design &d) {
     const Opts &o = d.o;

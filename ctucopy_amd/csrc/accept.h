@@ -33,6 +33,8 @@ inline bool streams_flags_unknown(uint32_t flags) {
            ((flags & CTU_STREAMS_SS_SIGNAL_STATE) && (flags & both) != both) || ((flags & CTU_STREAMS_SS_LARGE_STATE) && !(flags & CTU_STREAMS_SS_STATE));
 }
 int streams_check(const Design &d, uint32_t flags, std::string &err);
+// ... and ctu_streams_flags_for: the flags a set needs for this design (after spread_small_fft), whether or not any set takes it
+uint32_t streams_flags_for(const Design &d);
 
 // dctc with more values per frame (cepstra and c0) than phase 2 of the front ends accumulates: dct_wide_kernel behind a band-valued front end
 bool dct_wide(const Design &d);

@@ -145,6 +145,18 @@ int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flag
     }
 }
 
+int ctu_streams_flags_for(int argc, const char *const *argv, uint32_t *flags, char *reason, int64_t cap, int32_t *halo) {
+    uint32_t need = 0;
+    try {
+        ctu::Design d(ctu::Opts::from_args(to_args(argc, argv)));
+        spread_small_fft(d);
+        need = ctu::streams_flags_for(d);
+    } catch (const std::exception &) {  // (a bad command line: the check below says the parser's words)
+    }
+    if (flags) *flags = need;
+    return ctu_streams_config_check_ex(argc, argv, need, reason, cap, halo);
+}
+
 int64_t ctu_streams_step(int32_t window, int32_t wshift, int64_t total, int64_t *carry) {
     if (!stream_step_args_ok(window, wshift, total)) return CTU_ERR_INPUT;
     const int64_t F = stream_frames(total, window, wshift);

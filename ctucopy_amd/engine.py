@@ -51,7 +51,7 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step",
            "ctu_streams_push_vad", "ctu_streams_push_vad_host", "ctu_streams_finish_vad", "ctu_streams_finish_vad_host", "ctu_streams_vad_step",
            "ctu_streams_push_signal", "ctu_streams_push_signal_host", "ctu_streams_finish_signal", "ctu_streams_finish_signal_host", "ctu_streams_signal_step",
-           "ctu_streams_vad_rows_step"]
+           "ctu_streams_vad_rows_step", "ctu_streams_flags_for"]
 
 _lib = None
 
@@ -162,6 +162,8 @@ def load_library():
     if hasattr(L, "ctu_streams_vad_rows_step"):  # (likewise: stream sets with detector state behind row state)
         L.ctu_streams_vad_rows_step.restype = i64
         L.ctu_streams_vad_rows_step.argtypes = [i32, i32, i32, i32, i32, i64, ctypes.POINTER(i64)]
+    if hasattr(L, "ctu_streams_flags_for"):  # (likewise: the flag set a command line needs)
+        L.ctu_streams_flags_for.argtypes = [ctypes.c_int, argv_t, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, i64, ctypes.POINTER(i32)]
     _lib = L
     return L
 
@@ -249,6 +251,18 @@ def streams_config_check_ex(args, flags):
     halo = ctypes.c_int32(0)
     rc = L.ctu_streams_config_check_ex(n, arr, int(flags), buf, len(buf), ctypes.byref(halo))
     return int(rc), buf.value.decode(), int(halo.value)
+
+
+def streams_flags_for(args):
+    """(code, flags, reason, halo): the STREAMS_* bits a command line needs on a stream set (ctu_streams_flags_for), without touching a
+    GPU, and what streams_config_check_ex(args, flags) answers for them - CTU_OK, "" and the halo, or the refusal of that set.  The
+    flags are given in both outcomes (0 behind a command line the parser refuses)."""
+    L = load_library()
+    n, arr = _argv(args)
+    buf = ctypes.create_string_buffer(1024)
+    flags, halo = ctypes.c_uint32(0), ctypes.c_int32(0)
+    rc = L.ctu_streams_flags_for(n, arr, ctypes.byref(flags), buf, len(buf), ctypes.byref(halo))
+    return int(rc), int(flags.value), buf.value.decode(), int(halo.value)
 
 
 def streams_step(window, wshift, total):

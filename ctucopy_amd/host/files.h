@@ -30,16 +30,21 @@ struct FileCloser {
 };
 typedef std::unique_ptr<FILE, FileCloser> File;
 
-// canonical 44-byte WAVE header only, like src/io/in.cc:550-597; returns the number of samples the file holds
-inline size_t wave_samples(const ctu::Opts &o, FILE *f, size_t file_bytes) {
-    uint8_t b[44];
-    if (file_bytes < 44 || std::fread(b, 1, 44, f) != 44 || std::memcmp(b, "RIFF", 4)) throw Fatal("IN: No RIFF header in file!");
+// canonical 44-byte WAVE header only, like src/io/in.cc:550-597: the checks on its 44 bytes, in the reference's order; returns the data chunk's bytes
+inline uint32_t wave_header_data_bytes(const ctu::Opts &o, const uint8_t *b) {
+    if (std::memcmp(b, "RIFF", 4)) throw Fatal("IN: No RIFF header in file!");
     if (std::memcmp(b + 8, "WAVE", 4)) throw Fatal("IN: Not a WAVE file!");
     if (rd16(&b[20]) != 1) throw Fatal("IN: Not a PCM WAVE file!");
     if ((long)rd32(&b[24]) != o.fs) throw Fatal("IN: WAVE file reports different sampling rate than specified!");
     if (rd16(&b[22]) != 1) throw Fatal("IN: Input WAVE file is not mono!");
     if (rd16(&b[34]) != 16) throw Fatal("IN: Not 16 bits per sample!");
-    return std::min<size_t>(rd32(&b[40]) / 2, (file_bytes - 44) / 2);
+    return rd32(&b[40]);
+}
+// returns the number of samples the file holds
+inline size_t wave_samples(const ctu::Opts &o, FILE *f, size_t file_bytes) {
+    uint8_t b[44];
+    if (file_bytes < 44 || std::fread(b, 1, 44, f) != 44) throw Fatal("IN: No RIFF header in file!");
+    return std::min<size_t>(wave_header_data_bytes(o, b) / 2, (file_bytes - 44) / 2);
 }
 
 // HTK feature file (htkIN::new_file / get_frame, src/io/in.cc:629-709): the 12-byte header in the byte order -endian_in names, its
@@ -141,29 +146,65 @@ inline void write_file(const std::string &path, const std::vector<uint8_t> &byte
     std::fclose(f);
 }
 
-// HTK: nSamples, sampPeriod (100 ns), sampSize (bytes), parmKind, then float32 rows (src/io/out.cc:115-213)
-inline void write_htk(const std::string &path, const float *rows, int64_t n, const ctu_dims &d) {
+// What file mode and pipe mode (pipe.h) share of the writers: the bytes of a header and of rows / samples, as the reference's writers lay
+// them out.  The rows come from the engine in writer order (c1..cN, c0[, E]: include/ctu_engine.h), so placing c0 and E is done; what is
+// left is the byte order of -endian_out.
+// HTK: nSamples, sampPeriod (100 ns), sampSize (bytes), parmKind (src/io/out.cc:115-160)
+inline std::vector<uint8_t> htk_header(int64_t n, const ctu_dims &d) {
     std::vector<uint8_t> h;
     const bool big = d.swap_out;
     put32(h, (uint32_t)n, big);
     put32(h, d.htk_period, big);
     put16(h, (uint16_t)(4 * d.row_floats), big);
     put16(h, (uint16_t)d.htk_kind, big);
+    return h;
+}
+// nf float32 values of rows (src/io/out.cc:161-213); false: the stream refused them
+inline bool put_rows(FILE *f, const float *rows, size_t nf, bool big) {
+    if (nf == 0) return true;
+    if (!big) return std::fwrite(rows, 4, nf, f) == nf;  // rows are little-endian float32 as they stand
+    std::vector<uint32_t> sw(nf);
+    for (size_t i = 0; i < nf; i++) {
+        uint32_t x;
+        std::memcpy(&x, rows + i, 4);
+        sw[i] = __builtin_bswap32(x);
+    }
+    return std::fwrite(sw.data(), 4, nf, f) == nf;
+}
+// rawOUT::write (src/io/out.cc:493-499): int16 samples, byte-swapped for -endian_out big
+inline bool put_samples(FILE *f, const int16_t *x, size_t n, bool big) {
+    if (n == 0) return true;
+    if (!big) return std::fwrite(x, 2, n, f) == n;
+    std::vector<uint16_t> sw(n);
+    for (size_t i = 0; i < n; i++) sw[i] = __builtin_bswap16((uint16_t)x[i]);
+    return std::fwrite(sw.data(), 2, n, f) == n;
+}
+// waveOUT (src/io/out.cc:517-564): canonical 44-byte RIFF header for n samples
+inline std::vector<uint8_t> wave_header(size_t n, int fs) {
+    std::vector<uint8_t> b;
+    const uint32_t data = (uint32_t)(2 * n);
+    for (char c : std::string("RIFF")) b.push_back((uint8_t)c);
+    put32(b, data + 36, false);
+    for (char c : std::string("WAVEfmt ")) b.push_back((uint8_t)c);
+    put32(b, 16, false);
+    put16(b, 1, false);
+    put16(b, 1, false);
+    put32(b, (uint32_t)fs, false);
+    put32(b, (uint32_t)fs * 2, false);
+    put16(b, 2, false);
+    put16(b, 16, false);
+    for (char c : std::string("data")) b.push_back((uint8_t)c);
+    put32(b, data, false);
+    return b;
+}
+
+// HTK: the header, then float32 rows (src/io/out.cc:115-213)
+inline void write_htk(const std::string &path, const float *rows, int64_t n, const ctu_dims &d) {
+    const std::vector<uint8_t> h = htk_header(n, d);
     File f(std::fopen(path.c_str(), "wb"));
     if (!f) throw Fatal("OUT: Cannot create output file!");
-    const size_t nf = (size_t)n * d.row_floats;
-    bool ok = std::fwrite(h.data(), 1, h.size(), f.get()) == h.size();
-    if (!big) ok = ok && (nf == 0 || std::fwrite(rows, 4, nf, f.get()) == nf);  // rows are little-endian float32 as they stand
-    else {
-        std::vector<uint32_t> sw(nf);
-        for (size_t i = 0; i < nf; i++) {
-            uint32_t x;
-            std::memcpy(&x, rows + i, 4);
-            sw[i] = __builtin_bswap32(x);
-        }
-        ok = ok && (nf == 0 || std::fwrite(sw.data(), 4, nf, f.get()) == nf);
-    }
-    if (!ok) throw Fatal("OUT: Error in stream writing!");
+    if (std::fwrite(h.data(), 1, h.size(), f.get()) != h.size() || !put_rows(f.get(), rows, (size_t)n * d.row_floats, d.swap_out != 0))
+        throw Fatal("OUT: Error in stream writing!");
 }
 
 // KALDI binary matrix archive + index (src/io/out.cc:648-781)
@@ -261,37 +302,17 @@ struct PfileWriter {
     }
 };
 
-// rawOUT::write (src/io/out.cc:493-499): int16 samples, byte-swapped for -endian_out big
+// rawOUT: the samples alone
 inline void write_raw(const std::string &path, const int16_t *x, size_t n, bool big) {
     File f(std::fopen(path.c_str(), "wb"));
     if (!f) throw Fatal("OUT: Cannot open output stream!");
-    bool ok;
-    if (!big) ok = n == 0 || std::fwrite(x, 2, n, f.get()) == n;
-    else {
-        std::vector<uint16_t> sw(n);
-        for (size_t i = 0; i < n; i++) sw[i] = __builtin_bswap16((uint16_t)x[i]);
-        ok = n == 0 || std::fwrite(sw.data(), 2, n, f.get()) == n;
-    }
-    if (!ok) throw Fatal("OUT: Error in stream writing!");
+    if (!put_samples(f.get(), x, n, big)) throw Fatal("OUT: Error in stream writing!");
 }
 
-// waveOUT (src/io/out.cc:517-564): canonical 44-byte RIFF header, sizes patched at close, samples in host order
+// waveOUT: the header with its sizes, samples in host order
 inline void write_wave(const std::string &path, const int16_t *x, size_t n, int fs) {
-    std::vector<uint8_t> b;
-    const uint32_t data = (uint32_t)(2 * n);
-    for (char c : std::string("RIFF")) b.push_back((uint8_t)c);
-    put32(b, data + 36, false);
-    for (char c : std::string("WAVEfmt ")) b.push_back((uint8_t)c);
-    put32(b, 16, false);
-    put16(b, 1, false);
-    put16(b, 1, false);
-    put32(b, (uint32_t)fs, false);
-    put32(b, (uint32_t)fs * 2, false);
-    put16(b, 2, false);
-    put16(b, 16, false);
-    for (char c : std::string("data")) b.push_back((uint8_t)c);
-    put32(b, data, false);
+    const std::vector<uint8_t> b = wave_header(n, fs);
     File f(std::fopen(path.c_str(), "wb"));
     if (!f) throw Fatal("OUT: Cannot open data file!");
-    if (std::fwrite(b.data(), 1, b.size(), f.get()) != b.size() || (n && std::fwrite(x, 2, n, f.get()) != n)) throw Fatal("OUT: Error in stream writing!");
+    if (std::fwrite(b.data(), 1, b.size(), f.get()) != b.size() || !put_samples(f.get(), x, n, false)) throw Fatal("OUT: Error in stream writing!");
 }

@@ -2,8 +2,10 @@
 // Keeps the reference's command line (src/io/opts.cc:644-846), `-S` list format (`fin fout [spk] [vadfile]`, src/io/batch.cc:349-356),
 // input decoders and feature writers (files.h), so that it is a drop-in for batch feature extraction.  The per-frame chain itself runs
 // on the GPU(s) behind include/ctu_engine.h; this file only moves bytes, with the plumbing of pipeline.h.
-// real_main is the list of steps - parse_host_flags, read_items, make_engines, cut_at_end_of_vad_stream, open_writers, cmvn_stat_path,
+// real_main is the list of steps - parse_host_flags, read_items, pipe_stage, make_engines, cut_at_end_of_vad_stream, open_writers, cmvn_stat_path,
 // run_pipeline, cmvn_pass -; what they share is in Run, handed on by reference.
+// pipe_stage is the whole run of -online_in (pipe.h): one stream of a stream set on the first engine, fed from stdin as the bytes arrive.
+// -i <file> -online_out is the list of one file, whose writer is stdout (write_rows_out, write_signal_files).
 // run_pipeline (the counterpart of BATCH::process, src/io/batch.cc:326-421) has three stages that overlap batch by batch:
 //   read_batches  - size_batch sizes the next files; fill_batch shards them over the GPUs by length (LPT; no collective: every utterance is
 //                   independent) and reads / decodes them straight into page-locked arenas with a pool of I/O threads;
@@ -21,6 +23,7 @@
 #include <unordered_map>
 
 #include "files.h"
+#include "pipe.h"
 #include "pipeline.h"
 
 namespace {
@@ -69,6 +72,8 @@ struct Run {
     int io_threads = 0;     // --io-threads N: file readers (default: the hardware threads, at most 16)
     int write_threads = 0;  // --write-threads N: file writers (default 1: creating files in one directory does not scale)
     int batch_mib = 256;    // --batch-mib M: PCM per batch
+    size_t pipe_read_bytes = 1 << 20;  // --pipe-read-bytes N: -online_in reads stdin in reads of at most N bytes
+    bool pipe_drop = false;  // -online_in with -vad_apply_mode drop: the engine runs with `none`, the stage drops the rows (pipe_stage)
     ctu::Opts o;
     ctu_dims d;
     std::vector<Item> items;
@@ -93,6 +98,7 @@ void parse_host_flags(Run &r, int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--io-threads") && i + 1 < argc) r.io_threads = std::max(1, std::atoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--write-threads") && i + 1 < argc) r.write_threads = std::max(1, std::atoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--batch-mib") && i + 1 < argc) r.batch_mib = std::max(1, std::atoi(argv[++i]));
+        else if (!std::strcmp(argv[i], "--pipe-read-bytes") && i + 1 < argc) r.pipe_read_bytes = (size_t)std::min(std::max(1ll, std::atoll(argv[++i])), 1ll << 25);  // (a push holds at most 2^26 samples)
         else if (!std::strcmp(argv[i], "--gpu-map") && i + 1 < argc) {
             std::istringstream ms(argv[++i]);
             std::string tok;
@@ -106,8 +112,8 @@ void parse_host_flags(Run &r, int argc, char **argv) {
 }
 // the work list: -i / -o, or the -S list
 std::vector<Item> read_items(const ctu::Opts &o) {
-    if (o.pipe_in || o.pipe_out) throw Fatal("ENGINE: online (pipe) mode is not supported");
-    if (!o.in.empty()) return {{o.in, o.out, "", o.vad_out}};
+    if (o.pipe_in) return {};  // stdin is no list: pipe_stage
+    if (!o.in.empty()) return {{o.in, o.out, "", o.vad_out}};  // (-online_out: no name, the writers take stdout)
     if (o.list.empty()) throw Fatal("BATCH: Nothing to do!");
     std::ifstream lf(o.list);
     if (!lf) throw Fatal("BATCH: Cannot open list file!");
@@ -136,7 +142,7 @@ void make_engines(Run &r) {
     // call save_frame, so the VAD does not see them), the last pass normalises a vector and THEN hands it to save_frame - the VAD's ring,
     // its decision, the drop.  The engine therefore delivers every row (apply mode none) and cmvn_pass does the VAD's part on the
     // normalised rows: the ring's phase along the list, the rows a short file does not write, the dropped frames.
-    if (r.cmvn_vad) {
+    if (r.cmvn_vad || r.pipe_drop) {  // (a pipe with -vad_apply_mode drop likewise: pipe_stage)
         cargs.push_back("-vad_apply_mode");
         cargs.push_back("none");
     }
@@ -340,6 +346,15 @@ void run_batch(Run &r, Batch &b) {
         if (!b.sh[g].idx.empty()) run_shard(r, r.gpus[g].eng, b.sh[g]);
     });
 }
+// -online_out: one file in, its bytes to stdout as the reference's writers put them on a stream - rows without the HTK header
+// (src/io/out.cc:115-137), samples alone (out.cc:478)
+void to_stdout(bool ok) {
+    if (!ok || std::fflush(stdout) != 0) throw Fatal("OUT: Error in stream writing!");
+}
+void write_rows_out(const Run &r, const std::string &path, const float *rows, int64_t nr, const ctu_dims &dh) {
+    if (r.o.pipe_out) to_stdout(put_rows(stdout, rows, (size_t)nr * dh.row_floats, dh.swap_out != 0));
+    else write_htk(path, rows, nr, dh);
+}
 std::pair<const float *, int64_t> rows_of(const Run &r, Batch &b, size_t i) {
     auto [sh, k] = b.slot(i);
     return {static_cast<const float *>(sh.rows.get()) + sh.ro[k] * r.d.row_floats, sh.kept[k]};
@@ -349,7 +364,8 @@ void write_signal_files(Run &r, Batch &b) {
     parallel_for(r.write_threads, b.n, [&](size_t i) {
         auto [sh, k] = b.slot(i);
         const int16_t *x = static_cast<const int16_t *>(sh.rows.get()) + sh.so[k];
-        if (r.o.format_out == "raw") write_raw(r.items[b.pos + i].fout, x, (size_t)sh.nout[k], r.d.swap_out != 0);
+        if (r.o.pipe_out) to_stdout(put_samples(stdout, x, (size_t)sh.nout[k], r.d.swap_out != 0));  // (raw: the parser refuses wave here)
+        else if (r.o.format_out == "raw") write_raw(r.items[b.pos + i].fout, x, (size_t)sh.nout[k], r.d.swap_out != 0);
         else write_wave(r.items[b.pos + i].fout, x, (size_t)sh.nout[k], r.o.fs);
     });
 }
@@ -389,7 +405,7 @@ void write_feature_files(Run &r, Batch &b) {
             ctu_dims dh = d;
             if (r.o.fea_trap && !d.rows_in && b.pos + i > 0) dh.htk_kind = (d.htk_kind & ~077) | 8;
             auto [rows, nr] = rows_of(r, b, i);
-            write_htk(it.fout, rows, nr, dh);
+            write_rows_out(r, it.fout, rows, nr, dh);
         }
     });
     if (!per_file)
@@ -584,7 +600,7 @@ void cmvn_apply_and_write(Run &r, std::vector<CorpusShard> &sh, int n_spk, const
         if (r.cmvn_vad) nr = vad_on_normalised_rows(r, i, vr, rows, nr);
         if (r.ark) r.ark->add(r.items[i].fout, rows, nr, r.d.row_floats);
         else if (r.pf) r.pf->add(rows, nr, r.d.row_floats);
-        else write_htk(r.items[i].fout, rows, nr, r.d);
+        else write_rows_out(r, r.items[i].fout, rows, nr, r.d);
     }
 }
 
@@ -599,6 +615,43 @@ void cmvn_pass(Run &r, const std::string &stat_path) {
         for (const Item &it : r.items)
             if (!it.fvad.empty()) write_file(it.fvad, std::vector<uint8_t>(), "FileWriter: cannot open file!");
     if (r.o.apply_cmvn) cmvn_apply_and_write(r, sh, n_spk, mean, var);
+}
+
+// -online_in: the whole run.  What no stream set takes is refused ahead of the engine and of the first byte of input, in the set's words.
+int pipe_stage(Run &r) {
+    const ctu::Opts &o = r.o;
+    if (o.format_out == "ark" || o.format_out == "pfile")
+        throw Fatal("ENGINE: online input: -format_out " + o.format_out + " (an archive is written for a list; a pipe writes htk, raw or wave)");
+    r.pipe_drop = o.do_vad() && o.vad_apply_mode == "drop";
+    std::vector<const char *> cargs;
+    for (auto &a : r.args) cargs.push_back(a.c_str());
+    if (r.pipe_drop) {
+        cargs.push_back("-vad_apply_mode");
+        cargs.push_back("none");
+    }
+    PipeJob job;
+    char reason[1024];
+    const int rc = ctu_streams_flags_for((int)cargs.size(), cargs.data(), &job.flags, reason, sizeof reason, &job.halo);
+    if (rc == CTU_ERR_OPTS) throw Fatal(reason);
+    if (rc != CTU_OK) {
+        const std::string why(reason), lead("ENGINE: ");
+        throw Fatal("ENGINE: online input: " + (why.compare(0, lead.size(), lead) == 0 ? why.substr(lead.size()) : why));
+    }
+    (void)PipeDecoder(o);  // (an input format outside raw | alaw | mulaw | wave: the reader's words)
+    if (o.do_vad() && o.vad_out_mode != "none") {
+        if (o.vad_out.empty()) throw Fatal("VAD::new_file(): invalid filename!");
+        job.vad_path = o.vad_out;
+    }
+    if (r.ngpu > 1 && o.verbose) std::fprintf(stderr, "ENGINE: online input is one stream: running on one GPU\n");
+    r.ngpu = 1;
+    if (!r.gpu_map.empty()) r.gpu_map.resize(1);
+    make_engines(r);
+    job.eng = r.gpus[0].eng;
+    job.read_bytes = r.pipe_read_bytes;
+    job.drop = r.pipe_drop;
+    const int64_t frames = run_pipe(job, o, r.d);
+    if (o.verbose) std::fprintf(stderr, "processing: <stdin> - %lld frames.\n", (long long)frames);
+    return 0;
 }
 
 int real_main(int argc, char **argv) {
@@ -618,6 +671,7 @@ int real_main(int argc, char **argv) {
     r.signal_out = o.format_out == "raw" || o.format_out == "wave";
     if (!r.signal_out && o.format_out != "htk" && o.format_out != "ark" && o.format_out != "pfile") throw Fatal("OUT: Unknown output file format!");
     r.items = read_items(o);
+    if (o.pipe_in) return pipe_stage(r);
     // hwss / fwss / 2fwss chain the list through the noise seed (src/nr/nr.cc:212-221): one GPU, files in list order
     const bool chained = o.nr_mode == "hwss" || o.nr_mode == "fwss" || o.nr_mode == "2fwss";
     if (chained && r.ngpu > 1) {

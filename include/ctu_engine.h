@@ -349,6 +349,16 @@ int ctu_streams_config_check(int argc, const char *const *argv, char *reason, in
 /* The two calls above are these with flags 0.  *halo (may be NULL) receives H of an accepted configuration. */
 int ctu_streams_create_ex(ctu_engine *, int32_t n_streams, int64_t max_push_samples, uint32_t flags, ctu_streams **out);
 int ctu_streams_config_check_ex(int argc, const char *const *argv, uint32_t flags, char *reason, int64_t cap, int32_t *halo);
+/* The flag set a configuration needs (no device): the union of the kinds of state its options call for - row state for -fea_delta /
+ * -fea_trap / -fea_Z_exp / -fea_Z_block, noise state for -nr_mode exten, detector state for the VAD module (and CTU_STREAMS_VAD_ROW_STATE
+ * where it meets the row state), signal state for -format_out raw | wave, large-transform state beside the noise or the signal state on
+ * 1024 .. 4096-point frames, trap state for trapdct, subtraction state for hwss / fwss / 2fwss (with CTU_STREAMS_SS_SIGNAL_STATE ahead of
+ * speech output and CTU_STREAMS_SS_LARGE_STATE on 2048- / 4096-point frames).  No bit is set that the configuration does not need: an
+ * accepted configuration is refused with any one of them cleared.  *flags (may be NULL) is written in both outcomes; the return code,
+ * `reason` and *halo are those of ctu_streams_config_check_ex for that flag set - so a configuration no set takes comes back with the
+ * refusal of the set that came closest, and a bad command line with the parser's text and flags 0.  A host that drives one stream per
+ * input (the pipe mode of bin/ctucopy) creates its set with these flags. */
+int ctu_streams_flags_for(int argc, const char *const *argv, uint32_t *flags, char *reason, int64_t cap, int32_t *halo);
 int ctu_streams_push(ctu_streams *, int32_t n, const int32_t *stream_ids, const int16_t *d_pcm, const int64_t *sample_off,
                      const int64_t *n_samples, float *d_rows, int64_t rows_capacity, int64_t *row_counts, void *stream);
 /* Host-buffer form: h_pcm[i] points at stream i's new samples, h_rows receives the rows; page-locked rows (ctu_host_alloc) are
