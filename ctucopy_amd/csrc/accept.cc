@@ -365,19 +365,19 @@ static bool ss_frame_shape(const Design &d) {
 // Burg-cepstral VAD criterion fused into the front end (vad_fused.h): 14 coefficients (the preset's detector)
 bool vf_eligible(const Design &d) {
     const Opts &o = d.o;
-    return CTU_VF && CTU_MD && plain_cepstral(d) && o.do_vad() && o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "lpc" &&
+    return plain_cepstral(d) && o.do_vad() && o.vad_cri_mode == "cepdist" && o.vad_cepdist_mode == "lpc" &&
            fused_frame_shape(d) && o.vad_lpc_coefs == VF_NC && d.post_order == 0;
 }
 // the compressed-band LP chain (PLP and friends: -fb_inld, at most 16 lags, no energy column, no NR, no VAD): its cosine iDFT
 // (src/fea/fea_impl.cc:181-198) is the same contraction over the bands as the DCT and takes the same MFMA tail
 static bool lp_md_eligible(const Design &d) {
     const Opts &o = d.o;
-    return CTU_MD && CTU_LP_MD && (d.kind == FeaKind::Lpc || d.kind == FeaKind::Lpa) && o.fb_inld && o.fea_lporder + 1 <= 16 && !o.nr_when_afterFB && !o.fea_E &&
+    return (d.kind == FeaKind::Lpc || d.kind == FeaKind::Lpa) && o.fb_inld && o.fea_lporder + 1 <= 16 && !o.nr_when_afterFB && !o.fea_E &&
            o.fb_power && o.remove_dc && !o.remove_dc1 && !d.signal_out && !o.do_vad() && o.nr_mode == "none";
 }
 bool md_eligible(const Design &d) {
     // (the *ss modes on another window than the presets' run the run-time-flag instantiation, which has no MFMA tail)
-    return (CTU_MD && plain_cepstral(d) && (!d.o.do_vad() || vf_eligible(d)) && !(ss_mode_of(d.o) && !fused_frame_shape(d))) || lp_md_eligible(d);
+    return (plain_cepstral(d) && (!d.o.do_vad() || vf_eligible(d)) && !(ss_mode_of(d.o) && !fused_frame_shape(d))) || lp_md_eligible(d);
 }
 // hwss / fwss / 2fwss with the Burg cepstral detector (frontend_kernel<..., SS>): 25 ms frames at 8 or 16 kHz, the
 // presets' 12 cepstral coefficients for the detector, the plain chain into cepstra or band energies
@@ -387,7 +387,7 @@ int ss_mode_of(const Opts &o) { return o.nr_mode == "hwss" ? 1 : o.nr_mode == "f
 static bool ss_signal_eligible(const Design &d) {
     const Opts &o = d.o;
     const bool det_ok = (o.vadmode == "burg" && o.fea_ncepcoefs >= 2 && o.fea_ncepcoefs <= SS_NC) || o.vadmode == "file";
-    return CTU_SY && d.signal_out && ss_mode_of(o) && det_ok && ss_frame_shape(d) && o.remove_dc && !o.remove_dc1 && !o.rasta && !o.do_vad();
+    return d.signal_out && ss_mode_of(o) && det_ok && ss_frame_shape(d) && o.remove_dc && !o.remove_dc1 && !o.rasta && !o.do_vad();
 }
 bool ss_eligible(const Design &d) {
     const Opts &o = d.o;
@@ -400,7 +400,7 @@ bool ss_eligible(const Design &d) {
     const bool det_ok = (o.vadmode == "burg" && o.fea_ncepcoefs >= 2 && o.fea_ncepcoefs <= SS_NC) || o.vadmode == "file";
     // CMVN is two passes over the list in the reference (statistics, then the rows): the second starts from the noise vector the first
     // left behind, and no oracle restates that - refused rather than guessed
-    return CTU_MD && ss_mode_of(o) && det_ok && !o.nr_when_afterFB && ss_frame_shape(d) && kind_ok && o.remove_dc && !o.remove_dc1 && !o.do_vad() && !d.signal_out && !o.rasta &&
+    return ss_mode_of(o) && det_ok && !o.nr_when_afterFB && ss_frame_shape(d) && kind_ok && o.remove_dc && !o.remove_dc1 && !o.do_vad() && !d.signal_out && !o.rasta &&
            !o.stat_cmvn && !o.apply_cmvn;
 }
 

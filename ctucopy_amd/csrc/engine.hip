@@ -279,12 +279,11 @@ void lift(int v, F &&f) {
 // `xs`: the launch of a stream set with noise or subtraction state (frontend_kernel<..., XS>; the generic walk: the same rows bit for bit).
 // (with detector state as well: the fused Burg-cepstral criterion behind exten, C4's front end - its cepstra go to the scratch by frame, nothing of it runs along a file)
 // (with signal state: the one instantiation per (NZ, MODE) a speech-output design runs on - FEAT_BANDS, 16 coefficient rows, GEN_FULL,
-// with SY, or in a build without it (CTU_SY=0) with VX ahead of synth_kernel.  VX stays out otherwise: the VAD's export is not carried
-// behind exten's state, and streams_unsupported_reason refuses those configurations)
-constexpr bool fe_streamed_signal(const FeSel &k) { return k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL && !k.vf && !k.ss && (CTU_SY ? k.sy && !k.vx : k.vx && !k.sy); }
+// with SY.  VX stays out: the VAD's export is not carried behind exten's state, and streams_unsupported_reason refuses those configurations)
+constexpr bool fe_streamed_signal(const FeSel &k) { return k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL && !k.vf && !k.ss && k.sy && !k.vx; }
 // (with subtraction state: the twin of every feature-path *ss instantiation - a set runs the engine's own instantiation plus the state traffic)
 // (with signal state as well: the twin of the one speech-output *ss instantiation per mode, FEAT_BANDS, 16 coefficient rows, GEN_FULL)
-constexpr bool fe_streamed_ss(const FeSel &k) { return k.ss && !k.vx && !k.vf && (!k.sy || (CTU_SY && k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL)); }
+constexpr bool fe_streamed_ss(const FeSel &k) { return k.ss && !k.vx && !k.vf && (!k.sy || (k.feat == FEAT_BANDS && k.nc == 16 && k.gen == GEN_FULL)); }
 constexpr bool fe_streamed(const FeSel &k) { return fe_streamed_signal(k) || fe_streamed_ss(k) || (!k.vx && !k.ss && !k.sy && (k.gen == GEN_EXTEN || (k.gen == GEN_FULL && !k.vf))); }
 void launch_frontend(ctu_engine *e, dim3 grid, hipStream_t s, const KParams &kp, bool xs = false) {
     const FeSel &k = e->tab.sel;
@@ -346,7 +345,7 @@ KParams engine_kparams(const ctu_engine *e) {
     kp.band_to_scratch = d.kind == ctu::FeaKind::TrapDct ? 1 : e->tab.dctw ? 2 : 0;  // 2: the bands to the scratch, the energy column (-fea_E) to its slot of the row
     kp.lp_is_lpa = d.kind == ctu::FeaKind::Lpa;
     kp.syn_scale = 1.0f / (float)d.wfft;
-    kp.vad_export = (signal && !e->tab.sel.sy) ? 1 : ((!e->geom.do_vad || e->tab.sel.vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0)));
+    kp.vad_export = (!e->geom.do_vad || e->tab.sel.vf || signal) ? 0 : (e->vp.cri == 1 ? 1 : (e->vp.cri == 0 ? 2 : 0));
     kp.vad_nc = e->vp.ncoef;
     kp.ss_mode = e->tab.ss; kp.ss_init = d.o.nr_initsegs; kp.ss_nc = d.o.fea_ncepcoefs; kp.han_off = t.han_off;
     kp.nr_b = (float)d.o.nr_b; kp.ss_q = d.o.nr_q;
@@ -569,7 +568,7 @@ int run_ss_chain(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStrea
     }
     for (int iter = 0;; iter++) {
         // the detector never sees a subtracted spectrum (nr.cc:278-295): its decisions are those of the first pass
-        kp.ss_cached = e->tab.ss_file ? 1 : (iter > 0 ? CTU_SS_CACHE : 0);
+        kp.ss_cached = e->tab.ss_file || iter > 0;
         HIP_TRY(hipMemcpyAsync(pl->ss_seed.p, seed.data(), nk * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(pl->ss_dirty.p, dirty.data(), dirty.size(), hipMemcpyHostToDevice, s));
         pass();
@@ -644,9 +643,9 @@ void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
     const int tl = d.o.fea_trapdct_traplen, nd = d.o.fea_trapdct_ndct;
     const int ns = (tl + 3) / 4;
     if (e->tab.trap_bf16) {
-        constexpr int NT16 = CTU_TRAP_F16 ? 2 : 3;
+        constexpr int NT16 = 2;  // fp16 terms per value (trap_kernel.h)
         const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16;
-        hipLaunchKernelGGL((trapdct_split16_kernel<CTU_TRAP_F16 != 0>), dim3(std::max(pl->hp.n_chunks128, 1)), dim3(512), shm16, s,
+        hipLaunchKernelGGL(trapdct_split16_kernel, dim3(std::max(pl->hp.n_chunks128, 1)), dim3(512), shm16, s,
                            pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->hp.n_chunks128, d.B, nd, d.D);
     } else {
         const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float);
@@ -724,8 +723,7 @@ void stage_cms(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) 
 // The fused path left the lattice's output of every frame behind: the coefficient recursion and a -> c one frame per lane,
 // then the detector's recurrences, sixteen utterances per wave
 void stage_fused_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipStream_t s, uint8_t *d_vad, bool replay) {
-    if (CTU_VF_A2C)
-        hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((x.total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)x.total_frames);
+    hipLaunchKernelGGL((vad_a2c_kernel<VF_NC>), dim3((unsigned)((x.total_frames + 255) / 256)), dim3(256), 0, s, pl->vad_cf.p, (int64_t)x.total_frames);
     if (replay) lift<0, 1, 2, 3>(e->vp.thr, [&](auto thr) {
         hipLaunchKernelGGL((vad_lanes_kernel<VF_NC, decltype(thr)::value>), dim3((pl->hp.n_live + 15) / 16), dim3(64), 0, s, pl->vad_cf.p, pl->vf_order.p, pl->hp.n_live,
                            pl->d_row_off.p, d_vad, e->vp);
@@ -1523,12 +1521,7 @@ int ctu_engine_run_signal(ctu_engine *e, const ctu_plan *pl, const int16_t *d_pc
         sp.K = d.K; sp.wfft = d.wfft; sp.window = d.window; sp.wshift = d.wshift;
         sp.inv_n = 1.0f / (float)d.wfft;
         sp.corr = d.ola_corr;
-        if (pl->ext.total_frames > 0 && e->tab.big) launch_bigsynth(e, pl, pl->ext, s, sp.inv_n);
-        else if (pl->ext.total_frames > 0 && !e->tab.sel.sy) {
-            const int g = (int)std::min<int64_t>((pl->ext.total_frames + 7) / 8, (int64_t)e->n_cu * 8);
-            hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)pl->ext.total_frames, sp);
-            HIP_TRY(hipGetLastError());
-        }
+        if (pl->ext.total_frames > 0 && e->tab.big) launch_bigsynth(e, pl, pl->ext, s, sp.inv_n);  // (below 1024 points the front end's SY instantiations wrote the frames)
         int64_t longest = 0;
         for (int64_t n : pl->hp.out_samples) longest = std::max(longest, n);
         const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((longest + 255) / 256, 64));

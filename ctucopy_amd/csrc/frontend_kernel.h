@@ -18,10 +18,7 @@ static_assert(paircol_macro_rows_are_the_maps(), "CTU_ADDTID16_PC / CTU_READ2_PA
 
 // NZ = number of 32-sample rows that can hold non-zero input (ceil(window/32)); rows >= NZ are
 // literal zeros so the compiler prunes the first butterflies.
-#ifndef CTU_STAMP
-#define CTU_STAMP 0     // diagnostic build: per-wave s_memtime sums per code segment (never in production)
-#endif
-#if CTU_STAMP
+#if CTU_STAMP  // (layout_constants.h)
 #define STAMP(i)                                                                                   \
     do {                                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -33,24 +30,6 @@ static_assert(paircol_macro_rows_are_the_maps(), "CTU_ADDTID16_PC / CTU_READ2_PA
     } while (0)
 #else
 #define STAMP(i) do { } while (0)
-#endif
-#ifndef CTU_PK
-#define CTU_PK 1        // 1: DUAL with the two passes in the halves of packed registers (v_pk_*_f32 for all of phase 1's arithmetic); 0: scalar lock step (round 3)
-#endif
-#ifndef CTU_ABL
-#define CTU_ABL 0       // diagnostic builds only (wrong results): bit 0 no lane-0 selects in the untangle, 1 no mean removal, 2 no imaginary
-#endif                  // transpose, 3 no mirror fetch, 4 no P stores of the mirror half, 5 no inter-stage twiddles, 6 no phase 2, 7 no second DFT: what a unit of VALU / LDS work costs
-#ifndef CTU_CAP_WAVES
-#define CTU_CAP_WAVES 1  // 0: the front end's instantiations may run more waves per SIMD than the launch is laid out for (A/B)
-#endif
-#ifndef CTU_VF8
-#define CTU_VF8 1  // 0: the fused VAD criterion of the 256-point mode as two lattices of 16 lanes x 13 samples (A/B)
-#endif
-#ifndef CTU_BURG_UNROLL2
-#define CTU_BURG_UNROLL2 0  // 1: the two lattices of a 16-lane group unrolled into one block (the scheduler may interleave them)
-#endif
-#ifndef CTU_EXTEN_F64
-#define CTU_EXTEN_F64 0 // 1: exten state (Navg, Yavg) and its update in double.  Measured (tools/probes/sweep_err.py, exten_err.py): no accuracy gain - the residual is fp32 FFT noise amplified where a bin is almost fully suppressed - and -30 % throughput
 #endif
 
 // MODE 0: 512-point real FFT, one frame per 16-lane group, NZ = rows of 32 samples, two passes of 4 frames.
@@ -95,7 +74,7 @@ static_assert(paircol_macro_rows_are_the_maps(), "CTU_ADDTID16_PC / CTU_READ2_PA
 //         leave by frame for the set's overlap-add (stream_signal_kernels.h); what runs along the file inside the kernel is exten's
 //         state alone.  gfx950, hipcc -O3, from the code object's metadata: MODE 1 (NZ 13 and 16) 137 VGPRs, 106 SGPRs, MODE 0 (NZ 13
 //         and 16) 177 VGPRs, 106 SGPRs - the VGPRs of the offline SY instantiations; 48 / 60 SGPRs are kept in VGPR lanes (offline:
-//         36 / 52); no VGPR spills, no scratch.  (A build with CTU_SY=0 takes the VX form of the same instantiation ahead of synth_kernel.)
+//         36 / 52); no VGPR spills, no scratch.
 //         With SS (a set with subtraction state, CTU_STREAMS_SS_STATE): the twin of every feature-path SS instantiation (no SY) - the noise
 //         estimate(s) and the detector's record of hwss / fwss / 2fwss travel as exten's state does (xss_slot below; the slot's layout:
 //         xs_ss_floats, layout_constants.h), every file starts from the zero seed, and neither ss_seed, ss_last nor ss_dirty is touched.
@@ -104,8 +83,8 @@ static_assert(paircol_macro_rows_are_the_maps(), "CTU_ADDTID16_PC / CTU_READ2_PA
 //         With SS and SY (a set with both, CTU_STREAMS_SS_SIGNAL_STATE): the twin of the one speech-output SS instantiation per MODE,
 //         <13, FEAT_BANDS, MODE, no VX, 16, GEN_FULL, SS, SY, XS>.  Nothing of its own: the slot traffic is the feature path's, the frames
 //         leave by frame as behind exten, and ss_last with its Nyquist sign flip - the next file's seed - is compiled out.
-// (fe_waves_per_simd, the waves per SIMD an instantiation is compiled for, and its switches CTU_LB / CTU_SY_LB / CTU_VF1_LB: layout_constants.h)
-// (fe_dual, the DUAL instantiations of phase 1 below, and its switch CTU_DUAL: layout_constants.h - tables.cc halves their window table)
+// (fe_waves_per_simd, the waves per SIMD an instantiation is compiled for, and its values FE_LB / FE_SY_LB: layout_constants.h)
+// (fe_dual, the DUAL instantiations of phase 1 below: layout_constants.h - tables.cc halves their window table)
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
 template <class F, int... S>
@@ -118,13 +97,11 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 template <int NZ, int FEAT, int MODE, bool VX, int NC, int GEN, int LPO = 0, bool MD = false, bool VF = false, bool SS = false, bool SY = false, class WALK = walk_generic, bool XS = false>
-#if CTU_CAP_WAVES
 // also the MOST waves per SIMD the register file is laid out for: a workgroup is eight waves and the grid is at most two workgroups per
 // CU (engine.hip: max_wg), i.e. four per SIMD when they are dealt evenly.  An instantiation that needs 96 registers or fewer would be
 // allowed five or six, and the dispatcher then fills SIMDs unevenly with the same sixteen waves (measured: the exten chains, which last
 // as long as their slowest wave, +22 .. +40 % when the kernel dropped from 97 to 96 registers)
 __attribute__((amdgpu_waves_per_eu(fe_waves_per_simd(MODE, VF, SS, SY), fe_waves_per_simd(MODE, VF, SS, SY))))
-#endif
 __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void frontend_kernel(const KParams p) {
     constexpr bool FULL = GEN == GEN_FULL || GEN == GEN_DC1;  // GEN_DC1 = GEN_FULL plus -remove_dc1 (its offsets cost registers the others need)
     static_assert(!MD || ((FEAT == FEAT_DCTC || FEAT == FEAT_LP) && NC == 16), "MD: DCT / cosine-iDFT tail with 16 coefficient rows");
@@ -169,37 +146,25 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
     unsigned long long st_acc[16] = {0}, st_prev;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
 #endif
-#ifdef CTU_PRIO  // experiment: static priority for the later-dispatched half of the workgroup (waves 4-7)
-    if (wave >= 4) __builtin_amdgcn_s_setprio(CTU_PRIO);
-#endif
-#ifdef CTU_STAGGER  // experiment: half of the waves start late, so that partners on a SIMD sit in different phases of a step
-    if (CTU_STAGGER_SEL) {
-        for (int i = 0; i < CTU_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     int tile = as_const(p.wg_first)[per_wave ? blockIdx.x * NWAVE + wave : blockIdx.x];
     if (tile < 0) return;
     TileRec rec = load_rec(p.tiles, tile);
 
     // exten NR state (src/nr/nr.cc:86-93): lane = bin (bin = lane + 64 j), carried along the wave's utterance
     constexpr int NJ = MODE == 1 ? 3 : 5;  // ceil(K / 64): K = 129 / 257
-#if CTU_EXTEN_F64
-    typedef double xstate_t;
-#else
-    typedef float xstate_t;
-#endif
-    xstate_t navg[NJ], yavg[NJ];
+    // exten's state in float (in double: no accuracy gain - the residual is fp32 FFT noise amplified where a bin is almost fully suppressed - and -30 % throughput)
+    float navg[NJ], yavg[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
-        navg[j] = (xstate_t)0.95;
-        yavg[j] = (xstate_t)0.05;
+        navg[j] = 0.95f;
+        yavg[j] = 0.05f;
     }
     // XS: the chain is one of whole streams (engine.hip: ctu_streams_push).  The state of a stream comes from its slot of p.xstate when
     // the wave enters the first tile the stream has in this launch - unless that tile starts a file - and goes back behind the last
     // one; between the tiles of a stream it stays in registers, as it does along an utterance.  Lane = bin: every access is a dword per
     // lane, 256 contiguous bytes per wave; the floats travel as they stand, so a save and restore is exact.
     bool xs_first = true;  // the tile at hand is the first its stream has in this launch
-    auto xs_slot = [&](int t) { return uniform_ptr(reinterpret_cast<xstate_t *>(p.xstate) + (size_t)as_const(p.tile_utt)[t] * (2 * 64 * NJ)); };
+    auto xs_slot = [&](int t) { return uniform_ptr(reinterpret_cast<float *>(p.xstate) + (size_t)as_const(p.tile_utt)[t] * (2 * 64 * NJ)); };
 
     // -remove_dc1: ov[0] = o_t, ov[j] = o_{t-j} of one frame; what position i of the frame has had subtracted so far
     constexpr int DCJ = 8;
@@ -252,9 +217,9 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         // not by issue.  Every instantiation of the plain chain and of the plain chain + intensity-loudness law (round 4; rounds 2-3: the
         // headline instantiation only): phase 1 does not depend on the feature tail.
         constexpr bool DUAL = fe_dual(NZ, MODE, VX, GEN, VF, SS, SY);
-        if constexpr (DUAL && CTU_PK) {
+        if constexpr (DUAL) {
             // The two passes as the two halves of packed registers: every add / multiply / FMA of phase 1 is a v_pk_*_f32 that
-            // serves slots 0-3 and 4-7 together (kernel_common.h: cx2).  Same statements as the scalar DUAL block below.
+            // serves slots 0-3 and 4-7 together (kernel_common.h: cx2).
             if (nv > 0) {
                 cx2 v[16];
                 const int f0 = slot0 + fg, f1 = f0 + 4;
@@ -307,7 +272,6 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     v[2 * h + 1] = cmul_s(v[2 * h + 1], tw.x, tw.y);
                     if (2 * h + 2 < 16) v[2 * h + 2] = cmul_s(v[2 * h + 2], tw.z, tw.w);
                 }
-#if CTU_PAIRCOL
                 // Stage 2 on column pairs (paircol_map.h): from here on the lane is (frame slot f8 = 4 pass + fg, pair p) and the halves of
                 // every register pair are the frame's mirror columns c_lo(p) | c_hi(p), so the untangle finds Z[256 - k] in its own lane.
                 const int pc_p = paircol::lane_p(lane);
@@ -356,8 +320,8 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                         const v2f ar = v[k2].x, ai = v[k2].y;
                         const v2f sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
                         // tr = di * wr + dr * wi, ti = di * wi - dr * wr, |u|^2 and |v|^2 with the one product and the one FMA of each stated:
-                        // which of two products the compiler fuses is its choice, and the block below (CTU_PAIRCOL = 0) compiles in every
-                        // instantiation to these - fma(dr, wi, di wr), fma(di, wi, -(dr wr)), fma(re, re, im im) - so the rows agree to the bit
+                        // which of two products the compiler fuses would be its choice otherwise - fma(dr, wi, di wr), fma(di, wi, -(dr wr)),
+                        // fma(re, re, im im) are what the layout before this one compiled to, so the rows agree with its rows to the bit
                         const v2f tr = {__builtin_fmaf(dr.x, wi0, di.x * wr0), __builtin_fmaf(dr.y, wi1, di.y * wr1)};
                         const v2f ti = {__builtin_fmaf(di.x, wi0, -(dr.x * wr0)), __builtin_fmaf(di.y, wi1, -(dr.y * wr1))};
                         const v2f ur = sr + tr, ui = si + ti, vr = sr - tr, vi = si - ti;
@@ -374,188 +338,6 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                         pk_lo[128] = p128.x;  // (lane p = 0: pk_lo is the row itself - no fifth address register)
                         pk_lo[0] = 1e-10f;
                     }
-                }
-#else
-                {   // both transposes at once through the wave's eight rows (layout: CTU_ADDTID16_P)
-                    const uint32_t sa = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lvoid_t *)Pw);
-                    const uint32_t rd = (uint32_t)(size_t)(lvoid_t *)(Pw + 129 * l16 + 16 * fg);
-#define CTU_E_XA(i) v[i].x.x
-#define CTU_E_XB(i) v[i].x.y
-#define CTU_E_YA(i) v[i].y.x
-#define CTU_E_YB(i) v[i].y.y
-                    __builtin_amdgcn_wave_barrier();
-                    CTU_ADDTID16_P(CTU_E_XA, sa, 0);
-                    CTU_ADDTID16_P(CTU_E_XB, sa, 256);
-                    v2f re[16], im[16];
-                    CTU_READ2_PAIRS16(re, rd);
-                    CTU_ADDTID16_P(CTU_E_YA, sa, 0);
-                    CTU_ADDTID16_P(CTU_E_YB, sa, 256);
-                    CTU_READ2_PAIRS16(im, rd);
-#pragma unroll
-                    for (int n2 = 0; n2 < 16; n2++) v[n2] = cx2{re[n2], im[n2]};
-                    __builtin_amdgcn_wave_barrier();
-#undef CTU_E_XA
-#undef CTU_E_XB
-#undef CTU_E_YA
-#undef CTU_E_YB
-                }
-                dft16(v);
-                float *pr0 = Pw + fg * PSTRIDE, *pr1 = Pw + (4 + fg) * PSTRIDE;
-#pragma unroll
-                for (int k2 = 0; k2 < 8; k2++) {
-                    const float4 u4q = ltw4[8 + (k2 >> 1)];
-                    const float wr = (k2 & 1) ? u4q.z : u4q.x, wi = (k2 & 1) ? u4q.w : u4q.y;
-                    const int k = l16 + 16 * k2;
-                    v2f br = {mirror_fetch(v[15 - k2].x.x, partner), mirror_fetch(v[15 - k2].x.y, partner)};
-                    v2f bi = {mirror_fetch(v[15 - k2].y.x, partner), mirror_fetch(v[15 - k2].y.y, partner)};
-                    if (l16 == 0) {
-                        br = v[(16 - k2) & 15].x;
-                        bi = v[(16 - k2) & 15].y;
-                    }
-                    const v2f ar = v[k2].x, ai = v[k2].y;
-                    const v2f sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
-                    const v2f tr = di * wr + dr * wi;
-                    const v2f ti = di * wi - dr * wr;
-                    const v2f ur = sr + tr, ui = si + ti, vr = sr - tr, vi = si - ti;
-                    // the untangle's 1/4 is in the window (the engine scales this instantiation's table by 1/2: ctu_engine::half_window)
-                    const v2f pk = ur * ur + ui * ui, pm = vr * vr + vi * vi;
-                    pr0[k] = pk.x;
-                    pr1[k] = pk.y;
-                    pr0[256 - k] = pm.x;
-                    pr1[256 - k] = pm.y;
-                }
-                if (l16 == 0) {  // bin 128 is its own mirror (no 1/4 there: the halved window is undone); bin 0 floor (src/io/in.cc:390)
-                    const v2f a = v[8].x * 2.f, b = v[8].y * 2.f;
-                    const v2f p128 = a * a + b * b;
-                    pr0[128] = p128.x;
-                    pr1[128] = p128.y;
-                    pr0[0] = pr1[0] = 1e-10f;
-                }
-#endif  // CTU_PAIRCOL
-            }
-        } else
-        if constexpr (DUAL) {
-            if (nv > 0) {
-                float2 v0[16], v1[16];
-                const int f0 = slot0 + fg, f1 = f0 + 4;
-                const int c0 = f0 < nvalid ? f0 : nvalid - 1, c1 = f1 < nvalid ? f1 : nvalid - 1;  // duplicates are never stored
-                const bool st0 = (l16 == 0) && (rec.t0 + c0 == 0), st1 = (l16 == 0) && (rec.t0 + c1 == 0);
-                {
-                    const int16_t *x0p = p.pcm + rec.sbase + (int64_t)c0 * p.wshift + 2 * l16 - 2;
-                    const int16_t *x1p = p.pcm + rec.sbase + (int64_t)c1 * p.wshift + 2 * l16 - 2;
-                    pcm4 q0[NZ], q1[NZ];
-#pragma unroll
-                    for (int j = 0; j < NZ; j++) q0[j] = *reinterpret_cast<const pcm4 *>(x0p + 32 * j);
-#pragma unroll
-                    for (int j = 0; j < NZ; j++) q1[j] = *reinterpret_cast<const pcm4 *>(x1p + 32 * j);
-                    float dc0 = 0.f, dc1 = 0.f;
-#pragma unroll
-                    for (int j = 0; j < NZ; j++) {
-                        const float4 w4 = lc[(LC_WIN + 2 * j) >> 2];  // two rows of window pairs per float4
-                        const float w0 = (j & 1) ? w4.z : w4.x, w1 = (j & 1) ? w4.w : w4.y;
-                        float am = (float)(int16_t)(q0[j].lo >> 16), bm = (float)(int16_t)(q1[j].lo >> 16);
-                        const float a0 = (float)(int16_t)(q0[j].hi & 0xffffu), a1 = (float)(int16_t)(q0[j].hi >> 16);
-                        const float b0 = (float)(int16_t)(q1[j].hi & 0xffffu), b1 = (float)(int16_t)(q1[j].hi >> 16);
-                        if (j == 0) {  // first sample of the file: history is 0
-                            am = st0 ? 0.f : am;
-                            bm = st1 ? 0.f : bm;
-                        }
-                        const float ya0 = w0 * (a0 - p.preem * am), ya1 = w1 * (a1 - p.preem * a0);
-                        const float yb0 = w0 * (b0 - p.preem * bm), yb1 = w1 * (b1 - p.preem * b0);
-                        v0[j] = make_float2(ya0, ya1);
-                        v1[j] = make_float2(yb0, yb1);
-                        dc0 += ya0 + ya1;
-                        dc1 += yb0 + yb1;
-                    }
-#pragma unroll
-                    for (int j = NZ; j < 16; j++) v0[j] = v1[j] = make_float2(0.f, 0.f);
-                    // mean of the windowed frame over `window` samples (src/io/in.cc:375-382); rows < NZ-1 are fully inside
-                    const float m0 = row16_allreduce_add(dc0) * p.inv_window, m1 = row16_allreduce_add(dc1) * p.inv_window;
-                    const float4 mk = lc[(LC_MASK + 2 * (NZ - 1)) >> 2];
-                    const float mx = ((NZ - 1) & 1) ? mk.z : mk.x, my = ((NZ - 1) & 1) ? mk.w : mk.y;
-#pragma unroll
-                    for (int j = 0; j < ((CTU_ABL & 2) ? 1 : NZ - 1); j++) {
-                        v0[j].x -= m0;
-                        v0[j].y -= m0;
-                        v1[j].x -= m1;
-                        v1[j].y -= m1;
-                    }
-                    v0[NZ - 1].x -= m0 * mx;
-                    v0[NZ - 1].y -= m0 * my;
-                    v1[NZ - 1].x -= m1 * mx;
-                    v1[NZ - 1].y -= m1 * my;
-                }
-                dft16(v0);
-                dft16(v1);
-#pragma unroll
-                for (int h = 0; h < ((CTU_ABL & 32) ? 1 : 8); h++) {
-                    const float4 tw = ltw4[h];  // (k1 = 2h+1, k1 = 2h+2)
-                    v0[2 * h + 1] = cmul(v0[2 * h + 1], make_float2(tw.x, tw.y));
-                    v1[2 * h + 1] = cmul(v1[2 * h + 1], make_float2(tw.x, tw.y));
-                    if (2 * h + 2 < 16) {
-                        v0[2 * h + 2] = cmul(v0[2 * h + 2], make_float2(tw.z, tw.w));
-                        v1[2 * h + 2] = cmul(v1[2 * h + 2], make_float2(tw.z, tw.w));
-                    }
-                }
-#ifdef CTU_PAD_SALU  // diagnostic builds: what N more scalar / vector / LDS instructions per step cost (results unchanged)
-                {
-                    uint32_t pad_ = 0;
-                    asm volatile(".rept %c1\n\ts_add_u32 %0, %0, 1\n\t.endr" : "+s"(pad_) : "n"(CTU_PAD_SALU) : "scc");
-                }
-#endif
-#ifdef CTU_PAD_VALU
-                {
-                    float pad_ = 0.f;
-                    asm volatile(".rept %c1\n\tv_add_f32 %0, %0, %0\n\t.endr" : "+v"(pad_) : "n"(CTU_PAD_VALU));
-                }
-#endif
-#ifdef CTU_PAD_LDS
-                {
-                    f32x4 pad_;
-                    asm volatile(".rept %c2\n\tds_read_b128 %0, %1\n\t.endr\n\ts_waitcnt lgkmcnt(0)" : "=&v"(pad_) : "v"((uint32_t)(size_t)(lvoid_t *)(ltw + 4 * lane)), "n"(CTU_PAD_LDS) : "memory");
-                }
-#endif
-                float *pr0 = Pw + fg * PSTRIDE, *pr1 = Pw + (4 + fg) * PSTRIDE;
-                auto untangle = [&](const float2 (&v)[16], float *prow, int k2, float wr, float wi) {
-                    const int k = l16 + 16 * k2;
-                    float br = (CTU_ABL & 8) ? v[15 - k2].x : mirror_fetch(v[15 - k2].x, partner);
-                    float bi = (CTU_ABL & 8) ? v[15 - k2].y : mirror_fetch(v[15 - k2].y, partner);
-                    if (!(CTU_ABL & 1) && l16 == 0) {
-                        br = v[(16 - k2) & 15].x;
-                        bi = v[(16 - k2) & 15].y;
-                    }
-                    const float ar = v[k2].x, ai = v[k2].y;
-                    const float sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
-                    const float tr = wr * di + wi * dr;
-                    const float ti = wi * di - wr * dr;
-                    const float ur = sr + tr, ui = si + ti, vr = sr - tr, vi = si - ti;
-                    // the untangle's 1/4 is in the window (the engine scales this instantiation's table by 1/2: ctu_engine::half_window)
-                    if (CTU_ABL & 16) prow[k] = (ur * ur + ui * ui) + (vr * vr + vi * vi);
-                    else {
-                        prow[k] = ur * ur + ui * ui;
-                        prow[256 - k] = vr * vr + vi * vi;
-                    }
-                };
-                // both transposes at once: slots 0-3 through the wave's rows 0-3, slots 4-7 through rows 4-7 (their own
-                // spectra land there afterwards)
-                wave_transpose16_dual(v0, v1, (uint32_t)(size_t)(lvoid_t *)Pw, (uint32_t)(size_t)(lvoid_t *)scratch,
-                                      Pw + 65 * l16 + 16 * fg, scratch + 65 * l16 + 16 * fg);
-                if (!(CTU_ABL & 128)) {
-                    dft16(v0);
-                    dft16(v1);
-                }
-#pragma unroll
-                for (int k2 = 0; k2 < 8; k2++) {
-                    const float4 u4q = ltw4[8 + (k2 >> 1)];
-                    const float wr = (k2 & 1) ? u4q.z : u4q.x, wi = (k2 & 1) ? u4q.w : u4q.y;
-                    untangle(v0, pr0, k2, wr, wi);
-                    untangle(v1, pr1, k2, wr, wi);
-                }
-                if (l16 == 0) {  // bin 128 is its own mirror (no 1/4 there: the halved window is undone); bin 0 floor (src/io/in.cc:390)
-                    const float a0 = 2.f * v0[8].x, b0 = 2.f * v0[8].y, a1 = 2.f * v1[8].x, b1 = 2.f * v1[8].y;
-                    pr0[128] = a0 * a0 + b0 * b0;
-                    pr1[128] = a1 * a1 + b1 * b1;
-                    pr0[0] = pr1[0] = 1e-10f;
                 }
             }
         } else
@@ -809,8 +591,8 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
             typedef std::remove_reference_t<decltype(out[0])> real_t;  // float, or double for the *ss detector (vad_fused.h)
             // the VAD module's criterion (no Hann window, float): the lattice only - {alpha, k_m} go to the scratch rows and
             // vad_a2c_kernel finishes the cepstra one frame per lane; the *ss detector needs its cepstra here and now
-            constexpr bool rc_only = CTU_VF_A2C && !decltype(HANN)::value && sizeof(real_t) == 4;
-            constexpr bool VF8 = CTU_VF8 && MODE == 1 && !decltype(HANN)::value && sizeof(real_t) == 4;
+            constexpr bool rc_only = !decltype(HANN)::value && sizeof(real_t) == 4;
+            constexpr bool VF8 = MODE == 1 && !decltype(HANN)::value && sizeof(real_t) == 4;
             // the *ss detector of the run-time-flag instantiations takes the window at run time too (any window the lanes' 13 / 25 samples
             // cover: up to 208 / 400): the lane and register of the window's last sample are looked up per order instead of being named
             constexpr bool RTW = decltype(HANN)::value && GEN == GEN_FULL;
@@ -852,9 +634,6 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                 out[0] = cc[0];  // lane 8 f + i: entries i and i + 8 of frame slot f
                 out[1] = cc[1];
             } else
-#if CTU_BURG_UNROLL2
-#pragma unroll
-#endif
             for (int xb = 0; xb < 2; xb++) {  // frame A, then frame B of this 16-lane group
                 const float *tx = Pw + (2 * fg + xb) * VF_FSTRIDE + VF_SPL * l16;
                 float x[VF_SPL];
@@ -1062,8 +841,8 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
             if (rec.t0 == 0 && slot0 == 0 && f_lo == 0) {  // new file: Navg = 0.95, Yavg = 0.05
 #pragma unroll
                 for (int j = 0; j < NJ; j++) {
-                    navg[j] = (xstate_t)0.95;
-                    yavg[j] = (xstate_t)0.05;
+                    navg[j] = 0.95f;
+                    yavg[j] = 0.05f;
                 }
             } else {
                 if constexpr (XS) {
@@ -1077,7 +856,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     }
                 }
             }
-            const xstate_t pp = (xstate_t)p.nr_p_d, qq = (xstate_t)1.0 - pp;
+            const float pp = (float)p.nr_p_d, qq = 1.0f - pp;
             // the next frame's values are read while this frame's recurrence runs (the chain goes through Navg / Yavg in
             // registers, not through LDS); bins beyond K read the row's padding / the next row: finite, never stored
             float Xn[NJ];
@@ -1096,38 +875,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
 #pragma unroll
                 for (int j = 0; j < NJ; j++) {
                     // H = Navg / (Navg^a + Yavg^a)^(1/a); the output X - H X is formed as X (1 - H) with 1 - H written
-                    // without cancellation.  Double state: the reciprocal root / reciprocal start from the float
-                    // instructions and take one Newton step in double.
-#if CTU_EXTEN_F64
-                    const double na = navg[j], ya = yavg[j], Xd = (double)X[j];
-                    double H, omH;
-                    if (p.nr_a == 1.0f) {
-                        const double s_ = na + ya;
-                        double ir = (double)__builtin_amdgcn_rcpf((float)s_);
-                        ir = ir * (2.0 - s_ * ir);
-                        ir = ir * (2.0 - s_ * ir);
-                        H = na * ir;
-                        omH = ya * ir;
-                    } else if (p.nr_a == 2.0f) {
-                        const double r2 = na * na + ya * ya;
-                        double ir = (double)__builtin_amdgcn_rsqf((float)r2);
-                        ir = ir * (1.5 - 0.5 * r2 * ir * ir);
-                        ir = ir * (1.5 - 0.5 * r2 * ir * ir);
-                        const double r = r2 * ir, dn = r * (r + na);
-                        double id = (double)__builtin_amdgcn_rcpf((float)dn);
-                        id = id * (2.0 - dn * id);
-                        id = id * (2.0 - dn * id);
-                        H = na * ir;
-                        omH = (ya * ya) * id;
-                    } else {
-                        H = na / pow(pow(na, (double)p.nr_a) + pow(ya, (double)p.nr_a), 1.0 / (double)p.nr_a);
-                        omH = 1.0 - H;
-                    }
-                    const double N = H * Xd;
-                    navg[j] = pp * na + qq * N;
-                    yavg[j] = fabs(Xd - navg[j]);
-                    X[j] = (float)(Xd * omH);
-#else
+                    // without cancellation.
                     float H, omH;
                     if (p.nr_a == 1.0f) {
                         const float ir = __builtin_amdgcn_rcpf(navg[j] + yavg[j]);
@@ -1147,7 +895,6 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                     navg[j] = pp * navg[j] + qq * N;
                     yavg[j] = fabsf(X[j] - navg[j]);
                     X[j] = X[j] * omH;
-#endif
                 }
 #pragma unroll
                 for (int j = 0; j < NJ; j++)
@@ -1242,7 +989,7 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
         // ================= phase 2 (wave-local): lane = (frame, band group) =================
         // The step's 8 frames x 8 band groups.  Bands are dealt to (slot, group) cells by the host so that the
         // 8 bands of a slot have similar widths; every group walks the same number of 4-bin chunks per slot.
-        if (o_dbg != 1 && !o_skip_phase2 && nv > 0 && !(CTU_ABL & 64)) {
+        if (o_dbg != 1 && !o_skip_phase2 && nv > 0) {
             // lane -> (frame f8, group g).  MD: lane = f8 + 8 h + 16 kk with g = kk + 4 h, the B-operand layout of the MFMA
             const int f8 = MD ? (lane & 7) : (lane >> 3), g = MD ? (((lane >> 3) & 1) * 4 + (lane >> 4)) : (lane & 7);
             const int fslot = slot0 + f8;
@@ -1537,17 +1284,17 @@ __global__ __launch_bounds__(WG, fe_waves_per_simd(MODE, VF, SS, SY)) void front
                 float mine_ab[2];
                 rebuild_cepstra(std::integral_constant<int, VF_NC>{}, std::false_type{}, mine_ab);
                 // the cepstra go to the scratch rows of their frames; vad_lanes_kernel replays the detector's recurrences with one
-                // utterance per lane (vad_kernels.h).  256-point mode: mine_ab[x] of lane 16 fg + i = coefficient i of frame slot
-                // 2 fg + x; 512-point mode: of frame slot 4 x + fg.
+                // utterance per lane (vad_kernels.h).  512-point mode: mine_ab[x] of lane 16 fg + i = coefficient i of frame slot
+                // 4 x + fg.
 #pragma unroll
                 for (int x = 0; x < 2; x++) {
-                    if constexpr (CTU_VF8 && MODE == 1) {  // lane 8 f + i: coefficients i and i + 8 of frame slot f
+                    if constexpr (MODE == 1) {  // lane 8 f + i: coefficients i and i + 8 of frame slot f
                         int ln = lane;
                         asm volatile("" : "+v"(ln));  // the lane's offset is two instructions: not worth a register across the whole step loop
                         const int sl = ln >> 3, ci = (ln & 7) + 8 * x;
                         if (sl < nv && ci < VF_NC) uniform_ptr(p.vad_cf + (rbase + slot0) * VFC_STRIDE)[(unsigned)(sl * VFC_STRIDE + ci)] = mine_ab[x];
                     } else {
-                        const int sl = MODE == 1 ? 2 * fg + x : 4 * x + fg;
+                        const int sl = 4 * x + fg;
                         if (sl < nv && l16 < VF_NC) uniform_ptr(p.vad_cf + (rbase + slot0) * VFC_STRIDE)[(unsigned)(sl * VFC_STRIDE + l16)] = mine_ab[x];
                     }
                 }

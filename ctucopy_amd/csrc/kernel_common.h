@@ -73,9 +73,6 @@ struct KParams {
     void *xstate;  // XS instantiations (a stream set with noise state): exten's Navg | Yavg of every stream, [n_streams][2][64 NJ]; tile_utt is then the stream of every tile.  With SS (a set with subtraction state): [n_streams][xs_ss_floats(NJ)], Navg | Nravg | the detector's record
 };
 
-#ifndef CTU_VF_A2C
-#define CTU_VF_A2C 1  // fused Burg-cepstral criterion: 1 = the front end stops at the lattice and vad_a2c_kernel finishes the cepstra (vad_fused.h); 0: the tail stays inside the front end (A/B)
-#endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));  // MFMA accumulator
 typedef int int32x4 __attribute__((ext_vector_type(4)));
 typedef int int32x2 __attribute__((ext_vector_type(2)));
@@ -194,50 +191,9 @@ __device__ __forceinline__ void dft16(cx2 (&v)[16]) {  // as dft16(float2[16]) a
                      : "memory");                                                                                                    \
     } while (0)
 
-// The same for sixteen arbitrary float expressions E(i), i = 0..15 (the halves of packed pairs), rows 516 bytes apart
-// starting OFF bytes behind BASE: the layout of the packed transpose with the passes in the halves through stage 2 as well
-// (frontend_kernel.h, CTU_PK with CTU_PAIRCOL = 0; the default build compiles CTU_ADDTID16_PC below instead) - row k1 of pass A at
-// dword 129 k1, of pass B at 129 k1 + 64, so that one ds_read2_b32 (offset0 = n2, offset1 = 64 + n2) returns the
-// (pass A, pass B) pair of an element into one register pair, and lane (k1, fg) reading dword 129 k1 + 16 fg + n2 meets
-// bank (k1 + 16 fg + n2) mod 32: distinct over each half wave.  16 x 129 dwords fit the wave's eight P rows (2080).
-#define CTU_ADDTID16_P(E, BASE, OFF)                                                                                                 \
-    do {                                                                                                                             \
-        uint32_t keep_;                                                                                                              \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %17\n\ts_nop 0\n\t"                                                         \
-                     "ds_write_addtid_b32 %1 offset:%c18\n\tds_write_addtid_b32 %2 offset:516+%c18\n\tds_write_addtid_b32 %3 offset:1032+%c18\n\t"  \
-                     "ds_write_addtid_b32 %4 offset:1548+%c18\n\tds_write_addtid_b32 %5 offset:2064+%c18\n\tds_write_addtid_b32 %6 offset:2580+%c18\n\t" \
-                     "ds_write_addtid_b32 %7 offset:3096+%c18\n\tds_write_addtid_b32 %8 offset:3612+%c18\n\tds_write_addtid_b32 %9 offset:4128+%c18\n\t" \
-                     "ds_write_addtid_b32 %10 offset:4644+%c18\n\tds_write_addtid_b32 %11 offset:5160+%c18\n\tds_write_addtid_b32 %12 offset:5676+%c18\n\t" \
-                     "ds_write_addtid_b32 %13 offset:6192+%c18\n\tds_write_addtid_b32 %14 offset:6708+%c18\n\tds_write_addtid_b32 %15 offset:7224+%c18\n\t" \
-                     "ds_write_addtid_b32 %16 offset:7740+%c18\n\ts_mov_b32 m0, %0"                                                        \
-                     : "=&s"(keep_)                                                                                                  \
-                     : "v"(E(0)), "v"(E(1)), "v"(E(2)), "v"(E(3)), "v"(E(4)), "v"(E(5)), "v"(E(6)), "v"(E(7)), "v"(E(8)), "v"(E(9)),   \
-                       "v"(E(10)), "v"(E(11)), "v"(E(12)), "v"(E(13)), "v"(E(14)), "v"(E(15)), "s"(BASE), "n"(OFF)                    \
-                     : "memory");                                                                                                    \
-    } while (0)
-
-// The sixteen (pass A, pass B) pairs of one component back from that layout: ds_read2_b32 with offset0 = n2, offset1 = 64 + n2
-// fills a register pair with the two passes' values (the compiler's own pairing of ds_read_b32s goes by adjacent addresses,
-// which would pair n2 with n2 + 1 and cost a move per value).  Inline assembly is invisible to the compiler's wait-count
-// insertion: the statement waits for its own reads.
-#define CTU_READ2_PAIRS16(R, ADDR)                                                                                                   \
-    asm volatile("ds_read2_b32 %0, %16 offset0:0 offset1:64\n\tds_read2_b32 %1, %16 offset0:1 offset1:65\n\t"                        \
-                 "ds_read2_b32 %2, %16 offset0:2 offset1:66\n\tds_read2_b32 %3, %16 offset0:3 offset1:67\n\t"                        \
-                 "ds_read2_b32 %4, %16 offset0:4 offset1:68\n\tds_read2_b32 %5, %16 offset0:5 offset1:69\n\t"                        \
-                 "ds_read2_b32 %6, %16 offset0:6 offset1:70\n\tds_read2_b32 %7, %16 offset0:7 offset1:71\n\t"                        \
-                 "ds_read2_b32 %8, %16 offset0:8 offset1:72\n\tds_read2_b32 %9, %16 offset0:9 offset1:73\n\t"                        \
-                 "ds_read2_b32 %10, %16 offset0:10 offset1:74\n\tds_read2_b32 %11, %16 offset0:11 offset1:75\n\t"                    \
-                 "ds_read2_b32 %12, %16 offset0:12 offset1:76\n\tds_read2_b32 %13, %16 offset0:13 offset1:77\n\t"                    \
-                 "ds_read2_b32 %14, %16 offset0:14 offset1:78\n\tds_read2_b32 %15, %16 offset0:15 offset1:79\n\t"                    \
-                 "s_waitcnt lgkmcnt(0)"                                                                                              \
-                 : "=&v"(R[0]), "=&v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]), "=&v"(R[8]), \
-                   "=&v"(R[9]), "=&v"(R[10]), "=&v"(R[11]), "=&v"(R[12]), "=&v"(R[13]), "=&v"(R[14]), "=&v"(R[15])                       \
-                 : "v"(ADDR)                                                                                                         \
-                 : "memory")
-
-// The pair-column layout of the packed transpose (frontend_kernel.h, CTU_PAIRCOL; every index map: paircol_map.h).  The stores are the
-// same sixteen add-TID stores per component and pass, linear in the stage-1 lane 16 fg + n2; only the row bases differ: rows 65 dwords
-// (260 bytes) apart, row 2 p for column c_lo(p) = p and row 2 p + 1 for its mirror column c_hi(p) = 16 - p (p = 0: columns 0 and 8),
+// The pair-column layout of the packed transpose (frontend_kernel.h, the DUAL block; every index map: paircol_map.h).  The same sixteen
+// add-TID stores for sixteen arbitrary float expressions E(i) (the halves of packed pairs), once per component and pass, linear in the
+// stage-1 lane 16 fg + n2, OFF bytes behind BASE: rows 65 dwords (260 bytes) apart, row 2 p for column c_lo(p) = p and row 2 p + 1 for its mirror column c_hi(p) = 16 - p (p = 0: columns 0 and 8),
 // pass B 1041 dwords behind pass A (OFF = 4164): 1041 + 15 x 65 + 64 = 2080 dwords, exactly the wave's eight P rows.
 // The row offsets below are paircol::store_byte(k1, 0), k1 = 0..15 (asserted beside the kernel).
 #define CTU_ADDTID16_PC(E, BASE, OFF)                                                                                                \
@@ -260,6 +216,8 @@ __device__ __forceinline__ void dft16(cx2 (&v)[16]) {  // as dft16(float2[16]) a
 // The sixteen (column c_lo, column c_hi) pairs of one component back from that layout: the stage-2 lane (frame slot f8, pair p) reads
 // from ADDR = the wave's rows + paircol::read_dword(lane) with offset0 = n2, offset1 = 65 + n2.  Over a half wave (pass, fg & 1, p) the
 // sixteen lanes of pass A start at the even banks 2 p + 16 (fg & 1), those of pass B at the odd banks 17 more; offset1 moves all by one.
+// (The compiler's own pairing of ds_read_b32s goes by adjacent addresses and would cost a move per value.  Inline assembly is invisible
+// to its wait-count insertion: the statement waits for its own reads.)
 #define CTU_READ2_PAIRCOL16(R, ADDR)                                                                                                 \
     asm volatile("ds_read2_b32 %0, %16 offset0:0 offset1:65\n\tds_read2_b32 %1, %16 offset0:1 offset1:66\n\t"                        \
                  "ds_read2_b32 %2, %16 offset0:2 offset1:67\n\tds_read2_b32 %3, %16 offset0:3 offset1:68\n\t"                        \
@@ -300,44 +258,6 @@ __device__ __forceinline__ void wave_transpose16(float2 (&v)[16], uint32_t sbase
     __builtin_amdgcn_wave_barrier();
 }
 
-// Two such transposes at once (two independent sets of 16 x 16 values, scratch areas sa / sb): the stores of both go out
-// before the reads of either, so the LDS round trips overlap.
-__device__ __forceinline__ void wave_transpose16_dual(float2 (&va)[16], float2 (&vb)[16], uint32_t sa, uint32_t sb, const float *rda,
-                                                      const float *rdb) {
-    sa = __builtin_amdgcn_readfirstlane(sa);
-    sb = __builtin_amdgcn_readfirstlane(sb);
-    __builtin_amdgcn_wave_barrier();
-    CTU_ADDTID16(va, x, sa);
-    CTU_ADDTID16(vb, x, sb);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    float rea[16], reb[16];
-#pragma unroll
-    for (int n2 = 0; n2 < 16; n2++) rea[n2] = rda[n2];
-#pragma unroll
-    for (int n2 = 0; n2 < 16; n2++) reb[n2] = rdb[n2];
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#if defined(CTU_ABL) && (CTU_ABL & 4)  // diagnostic: no imaginary transpose (wrong results)
-#pragma unroll
-    for (int n2 = 0; n2 < 16; n2++) {
-        va[n2] = make_float2(rea[n2], va[n2].y);
-        vb[n2] = make_float2(reb[n2], vb[n2].y);
-    }
-    return;
-#endif
-    CTU_ADDTID16(va, y, sa);
-    CTU_ADDTID16(vb, y, sb);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int n2 = 0; n2 < 16; n2++) va[n2] = make_float2(rea[n2], rda[n2]);
-#pragma unroll
-    for (int n2 = 0; n2 < 16; n2++) vb[n2] = make_float2(reb[n2], rdb[n2]);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // Wave-uniform tables are read through constant-address-space pointers so that they become scalar
 // loads (s_load_dword*) into SGPRs instead of per-lane VMEM loads.
 typedef __attribute__((address_space(4))) const float cf32;
@@ -373,19 +293,10 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
 }
-// The mirror-bin partner of the untangle steps: lane l of a 16-lane row reads lane (16 - l) & 15.  CTU_DPPMIRROR = 1:
-// row_mirror then row_ror:1 on the VALU (lane l <- mirror lane l-1 = original lane 16-l), no LDS crossbar cycles;
-// 0: ds_bpermute (`partner` = byte address of the source lane).
-#ifndef CTU_DPPMIRROR
-#define CTU_DPPMIRROR 0
-#endif
+// The mirror-bin partner of the untangle steps: lane l of a 16-lane row reads lane (16 - l) & 15 by ds_bpermute
+// (`partner` = byte address of the source lane).
 __device__ __forceinline__ float mirror_fetch(float x, int partner) {
-#if CTU_DPPMIRROR
-    (void)partner;
-    return dpp_mov<0x121>(dpp_mov<0x140>(x));
-#else
     return __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(x)));
-#endif
 }
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double x) {

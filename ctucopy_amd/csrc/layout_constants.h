@@ -1,48 +1,18 @@
 // Every constant, enum and build switch that host-only code shares with the kernels: plain C++, no HIP.
 // Included by kernel_common.h (the kernels), by accept.cc / tables.cc (what is accepted, which instantiation runs, what the tables
 // hold), by plan_host.h / plan.cc (the plan of an offline run) and by stream_plan.h (the push planner); all of these but the kernels
-// compile without hipcc.  The kernel headers define none
-// of these themselves, and every #ifndef CTU_... switch below is defined here only, so the host units and engine.hip see one value.
+// compile without hipcc.  The kernel headers define none of these themselves.
+//
+// Build switches: CTU_STAMP below and CTU_DIAG are all there are - no other file of csrc/ or host/ defines one
+// (tests/test_build_switches_cpu.py) - and both are instruments, not alternatives: every kernel has one code path.  An A/B is a
+// comparison of two commits' libraries (tools/build_variant.sh, CTU_ENGINE_LIB), or of a switch that lives for one pull request.
+// (CTU_DIAG is only ever tested: a -DCTU_DIAG build reads CTU_DEBUG_MODE at run time.)
 #pragma once
 
 #include <cstdint>
 
-// ---- build switches (A/B and diagnostic builds pass -DCTU_...=0)
-#ifndef CTU_MD
-#define CTU_MD 1        // the DCT tail on the matrix cores for the plain cepstral chains (what fe_select instantiates with MD)
-#endif
-#ifndef CTU_VF
-#define CTU_VF 1        // the Burg-cepstral VAD criterion fused into the front end (vad_fused.h)
-#endif
-#ifndef CTU_SY
-#define CTU_SY 1        // 0: speech-enhancement output through the exported spectra and synth_kernel (round 1's path)
-#endif
-#ifndef CTU_LP_MD
-#define CTU_LP_MD 1     // 0: the lags of the compressed-band LP chain on the VALU (cell_accumulate + cells_reduce), for A/B
-#endif
-#ifndef CTU_SS_CACHE
-#define CTU_SS_CACHE 1  // 0: every pass of the *ss modes' seed iteration runs the detector again (A/B)
-#endif
-#ifndef CTU_DUAL
-#define CTU_DUAL 1      // the two passes of the 512-point mode side by side in the headline instantiation (frontend_kernel.h: DUAL)
-#endif
-#ifndef CTU_PAIRCOL
-#define CTU_PAIRCOL 1   // the packed DUAL block's second stage on the two mirror columns of one frame per lane (paircol_map.h): the untangle's partner bin in-lane; 0: the passes stay in the halves and the partner comes by ds_bpermute (A/B)
-#endif
-#ifndef CTU_LB
-#define CTU_LB 4        // waves per SIMD the front end's register allocator must leave room for (2 workgroups x 8 waves / 4 SIMDs)
-#endif
-#ifndef CTU_SY_LB
-#define CTU_SY_LB 2     // register budget of the synthesis instantiations (SY): 256 VGPRs, one workgroup per CU.  Measured (profiles/r03_ab_sy_register_budget.txt): at 128 VGPRs they spill 200 bytes per lane; 2 -> -25 % kernel time, 3 -> -21 %
-#endif
-#ifndef CTU_VF1_LB
-#define CTU_VF1_LB CTU_LB  // experiment: register budget of the fused-detector instantiations of the 256-point mode
-#endif
-#ifndef CTU_TRAP_BF16
-#define CTU_TRAP_BF16 1  // 0: TRAP-DCT on the fp32 matrix pipe only (trapdct_mfma_kernel)
-#endif
-#ifndef CTU_TRAP_F16
-#define CTU_TRAP_F16 1   // 1: two fp16 terms, three products; 0: three bf16 terms, six products (trap_kernel.h)
+#ifndef CTU_STAMP
+#define CTU_STAMP 0     // diagnostic build: per-wave s_memtime sums per code segment of frontend_kernel (never in production)
 #endif
 
 namespace {
@@ -72,10 +42,12 @@ constexpr int LDS_2WG = 80 * 1024;     // two workgroups per CU fit when a workg
 constexpr int ROWS_WG_PER_CU = 8;      // rows_ingest_kernel: workgroups of four waves per CU: 32 waves, each with a tile of 64 rows in flight
 constexpr int VFC_STRIDE = 16;         // vad_kernels.h: floats per frame in the cepstra scratch: the fused path's 14 coefficients, 64-byte rows
 // Waves per SIMD a front-end instantiation is compiled for (frontend_kernel's launch bounds; PlanGeom sizes the chains by it).
+constexpr int FE_LB = 4;     // waves per SIMD the front end's register allocator must leave room for (2 workgroups x 8 waves / 4 SIMDs)
+constexpr int FE_SY_LB = 2;  // register budget of the synthesis instantiations (SY): 256 VGPRs, one workgroup per CU.  Measured (profiles/r03_ab_sy_register_budget.txt): at 128 VGPRs they spill 200 bytes per lane; 2 -> -25 % kernel time, 3 -> -21 %
 // The fused detector paths of the 512-point mode (VF / SS with MODE 0) keep both passes' transform outputs and a 25-sample
 // lattice per lane alive: 256 VGPRs, one workgroup per CU (their staging area takes the LDS of the second one anyway).
 constexpr int fe_waves_per_simd(int mode, bool vf, bool ss, bool sy = false) {
-    return ((vf || ss) && mode == 0) ? 2 : (sy ? CTU_SY_LB : ((vf || ss) ? CTU_VF1_LB : CTU_LB));
+    return ((vf || ss) && mode == 0) ? 2 : (sy ? FE_SY_LB : FE_LB);
 }
 
 constexpr int PSTRIDE = 260;   // floats per P-tile row: 257 bins padded so rows stay 16-byte aligned (b128 reads in phase 2)
@@ -128,7 +100,7 @@ constexpr int DCTW_KC = 64, DCTW_MAX = 64;  // dctw_kernel.h: bands per chunk of
 
 // The DUAL instantiations of frontend_kernel (its phase 1).  They take their window table scaled by 1/2 (tables.cc asks this same function).
 constexpr bool fe_dual(int nz, int mode, bool vx, int gen, bool vf, bool ss, bool sy) {
-    return CTU_DUAL && mode == 0 && (gen == GEN_PLAIN || gen == GEN_INLD) && !vx && nz < 16 && !vf && !ss && !sy;
+    return mode == 0 && (gen == GEN_PLAIN || gen == GEN_INLD) && !vx && nz < 16 && !vf && !ss && !sy;
 }
 
 // VAD module parameters (src/vad/vad.cc, src/vad/vad.h; filled by tables.cc, used by vad_kernels.h and by the fused path of the front end)

@@ -1,4 +1,4 @@
-// The index maps of the pair-column second stage of phase 1 (frontend_kernel.h, CTU_PAIRCOL): plain C++, no HIP.
+// The index maps of the pair-column second stage of phase 1 (frontend_kernel.h, the DUAL block): plain C++, no HIP.
 //
 // Stage 1 of the packed DUAL block leaves element (k1, pass, fg, n2) of a step in lane 16 fg + n2, register k1, half `pass`.  Stage 2 runs
 // one frame's two MIRROR columns in the two halves of a lane's register pairs: lane (f8, p), f8 = 4 pass + fg the frame slot of the step,

@@ -46,7 +46,7 @@ PlanGeom plan_geom(const Design &d, const EngineTables &tab, const Spread &sp, i
     g.row_off_dev = g.do_vad || g.ss_detector;
     g.signal_out = d.signal_out;
     g.pss = g.ss_big && d.signal_out;
-    g.spectra = (d.signal_out && !k.sy) || g.vad_burg || g.ss_big;
+    g.spectra = (d.signal_out && !k.sy) || g.vad_burg || g.ss_big;  // (signal output without SY: on 1024- to 4096-point transforms, where fe_select leaves k.sy unset)
     g.dc1 = o.remove_dc1;
     g.logmel = d.kind == FeaKind::TrapDct || tab.dctw;
     g.lp_tail = (tab.feat == FEAT_LP || tab.feat == FEAT_LPD) && (!tab.big || tab.path == BIG_WAVE1K) && !d.signal_out;

@@ -66,7 +66,6 @@ struct StreamSetFacts {
     int mode = 0;
     bool per_wave = false;    // PlanGeom::per_wave, chain_slots, max_wg
     int chain_slots = 0, max_wg = 0;
-    bool exten_f64 = false;   // CTU_EXTEN_F64
 };
 
 struct StreamSetShape {
@@ -152,7 +151,7 @@ inline StreamSetShape stream_set_shape(const ctu::Design &d, uint32_t flags, con
         // [2][64 NJ] of xstate_t (frontend_kernel.h), [2][64 * 9] floats (wave1k_kernel.h), [2][256 NB] floats (bigfft_kernel.h); with
         // subtraction state the slot of layout_constants.h - both noise estimates and the detector's record, on large transforms in doubles
         const int nj = f.mode == 1 ? 3 : 5;
-        s.xstate_floats = s.ss ? (f.big ? xs_ss_big_floats(d.wfft / 256) : xs_ss_floats(nj)) : !f.big ? 2 * 64 * nj * (f.exten_f64 ? 2 : 1) : f.wave1k ? 2 * 64 * 9 : 2 * 256 * (d.wfft / 256 / 2 + 1);
+        s.xstate_floats = s.ss ? (f.big ? xs_ss_big_floats(d.wfft / 256) : xs_ss_floats(nj)) : !f.big ? 2 * 64 * nj : f.wave1k ? 2 * 64 * 9 : 2 * 256 * (d.wfft / 256 / 2 + 1);
     }
     s.n_heads = chain_deal(n_streams, g.max_chains).heads();
     // the lead, a full carry, a full push (and no shorter than the shortest file a delta chain is defined on: the plan of a set whose

@@ -6,7 +6,7 @@
 // w - s samples behind them it keeps the partial sums: its tail, w - s doubles in HBM, zero at create and after a finish.
 //
 //   stream_ola_kernel        a stream goes from F0 to F0 + T frames: its time-domain frames are rows row0 .. row0 + T - 1 of the plan's
-//                            ybuf (the front end's SY instantiations, or synth_kernel, wrote them).  Output sample j < T s is the tail's
+//                            ybuf (the front end's SY instantiations, or bigsynth_kernel, wrote them).  Output sample j < T s is the tail's
 //                            entry j (0.0 past the tail) plus the push's frames over it in ascending order, then ola_round.  The new
 //                            tail's entry j < w - s is the old entry j + T s (0.0 past it) plus the push's frames over sample T s + j.
 //                            Continuing a partial sum in frame order is the offline run's sequence of additions, so given the same

@@ -213,7 +213,6 @@ int ctu_streams_create_ex(ctu_engine *e, int32_t n_streams, int64_t max_push_sam
     StreamSetFacts f;
     f.ss = e->tab.ss; f.big = e->tab.big; f.ss_file = e->tab.ss_file; f.wave1k = e->tab.path == BIG_WAVE1K; f.mode = e->tab.sel.mode;
     f.per_wave = e->geom.per_wave; f.chain_slots = e->geom.chain_slots; f.max_wg = e->geom.max_wg;
-    f.exten_f64 = CTU_EXTEN_F64 != 0;
     std::unique_ptr<ctu_streams> st(new ctu_streams);
     st->eng = e;
     st->max_push = max_push_samples;
@@ -452,8 +451,7 @@ int push_rows(ctu_streams *st, int k, int n, const PushLayout &L, const RunExten
     return CTU_OK;
 }
 // ... on a set with signal state: the front end leaves the time-domain frames of the push in the plan's ybuf, a row per frame (its SY
-// instantiations - behind hwss / fwss / 2fwss run_chain's one streamed pass from the streams' slots; in a build without them
-// synth_kernel from the exported spectra; on 1024 .. 4096-point frames bigsynth_kernel from bigfft_kernel's), and stream_ola_kernel adds
+// instantiations - behind hwss / fwss / 2fwss run_chain's one streamed pass from the streams' slots; on 1024 .. 4096-point frames bigsynth_kernel from bigfft_kernel's), and stream_ola_kernel adds
 // them onto every stream's tail - stream_ola_big_kernel a tail of more than OLA_TAIL_MAX entries
 int push_signal(ctu_streams *st, int k, int n, const PushLayout &L, const RunExtent &x, const PushOutput &o, hipStream_t s) {
     ctu_engine *e = st->eng;
@@ -464,14 +462,6 @@ int push_signal(ctu_streams *st, int k, int n, const PushLayout &L, const RunExt
     e->in_signal_call = false;
     if (rc != CTU_OK) return rc;
     if (e->tab.big) launch_bigsynth(e, pl, x, s, 1.0f / (float)d.wfft);  // (large transforms: bigfft_kernel exported the spectra)
-    else if (!e->tab.sel.sy) {  // the spectra of the push's frames back to the time domain (ctu_engine_run_signal's launch, over this extent)
-        SynthParams yp;
-        yp.K = d.K; yp.wfft = d.wfft; yp.window = d.window; yp.wshift = d.wshift;
-        yp.inv_n = 1.0f / (float)d.wfft;
-        yp.corr = d.ola_corr;
-        const int g = (int)std::min<int64_t>((L.base_rows + 7) / 8, (int64_t)e->n_cu * 8);
-        hipLaunchKernelGGL(synth_kernel, dim3(g), dim3(256), 0, s, pl->xri.p, pl->pnr.p, pl->ybuf.p, (long long)L.base_rows, yp);
-    }
     if (st->sh.ola_big) {  // the owner of every tail, then the slices of the samples past it
         const int64_t past = std::max<int64_t>(L.most - (d.window - d.wshift), 0);
         hipLaunchKernelGGL(stream_ola_big_kernel, dim3((unsigned)n, 1u + (unsigned)((past + OLA_SLICE - 1) / OLA_SLICE)), dim3(256), 0, s,

@@ -313,7 +313,7 @@ FeSel fe_select(const Design &d, const Phase2Tables *t) {
     const bool signal = d.signal_out, exten = o.nr_mode == "exten";
     // ---- what the configuration and its tables fix
     k.mode = d.wfft == 256;
-    k.sy = signal && CTU_SY;
+    k.sy = signal;
     k.ss = ss_eligible(d);
     k.vf = !signal && vf_eligible(d);
     k.md = t && t->md;             // the tables are laid out for the MFMA tail's lane map
@@ -324,8 +324,8 @@ FeSel fe_select(const Design &d, const Phase2Tables *t) {
     // at most 13 rows - the window table is zero beyond the window); every other window, and -remove_dc1, takes the generic row count
     const int rows = k.mode ? (d.window + 15) / 16 : (d.window + 31) / 32;
     k.nz = (!o.remove_dc1 && (rows == 13 || (k.ss && rows < 13))) ? 13 : 16;
-    // the spectra leave the kernel for the VAD kernels (Burg-cepstral and energy criteria) or, in builds without SY, for synth_kernel
-    k.vx = (signal && !k.sy) || (o.do_vad() && !k.vf && !signal && (o.vad_cri_mode == "energy" || o.vad_cepdist_mode == "lpc"));
+    // the spectra leave the kernel for the VAD kernels (Burg-cepstral and energy criteria)
+    k.vx = o.do_vad() && !k.vf && !signal && (o.vad_cri_mode == "energy" || o.vad_cepdist_mode == "lpc");
     bool diag = false;
 #ifdef CTU_DIAG  // phase ablation (ctu_engine_run: kp.dbg) is a run-time flag
     diag = getenv("CTU_DEBUG_MODE") && atoi(getenv("CTU_DEBUG_MODE")) != 0;
@@ -376,48 +376,27 @@ FeSel fe_select(const Design &d, const Phase2Tables *t) {
 
 namespace {
 
-// TRAP-DCT: the folded table and, where trapdct_bf16_kernel serves the shape, its
-// A operands: G shifted by the frame phase c, zero-padded to 128 taps, each value split into three
-// bf16 terms (round to nearest even at every step, as the device splits the data)
+// TRAP-DCT: the folded table and, where trapdct_split16_kernel serves the shape, its
+// A operands: G shifted by the frame phase c, zero-padded to 128 taps, each value split into two
+// fp16 terms (round to nearest even at every step, as the device splits the data)
 void build_trap(const Design &d, EngineTables &e) {
     e.trapG.assign(d.trap.begin(), d.trap.end());
     const int tl = d.o.fea_trapdct_traplen, nd = d.o.fea_trapdct_ndct, half = (tl - 1) / 2;
-    e.trap_bf16 = CTU_TRAP_BF16 && nd <= 16 && half <= TB_OFF && 7 + (TB_OFF - half) + tl <= 128 && d.B <= 24;  // 24 bands: 62 KB of LDS (tile 38 KB + two fragment buffers 24 KB): two workgroups per CU
+    e.trap_bf16 = nd <= 16 && half <= TB_OFF && 7 + (TB_OFF - half) + tl <= 128 && d.B <= 24;  // 24 bands: 62 KB of LDS (tile 38 KB + two fragment buffers 24 KB): two workgroups per CU
     if (!e.trap_bf16) return;
-    auto rn = [](float v) {
-        uint32_t u;
-        std::memcpy(&u, &v, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    };
-    auto up = [](uint16_t h) {
-        uint32_t u = (uint32_t)h << 16;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
-    const bool f16 = CTU_TRAP_F16;
-    const int NT = f16 ? 2 : 3;
+    const int NT = 2;
     e.trapG16.assign((size_t)8 * 4 * NT * 64 * 4, 0u);  // records of four words
     for (int c = 0; c < 8; c++)
         for (int s_ = 0; s_ < 4; s_++)
             for (int lane = 0; lane < 64; lane++) {
                 const int m = lane & 15, q = lane >> 4;
-                uint16_t term[3][8];
+                uint16_t term[NT][8];
                 for (int i = 0; i < 8; i++) {
                     const int j = 32 * s_ + 8 * q + i - c - (TB_OFF - half);
                     const float v = (m < nd && j >= 0 && j < tl) ? (float)d.trap[(size_t)m * tl + j] : 0.f;
-                    if (f16) {
-                        const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
-                        std::memcpy(&term[0][i], &h, 2);
-                        std::memcpy(&term[1][i], &l, 2);
-                        term[2][i] = 0;
-                    } else {
-                        term[0][i] = rn(v);
-                        const float r1 = v - up(term[0][i]);
-                        term[1][i] = rn(r1);
-                        term[2][i] = rn(r1 - up(term[1][i]));
-                    }
+                    const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
+                    std::memcpy(&term[0][i], &h, 2);
+                    std::memcpy(&term[1][i], &l, 2);
                 }
                 for (int sp = 0; sp < NT; sp++) {
                     uint32_t *w = &e.trapG16[((((size_t)c * 4 + s_) * NT + sp) * 64 + lane) * 4];

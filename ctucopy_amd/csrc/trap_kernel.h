@@ -75,14 +75,12 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same contraction on the 16-bit matrix pipe with fp32 accuracy.  Every operand is split into 16-bit terms and the
-// significant cross products accumulate in fp32:
-//   F16 = true   two fp16 terms  (x = h + l to 2^-22):  hh, hl, lh            3 MFMAs per 32 taps  (ll, 2^-22, dropped)
-//   F16 = false  three bf16 terms (x = h + m + l to 2^-24): hh, hm, mh, hl, lh, mm   6 MFMAs     (ml, lm, ll dropped)
-// v_mfma_f32_16x16x32_{f16,bf16} do 8x the multiply-adds of the fp32 form per cycle.  The kernel is bound by that pipe
+// significant cross products accumulate in fp32: two fp16 terms (x = h + l to 2^-22), hh, hl, lh - 3 MFMAs per 32 taps (ll, 2^-22, dropped).
+// v_mfma_f32_16x16x32_f16 does 8x the multiply-adds of the fp32 form per cycle.  The kernel is bound by that pipe
 // at the clock the chip holds under it (neither the barrier, nor occupancy, nor the stores, nor the dependency chain of
-// the accumulator moved its time), so the fp16 split - half the MFMAs - is the one that runs; the log-mel values are
+// the accumulator moved its time), so the fp16 split - half the MFMAs of three bf16 terms and six products - is the one that runs; the log-mel values are
 // centred per band (|x| of a few units) and G is at most 1, far inside fp16's range, and an element's absolute error is
-// max(2^-22 |x|, 3e-8) (fp16 subnormal spacing).  The bf16 form (any range) is kept for the record.
+// max(2^-22 |x|, 3e-8) (fp16 subnormal spacing).
 // The Toeplitz operand X[j][t] = x[t + j - half] wants 8 consecutive taps per lane (16-byte LDS reads), i.e. a start that
 // is a multiple of 8 for every column: the 16 columns of an MFMA are therefore output frames 8 apart (t = tc + 8 n + c),
 // and each of the 8 phases c has its own copy of G shifted by c taps (host table, zero-padded to K = 128):
@@ -90,7 +88,6 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
 // (rows of G sum to zero, so the per-band constant x0 - the tile's centre value - drops out and keeps the split small).
 // One workgroup (8 waves, at most 128 VGPRs: two workgroups = four waves per SIMD on a CU) = 128 output frames x all
 // bands; wave w takes bands w, w+8, ...; A fragments of a phase (4 k-steps x NT terms) live in registers meanwhile.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int TB_TT = 264;   // tile row in frames: 8 * 15 + 127 < 256 used; 528 bytes per row spreads the bands over the banks and keeps 16-byte alignment
 
@@ -98,38 +95,23 @@ constexpr int TB_TT = 264;   // tile row in frames: 8 * 15 + 127 < 256 used; 528
 // latency of a phase's row stores in front of the next phase.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__device__ __forceinline__ unsigned bf16_rn(float v) {  // round to nearest even, finite inputs
-    unsigned u = __float_as_uint(v);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
 __device__ __forceinline__ unsigned f16_bits(_Float16 h) { return (unsigned)__builtin_bit_cast(unsigned short, h); }
 
-// the 16-bit terms of a value, most significant first
-template <bool F16>
-__device__ __forceinline__ void split16(float v, unsigned (&t)[3]) {
-    if constexpr (F16) {
-        const _Float16 h = (_Float16)v;  // v_cvt_f16_f32, round to nearest even
-        const _Float16 l = (_Float16)(v - (float)h);
-        t[0] = f16_bits(h);
-        t[1] = f16_bits(l);
-        t[2] = 0;
-    } else {
-        t[0] = bf16_rn(v);
-        const float r1 = v - __uint_as_float(t[0] << 16);
-        t[1] = bf16_rn(r1);
-        t[2] = bf16_rn(r1 - __uint_as_float(t[1] << 16));
-    }
+// the two fp16 terms of a value, most significant first
+__device__ __forceinline__ void split16(float v, unsigned (&t)[2]) {
+    const _Float16 h = (_Float16)v;  // v_cvt_f16_f32, round to nearest even
+    const _Float16 l = (_Float16)(v - (float)h);
+    t[0] = f16_bits(h);
+    t[1] = f16_bits(l);
 }
 
 #ifndef TB_WGS
 #define TB_WGS 2
 #endif
-template <bool F16>
 __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const float *__restrict__ logmel, float *__restrict__ rows,
                                                                 const uint4 *__restrict__ Gtab, const int4 *__restrict__ utt_info,
                                                                 const int *__restrict__ chunk_tab, int n_chunks, int B, int ndct, int D) {
-    constexpr int NT = F16 ? 2 : 3;       // terms per operand
+    constexpr int NT = 2;                 // terms per operand
     constexpr int NA = 4 * NT * 64;       // uint4 fragments of a phase
     extern __shared__ __align__(16) unsigned short xt[];  // [NT][B][TB_TT] terms, then x0[B] floats, then the fragment buffers
     if ((int)blockIdx.x >= n_chunks) return;
@@ -166,9 +148,9 @@ __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const floa
             const int e = tid + 512 * it;
             if (e < 128 * B) {
                 const int pr = e / B, b = e - pr * B;
-                unsigned ta[3], tb[3];
-                split16<F16>(v0[it] - x0[b], ta);
-                split16<F16>(v1[it] - x0[b], tb);
+                unsigned ta[NT], tb[NT];
+                split16(v0[it] - x0[b], ta);
+                split16(v1[it] - x0[b], tb);
 #pragma unroll
                 for (int sp = 0; sp < NT; sp++) xt32[((sp * B + b) * TB_TT >> 1) + pr] = ta[sp] | (tb[sp] << 16);
             }
@@ -194,7 +176,7 @@ __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const floa
 #pragma unroll
             for (int sp = 0; sp < NT; sp++) a[s_][sp] = ab[(s_ * NT + sp) * 64 + lane];
         const int t_out = tc + 8 * n + c;
-        // a band of the wave: 4 x NT tile fragments from LDS, 12 (fp16) or 24 (bf16) MFMAs, one row store; four waves per
+        // a band of the wave: 4 x NT tile fragments from LDS, 12 MFMAs, one row store; four waves per
         // SIMD cover each other's LDS round trips
         for (int b = wave; b < B; b += 8) {
             uint4 X[4][NT];
@@ -208,22 +190,11 @@ __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const floa
 #pragma unroll
             for (int s_ = 0; s_ < 4; s_++) {
                 // smallest terms first
-                if constexpr (F16) {
 #define MF(A_, X_) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A_), __builtin_bit_cast(f16x8, X_), acc, 0, 0, 0)
-                    MF(a[s_][1], X[s_][0]);
-                    MF(a[s_][0], X[s_][1]);
-                    MF(a[s_][0], X[s_][0]);
+                MF(a[s_][1], X[s_][0]);
+                MF(a[s_][0], X[s_][1]);
+                MF(a[s_][0], X[s_][0]);
 #undef MF
-                } else {
-#define MB(A_, X_) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, X_), acc, 0, 0, 0)
-                    MB(a[s_][1], X[s_][1]);
-                    MB(a[s_][NT - 1], X[s_][0]);
-                    MB(a[s_][0], X[s_][NT - 1]);
-                    MB(a[s_][1], X[s_][0]);
-                    MB(a[s_][0], X[s_][1]);
-                    MB(a[s_][0], X[s_][0]);
-#undef MB
-                }
             }
             if (t_out < T) {
                 if (ndct == 16 && (D & 3) == 0) {

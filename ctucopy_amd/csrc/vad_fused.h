@@ -166,12 +166,6 @@ __device__ __forceinline__ void vf_inverse_fft(float2 (&vn)[16], const float4 *l
 // T = float (the VAD module's criterion: identical decisions to the double oracle on every test recording) or double
 // (the *ss modes' detector: it sees spectra raised to the power a, whose frames are nearly sinusoidal - reflection
 // coefficients within 1e-6 of +-1 - and a float lattice then loses the cepstra's digits that the threshold test needs).
-#ifndef CTU_BURG_RCP
-#define CTU_BURG_RCP 1  // 0: the reflection coefficient by the IEEE division sequence (A/B)
-#endif
-#ifndef CTU_BURG_DREC
-#define CTU_BURG_DREC 0  // 1: the denominator of order m+1 from that of order m, D' = (1 - k^2) D - f[m]^2 - b[N-1]^2, instead of the sum
-#endif
 // The tail of the Burg estimator behind the lattice: from the reflection coefficients (FROM_RC: the polynomial is rebuilt first,
 // a_i <- a_i + k a_{m-i}, Burg.h:88-93) to the LPC cepstrum c_0 = ln alpha, c_m = -a_m - (1/m) sum_{k<m} (m-k) c_{m-k} a_k
 // (Burg.h:143-151).  One definition for the front end (all lanes of a frame) and for vad_a2c_kernel (one frame per lane), so that
@@ -252,7 +246,6 @@ __device__ __forceinline__ void vf_burg_cepstrum(const float (&x)[SPL], int l16,
     };
     clear_last();
     T a[NC];
-    T den_next = 0;
     if constexpr (RC_ONLY && FOLD) {
 #pragma unroll
         for (int h = 0; h < (NC + LPF - 1) / LPF; h++) cc[h] = 0;
@@ -267,29 +260,24 @@ __device__ __forceinline__ void vf_burg_cepstrum(const float (&x)[SPL], int l16,
             // row_ror:1: the lane before this one; a frame's first lane reads the last lane of a neighbour - the entry clear_last() keeps
             // at zero (LPF = 8: SPL * LPF = window exactly) or a sample of the padding beyond the window (zero as well)
             const T eb_prev = dpp_mov<0x121>(eb[VF_SPL - 1]);
-            constexpr bool DREC = CTU_BURG_DREC && sizeof(T) == 4 && JW >= 0 && LPF == 16;
             T n0 = 0, n1 = 0, d0 = 0, d1 = 0;
 #pragma unroll
             for (int j = 0; j < VF_SPL; j++) {
                 const T bm = j == 0 ? eb_prev : eb[j - 1];
                 if (j & 1) {
                     n1 += ef[j] * bm;
-                    if (!DREC || ik == 1) {
-                        d1 += ef[j] * ef[j];
-                        d1 += bm * bm;
-                    }
+                    d1 += ef[j] * ef[j];
+                    d1 += bm * bm;
                 } else {
                     n0 += ef[j] * bm;
-                    if (!DREC || ik == 1) {
-                        d0 += ef[j] * ef[j];
-                        d0 += bm * bm;
-                    }
+                    d0 += ef[j] * ef[j];
+                    d0 += bm * bm;
                 }
             }
             const T num = row_sum(n0 + n1);
-            const T den = (!DREC || ik == 1) ? row_sum(d0 + d1) : den_next;
+            const T den = row_sum(d0 + d1);
             T rc;
-            if constexpr (CTU_BURG_RCP && sizeof(T) == 4) {
+            if constexpr (sizeof(T) == 4) {
                 // the float lattice's quotient by v_rcp_f32 and one correction of the quotient (the residual by FMA): as exact as the
                 // IEEE sequence for a denominator in the normal range (a sum of squares of samples), four instructions instead of ten
                 // on the chain every lane of the frame waits for
@@ -307,12 +295,6 @@ __device__ __forceinline__ void vf_burg_cepstrum(const float (&x)[SPL], int l16,
                 const T nef = ef[j] + rc * bm, neb = bm + rc * ef[j];
                 ef[j] = nef;
                 eb[j] = neb;
-            }
-            if constexpr (DREC) {
-                // sample ik's forward error (lane 0, or lane 1's first register) and the window's last backward error
-                const T fe = ik < VF_SPL ? (lane0 ? ef[ik < VF_SPL ? ik : 0] : (T)0) : (l16 == 1 ? ef[0] : (T)0);
-                const T be = lanew ? eb[JW] : (T)0;
-                den_next = ((T)1 - rc * rc) * den - row_sum(fe * fe + be * be);
             }
             clear_last();
             if constexpr (RC_ONLY && FOLD) cc[ik / LPF] = l16 == ik % LPF ? rc : cc[ik / LPF];

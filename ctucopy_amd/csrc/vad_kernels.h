@@ -6,7 +6,7 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------
 // VAD module (src/vad/vad.cc, src/vad/vad.h, src/vdet/Burg.h).  Kernel A (vad_burg_kernel) is frame-parallel: HC2R of
-// the post-NR spectrum with the original phase, Burg lattice, a -> c, in CTU_VAD_REAL arithmetic.  Kernel B
+// the post-NR spectrum with the original phase, Burg lattice, a -> c, in `vreal` arithmetic.  Kernel B
 // (vad_decide_kernel) is one wave per utterance and replays the sequential, discontinuous part in double: cepstral
 // distance to the adaptive background, threshold recurrences, background update, majority ("median") filter.
 // ------------------------------------------------------------------------------------------------
@@ -14,12 +14,9 @@ namespace {
 // vad_burg_kernel: one wave per frame (4 waves per workgroup, persistent): the frame's samples live in registers,
 // strided over the lanes (sample j = lane + 64 q); reductions are DPP row rotations + v_readlane (wave_sum_fast), no
 // workgroup barrier inside the lattice.
-#ifndef CTU_VAD_REAL
-#define CTU_VAD_REAL float   // arithmetic of the HC2R + Burg kernel.  Its inputs (the front end's spectra) are float; on the
-                             // reference recordings float and double give the same decisions, frame for frame, as the oracle
-                             // (626 of 1186 on CS3 @ 8 kHz, the count the compiled reference wrote); double costs 1.6x
-#endif
-typedef CTU_VAD_REAL vreal;
+typedef float vreal;  // arithmetic of the HC2R + Burg kernel.  Its inputs (the front end's spectra) are float; on the
+                      // reference recordings float and double give the same decisions, frame for frame, as the oracle
+                      // (626 of 1186 on CS3 @ 8 kHz, the count the compiled reference wrote); double costs 1.6x
 
 __device__ __forceinline__ float lane_read(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
 __device__ __forceinline__ double lane_read(double x, int l) {
@@ -394,9 +391,8 @@ __device__ __forceinline__ int vad_quad_step(VadQuad &r, const VadParams &vp, co
         double sum = 0.0;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int k = 4 * pq + i;
             // c0 itself is not part of the distance; vad_a2c_kernel stores zeros there and in the row's padding
-            const double dl = (CTU_VF_A2C || (k >= 1 && k < NCL)) ? ci[i] - r.c0[i] : 0.0;
+            const double dl = ci[i] - r.c0[i];
             sum += dl * dl;
         }
         sum += dpp_mov<0xB1>(sum);  // quad_perm [1,0,3,2]

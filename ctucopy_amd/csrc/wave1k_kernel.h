@@ -56,16 +56,13 @@ constexpr int W1K_PLANE = 8 * W1K_TS;            // the plane: re and im of a tr
                                                  // spectrum P[513 (+3)] takes its place once the transform is done
 constexpr int W1K_WAVE_FLOATS = W1K_PLANE + 64 + 64 + 64;  // plane / P | Y[64] | Ylog[64] | partial band sums [64]
 constexpr int W1K_TW_FLOATS = 2 * (512 + 64 + 512);        // W1024^m for m < 512 | t1[8][8] | t2[8][64], float2 each
-#ifndef CTU_W1K_WAVES
-#define CTU_W1K_WAVES 4  // measured (profiles/r03_ab_wave1k_occupancy.txt, 1.78 M frames): 4 waves x 5 workgroups per CU (96 VGPRs) 2.86 ms,
-#define CTU_W1K_LB 5     // 8 x 3 (80 VGPRs, 35 spilled) 3.09 ms, 4 x 4 (120 VGPRs, none spilled) 3.05 ms; round 3's first version (163 VGPRs, 3 per SIMD) 4.10 ms
-#endif
-constexpr int W1K_WAVES = CTU_W1K_WAVES;         // waves per workgroup
+constexpr int W1K_WAVES = 4;  // waves per workgroup.  Measured (profiles/r03_ab_wave1k_occupancy.txt, 1.78 M frames): 4 waves x 5 workgroups per CU (96 VGPRs) 2.86 ms,
+constexpr int W1K_LB = 5;     // 8 x 3 (80 VGPRs, 35 spilled) 3.09 ms, 4 x 4 (120 VGPRs, none spilled) 3.05 ms; round 3's first version (163 VGPRs, 3 per SIMD) 4.10 ms
 // Host side, the carve-up below: the waves' areas | window pairs | twiddles | the projection's tables (two floats of slack ahead of the doubles)
 // | the bank's segment table [64][4] + [B][2] | 64 bytes of slack; workgroups a CU as the launch bounds have it
 LdsFit wave1k_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
     return lds_fit(((size_t)W1K_WAVES * W1K_WAVE_FLOATS + 1024 + W1K_TW_FLOATS + 2) * 4 + big_proj_lds(d, feat, ncoef_out, fb_total) + (size_t)(256 + 2 * d.B) * 4 + 64,
-                   CTU_W1K_LB * 4 / W1K_WAVES);
+                   W1K_LB * 4 / W1K_WAVES);
 }
 
 // A frame is one wave's serial chain of ~40 LDS round trips: what hides them is other waves, so the kernel is built for five
@@ -80,7 +77,7 @@ LdsFit wave1k_lds(const ctu::Design &d, int feat, int ncoef_out, int fb_total) {
 // gfx950, hipcc -O3, from the code object's metadata: <true> 128 VGPRs, 106 SGPRs, 85 SGPRs kept in VGPR lanes; <true, XS> 128 VGPRs,
 // 106 SGPRs, 100 kept in VGPR lanes; no VGPR spills and no scratch in either.
 template <bool EXTEN, bool XS = false>
-__global__ __launch_bounds__(64 * W1K_WAVES, EXTEN ? CTU_W1K_LB - 1 : CTU_W1K_LB) void wave1k_kernel(const BigParams p, void *lp_r, int lp_stride) {
+__global__ __launch_bounds__(64 * W1K_WAVES, EXTEN ? W1K_LB - 1 : W1K_LB) void wave1k_kernel(const BigParams p, void *lp_r, int lp_stride) {
     extern __shared__ __align__(16) float smem[];
     constexpr int Nc = 512;
     const int K = p.K;  // 513

@@ -32,11 +32,11 @@ static const char *BEYOND = "internal: a signal set beyond the 512-point front e
 enum : uint32_t { ROW = CTU_STREAMS_ROW_STATE, NR = CTU_STREAMS_NR_STATE, VAD = CTU_STREAMS_VAD_STATE, SIG = CTU_STREAMS_SIGNAL_STATE,
                   LARGE = CTU_STREAMS_LARGE_STATE, TRAP = CTU_STREAMS_TRAP_STATE, SS = CTU_STREAMS_SS_STATE };
 
-// engine facts: {ss, big, ss_file, wave1k, mode, per_wave, chain_slots, max_wg, exten_f64}
-static StreamSetFacts facts(int ss, bool big, bool wave1k, int mode, bool per_wave, int chain_slots = 4096, bool f64 = false, bool ss_file = false) {
+// engine facts: {ss, big, ss_file, wave1k, mode, per_wave, chain_slots, max_wg}
+static StreamSetFacts facts(int ss, bool big, bool wave1k, int mode, bool per_wave, int chain_slots = 4096, bool ss_file = false) {
     StreamSetFacts f;
     f.ss = ss; f.big = big; f.ss_file = ss_file; f.wave1k = wave1k; f.mode = mode;
-    f.per_wave = per_wave; f.chain_slots = chain_slots; f.max_wg = 512; f.exten_f64 = f64;
+    f.per_wave = per_wave; f.chain_slots = chain_slots; f.max_wg = 512;
     return f;
 }
 
@@ -104,12 +104,8 @@ static const Row rows[] = {
      nullptr, 2, 200, 80, 127, 126, true, 254, 26, 0, 200, 0, 8, 10360, 0, 0, 39624, 96, 0, 127},
     {"exten, 256 points", F8 " -nr_mode exten", NR, facts(0, false, false, 1, true), 3, 1000, 40,
      nullptr, 16, 200, 80, 0, 0, false, 0, 13, 0, 200, 384, 8, 1207, 0, 0, 0, 0, 0, 0},
-    {"exten, 256 points, CTU_EXTEN_F64", F8 " -nr_mode exten", NR, facts(0, false, false, 1, true, 4096, true), 3, 1000, 40,
-     nullptr, 16, 200, 80, 0, 0, false, 0, 13, 0, 200, 768, 8, 1207, 0, 0, 0, 0, 0, 0},
     {"exten, 512 points", F16 " -nr_mode exten", NR, facts(0, false, false, 0, true), 3, 1000, 40,
      nullptr, 16, 400, 160, 0, 0, false, 0, 13, 0, 400, 640, 8, 1407, 0, 0, 0, 0, 0, 0},
-    {"exten, 512 points, CTU_EXTEN_F64", F16 " -nr_mode exten", NR, facts(0, false, false, 0, true, 4096, true), 3, 1000, 40,
-     nullptr, 16, 400, 160, 0, 0, false, 0, 13, 0, 400, 1280, 8, 1407, 0, 0, 0, 0, 0, 0},
     {"exten on wave1k", F16 " -nr_mode exten -w 50", NR | LARGE, facts(0, true, true, 0, true), 3, 1000, 40,
      nullptr, 16, 800, 160, 0, 0, false, 0, 13, 0, 800, 1152, 8, 1807, 0, 0, 0, 0, 0, 0},
     {"exten on bigfft, 1024 points", F16 " -nr_mode exten -w 50", NR | LARGE, facts(0, true, false, 0, true, 2048), 3, 1000, 40,
@@ -161,7 +157,7 @@ static const Row rows[] = {
      CHAINS, 0, 0, 0, 0, 0, false, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
     {"hwss on large frames", F16 " -nr_mode hwss -vad burg -w 100", SS, facts(1, true, false, 0, true, 2048), 3, 1000, 40,
      CHAINS, 0, 0, 0, 0, 0, false, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-    {"hwss with -vad file=", F8 " -nr_mode hwss -vad file=x", SS, facts(1, false, false, 1, true, 4096, false, true), 3, 1000, 40,
+    {"hwss with -vad file=", F8 " -nr_mode hwss -vad file=x", SS, facts(1, false, false, 1, true, 4096, true), 3, 1000, 40,
      CHAINS, 0, 0, 0, 0, 0, false, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
     {"exten on large frames without the large flag", F16 " -nr_mode exten -w 100", NR, facts(0, true, false, 0, true, 2048), 3, 1000, 40,
      CHAINS, 0, 0, 0, 0, 0, false, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},

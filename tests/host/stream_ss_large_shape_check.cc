@@ -37,7 +37,7 @@ enum : uint32_t { ROW = CTU_STREAMS_ROW_STATE, NR = CTU_STREAMS_NR_STATE, VAD = 
 static StreamSetFacts facts(int ss, bool big, bool ss_file = false, int chain_slots = 2048, int mode = 0) {
     StreamSetFacts f;
     f.ss = ss; f.big = big; f.ss_file = ss_file; f.wave1k = false; f.mode = mode;
-    f.per_wave = true; f.chain_slots = chain_slots; f.max_wg = 512; f.exten_f64 = false;
+    f.per_wave = true; f.chain_slots = chain_slots; f.max_wg = 512;
     return f;
 }
 

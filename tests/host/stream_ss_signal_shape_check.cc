@@ -34,7 +34,7 @@ enum : uint32_t { ROW = CTU_STREAMS_ROW_STATE, NR = CTU_STREAMS_NR_STATE, VAD = 
 static StreamSetFacts facts(int ss, int mode, bool big = false, bool ss_file = false, int chain_slots = 4096) {
     StreamSetFacts f;
     f.ss = ss; f.big = big; f.ss_file = ss_file; f.wave1k = false; f.mode = mode;
-    f.per_wave = true; f.chain_slots = chain_slots; f.max_wg = 512; f.exten_f64 = false;
+    f.per_wave = true; f.chain_slots = chain_slots; f.max_wg = 512;
     return f;
 }
 

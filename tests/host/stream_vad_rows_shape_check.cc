@@ -35,7 +35,7 @@ enum : uint32_t { ROW = CTU_STREAMS_ROW_STATE, NR = CTU_STREAMS_NR_STATE, VAD = 
 static StreamSetFacts facts(bool big = false, bool per_wave = false) {
     StreamSetFacts f;
     f.ss = 0; f.big = big; f.ss_file = false; f.wave1k = false; f.mode = 1;
-    f.per_wave = per_wave; f.chain_slots = 4096; f.max_wg = 512; f.exten_f64 = false;
+    f.per_wave = per_wave; f.chain_slots = 4096; f.max_wg = 512;
     return f;
 }
 

@@ -1,4 +1,4 @@
-"""Stage 2 of the packed DUAL front end on column pairs (frontend_kernel.h, CTU_PAIRCOL; maps: paircol_map.h).
+"""Stage 2 of the packed DUAL front end on column pairs (frontend_kernel.h, the DUAL block; maps: paircol_map.h).
 
 Two things are held:
   every bin, seen directly   band spectra (-fea_kind spec on the plain chain) of inputs that put their energy into one bin - the two

@@ -1,4 +1,4 @@
-"""TRAP-DCT (C5): error of the device rows against the oracle on fixture and synthetic utterances (which split is built: see CTU_TRAP_F16)."""
+"""TRAP-DCT (C5): error of the device rows against the oracle on fixture and synthetic utterances (the two-term fp16 split of trap_kernel.h)."""
 import sys, os, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from ctucopy_amd import Engine, synth
