@@ -65,6 +65,7 @@
 #include "bigss_kernel.h"
 #include "stream_kernels.h"
 #include "stream_set_shape.h"
+#include "wire_layout.h"
 
 namespace {
 

@@ -66,7 +66,8 @@ inline int64_t stream_vad_rows_out(int H, int wmax, int h, int64_t F) { return s
 
 // One stream of a push (host-built: the prefix sums over the push are the host's, which mirrors the counts)
 struct StreamPush {
-    long long src;    // where its new samples start in the caller's arena (samples)
+    long long src;    // where its new samples start in the caller's buffer: an element of it - a sample, or with a wire layout whatever
+                      // the layout's format counts in; sample k is element src + k * stride of the layout (1 without)
     long long slot;   // where its slot starts in the push arena (samples, a multiple of PCM_ALIGN)
     long long row0;   // first row of the push it writes
     int id, n;        // stream, new samples
@@ -152,9 +153,10 @@ struct PushLayout {
 
 // Plans the push of n_samples[i] new samples to stream ids[i], i < n (ids in range and distinct, counts >= 0: the caller has checked).
 // false, with nothing the caller may use in L, when the push does not fit the arena or the tile list - or, on a set with signal state,
-// delivers more samples than L.capacity (L.over_capacity says which).
+// delivers more samples than L.capacity (L.over_capacity says which).  src_base: the element of the caller's layout that the buffer the
+// kernels read starts at - the first of the covering range a host wire form has uploaded, 0 everywhere else.
 inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const uint8_t *hsel, int n, const int32_t *ids, const int64_t *n_samples,
-                             const int64_t *sample_off, PushLayout &L) {
+                             const int64_t *sample_off, PushLayout &L, const int64_t src_base = 0) {
     int live = 0;
     if (g.chained)  // the streams that complete a frame, dealt in turn onto at most max_chains chains
         for (int i = 0; i < n; i++) {
@@ -175,7 +177,7 @@ inline bool stream_plan_push(const PushGeom &g, const int64_t *consumed, const u
         const int64_t F = stream_frames(c, g.window, g.wshift), T = stream_frames(c + n_samples[i], g.window, g.wshift) - F;
         const int64_t len = STREAM_LEAD + (c - F * g.wshift) + n_samples[i];  // the stitched utterance: an utterance of the arena (pcm_slot)
         StreamPush &p = L.push[i];
-        p.src = n_samples[i] ? sample_off[i] : 0;
+        p.src = n_samples[i] ? sample_off[i] - src_base : 0;
         p.slot = so;
         p.row0 = ro;
         p.id = ids[i];

@@ -474,9 +474,25 @@ int push_signal(ctu_streams *st, int k, int n, const PushLayout &L, const RunExt
     return CTU_OK;
 }
 
+// How the new samples of a push lie in the caller's buffer: null layout - native int16_t, contiguous per stream, today's path; else the
+// wire layout (checked by the caller: wire_layout_fault) and the element of it the buffer handed to the kernels starts at
+struct PushSource {
+    const ctu_wire_layout *wire = nullptr;
+    int64_t base = 0;
+};
+
+// stream_stitch_wire_kernel by the layout: a contiguous source (stride 1) takes the instantiation with the wide loads
+void launch_stitch_wire(const ctu_wire_layout &w, dim3 grid, hipStream_t s, const StreamParams &sp) {
+    lift<CTU_WIRE_S16, CTU_WIRE_S16_SWAPPED, CTU_WIRE_ALAW, CTU_WIRE_MULAW>(w.format, [&](auto fmt) {
+        lift<0, 1>(w.stride > 1 ? 1 : 0, [&](auto strided) {
+            hipLaunchKernelGGL((stream_stitch_wire_kernel<decltype(fmt)::value, decltype(strided)::value != 0>), grid, dim3(256), 0, s, sp, (long long)w.stride);
+        });
+    });
+}
+
 // Every push: check, plan, commit, launch.  The set's kind says what goes out (rows: what of `o` is counted in rows; samples likewise)
-int push_common(ctu_streams *st, bool want_signal, int32_t n, const int32_t *ids, const int16_t *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
-                const PushOutput &o, void *stream) {
+int push_common(ctu_streams *st, bool want_signal, int32_t n, const int32_t *ids, const void *d_pcm, const int64_t *sample_off, const int64_t *n_samples,
+                const PushOutput &o, void *stream, const PushSource &from = PushSource()) {
     if (!st) return CTU_ERR_INPUT;
     ctu_engine *e = st->eng;
     const ctu::Design &d = *e->design;
@@ -517,7 +533,7 @@ int push_common(ctu_streams *st, bool want_signal, int32_t n, const int32_t *ids
         L.consumed = st->next_consumed.data(); L.hsel = st->next_hsel.data(); L.replay = st->replay.h[k];
         if (sh.signal) L.capacity = o.capacity;
         if (sh.vad_rows) L.calls = st->vcalls.h[k];
-        if (!stream_plan_push(sh.g, st->consumed.data(), st->hsel.data(), n, ids, n_samples, sample_off, L)) {
+        if (!stream_plan_push(sh.g, st->consumed.data(), st->hsel.data(), n, ids, n_samples, sample_off, L, from.base)) {
             if (L.over_capacity) return refuse(e, no_room);
             throw std::runtime_error("internal: a push beyond the set's arena");
         }
@@ -535,13 +551,14 @@ int push_common(ctu_streams *st, bool want_signal, int32_t n, const int32_t *ids
         x.n_heads = L.n_heads ? L.n_heads : pl->ext.n_heads;
         x.xstate = st->xstate.p;
         StreamParams sp;
-        sp.push = st->desc.d[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = d_pcm; sp.tiles = pl->tiles.p;
+        sp.push = st->desc.d[k].p; sp.state = st->state.p; sp.carry = st->carry.p; sp.arena = st->arena.p; sp.src = static_cast<const int16_t *>(d_pcm); sp.tiles = pl->tiles.p;
         sp.cstride = sh.cstride; sp.window = d.window; sp.wshift = d.wshift;
         sp.n_tiles = L.tiles; sp.grid = L.grid;
         sp.tile_stream = L.n_heads ? pl->tile_utt.p : nullptr;
         if (L.n_heads) st->heads.upload(k, (size_t)L.n_heads, s);
         HIP_TRY(hipEventRecord(st->ev[0], s));
-        hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)L.slices), dim3(256), 0, s, sp);
+        if (from.wire) launch_stitch_wire(*from.wire, dim3((unsigned)n, (unsigned)L.slices), s, sp);
+        else hipLaunchKernelGGL(stream_stitch_kernel, dim3((unsigned)n, (unsigned)L.slices), dim3(256), 0, s, sp);
         HIP_TRY(hipEventRecord(st->ev[1], s));
         HIP_TRY(hipGetLastError());
         const int rc = !L.tiles ? CTU_OK : sh.signal ? push_signal(st, k, n, L, x, o, s) : push_rows(st, k, n, L, x, o, s);
@@ -562,6 +579,20 @@ int push_common(ctu_streams *st, bool want_signal, int32_t n, const int32_t *ids
     });
 }
 
+// The staging area of the host forms (and the device rows or samples ahead of the download), allocated on first use: n_streams *
+// max_push_samples int16_t, which the host wire forms use by bytes
+void host_stage_alloc(ctu_streams *st) {
+    if (st->h_stage) return;
+    ctu_engine *e = st->eng;
+    const size_t cap = (size_t)st->sh.n_streams * (size_t)st->max_push;
+    st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
+    if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
+    st->d_stage.alloc(cap);
+    // (a stream delivers wshift samples per frame, and a push completes frames out of its own samples and fewer than `window` carried ones)
+    if (st->sh.signal) st->d_sig.alloc((size_t)st->sh.n_streams * ((size_t)st->max_push + (size_t)e->design->window));
+    // (a push that brings a stream's frame wmax + 2 also delivers the rows of the wmax + 1 frames before it)
+    else st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->hp.total_frames + (int64_t)st->sh.n_streams * (st->sh.g.wmax + 1), 1) * e->design->D);
+}
 // The staging half of the host form of a push: the arguments checked, the staging area (and the device rows or samples ahead of the
 // download) allocated on first use, the samples copied and uploaded, st->offs filled
 int host_stage(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *const *h_pcm, const int64_t *n_samples) {
@@ -575,16 +606,7 @@ int host_stage(ctu_streams *st, int32_t n, const int32_t *ids, const int16_t *co
     }
     return guarded(e, [&]() -> int {
         HIP_TRY(hipSetDevice(e->device));
-        const size_t cap = (size_t)st->sh.n_streams * (size_t)st->max_push;
-        if (!st->h_stage) {
-            st->h_stage = static_cast<int16_t *>(ctu_host_alloc(cap * sizeof(int16_t)));
-            if (!st->h_stage) throw std::runtime_error("page-locked staging of a stream set");
-            st->d_stage.alloc(cap);
-            // (a stream delivers wshift samples per frame, and a push completes frames out of its own samples and fewer than `window` carried ones)
-            if (st->sh.signal) st->d_sig.alloc((size_t)st->sh.n_streams * ((size_t)st->max_push + (size_t)e->design->window));
-            // (a push that brings a stream's frame wmax + 2 also delivers the rows of the wmax + 1 frames before it)
-            else st->d_rows.alloc((size_t)std::max<int64_t>(st->plan->hp.total_frames + (int64_t)st->sh.n_streams * (st->sh.g.wmax + 1), 1) * e->design->D);
-        }
+        host_stage_alloc(st);
         int64_t at = 0;
         for (int i = 0; i < n; i++) {
             st->offs[(size_t)i] = at;
@@ -659,6 +681,111 @@ int ctu_streams_push_signal_host(ctu_streams *st, int32_t n, const int32_t *ids,
                                            out_counts, nullptr);
     if (rc != CTU_OK) return rc;
     return host_fetch(st, n, out_counts, h_out, st->d_sig.p, sizeof(int16_t), false, nullptr);
+}
+
+// ---- wire input: the pushes above with the samples read through a ctu_wire_layout (stream_stitch_wire_kernel expands them on their way
+// into the slots; everything behind the stitch works from the push arena and is the plain push's)
+namespace {
+// The layout's own refusals, ahead of everything a push refuses
+int wire_refusal(ctu_streams *st, const ctu_wire_layout *w, const void *buf) {
+    if (const char *m = wire_layout_fault(w, buf)) return refuse(st->eng, std::string("push: ") + m);
+    return CTU_OK;
+}
+// The staging half of the host wire forms: the arguments checked, the covering range of the push uploaded in one copy - from a
+// page-locked buffer as it lies, from a pageable one through the set's page-locked staging - and its first element in *first
+int host_stage_wire(ctu_streams *st, int32_t n, const int32_t *ids, const void *h_in, const int64_t *elem_off, const int64_t *n_samples,
+                    const ctu_wire_layout *w, int64_t *first) {
+    ctu_engine *e = st->eng;
+    if (const int rc = wire_refusal(st, w, h_in); rc != CTU_OK) return rc;
+    if (!push_args_ok(st, n, ids, n_samples)) return refuse(e, "push: bad stream count or null argument");
+    int64_t fresh = 0;
+    for (int i = 0; i < n; i++) {
+        if (!push_count_ok(st, n_samples[i])) return refuse(e, "push: more samples than the set's max_push_samples (or fewer than none)");
+        if (n_samples[i] && (!elem_off || elem_off[i] < 0)) return refuse(e, "push: null or negative element offsets");
+        fresh += n_samples[i];
+    }
+    if (fresh && !h_in) return refuse(e, "push: null sample buffer");
+    const int64_t extent = wire_extent(w, n, elem_off, n_samples, first);
+    const size_t cap = (size_t)st->sh.n_streams * (size_t)st->max_push;
+    if (extent < 0 || (uint64_t)extent > cap)
+        return refuse(e, "push: the covering range of a host wire push is more than n_streams * max_push_samples elements (a sparse layout: the "
+                         "device form or the per-pointer calls)");
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        host_stage_alloc(st);
+        if (extent) {
+            const size_t unit = (size_t)wire_elem_bytes(w->format), bytes = (size_t)extent * unit;
+            const uint8_t *src = static_cast<const uint8_t *>(h_in) + (size_t)*first * unit;
+            if (!is_pinned(src)) {
+                std::memcpy(st->h_stage, src, bytes);
+                src = reinterpret_cast<const uint8_t *>(st->h_stage);
+            }
+            HIP_TRY(hipMemcpyAsync(st->d_stage.p, src, bytes, hipMemcpyHostToDevice, nullptr));
+        }
+        return CTU_OK;
+    });
+}
+// (the upload may still read the caller's buffer when the device form refuses: a host form is synchronised on return)
+int host_wire_done(int rc) {
+    if (rc != CTU_OK) (void)hipStreamSynchronize(nullptr);
+    return rc;
+}
+}  // namespace
+
+int ctu_streams_push_wire(ctu_streams *st, int32_t n, const int32_t *ids, const void *d_in, const int64_t *elem_off, const int64_t *n_samples,
+                          const ctu_wire_layout *w, float *d_rows, int64_t rows_capacity, int64_t *row_counts, uint8_t *d_vad, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    if (const int rc = wire_refusal(st, w, d_in); rc != CTU_OK) return rc;
+    PushOutput o;
+    o.d_rows = d_rows; o.d_vad = d_vad; o.capacity = rows_capacity; o.counts = row_counts;
+    PushSource from;
+    from.wire = w;
+    return push_common(st, false, n, ids, d_in, elem_off, n_samples, o, stream, from);
+}
+
+int ctu_streams_push_signal_wire(ctu_streams *st, int32_t n, const int32_t *ids, const void *d_in, const int64_t *elem_off, const int64_t *n_samples,
+                                 const ctu_wire_layout *w, int16_t *d_out, int64_t out_capacity, int64_t *out_counts, void *stream) {
+    if (!st) return CTU_ERR_INPUT;
+    if (const int rc = wire_refusal(st, w, d_in); rc != CTU_OK) return rc;
+    PushOutput o;
+    o.d_sig = d_out; o.capacity = out_capacity; o.counts = out_counts;
+    PushSource from;
+    from.wire = w;
+    return push_common(st, true, n, ids, d_in, elem_off, n_samples, o, stream, from);
+}
+
+int ctu_streams_push_wire_host(ctu_streams *st, int32_t n, const int32_t *ids, const void *h_in, const int64_t *elem_off, const int64_t *n_samples,
+                               const ctu_wire_layout *w, float *h_rows, int64_t rows_capacity, int64_t *row_counts, uint8_t *h_vad) {
+    if (!st) return CTU_ERR_INPUT;
+    if (const char *m = wrong_call(st, false, h_vad != nullptr, false)) return refuse(st->eng, m);
+    PushSource from;
+    from.wire = w;
+    if (const int rc = host_stage_wire(st, n, ids, h_in, elem_off, n_samples, w, &from.base); rc != CTU_OK) return rc;
+    PushOutput o;  // the device rows hold any push of the set; what the caller's buffer holds is the device form's check
+    o.d_rows = h_rows ? st->d_rows.p : nullptr; o.d_vad = h_vad ? st->vsink.p : nullptr; o.capacity = h_rows ? rows_capacity : 0; o.counts = row_counts;
+    if (const int rc = host_wire_done(push_common(st, false, n, ids, st->d_stage.p, elem_off, n_samples, o, nullptr, from)); rc != CTU_OK) return rc;
+    return host_fetch(st, n, row_counts, h_rows, st->d_rows.p, (size_t)st->eng->design->D * 4, true, h_vad);
+}
+
+int ctu_streams_push_signal_wire_host(ctu_streams *st, int32_t n, const int32_t *ids, const void *h_in, const int64_t *elem_off, const int64_t *n_samples,
+                                      const ctu_wire_layout *w, int16_t *h_out, int64_t out_capacity, int64_t *out_counts) {
+    if (!st) return CTU_ERR_INPUT;
+    if (const char *m = wrong_call(st, true, false, false)) return refuse(st->eng, m);
+    PushSource from;
+    from.wire = w;
+    if (const int rc = host_stage_wire(st, n, ids, h_in, elem_off, n_samples, w, &from.base); rc != CTU_OK) return rc;
+    PushOutput o;  // the device samples hold any push of the set; what the caller's buffer holds is the device form's check
+    o.d_sig = h_out ? st->d_sig.p : nullptr; o.capacity = h_out ? out_capacity : 0; o.counts = out_counts;
+    if (const int rc = host_wire_done(push_common(st, true, n, ids, st->d_stage.p, elem_off, n_samples, o, nullptr, from)); rc != CTU_OK) return rc;
+    return host_fetch(st, n, out_counts, h_out, st->d_sig.p, sizeof(int16_t), false, nullptr);
+}
+
+int64_t ctu_wire_extent(const ctu_wire_layout *w, int32_t n, const int64_t *elem_off, const int64_t *n_samples, int64_t *first) {
+    return wire_extent(w, n, elem_off, n_samples, first);
+}
+
+int64_t ctu_wire_expand(const ctu_wire_layout *w, const void *in, int64_t elem_off, int64_t n_samples, int16_t *out) {
+    return wire_expand(w, in, elem_off, n_samples, out);
 }
 
 int ctu_streams_finish(ctu_streams *st, int32_t id, float *d_rows, int64_t rows_capacity, int64_t *row_count, void *stream) {

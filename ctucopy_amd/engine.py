@@ -30,6 +30,14 @@ class CtuError(RuntimeError):
         self.code = code
 
 
+WIRE_FORMATS = {"s16": 0, "s16_swapped": 1, "alaw": 2, "mulaw": 3}  # CTU_WIRE_*
+
+
+class WireLayout(ctypes.Structure):
+    """ctu_wire_layout: how a stream's new samples lie in a buffer."""
+    _fields_ = [("format", ctypes.c_int32), ("stride", ctypes.c_int32)]
+
+
 class Dims(ctypes.Structure):
     _fields_ = [("fs", ctypes.c_int32), ("window", ctypes.c_int32), ("wshift", ctypes.c_int32),
                 ("wfft", ctypes.c_int32), ("nbins", ctypes.c_int32), ("nbands", ctypes.c_int32),
@@ -51,7 +59,9 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_streams_create_ex", "ctu_streams_config_check_ex", "ctu_streams_pending", "ctu_streams_finish_host", "ctu_streams_rows_step",
            "ctu_streams_push_vad", "ctu_streams_push_vad_host", "ctu_streams_finish_vad", "ctu_streams_finish_vad_host", "ctu_streams_vad_step",
            "ctu_streams_push_signal", "ctu_streams_push_signal_host", "ctu_streams_finish_signal", "ctu_streams_finish_signal_host", "ctu_streams_signal_step",
-           "ctu_streams_vad_rows_step", "ctu_streams_flags_for"]
+           "ctu_streams_vad_rows_step", "ctu_streams_flags_for",
+           "ctu_streams_push_wire", "ctu_streams_push_wire_host", "ctu_streams_push_signal_wire", "ctu_streams_push_signal_wire_host",
+           "ctu_wire_extent", "ctu_wire_expand"]
 
 _lib = None
 
@@ -164,6 +174,16 @@ def load_library():
         L.ctu_streams_vad_rows_step.argtypes = [i32, i32, i32, i32, i32, i64, ctypes.POINTER(i64)]
     if hasattr(L, "ctu_streams_flags_for"):  # (likewise: the flag set a command line needs)
         L.ctu_streams_flags_for.argtypes = [ctypes.c_int, argv_t, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, i64, ctypes.POINTER(i32)]
+    if hasattr(L, "ctu_streams_push_wire"):  # (likewise: wire input)
+        wl = ctypes.POINTER(WireLayout)
+        L.ctu_streams_push_wire.argtypes = [vp, i32, vp, vp, vp, vp, wl, vp, i64, vp, vp, vp]
+        L.ctu_streams_push_wire_host.argtypes = [vp, i32, vp, vp, vp, vp, wl, vp, i64, vp, vp]
+        L.ctu_streams_push_signal_wire.argtypes = [vp, i32, vp, vp, vp, vp, wl, vp, i64, vp, vp]
+        L.ctu_streams_push_signal_wire_host.argtypes = [vp, i32, vp, vp, vp, vp, wl, vp, i64, vp]
+        L.ctu_wire_extent.restype = i64
+        L.ctu_wire_extent.argtypes = [wl, i32, vp, vp, ctypes.POINTER(i64)]
+        L.ctu_wire_expand.restype = i64
+        L.ctu_wire_expand.argtypes = [wl, vp, i64, i64, vp]
     _lib = L
     return L
 
@@ -311,6 +331,42 @@ def streams_signal_step(window, wshift, total):
     if r < 0:
         raise CtuError(int(r), "ctu_streams_signal_step: bad argument")
     return int(r), int(pending.value)
+
+
+def _wire_layout(fmt, stride):
+    """The ctu_wire_layout of a format name (or CTU_WIRE_* number) and a stride; what the library refuses is passed on as it is."""
+    return WireLayout(int(WIRE_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt), int(stride))
+
+
+def _wire_elem_dtype(fmt):
+    return np.uint8 if WIRE_FORMATS.get(fmt, fmt) in (2, 3) else np.int16
+
+
+def wire_extent(elem_off, n_samples, fmt="s16", stride=1):
+    """(elements, first element) of the covering range of a push (ctu_wire_extent): from the lowest element any stream reads to the
+    highest; (0, 0) for a push without samples."""
+    off = np.ascontiguousarray(elem_off, dtype=np.int64)
+    ns = np.ascontiguousarray(n_samples, dtype=np.int64)
+    assert off.size == ns.size
+    w, first = _wire_layout(fmt, stride), ctypes.c_int64(0)
+    r = load_library().ctu_wire_extent(ctypes.byref(w), int(ns.size), off.ctypes.data, ns.ctypes.data, ctypes.byref(first))
+    if r < 0:
+        raise CtuError(int(r), "ctu_wire_extent: bad argument")
+    return int(r), int(first.value)
+
+
+def wire_expand(buf, elem_off, n_samples, fmt="s16", stride=1):
+    """int16 [n_samples]: the samples of a stream whose first is element `elem_off` of the numpy buffer `buf` (ctu_wire_expand)."""
+    buf = np.ascontiguousarray(buf)
+    w = _wire_layout(fmt, stride)
+    n, e0 = int(n_samples), int(elem_off)
+    if n > 0 and e0 >= 0 and w.stride >= 1:
+        assert (e0 + (n - 1) * w.stride + 1) * np.dtype(_wire_elem_dtype(fmt)).itemsize <= buf.nbytes
+    out = np.empty(max(n, 0), dtype=np.int16)
+    r = load_library().ctu_wire_expand(ctypes.byref(w), buf.ctypes.data, e0, n, out.ctypes.data)
+    if r < 0:
+        raise CtuError(int(r), "ctu_wire_expand: bad argument")
+    return out[:int(r)]
 
 
 class Streams:
@@ -497,6 +553,95 @@ class Streams:
         s = stream if stream is not None else torch.cuda.current_stream(out.device)
         self.engine._check(load_library().ctu_streams_finish_signal(self._h, int(sid), out.data_ptr(), out.numel(), ctypes.byref(cnt), s.cuda_stream))
         return int(cnt.value)
+
+    # ---- wire input: G.711 codes, swapped and channel-interleaved PCM as they lie in one buffer (ctu_streams_push_wire*)
+    def _wire_args(self, ids, elem_off, n_samples, fmt, stride, nbytes):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        off = np.ascontiguousarray(elem_off, dtype=np.int64)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int64)
+        w = _wire_layout(fmt, stride)
+        assert ids.size == off.size == ns.size
+        live = ns > 0
+        if w.stride >= 1 and live.any() and (off[live] >= 0).all():  # (what the library refuses is the library's to refuse)
+            last = int((off[live] + (ns[live] - 1) * w.stride).max())
+            assert (last + 1) * np.dtype(_wire_elem_dtype(w.format)).itemsize <= nbytes, "the layout reads past the buffer"
+        return ids, off, ns, w
+
+    def _split(self, ids, counts, *arrays):
+        out, at = {}, 0
+        for k, c in zip(ids.tolist(), counts):
+            part = tuple(a[at:at + int(c)] for a in arrays)
+            out[k] = part if len(part) > 1 else part[0]
+            at += int(c)
+        return out
+
+    def push_wire(self, buf, ids, elem_off, n_samples, fmt="s16", stride=1, want_vad=False):
+        """Host form of a wire push: `buf` one numpy buffer (pageable, or page-locked from host_alloc) of int16 / uint8 elements; sample k
+        of stream ids[i] is element elem_off[i] + k * stride of it, expanded by `fmt` ("s16", "s16_swapped", "alaw", "mulaw").  Returns
+        what push returns: {stream id: float32 [rows, D]}, with want_vad {stream id: (rows, decisions)}."""
+        buf = np.asarray(buf)
+        assert buf.flags["C_CONTIGUOUS"]
+        ids, off, ns, w = self._wire_args(ids, elem_off, n_samples, fmt, stride, buf.nbytes)
+        D, sh = self.engine.dims.row_floats, self.engine.dims.wshift
+        cap = int(sum(int(a) // sh + 1 + self.pending(int(k)) for k, a in zip(ids, ns) if 0 <= k < self.n and a >= 0))
+        rows = np.empty((cap, D), dtype=np.float32)
+        vad = np.zeros(max(cap, 1), dtype=np.uint8)
+        counts = np.zeros(max(ids.size, 1), dtype=np.int64)
+        self.engine._check(load_library().ctu_streams_push_wire_host(self._h, int(ids.size), ids.ctypes.data, buf.ctypes.data, off.ctypes.data, ns.ctypes.data,
+                                                                     ctypes.byref(w), rows.ctypes.data, cap, counts.ctypes.data,
+                                                                     vad.ctypes.data if want_vad else None))
+        return self._split(ids, counts, rows, vad) if want_vad else self._split(ids, counts, rows)
+
+    def push_wire_device(self, ids, buf, elem_off, n_samples, rows, fmt="s16", stride=1, stream=None, vad=None):
+        """Device form: buf a torch CUDA tensor (int16 or uint8 elements) read as push_wire reads its buffer; rows, vad and the result as
+        in push_device."""
+        import torch
+        assert buf.is_cuda and buf.is_contiguous() and rows.is_cuda and rows.dtype == torch.float32
+        ids, off, ns, w = self._wire_args(ids, elem_off, n_samples, fmt, stride, buf.numel() * buf.element_size())
+        counts = np.zeros(max(ids.size, 1), dtype=np.int64)
+        s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+        cap = rows.numel() // self.engine.dims.row_floats
+        if vad is not None:
+            assert vad.is_cuda and vad.dtype == torch.uint8 and vad.numel() >= cap
+        self.engine._check(load_library().ctu_streams_push_wire(self._h, int(ids.size), ids.ctypes.data, buf.data_ptr(), off.ctypes.data, ns.ctypes.data,
+                                                                ctypes.byref(w), rows.data_ptr(), cap, counts.ctypes.data,
+                                                                vad.data_ptr() if vad is not None else None, s.cuda_stream))
+        return counts[:ids.size]
+
+    def push_signal_wire(self, buf, ids, elem_off, n_samples, fmt="s16", stride=1, capacity=None):
+        """Host form of a wire push on a set with signal_state: the buffer as in push_wire, the result as push_signal's."""
+        buf = np.asarray(buf)
+        assert buf.flags["C_CONTIGUOUS"]
+        ids, off, ns, w = self._wire_args(ids, elem_off, n_samples, fmt, stride, buf.nbytes)
+        sh = self.engine.dims.wshift
+        cap = int(sum((int(a) // sh + 1) * sh for a in ns if a >= 0)) if capacity is None else int(capacity)
+        out = np.empty(max(cap, 1), dtype=np.int16)
+        counts = np.zeros(max(ids.size, 1), dtype=np.int64)
+        self.engine._check(load_library().ctu_streams_push_signal_wire_host(self._h, int(ids.size), ids.ctypes.data, buf.ctypes.data, off.ctypes.data,
+                                                                            ns.ctypes.data, ctypes.byref(w), out.ctypes.data, cap, counts.ctypes.data))
+        return self._split(ids, counts, out)
+
+    def push_signal_wire_device(self, ids, buf, elem_off, n_samples, out, fmt="s16", stride=1, stream=None):
+        """Device form: buf as in push_wire_device, out and the result as in push_signal_device."""
+        import torch
+        assert buf.is_cuda and buf.is_contiguous() and out.is_cuda and out.dtype == torch.int16
+        ids, off, ns, w = self._wire_args(ids, elem_off, n_samples, fmt, stride, buf.numel() * buf.element_size())
+        counts = np.zeros(max(ids.size, 1), dtype=np.int64)
+        s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+        self.engine._check(load_library().ctu_streams_push_signal_wire(self._h, int(ids.size), ids.ctypes.data, buf.data_ptr(), off.ctypes.data, ns.ctypes.data,
+                                                                       ctypes.byref(w), out.data_ptr(), out.numel(), counts.ctypes.data, s.cuda_stream))
+        return counts[:ids.size]
+
+    def push_interleaved(self, frames, ids=None, fmt="s16", want_vad=False):
+        """A [samples, channels] numpy block as capture hardware delivers it: channel j goes to stream ids[j] (default j), all of its
+        samples.  One buffer, one upload (push_wire with stride = channels, elem_off = j)."""
+        frames = np.asarray(frames)
+        assert frames.ndim == 2 and frames.flags["C_CONTIGUOUS"]
+        samples, channels = frames.shape
+        ids = np.arange(channels, dtype=np.int32) if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+        assert ids.size == channels
+        return self.push_wire(frames, ids, np.arange(channels, dtype=np.int64), np.full(channels, samples, dtype=np.int64), fmt=fmt, stride=channels,
+                              want_vad=want_vad)
 
     def frames(self, sid):
         """Rows of the current file delivered so far."""

@@ -3,10 +3,12 @@
 //   pipe_take     how many of the samples that wait go into the next push: up to the one that completes the last frame whose index is
 //                 7 (mod 8), so that every push ends a multiple of eight frames into the file - the condition under which the stream's
 //                 rows and samples are those of the offline run bit for bit; at the end of input, all of them
-//   PipeDecoder   bytes in, in reads that end anywhere - inside the WAVE header, in the middle of a sample -, int16 samples out
+//   PipeDecoder   bytes in, in reads that end anywhere - inside the WAVE header, in the middle of a sample -, whole elements out as they
+//                 were read: G.711 codes, 16-bit samples in the input's byte order.  What they are worth is the stream set's to say
+//                 (ctu_streams_push_wire_host with the decoder's layout) - or, for a caller that wants samples, wire_expand's
 //   PipeOut       stdout (no HTK header: out.cc:115-137; raw: the samples alone) or -o's file, whose header is patched at close
-//   run_pipe      read, decode, take, push, write and flush, until the input ends; then the stream's finish
-// Host only.  pipe_take and PipeDecoder call nothing of the engine but the pure ctu_streams_step.
+//   run_pipe      read, accumulate, take, push, write and flush, until the input ends; then the stream's finish
+// Host only.  pipe_take and PipeDecoder call nothing of the engine but the pure ctu_streams_step (and csrc/wire_layout.h, a header).
 #pragma once
 #include <cerrno>
 #include <csignal>
@@ -37,7 +39,11 @@ struct PipeDecoder {
           swap(opts.swap_in && !wave) {
         if (o.format_in != "raw" && !g711 && !wave) throw Fatal("IN: Unknown input file format!");
     }
-    void feed(const uint8_t *p, size_t n, std::vector<int16_t> &out) {
+    // what an element of the accumulated bytes is: a code, or a 16-bit sample in the input's byte order
+    ctu_wire_layout layout() const { return {g711 ? (alaw ? CTU_WIRE_ALAW : CTU_WIRE_MULAW) : swap ? CTU_WIRE_S16_SWAPPED : CTU_WIRE_S16, 1}; }
+    size_t elem_bytes() const { return g711 ? 1 : 2; }
+    // the whole elements of a read, appended to `out` byte for byte
+    void feed_wire(const uint8_t *p, size_t n, std::vector<uint8_t> &out) {
         if (wave && header_have < 44) {
             const size_t k = std::min(n, 44 - header_have);
             std::memcpy(header + header_have, p, k);
@@ -47,23 +53,42 @@ struct PipeDecoder {
             if (header_have < 44) return;
             wave_left = wave_header_data_bytes(o, header) / 2;
         }
+        if (n == 0) return;
         if (g711) {
-            for (size_t i = 0; i < n; i++) out.push_back(g711_to_linear(p[i], alaw));
+            out.insert(out.end(), p, p + n);
             return;
         }
-        for (size_t i = 0; i < n; i++) {
-            if (half < 0) {
-                half = p[i];
-                continue;
-            }
-            const uint16_t v = swap ? (uint16_t)((half << 8) | p[i]) : (uint16_t)(half | (p[i] << 8));
+        size_t at = 0;
+        if (half >= 0) {  // the byte kept from the read before, and the one that completes its sample
+            const uint8_t first = (uint8_t)half;
             half = -1;
-            if (wave && wave_left-- <= 0) {
-                wave_left = 0;
-                continue;
-            }
-            out.push_back((int16_t)v);
+            at = 1;
+            if (take_sample()) out.insert(out.end(), {first, p[0]});
         }
+        size_t whole = (n - at) / 2;
+        if (wave) {
+            const size_t kept = (size_t)std::min<int64_t>((int64_t)whole, wave_left);
+            wave_left -= (int64_t)kept;
+            out.insert(out.end(), p + at, p + at + 2 * kept);
+        } else out.insert(out.end(), p + at, p + at + 2 * whole);
+        at += 2 * whole;
+        if (at < n) half = p[at];
+    }
+    // ... and as samples, for a caller that has no stream set to expand them
+    void feed(const uint8_t *p, size_t n, std::vector<int16_t> &out) {
+        std::vector<uint8_t> raw;
+        feed_wire(p, n, raw);
+        const ctu_wire_layout w = layout();
+        const size_t have = out.size(), more = raw.size() / elem_bytes();
+        out.resize(have + more);
+        wire_expand(&w, raw.data(), 0, (int64_t)more, out.data() + have);
+    }
+    // (a sample past the WAVE header's data size is dropped, as the file reader stops there)
+    bool take_sample() {
+        if (!wave) return true;
+        if (wave_left <= 0) return false;
+        wave_left--;
+        return true;
     }
     // the end of input: a trailing half sample is dropped, as the file reader's n / 2 drops it
     void end() const {
@@ -186,8 +211,11 @@ inline int64_t run_pipe(const PipeJob &job, const ctu::Opts &o, const ctu_dims &
     };
 
     std::vector<uint8_t> bytes(job.read_bytes);
-    std::vector<int16_t> pend;
+    std::vector<uint8_t> pend;  // whole elements read and not yet pushed, as they were read
+    const ctu_wire_layout wire = dec.layout();
+    const size_t unit = dec.elem_bytes();
     const int32_t id = 0;
+    const int64_t from = 0;
     int64_t pushed = 0;
     for (bool eof = false; !eof;) {
         const ssize_t got = ::read(job.fd_in, bytes.data(), bytes.size());
@@ -195,16 +223,17 @@ inline int64_t run_pipe(const PipeJob &job, const ctu::Opts &o, const ctu_dims &
         if (got < 0) throw Fatal("IN: Cannot read data file!");
         eof = got == 0;
         if (eof) dec.end();
-        else dec.feed(bytes.data(), (size_t)got, pend);
-        if (eof && ctu_num_frames(eng, pushed + (int64_t)pend.size()) < 0) throw Fatal("IO: Signal shorter than one frame!");
-        const int64_t take = pipe_take(d.window, d.wshift, pushed, (int64_t)pend.size(), eof);
+        else dec.feed_wire(bytes.data(), (size_t)got, pend);
+        const int64_t waiting = (int64_t)(pend.size() / unit);
+        if (eof && ctu_num_frames(eng, pushed + waiting) < 0) throw Fatal("IO: Signal shorter than one frame!");
+        const int64_t take = pipe_take(d.window, d.wshift, pushed, waiting, eof);
         if (take == 0) continue;
-        const int16_t *src = pend.data();
-        int64_t cnt = 0;
-        const int rc = signal ? ctu_streams_push_signal_host(set.get(), 1, &id, &src, &take, h_sig, sig_cap, &cnt)
-                              : ctu_streams_push_vad_host(set.get(), 1, &id, &src, &take, h_rows, row_cap, &cnt, with_vad ? h_vad.data() : nullptr);
+        int64_t cnt = 0;  // the elements go up as read: the set expands codes and swaps bytes where it stitches them in
+        const int rc = signal ? ctu_streams_push_signal_wire_host(set.get(), 1, &id, pend.data(), &from, &take, &wire, h_sig, sig_cap, &cnt)
+                              : ctu_streams_push_wire_host(set.get(), 1, &id, pend.data(), &from, &take, &wire, h_rows, row_cap, &cnt,
+                                                           with_vad ? h_vad.data() : nullptr);
         if (rc != CTU_OK) throw Fatal(ctu_last_error(eng));
-        pend.erase(pend.begin(), pend.begin() + take);
+        pend.erase(pend.begin(), pend.begin() + take * (int64_t)unit);
         pushed += take;
         deliver(cnt);
     }

@@ -418,6 +418,59 @@ int64_t ctu_streams_vad_rows_step(int32_t window, int32_t wshift, int32_t filter
  * and its tails (with row state: and the row kernels behind them; with detector state: and the replay), ms3[2] stream_carry_kernel (and stream_rows_carry_kernel; trap state: stream_trap_kernel is in ms3[1]).  Blocks until that push has finished. */
 int ctu_streams_last_push_ms(ctu_streams *, float *ms3);
 
+/* ---- wire input: G.711 codes, byte-swapped and channel-interleaved PCM pushed as the caller holds them ----------------------------
+ * What a push accepts beside native-endian int16_t, contiguous per stream: telephony arrives as G.711 codes, a network or a file may
+ * hand over the other byte order, and capture hardware - a TDM trunk, a multichannel sound card, a microphone array - delivers frames
+ * of [sample][channel].  A ctu_wire_layout says how the new samples of every stream of a push lie in one buffer, and the four calls
+ * below are ctu_streams_push_vad (ctu_streams_push with a NULL vad buffer) and ctu_streams_push_signal, device and host form, with the
+ * samples expanded to int16_t on their way into the set: stream_stitch_wire_kernel reads the caller's buffer where stream_stitch_kernel
+ * reads d_pcm, so the expansion costs no launch and no pass through memory of its own.
+ *
+ * Sample k of stream stream_ids[i] is element elem_off[i] + k * stride of the buffer, k < n_samples[i].  Offsets count elements of the
+ * format - 2 bytes for the S16 formats, 1 byte for G.711 - from d_in / h_in.  stride = 1 is a contiguous run, stride = the number of
+ * channels with elem_off = the channel an interleaved block.  The ranges of different streams may interleave or overlap; the buffer is
+ * only read, and only at the elements named.  CTU_WIRE_S16 is the sample as it lies, CTU_WIRE_S16_SWAPPED exchanges the two bytes of an
+ * element, CTU_WIRE_ALAW / CTU_WIRE_MULAW is the expansion of src/io/amulaw.h:20-53, which ctu_decode_g711 computes.
+ *
+ * Kept: everything.  Rows, decisions, samples and counts are bit for bit those the plain call delivers for the same expanded samples, and
+ * so are ctu_streams_frames / ctu_streams_pending and every later push and finish, for every flag set a set can be created with - the
+ * wire calls add no flag, and ctu_streams_flags_for and the config checks answer as before.  What a set keeps of a stream is int16_t
+ * either way, so wire and plain pushes may alternate on one stream.  ctu_streams_last_push_ms reports stream_stitch_wire_kernel in ms3[0].
+ *
+ * Refused with CTU_ERR_INPUT before anything is launched or changed, in words that name the fault: a NULL layout, a format outside
+ * CTU_WIRE_S16 .. CTU_WIRE_MULAW, a stride below 1, a negative offset of a stream with samples, a buffer of 16-bit elements that is not
+ * 2-byte aligned - and everything the plain call refuses: repeats, foreign ids, more than max_push_samples, too little room, the wrong
+ * family of call for the set, a vad buffer on a set without detector state.  CTU_ERR_DEVICE is what it is for the plain pushes.
+ *
+ * The host forms take one buffer, not one pointer per stream.  They upload the covering range of the push - from the lowest element any
+ * of its streams reads to the highest, ctu_wire_extent - in one copy, a page-locked buffer (ctu_host_alloc) as it lies, a pageable one
+ * through the set's page-locked staging, and run the device form on it; they are synchronised on return.  A covering range of more than
+ * n_streams * max_push_samples elements is CTU_ERR_INPUT: that is the staging a set owns for the per-pointer host forms, so the wire
+ * forms add no memory to a set.  A layout that sparse - a few channels out of a long interleaved block - belongs to the device form,
+ * which reads nothing but the elements named, or to the per-pointer calls. */
+enum { CTU_WIRE_S16 = 0, CTU_WIRE_S16_SWAPPED = 1, CTU_WIRE_ALAW = 2, CTU_WIRE_MULAW = 3 };
+typedef struct {
+    int32_t format;   /* CTU_WIRE_*: the element type; an element is 2 bytes for the S16 formats, 1 byte for G.711 */
+    int32_t stride;   /* elements from one sample of a stream to its next: 1 = contiguous, n_channels = interleaved */
+} ctu_wire_layout;
+int ctu_streams_push_wire(ctu_streams *, int32_t n, const int32_t *stream_ids, const void *d_in, const int64_t *elem_off,
+                          const int64_t *n_samples, const ctu_wire_layout *, float *d_rows, int64_t rows_capacity, int64_t *row_counts,
+                          uint8_t *d_vad /* may be NULL */, void *stream);
+int ctu_streams_push_wire_host(ctu_streams *, int32_t n, const int32_t *stream_ids, const void *h_in, const int64_t *elem_off,
+                               const int64_t *n_samples, const ctu_wire_layout *, float *h_rows, int64_t rows_capacity, int64_t *row_counts,
+                               uint8_t *h_vad /* may be NULL */);
+int ctu_streams_push_signal_wire(ctu_streams *, int32_t n, const int32_t *stream_ids, const void *d_in, const int64_t *elem_off,
+                                 const int64_t *n_samples, const ctu_wire_layout *, int16_t *d_out, int64_t out_capacity, int64_t *out_counts,
+                                 void *stream);
+int ctu_streams_push_signal_wire_host(ctu_streams *, int32_t n, const int32_t *stream_ids, const void *h_in, const int64_t *elem_off,
+                                      const int64_t *n_samples, const ctu_wire_layout *, int16_t *h_out, int64_t out_capacity, int64_t *out_counts);
+/* The covering range of a push (pure): its length in elements, 0 for a push without samples, and in *first (may be NULL) its first
+ * element.  Streams without samples are not looked at.  CTU_ERR_INPUT for a bad layout, a negative count or a negative offset. */
+int64_t ctu_wire_extent(const ctu_wire_layout *, int32_t n, const int64_t *elem_off, const int64_t *n_samples, int64_t *first);
+/* The expansion on the host (pure): samples k < n_samples of a stream whose first is element elem_off of `in`, written to out[k].
+ * Returns n_samples, or CTU_ERR_INPUT for a bad layout, a negative count or offset, or a NULL buffer with samples to expand. */
+int64_t ctu_wire_expand(const ctu_wire_layout *, const void *in, int64_t elem_off, int64_t n_samples, int16_t *out);
+
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53
  * (alaw2lin, called from src/io/in.cc:481-560) bit for bit.  The caller lays the codes of an utterance at the same offsets
  * as its samples (ctu_plan_sample_offsets) and may decode the whole arena at once.  Asynchronous on `stream`. */
