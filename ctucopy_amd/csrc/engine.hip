@@ -24,6 +24,8 @@
 //   stream_plan.h      streaming input, host only and HIP-free: the descriptors of a push and the planner that fills them (slots, chains, rows)
 //   stream_set_shape.h streaming input, host only and HIP-free: what a stream set is - its kinds of state, halo, strides, the size of every buffer
 //   streams_host.h     streaming input, host side: the stream set, create by the shape / one push body (check, plan, commit, launch) / finish
+//   wire_in_kernels.h  offline wire input: a plan's utterances out of G.711 codes, swapped and strided PCM into its arena, dealt in pieces of the arena
+//   wire_plan.h        offline wire input, host only and HIP-free: the bound check ahead of that launch, its pieces, the bytes a range uploads
 //
 // Data layout in HBM
 //   pcm   : one packed int16 arena; utterance i starts at sample_off[i] (multiple of 8 samples)
@@ -39,8 +41,10 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <map>
 #include <set>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/ctu_engine.h"
@@ -66,6 +70,7 @@
 #include "stream_kernels.h"
 #include "stream_set_shape.h"
 #include "wire_layout.h"
+#include "wire_in_kernels.h"
 
 namespace {
 
@@ -191,9 +196,19 @@ struct ctu_plan {
     DevBuf<int> ring_src;              // [total_frames]
     DevBuf<float> ring_tmp;            // [total_frames][D]
     hipStream_t part_stream[2] = {nullptr, nullptr};
+    // wire input (ctu_plan_unpack_wire), made by the first call: the lengths, the arena offsets where the plan's stages keep none
+    // (d_sample_off) and the pieces of wire_unpack_kernel on the device; the element offsets of a call and the page-locked staging they go
+    // up from, which the next call reuses once the copy behind wire_free has read it; host-buffer runs: the device copy of the wire bytes
+    DevBuf<long long> wire_n, wire_off, wire_elem;
+    DevBuf<int> wire_piece;
+    DevBuf<uint8_t> h_wire;
+    long long *wire_stage = nullptr;
+    hipEvent_t wire_free = nullptr;
     ~ctu_plan() {
         for (hipStream_t st : part_stream)
             if (st) (void)hipStreamDestroy(st);
+        if (wire_free) (void)hipEventDestroy(wire_free);
+        if (wire_stage) (void)hipHostFree(wire_stage);
     }
     DevBuf<int> tile_utt;            // utterance of every tile (SS); the stream of every tile (a stream set with noise state)
     DevBuf<float> ss_seed, ss_last;  // SS: noise seeds per utterance [n_utt][K] and the vectors the utterances leave behind
@@ -1196,6 +1211,11 @@ struct HostInput {
     // with the VAD only (else empty): hands a range, which starts at utterance `first`, its share of the caller's majority-filter ring ...
     std::function<int(ctu_plan *sub, int first)> ring;
     std::function<void(const ctu_plan *, int64_t row0)> vad;  // ... and fetches a finished (sub)plan's bytes, which start at row `row0`
+    // wire input only (else empty / negative): which bytes of the caller's buffer a (sub)plan that starts at utterance `first` uploads - the
+    // covering range of its utterances, not a slice of an arena; called ahead of `stage` - and the bytes the 32 MiB rule judges the run by
+    std::function<std::pair<const char *, size_t>(ctu_plan *sub, int first)> range;
+    int64_t judged_bytes = -1;
+    std::function<void(ctu_plan *)> prepare;  // what every (sub)plan needs on the device ahead of the walk, so that no range allocates inside it
 };
 
 // (start, stop) of every range's front-end launch; destroyed on every way out of the run
@@ -1230,12 +1250,14 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
     const int D = e->design->D;
     HIP_TRY(hipSetDevice(e->device));
     const bool pin_in = is_pinned(in.base), pin_out = is_pinned(h_rows);
-    const int nparts = host_chunks(e, pl, pl->hp.total_samples * (int64_t)in.elem, pin_in && pin_out);
+    const int nparts = host_chunks(e, pl, in.judged_bytes >= 0 ? in.judged_bytes : pl->hp.total_samples * (int64_t)in.elem, pin_in && pin_out);
     if (const int rc = split_host_parts(e, pl, nparts); rc != CTU_OK) return rc;
     const bool ranges = nparts > 1 && pl->parts.size() > 1;
     const int np = ranges ? (int)pl->parts.size() : 1;
     auto part = [&](int k) { return ranges ? pl->parts[k].get() : pl; };
     auto first = [&](int k) { return ranges ? pl->part_first[k] : 0; };
+    if (in.prepare)
+        for (int k = 0; k < np; k++) in.prepare(part(k));
     const hipStream_t st[2] = {ranges ? pl->part_stream[0] : nullptr, ranges ? pl->part_stream[1] : nullptr};
     RangeEvents events;
     auto download = [&](int k) {
@@ -1255,12 +1277,14 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
             if (rc != CTU_OK) return rc;
         }
         if (sp->ext.total_frames) {
-            void *d_in = in.stage(sp);
-            sp->h_rows.reserve((size_t)sp->ext.total_frames * D);
             // a part's arena is the slice of the caller's that starts `head` elements ahead of its first utterance (split_host_parts)
             const char *src = static_cast<const char *>(in.base) + (pl->hp.sample_off[first(k)] - in.head) * (int64_t)in.elem;
-            if (pin_in) HIP_TRY(hipMemcpyAsync(d_in, src, (size_t)sp->hp.total_samples * in.elem, hipMemcpyHostToDevice, st[k & 1]));
-            else HIP_TRY(hipMemcpy(d_in, src, (size_t)sp->hp.total_samples * in.elem, hipMemcpyHostToDevice));
+            size_t bytes = (size_t)sp->hp.total_samples * in.elem;
+            if (in.range) std::tie(src, bytes) = in.range(sp, first(k));
+            void *d_in = in.stage(sp);
+            sp->h_rows.reserve((size_t)sp->ext.total_frames * D);
+            if (pin_in) HIP_TRY(hipMemcpyAsync(d_in, src, bytes, hipMemcpyHostToDevice, st[k & 1]));
+            else HIP_TRY(hipMemcpy(d_in, src, bytes, hipMemcpyHostToDevice));
             const int rc = in.run(sp, st[k & 1]);
             if (rc != CTU_OK) {  // earlier ranges are still in flight on the two streams: drain them before the caller reuses its buffers
                 if (ranges) {
@@ -1287,31 +1311,12 @@ int run_host_ranges(ctu_engine *e, ctu_plan *pl, const HostInput &in, float *h_r
 }
 }  // namespace
 
-int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm, float *h_rows, uint8_t *h_vad,
-                        int64_t *rows_per_utt) {
-    if (!e || !pl_ || pl_->eng != e) return CTU_ERR_INPUT;
-    if (e->geom.rows_in) {
-        set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows_host");
-        return CTU_ERR_INPUT;
-    }
-    ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
+// The host-buffer run of a plan over samples behind its checks (ctu_engine_run_host, ctu_engine_run_wire_host): `in` says what goes up and
+// how a range runs; the VAD's bytes, -vad_apply_mode drop and rows_per_utt are one statement for both.
+static int run_host_samples(ctu_engine *e, ctu_plan *pl, HostInput &in, float *h_rows, uint8_t *h_vad, int64_t *rows_per_utt) {
     const ctu::Design &d = *e->design;
-    if (rows_per_utt)
-        for (int i = 0; i < pl->hp.n_utt; i++) rows_per_utt[i] = pl->hp.frames[i];
-    if (pl->ext.total_frames == 0) return CTU_OK;
-    if (!h_pcm || !h_rows) {
-        set_error(e, "ENGINE: null host buffer");
-        return CTU_ERR_INPUT;
-    }
     return guarded(e, [&]() -> int {
         std::vector<uint8_t> v(e->geom.do_vad ? (size_t)pl->ext.total_frames : 0);
-        HostInput in{h_pcm, sizeof(int16_t), PCM_HEAD};
-        in.stage = [&](ctu_plan *p) {
-            p->h_pcm.reserve((size_t)p->hp.total_samples);
-            if (e->geom.do_vad) p->h_vad.reserve((size_t)p->ext.total_frames);
-            return p->h_pcm.p;
-        };
-        in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run(e, p, p->h_pcm.p, p->h_rows.p, p->h_vad.p, s); };
         if (e->geom.do_vad) {
             in.ring = [&](ctu_plan *sub, int first) { return ctu_plan_set_vad_ring(sub, pl->ring_hidx.empty() ? nullptr : pl->ring_hidx.data() + first); };
             in.vad = [&](const ctu_plan *p, int64_t row0) { HIP_TRY(hipMemcpy(v.data() + row0, p->h_vad.p, (size_t)p->ext.total_frames, hipMemcpyDeviceToHost)); };
@@ -1340,6 +1345,31 @@ int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm
         }
         return CTU_OK;
     });
+}
+
+int ctu_engine_run_host(ctu_engine *e, const ctu_plan *pl_, const int16_t *h_pcm, float *h_rows, uint8_t *h_vad,
+                        int64_t *rows_per_utt) {
+    if (!e || !pl_ || pl_->eng != e) return CTU_ERR_INPUT;
+    if (e->geom.rows_in) {
+        set_error(e, "ENGINE: this configuration starts from feature files (-format_in htk): use ctu_engine_run_rows_host");
+        return CTU_ERR_INPUT;
+    }
+    ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
+    if (rows_per_utt)
+        for (int i = 0; i < pl->hp.n_utt; i++) rows_per_utt[i] = pl->hp.frames[i];
+    if (pl->ext.total_frames == 0) return CTU_OK;
+    if (!h_pcm || !h_rows) {
+        set_error(e, "ENGINE: null host buffer");
+        return CTU_ERR_INPUT;
+    }
+    HostInput in{h_pcm, sizeof(int16_t), PCM_HEAD};
+    in.stage = [&](ctu_plan *p) {
+        p->h_pcm.reserve((size_t)p->hp.total_samples);
+        if (e->geom.do_vad) p->h_vad.reserve((size_t)p->ext.total_frames);
+        return p->h_pcm.p;
+    };
+    in.run = [&](ctu_plan *p, hipStream_t s) { return ctu_engine_run(e, p, p->h_pcm.p, p->h_rows.p, p->h_vad.p, s); };
+    return run_host_samples(e, pl, in, h_rows, h_vad, rows_per_utt);
 }
 
 // ---- runs that start from rows (-format_in htk) ------------------------------------------------------------------------------
@@ -1546,6 +1576,169 @@ int ctu_engine_run_signal_host(ctu_engine *e, const ctu_plan *pl, const int16_t 
         if (rc != CTU_OK) return rc;
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(h_out, out.p, (size_t)pl->hp.total_samples * 2, hipMemcpyDeviceToHost));
+        return CTU_OK;
+    });
+}
+
+// ---- offline wire input: a plan's utterances out of G.711 codes, swapped and channel-interleaved PCM (wire_in_kernels.h, wire_plan.h)
+namespace {
+// What the three wire calls refuse before anything is launched, uploaded or written.  `rows_call`: the call to use on an engine over rows.
+int wire_run_refusal(ctu_engine *e, const ctu_plan *pl, const void *buf, const int64_t *elem_off, const ctu_wire_layout *w, const char *rows_call) {
+    if (pl->eng != e) {
+        set_error(e, "wire: a plan of another engine");
+        return CTU_ERR_INPUT;
+    }
+    if (e->geom.rows_in) {
+        set_error(e, std::string("ENGINE: this configuration starts from feature files (-format_in htk): use ") + rows_call);
+        return CTU_ERR_INPUT;
+    }
+    const std::string why = wire_unpack_fault(w, buf, pl->hp.n_utt, pl->hp.nsamples.data(), elem_off);
+    if (!why.empty()) {
+        set_error(e, why);
+        return CTU_ERR_INPUT;
+    }
+    return CTU_OK;
+}
+bool plan_has_samples(const ctu_plan *pl) {
+    for (int64_t n : pl->hp.nsamples)
+        if (n > 0) return true;
+    return false;
+}
+// What the plan keeps on the device for wire_unpack_kernel, made by the first call (throws)
+void wire_prepare(ctu_plan *pl) {
+    if (pl->wire_free) return;
+    pl->wire_n.upload(pl->hp.nsamples);
+    if (!pl->d_sample_off.p) pl->wire_off.upload(pl->hp.sample_off);
+    pl->wire_piece.upload(wire_pieces(pl->hp.sample_off.data(), pl->hp.n_utt));
+    pl->wire_elem.alloc((size_t)pl->hp.n_utt);
+    if (!pl->wire_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&pl->wire_stage), (size_t)pl->hp.n_utt * sizeof(long long), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&pl->wire_free, hipEventDisableTiming));
+}
+// The launch behind the checks (throws): element offsets up from the plan's staging, stream-ordered; wire_unpack_kernel by the layout
+void wire_unpack(ctu_engine *e, ctu_plan *pl, const void *d_in, const int64_t *elem_off, const ctu_wire_layout &w, int16_t *d_pcm, hipStream_t s) {
+    HIP_TRY(hipSetDevice(e->device));
+    wire_prepare(pl);
+    HIP_TRY(hipEventSynchronize(pl->wire_free));  // the copy of the previous call has read the staging
+    for (int i = 0; i < pl->hp.n_utt; i++) pl->wire_stage[i] = pl->hp.nsamples[i] > 0 ? elem_off[i] : 0;
+    HIP_TRY(hipMemcpyAsync(pl->wire_elem.p, pl->wire_stage, (size_t)pl->hp.n_utt * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(pl->wire_free, s));
+    WireUnpack p;
+    p.src = d_in;
+    p.elem_off = pl->wire_elem.p;
+    p.sample_off = pl->d_sample_off.p ? pl->d_sample_off.p : pl->wire_off.p;
+    p.nsamples = pl->wire_n.p;
+    p.piece_first = pl->wire_piece.p;
+    p.pcm = d_pcm;
+    p.stride = w.stride;
+    const unsigned pieces = (unsigned)(pl->wire_piece.n - 1);
+    lift<CTU_WIRE_S16, CTU_WIRE_S16_SWAPPED, CTU_WIRE_ALAW, CTU_WIRE_MULAW>(w.format, [&](auto fmt) {
+        lift<0, 1>(w.stride != 1, [&](auto strided) {
+            hipLaunchKernelGGL((wire_unpack_kernel<decltype(fmt)::value, decltype(strided)::value != 0>), dim3(pieces), dim3(256), 0, s, p);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+}
+}  // namespace
+
+int ctu_plan_unpack_wire(ctu_engine *e, const ctu_plan *pl_, const void *d_in, const int64_t *elem_off, const ctu_wire_layout *w, int16_t *d_pcm,
+                         void *stream) {
+    if (!e || !pl_) return CTU_ERR_INPUT;
+    if (const int rc = wire_run_refusal(e, pl_, d_in, elem_off, w, "ctu_engine_run_rows"); rc != CTU_OK) return rc;
+    if (!plan_has_samples(pl_)) return CTU_OK;
+    if (!d_pcm) {
+        set_error(e, "ENGINE: null device buffer");
+        return CTU_ERR_INPUT;
+    }
+    ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the staging lives in the plan
+    return guarded(e, [&]() -> int {
+        wire_unpack(e, pl, d_in, elem_off, *w, d_pcm, (hipStream_t)stream);
+        return CTU_OK;
+    });
+}
+
+int ctu_engine_run_wire_host(ctu_engine *e, const ctu_plan *pl_, const void *h_in, const int64_t *elem_off, const ctu_wire_layout *w, float *h_rows,
+                             uint8_t *h_vad, int64_t *rows_per_utt) {
+    if (!e || !pl_) return CTU_ERR_INPUT;
+    if (const int rc = wire_run_refusal(e, pl_, h_in, elem_off, w, "ctu_engine_run_rows_host"); rc != CTU_OK) return rc;
+    if (e->design->signal_out) {
+        set_error(e, "ENGINE: this configuration writes speech (-format_out raw|wave): use ctu_engine_run_signal_wire_host");
+        return CTU_ERR_INPUT;
+    }
+    ctu_plan *pl = const_cast<ctu_plan *>(pl_);  // the device copies live in the plan
+    if (pl->ext.total_frames && !h_rows) {
+        set_error(e, "ENGINE: null host buffer");
+        return CTU_ERR_INPUT;
+    }
+    if (rows_per_utt)
+        for (int i = 0; i < pl->hp.n_utt; i++) rows_per_utt[i] = pl->hp.frames[i];
+    if (pl->ext.total_frames == 0) return CTU_OK;
+    const size_t unit = (size_t)wire_elem_bytes(w->format);
+    const int64_t *ns = pl->hp.nsamples.data();
+    struct Part {
+        std::vector<int64_t> rel;  // the utterances' offsets from the first element the part uploads
+        size_t bytes = 0;
+    };
+    std::map<const ctu_plan *, Part> parts;
+    HostInput in{h_in, unit, 0};
+    in.judged_bytes = wire_part_range(w, 0, pl->hp.n_utt, ns, elem_off, nullptr, nullptr) * (int64_t)unit;
+    in.range = [&](ctu_plan *p, int first) {
+        Part &pt = parts[p];
+        pt.rel.resize((size_t)p->hp.n_utt);
+        int64_t lo = 0;
+        pt.bytes = (size_t)wire_part_range(w, first, first + p->hp.n_utt, ns, elem_off, &lo, pt.rel.data()) * unit;
+        return std::make_pair(static_cast<const char *>(h_in) + lo * (int64_t)unit, pt.bytes);
+    };
+    in.stage = [&](ctu_plan *p) {
+        p->h_wire.reserve(parts[p].bytes);
+        p->h_pcm.reserve((size_t)p->hp.total_samples);
+        if (e->geom.do_vad) p->h_vad.reserve((size_t)p->ext.total_frames);
+        return p->h_wire.p;
+    };
+    in.prepare = [&](ctu_plan *p) {
+        if (p->ext.total_frames) wire_prepare(p);
+    };
+    in.run = [&](ctu_plan *p, hipStream_t s) {
+        wire_unpack(e, p, p->h_wire.p, parts[p].rel.data(), *w, p->h_pcm.p, s);
+        return ctu_engine_run(e, p, p->h_pcm.p, p->h_rows.p, p->h_vad.p, s);
+    };
+    return run_host_samples(e, pl, in, h_rows, h_vad, rows_per_utt);
+}
+
+int ctu_engine_run_signal_wire_host(ctu_engine *e, const ctu_plan *pl_, const void *h_in, const int64_t *elem_off, const ctu_wire_layout *w,
+                                    int16_t *h_out) {
+    if (!e || !pl_) return CTU_ERR_INPUT;
+    if (const int rc = wire_run_refusal(e, pl_, h_in, elem_off, w, "ctu_engine_run_rows_host"); rc != CTU_OK) return rc;
+    if (!e->design->signal_out) {
+        set_error(e, "ENGINE: ctu_engine_run_signal_wire_host needs -format_out raw|wave");
+        return CTU_ERR_INPUT;
+    }
+    ctu_plan *pl = const_cast<ctu_plan *>(pl_);
+    if (pl->hp.n_utt == 0) return CTU_OK;
+    if (!h_out) {
+        set_error(e, "ENGINE: null host buffer");
+        return CTU_ERR_INPUT;
+    }
+    return guarded(e, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        const size_t unit = (size_t)wire_elem_bytes(w->format), total = (size_t)pl->hp.total_samples;
+        std::vector<int64_t> rel((size_t)pl->hp.n_utt);
+        int64_t lo = 0;
+        const size_t bytes = plan_has_samples(pl) ? (size_t)wire_part_range(w, 0, pl->hp.n_utt, pl->hp.nsamples.data(), elem_off, &lo, rel.data()) * unit : 0;
+        DevBuf<uint8_t> wire;
+        DevBuf<int16_t> pcm, out;
+        wire.alloc(bytes);
+        pcm.alloc(total);
+        out.alloc(total);
+        HIP_TRY(hipMemset(pcm.p, 0, total * 2));
+        HIP_TRY(hipMemset(out.p, 0, total * 2));
+        if (bytes) {
+            HIP_TRY(hipMemcpy(wire.p, static_cast<const char *>(h_in) + lo * (int64_t)unit, bytes, hipMemcpyHostToDevice));
+            wire_unpack(e, pl, wire.p, rel.data(), *w, pcm.p, nullptr);
+        }
+        const int rc = ctu_engine_run_signal(e, pl, pcm.p, out.p, nullptr);
+        if (rc != CTU_OK) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(h_out, out.p, total * 2, hipMemcpyDeviceToHost));
         return CTU_OK;
     });
 }

@@ -61,7 +61,8 @@ EXPORTS = ["ctu_engine_create", "ctu_engine_destroy", "ctu_create_error", "ctu_l
            "ctu_streams_push_signal", "ctu_streams_push_signal_host", "ctu_streams_finish_signal", "ctu_streams_finish_signal_host", "ctu_streams_signal_step",
            "ctu_streams_vad_rows_step", "ctu_streams_flags_for",
            "ctu_streams_push_wire", "ctu_streams_push_wire_host", "ctu_streams_push_signal_wire", "ctu_streams_push_signal_wire_host",
-           "ctu_wire_extent", "ctu_wire_expand"]
+           "ctu_wire_extent", "ctu_wire_expand",
+           "ctu_plan_unpack_wire", "ctu_engine_run_wire_host", "ctu_engine_run_signal_wire_host"]
 
 _lib = None
 
@@ -184,6 +185,11 @@ def load_library():
         L.ctu_wire_extent.argtypes = [wl, i32, vp, vp, ctypes.POINTER(i64)]
         L.ctu_wire_expand.restype = i64
         L.ctu_wire_expand.argtypes = [wl, vp, i64, i64, vp]
+    if hasattr(L, "ctu_plan_unpack_wire"):  # (likewise: wire input of offline runs)
+        wl = ctypes.POINTER(WireLayout)
+        L.ctu_plan_unpack_wire.argtypes = [vp, vp, vp, vp, wl, vp, vp]
+        L.ctu_engine_run_wire_host.argtypes = [vp, vp, vp, vp, wl, vp, vp, vp]
+        L.ctu_engine_run_signal_wire_host.argtypes = [vp, vp, vp, vp, wl, vp]
     _lib = L
     return L
 
@@ -798,6 +804,83 @@ class Engine:
         s = stream if stream is not None else torch.cuda.current_stream(pcm.device)
         self._check(load_library().ctu_engine_run_signal(self._h, plan._h, pcm.data_ptr(), out.data_ptr(), s.cuda_stream))
         return out
+
+    # ---- wire input of offline runs: G.711 codes, swapped and channel-interleaved PCM as they lie in one buffer (ctu_plan_unpack_wire)
+    def _wire_plan_args(self, plan, elem_off, fmt, stride, nbytes):
+        off = np.ascontiguousarray(elem_off, dtype=np.int64)
+        w = _wire_layout(fmt, stride)
+        assert off.size == plan.n_utt
+        live = plan.nsamples > 0
+        if w.stride >= 1 and w.format in WIRE_FORMATS.values() and live.any() and (off[live] >= 0).all():  # (what the library refuses is the library's to refuse)
+            last = (off[live].astype(object) + (plan.nsamples[live].astype(object) - 1) * w.stride).max()
+            if last < 2 ** 62:
+                assert (int(last) + 1) * np.dtype(_wire_elem_dtype(w.format)).itemsize <= nbytes, "the layout reads past the buffer"
+        return off, w
+
+    def unpack_wire_device(self, plan, buf, elem_off, fmt="s16", stride=1, pcm=None, stream=None):
+        """buf: torch CUDA tensor of int16 / uint8 elements; sample k of utterance i of `plan` is element elem_off[i] + k * stride of it,
+        expanded by `fmt` ("s16", "s16_swapped", "alaw", "mulaw") into the plan's arena `pcm` (torch int16 CUDA tensor
+        [plan.total_samples], made when None; only the utterances' samples are written).  Returns pcm (async): run_device /
+        enhance_device take it."""
+        import torch
+        assert buf.is_cuda and buf.is_contiguous()
+        off, w = self._wire_plan_args(plan, elem_off, fmt, stride, buf.numel() * buf.element_size())
+        if pcm is None:
+            pcm = torch.zeros(plan.total_samples, dtype=torch.int16, device=buf.device)
+        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.numel() >= plan.total_samples
+        s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+        self._check(load_library().ctu_plan_unpack_wire(self._h, plan._h, buf.data_ptr(), off.ctypes.data, ctypes.byref(w), pcm.data_ptr(),
+                                                        s.cuda_stream))
+        return pcm
+
+    def run_wire_host(self, plan, buf, elem_off, fmt="s16", stride=1, want_vad=False, rows_out=None):
+        """run_host with the utterances read out of the numpy buffer `buf` (pageable, or page-locked from host_alloc) through a wire
+        layout (ctu_engine_run_wire_host): the wire bytes go up, the device expands them."""
+        buf = np.asarray(buf)
+        assert buf.flags["C_CONTIGUOUS"]
+        off, w = self._wire_plan_args(plan, elem_off, fmt, stride, buf.nbytes)
+        rows = rows_out if rows_out is not None else np.empty((plan.total_frames, self.dims.row_floats), dtype=np.float32)
+        per = np.zeros(plan.n_utt, dtype=np.int64)
+        vad = np.zeros(max(plan.total_frames, 1), dtype=np.uint8)
+        self._check(load_library().ctu_engine_run_wire_host(self._h, plan._h, buf.ctypes.data, off.ctypes.data, ctypes.byref(w), rows.ctypes.data,
+                                                            vad.ctypes.data if self.dims.has_vad else None, per.ctypes.data))
+        if want_vad:
+            return rows, vad[:plan.total_frames], per
+        return rows
+
+    def extract_wire(self, buf, elem_off, n_samples, fmt="s16", stride=1, want_vad=False):
+        """extract with utterance i the n_samples[i] samples that start at element elem_off[i] of `buf`, `stride` elements apart: list of
+        [rows, D] float32 arrays (and the VAD byte strings)."""
+        plan = self.plan(n_samples)
+        rows, vad, per = self.run_wire_host(plan, buf, elem_off, fmt=fmt, stride=stride, want_vad=True)
+        out = [rows[plan.row_off[i]:plan.row_off[i] + per[i]] for i in range(plan.n_utt)]
+        vads = [vad[plan.row_off[i]:plan.row_off[i + 1]] for i in range(plan.n_utt)]
+        vads = [v[v != 0] for v in vads]  # NUL = nothing written (an utterance the majority filter never got ready on)
+        plan.close()
+        return (out, vads) if want_vad else out
+
+    def enhance_wire(self, buf, elem_off, n_samples, fmt="s16", stride=1):
+        """enhance with the utterances read as in extract_wire (ctu_engine_run_signal_wire_host): list of int16 arrays."""
+        L = load_library()
+        buf = np.asarray(buf)
+        assert buf.flags["C_CONTIGUOUS"]
+        plan = self.plan(n_samples)
+        off, w = self._wire_plan_args(plan, elem_off, fmt, stride, buf.nbytes)
+        out = np.zeros(plan.total_samples, dtype=np.int16)
+        self._check(L.ctu_engine_run_signal_wire_host(self._h, plan._h, buf.ctypes.data, off.ctypes.data, ctypes.byref(w), out.ctypes.data))
+        n = L.ctu_plan_out_samples(plan._h)
+        res = [out[plan.sample_off[i]:plan.sample_off[i] + n[i]].copy() for i in range(plan.n_utt)]
+        plan.close()
+        return res
+
+    def extract_interleaved(self, frames, fmt="s16", want_vad=False):
+        """A [samples, channels] numpy block - a multichannel file as it lies - as one utterance per channel, in channel order: the
+        offline twin of Streams.push_interleaved (extract_wire with stride = channels, elem_off = the channel)."""
+        frames = np.asarray(frames)
+        assert frames.ndim == 2 and frames.flags["C_CONTIGUOUS"]
+        samples, channels = frames.shape
+        return self.extract_wire(frames, np.arange(channels, dtype=np.int64), np.full(channels, samples, dtype=np.int64), fmt=fmt, stride=channels,
+                                 want_vad=want_vad)
 
     # ---- feature files in (-format_in htk)
     def run_rows_device(self, plan, words, rows=None, stream=None):

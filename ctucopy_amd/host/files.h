@@ -30,21 +30,25 @@ struct FileCloser {
 };
 typedef std::unique_ptr<FILE, FileCloser> File;
 
-// canonical 44-byte WAVE header only, like src/io/in.cc:550-597: the checks on its 44 bytes, in the reference's order; returns the data chunk's bytes
-inline uint32_t wave_header_data_bytes(const ctu::Opts &o, const uint8_t *b) {
+// canonical 44-byte WAVE header only, like src/io/in.cc:550-597: the checks on its 44 bytes, in the reference's order; returns the data chunk's bytes.
+// channels: what --channels says (0: nothing - the file is mono, as in the reference)
+inline uint32_t wave_header_data_bytes(const ctu::Opts &o, const uint8_t *b, int channels = 0) {
     if (std::memcmp(b, "RIFF", 4)) throw Fatal("IN: No RIFF header in file!");
     if (std::memcmp(b + 8, "WAVE", 4)) throw Fatal("IN: Not a WAVE file!");
     if (rd16(&b[20]) != 1) throw Fatal("IN: Not a PCM WAVE file!");
     if ((long)rd32(&b[24]) != o.fs) throw Fatal("IN: WAVE file reports different sampling rate than specified!");
-    if (rd16(&b[22]) != 1) throw Fatal("IN: Input WAVE file is not mono!");
+    if (channels > 0 && rd16(&b[22]) != channels)
+        throw Fatal("IN: Input WAVE file holds " + std::to_string(rd16(&b[22])) + " channels, --channels says " + std::to_string(channels));
+    if (channels <= 0 && rd16(&b[22]) != 1) throw Fatal("IN: Input WAVE file is not mono!");
     if (rd16(&b[34]) != 16) throw Fatal("IN: Not 16 bits per sample!");
     return rd32(&b[40]);
 }
-// returns the number of samples the file holds
-inline size_t wave_samples(const ctu::Opts &o, FILE *f, size_t file_bytes) {
+// returns the number of samples the file holds - per channel: an incomplete [sample][channel] block at the end is dropped
+inline size_t wave_samples(const ctu::Opts &o, FILE *f, size_t file_bytes, int channels = 0) {
     uint8_t b[44];
     if (file_bytes < 44 || std::fread(b, 1, 44, f) != 44) throw Fatal("IN: No RIFF header in file!");
-    return std::min<size_t>(wave_header_data_bytes(o, b) / 2, (file_bytes - 44) / 2);
+    const size_t block = 2 * (size_t)std::max(channels, 1);
+    return std::min<size_t>(wave_header_data_bytes(o, b, channels) / block, (file_bytes - 44) / block);
 }
 
 // HTK feature file (htkIN::new_file / get_frame, src/io/in.cc:629-709): the 12-byte header in the byte order -endian_in names, its
@@ -76,11 +80,13 @@ inline void read_htk_rows(const ctu::Opts &o, const std::string &path, uint32_t 
     if (std::fseek(f.get(), 12, SEEK_SET) != 0 || std::fread(dst, 4, words, f.get()) != words) throw Fatal("IN: Cannot read data file!");
 }
 
-// number of samples `path` will decode to, without reading its data
-inline int64_t probe_samples(const ctu::Opts &o, const std::string &path) {
+// number of samples `path` will decode to, without reading its data; with --channels N (0: not given) the samples of one of its N
+// interleaved channels - a trailing incomplete block of N elements is dropped, as an odd byte of a mono raw file is
+inline int64_t probe_samples(const ctu::Opts &o, const std::string &path, int channels = 0) {
     if (o.format_in == "htk") return probe_htk_rows(o, path);
     const bool wave = o.format_in == "wave";
     if (o.format_in != "raw" && o.format_in != "alaw" && o.format_in != "mulaw" && !wave) throw Fatal("IN: Unknown input file format!");
+    const size_t block = (size_t)std::max(channels, 1) * (o.format_in == "raw" ? 2 : 1);  // bytes of one sample of every channel (raw, G.711)
     struct stat st;
     if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
         // not a plain file (or missing): let fopen decide, sizes by reading to the end
@@ -91,36 +97,44 @@ inline int64_t probe_samples(const ctu::Opts &o, const std::string &path) {
         while ((got = std::fread(tmp, 1, sizeof tmp, f.get())) > 0) n += got;
         if (wave) {
             std::rewind(f.get());
-            return (int64_t)wave_samples(o, f.get(), n);
+            return (int64_t)wave_samples(o, f.get(), n, channels);
         }
-        return (int64_t)(o.format_in == "raw" ? n / 2 : n);
+        return (int64_t)(n / block);
     }
     const size_t bytes = (size_t)st.st_size;
     if (wave) {
         File f(std::fopen(path.c_str(), "rb"));
         if (!f) throw Fatal("IN: Cannot open file!");
-        return (int64_t)wave_samples(o, f.get(), bytes);
+        return (int64_t)wave_samples(o, f.get(), bytes, channels);
     }
-    return (int64_t)(o.format_in == "raw" ? bytes / 2 : bytes);
+    return (int64_t)(bytes / block);
 }
 
-// reads `n` samples of `path` into dst (raw / a-law / mu-law / WAVE, src/io/in.cc:434-619, src/io/amulaw.h:20-53)
-inline void decode_into(const ctu::Opts &o, const std::string &path, int16_t *dst, size_t n) {
+// `bytes` bytes of the data of `path` as they lie in the file (raw / a-law / mu-law from the file's start, WAVE behind its 44-byte
+// header): the one reader of file mode.  What there is to expand in them - G.711 codes, the other byte order, interleaved channels - the
+// engine expands (wire input, main.cc); little-endian mono PCM is the samples themselves
+inline void read_wire_bytes(const ctu::Opts &o, const std::string &path, void *dst, size_t bytes) {
     const bool wave = o.format_in == "wave";
     File f(std::fopen(path.c_str(), "rb"));
     if (!f) throw Fatal(wave ? "IN: Cannot open file!" : "IN: Cannot open data file!");
     if (wave && std::fseek(f.get(), 44, SEEK_SET) != 0) throw Fatal("IN: No RIFF header in file!");
+    if (std::fread(dst, 1, bytes, f.get()) != bytes) throw Fatal("IN: Cannot read data file!");
+}
+
+// `n` samples of the mono file `path` as int16_t in dst (src/io/in.cc:434-619), for whoever needs samples on the host: the bytes as
+// above, then wire_expand - the host statement of the expansion (csrc/wire_layout.h) - where the format has something to expand.  In
+// place: the codes go to the upper half of the samples' own bytes and are expanded from the front (code i sits at byte n + i >= 2 i + 1)
+inline void decode_into(const ctu::Opts &o, const std::string &path, int16_t *dst, size_t n) {
+    const bool g711 = o.format_in == "alaw" || o.format_in == "mulaw", wave = o.format_in == "wave";
     uint8_t *bytes = reinterpret_cast<uint8_t *>(dst);
-    if (o.format_in == "alaw" || o.format_in == "mulaw") {
-        // the codes go to the upper half of the samples' own bytes and are expanded from the front (code i sits at byte n + i >= 2 i + 1)
-        if (std::fread(bytes + n, 1, n, f.get()) != n) throw Fatal("IN: Cannot read data file!");
-        const bool alaw = o.format_in == "alaw";
-        for (size_t i = 0; i < n; i++) dst[i] = g711_to_linear(bytes[n + i], alaw);
-        return;
+    read_wire_bytes(o, path, g711 ? bytes + n : bytes, g711 ? n : 2 * n);
+    if (g711) {  // (wire_expand reads element k ahead of writing sample k, k ascending: what the in-place expansion rests on)
+        const ctu_wire_layout w = {o.format_in == "alaw" ? CTU_WIRE_ALAW : CTU_WIRE_MULAW, 1};
+        wire_expand(&w, bytes + n, 0, (int64_t)n, dst);
+    } else if (o.swap_in && !wave) {
+        const ctu_wire_layout w = {CTU_WIRE_S16_SWAPPED, 1};
+        wire_expand(&w, bytes, 0, (int64_t)n, dst);
     }
-    if (std::fread(bytes, 2, n, f.get()) != n) throw Fatal("IN: Cannot read data file!");
-    if (o.swap_in && !wave)
-        for (size_t i = 0; i < n; i++) dst[i] = (int16_t)((uint16_t)dst[i] << 8 | (uint16_t)dst[i] >> 8);
 }
 
 // ---------------------------------------------------------------- writers

@@ -6,10 +6,14 @@
 // run_pipeline, cmvn_pass -; what they share is in Run, handed on by reference.
 // pipe_stage is the whole run of -online_in (pipe.h): one stream of a stream set on the first engine, fed from stdin as the bytes arrive.
 // -i <file> -online_out is the list of one file, whose writer is stdout (write_rows_out, write_signal_files).
+// --channels N: every file of the list holds N interleaved channels; expand_channels makes the list the one of its channels - N items per
+// line, file-major, channel-minor, targets out_<c> - ahead of batching, and a file's items stay together in a batch and on a GPU.
 // run_pipeline (the counterpart of BATCH::process, src/io/batch.cc:326-421) has three stages that overlap batch by batch:
 //   read_batches  - size_batch sizes the next files; fill_batch shards them over the GPUs by length (LPT; no collective: every utterance is
-//                   independent) and reads / decodes them straight into page-locked arenas with a pool of I/O threads;
-//   run_batch     - one thread per GPU: run_shard = plan + ctu_engine_run_host on its shard;
+//                   independent) and reads them straight into page-locked arenas with a pool of I/O threads: little-endian mono PCM as the
+//                   arena of samples, everything there is something to expand in - a-law, mu-law, the other byte order, interleaved
+//                   channels - as the files lie, back to back (wire_files.h), for the device to expand;
+//   run_batch     - one thread per GPU: run_shard = plan + ctu_engine_run_host (ctu_engine_run_wire_host) on its shard;
 //   write_batches - write_batch: the verbose lines, then write_signal_files (raw / WAVE), stash_for_cmvn, or write_feature_files (HTK / VAD
 //                   files by the same pool straight from the page-locked rows, ark / pfile in list order).
 // A Batch owns its page-locked buffers (PinBuf) and a Plan its ctu_plan: both are given back where their holder dies, on every path.
@@ -25,11 +29,13 @@
 #include "files.h"
 #include "pipe.h"
 #include "pipeline.h"
+#include "wire_files.h"
 
 namespace {
 
 struct Item {
     std::string fin, fout, spk, fvad;
+    int chan = 0;  // --channels: the channel of fin this item is, 0-based (expand_channels)
 };
 struct Gpu {
     ctu_engine *eng = nullptr;
@@ -50,9 +56,10 @@ Plan make_plan(ctu_engine *eng, const std::vector<int64_t> &ns) {
 struct Shard {
     std::vector<size_t> idx;      // positions in the batch, list order
     std::vector<int64_t> ns, so;  // samples per utterance, arena offsets (ctu_arena_layout)
+    std::vector<int64_t> eo;      // wire input: every utterance's first element in the arena, which then holds the files' bytes as they lie
     std::vector<int32_t> hidx;    // VAD: the majority filter's ring index every utterance starts with (the list is one process's)
     int64_t total_samples = 0, total_frames = 0;
-    PinBuf arena, rows;           // int16 in; float32 rows (or int16 samples with -format_out raw|wave) out
+    PinBuf arena, rows;           // int16 in (wire input: the files back to back, wire_arena_layout); float32 rows (or int16 samples with -format_out raw|wave) out
     std::vector<int64_t> ro, kept, nout;
     std::vector<uint8_t> vad;
 };
@@ -72,6 +79,8 @@ struct Run {
     int io_threads = 0;     // --io-threads N: file readers (default: the hardware threads, at most 16)
     int write_threads = 0;  // --write-threads N: file writers (default 1: creating files in one directory does not scale)
     int batch_mib = 256;    // --batch-mib M: PCM per batch
+    int channels = 0;       // --channels N: every input file interleaves N channels, each a file of the list in its own right (0: not given, mono)
+    int wire_format = -1;   // CTU_WIRE_*: the files go to the engine as they lie (ctu_engine_run_wire_host); -1: decoded samples (wire_format_of)
     size_t pipe_read_bytes = 1 << 20;  // --pipe-read-bytes N: -online_in reads stdin in reads of at most N bytes
     bool pipe_drop = false;  // -online_in with -vad_apply_mode drop: the engine runs with `none`, the stage drops the rows (pipe_stage)
     ctu::Opts o;
@@ -98,6 +107,12 @@ void parse_host_flags(Run &r, int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--io-threads") && i + 1 < argc) r.io_threads = std::max(1, std::atoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--write-threads") && i + 1 < argc) r.write_threads = std::max(1, std::atoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--batch-mib") && i + 1 < argc) r.batch_mib = std::max(1, std::atoi(argv[++i]));
+        else if (!std::strcmp(argv[i], "--channels")) {
+            char *end = nullptr;
+            const long n = i + 1 < argc ? std::strtol(argv[++i], &end, 10) : 0;
+            if (!end || end == argv[i] || *end || n < 1 || n > INT32_MAX) throw Fatal("ENGINE: --channels needs the number of interleaved channels of every input file, 1 or more");  // (a ctu_wire_layout's stride is an int32_t)
+            r.channels = (int)n;
+        }
         else if (!std::strcmp(argv[i], "--pipe-read-bytes") && i + 1 < argc) r.pipe_read_bytes = (size_t)std::min(std::max(1ll, std::atoll(argv[++i])), 1ll << 25);  // (a push holds at most 2^26 samples)
         else if (!std::strcmp(argv[i], "--gpu-map") && i + 1 < argc) {
             std::istringstream ms(argv[++i]);
@@ -160,10 +175,10 @@ std::string cut_at_end_of_vad_stream(Run &r) {
     if (!vf) return "";
     std::vector<unsigned char> bytes((std::istreambuf_iterator<char>(vf)), std::istreambuf_iterator<char>());
     int64_t usable = (int64_t)(std::find(bytes.begin(), bytes.end(), (unsigned char)0xFF) - bytes.begin()), used = 0;
+    int64_t T = -1;
     for (size_t i = 0; i < r.items.size(); i++) {
-        int64_t T;
         try {
-            T = ctu_num_frames(r.gpus[0].eng, probe_samples(r.o, r.items[i].fin));
+            if (r.items[i].chan == 0) T = ctu_num_frames(r.gpus[0].eng, probe_samples(r.o, r.items[i].fin, r.channels));  // (a file is asked once: its channels are equally long)
         } catch (...) {
             break;  // the reader reports the unreadable file where the reference would
         }
@@ -217,24 +232,32 @@ struct ListCursor {
 std::vector<int64_t> size_batch(Run &r, ListCursor &c) {
     const size_t batch_samples = (size_t)r.batch_mib << 19;  // samples of PCM per batch (default 1 GiB)
     const size_t unit = r.d.rows_in ? 2 * (size_t)r.d.row_floats_in : 1;  // -format_in htk: a "sample" is a row of that many floats, batches stay sized in bytes
+    const size_t nch = (size_t)std::max(r.channels, 1);  // the channels of a file stay in one batch: it ends between files only
     std::vector<int64_t> ns;
     size_t total = 0, end = c.pos;
     bool stop = false;
-    while (!stop && end < r.items.size() && (total < batch_samples || end == c.pos)) {
+    auto room = [&] { return total < batch_samples || end == c.pos || (end - c.pos) % nch != 0; };
+    while (!stop && end < r.items.size() && room()) {
         if (end >= c.probed.size()) {
             const size_t first = c.probed.size(), group = std::min<size_t>(r.items.size() - first, 1024);
             c.probed.resize(first + group);
             c.probe_err.resize(first + group);
             parallel_for(r.io_threads, group, [&](size_t i) {
+                if (r.items[first + i].chan != 0) return;  // a file is asked once, with its first channel
                 try {
-                    c.probed[first + i] = probe_samples(r.o, r.items[first + i].fin);
+                    c.probed[first + i] = probe_samples(r.o, r.items[first + i].fin, r.channels);
                     if (ctu_num_frames(r.gpus[0].eng, c.probed[first + i]) < 0) throw Fatal("IO: Signal shorter than one frame!");
                 } catch (...) {
                     c.probe_err[first + i] = std::current_exception();
                 }
             });
+            for (size_t i = first; i < first + group; i++)  // its other channels are as long (their first may lie in the group before)
+                if (r.items[i].chan != 0) {
+                    c.probed[i] = c.probed[i - 1];
+                    c.probe_err[i] = c.probe_err[i - 1];
+                }
         }
-        for (; end < c.probed.size() && (total < batch_samples || end == c.pos); end++) {
+        for (; end < c.probed.size() && room(); end++) {
             if (c.probe_err[end]) {  // a bad file ends the batch in front of it; it fails the batch it would start
                 if (end == c.pos) std::rethrow_exception(c.probe_err[end]);
                 stop = true;
@@ -250,16 +273,18 @@ std::vector<int64_t> size_batch(Run &r, ListCursor &c) {
 void fill_batch(Run &r, ListCursor &c, Batch &b, const std::vector<int64_t> &ns) {
     const ctu_dims &d = r.d;
     const size_t n = b.n = ns.size();
-    // longest-processing-time sharding over the GPUs by length; list order inside a shard
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return ns[x] > ns[y]; });
+    // longest-processing-time sharding over the GPUs by length; list order inside a shard.  What is dealt is a file: with --channels its
+    // nch items, which follow each other and are equally long, go to one GPU
+    const size_t nch = (size_t)std::max(r.channels, 1), files = n / nch;
+    std::vector<size_t> order(files);
+    for (size_t i = 0; i < files; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return ns[x * nch] > ns[y * nch]; });
     b.sh.resize(r.ngpu);
     std::vector<size_t> load(r.ngpu, 0);
-    for (size_t i : order) {
+    for (size_t f : order) {
         const int g = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        b.sh[g].idx.push_back(i);
-        load[g] += (size_t)ns[i];
+        for (size_t c_ = 0; c_ < nch; c_++) b.sh[g].idx.push_back(f * nch + c_);
+        load[g] += (size_t)ns[f * nch] * nch;
     }
     b.where.resize(n);
     std::vector<int32_t> hidx_of(n, 0);
@@ -280,13 +305,26 @@ void fill_batch(Run &r, ListCursor &c, Batch &b, const std::vector<int64_t> &ns)
         sh.so.resize(sh.ns.size() + 1);
         sh.total_samples = d.rows_in ? ctu_rows_arena_layout(sh.ns.data(), (int)sh.ns.size(), d.row_floats_in, sh.so.data()) : ctu_arena_layout(sh.ns.data(), (int)sh.ns.size(), sh.so.data());
         if (sh.idx.empty()) continue;
+        if (r.wire_format >= 0) {  // the files as they lie, back to back: utterance k is channel `chan` of its file, nch elements from sample to sample
+            const int64_t unit = r.wire_format == CTU_WIRE_ALAW || r.wire_format == CTU_WIRE_MULAW ? 1 : 2;
+            std::vector<int64_t> file_bytes, byte_off;
+            for (size_t k = 0; k < sh.idx.size(); k += nch) file_bytes.push_back(sh.ns[k] * (int64_t)nch * unit);
+            sh.arena = r.pool.get((size_t)std::max<int64_t>(wire_arena_layout(file_bytes, byte_off), 1));
+            for (size_t k = 0; k < sh.idx.size(); k++) sh.eo.push_back(byte_off[k / nch] / unit + r.items[b.pos + sh.idx[k]].chan);
+            continue;
+        }
         // the bytes between utterances are read under zero weights and need no particular value (include/ctu_engine.h)
         sh.arena = r.pool.get((size_t)sh.total_samples * (d.rows_in ? sizeof(uint32_t) : sizeof(int16_t)));
     }
     parallel_for(r.io_threads, n, [&](size_t i) {
         auto [sh, k] = b.slot(i);
-        if (d.rows_in) read_htk_rows(r.o, r.items[b.pos + i].fin, static_cast<uint32_t *>(sh.arena.get()) + sh.so[k], (size_t)sh.ns[k]);
-        else decode_into(r.o, r.items[b.pos + i].fin, static_cast<int16_t *>(sh.arena.get()) + sh.so[k], (size_t)sh.ns[k]);
+        const Item &it = r.items[b.pos + i];
+        if (d.rows_in) read_htk_rows(r.o, it.fin, static_cast<uint32_t *>(sh.arena.get()) + sh.so[k], (size_t)sh.ns[k]);
+        else if (r.wire_format < 0) decode_into(r.o, it.fin, static_cast<int16_t *>(sh.arena.get()) + sh.so[k], (size_t)sh.ns[k]);
+        else if (it.chan == 0) {  // a file is read once, where its first channel starts
+            const size_t unit = r.wire_format == CTU_WIRE_ALAW || r.wire_format == CTU_WIRE_MULAW ? 1 : 2;
+            read_wire_bytes(r.o, it.fin, static_cast<uint8_t *>(sh.arena.get()) + (size_t)sh.eo[k] * unit, (size_t)sh.ns[k] * nch * unit);
+        }
     });
 }
 void read_batches(Run &r, BatchChan &to_engine, const std::atomic<bool> &giving_up) {
@@ -322,12 +360,14 @@ void run_shard(Run &r, ctu_engine *eng, Shard &sh) {
     sh.total_frames = ctu_plan_total_frames(plan);
     sh.ro.assign(ro, ro + n + 1);
     sh.kept.assign(n, 0);
+    const ctu_wire_layout wire = {r.wire_format, std::max(r.channels, 1)};  // (wire input: the files as they lie, an utterance per channel)
     if (r.signal_out) {  // -format_out raw|wave: samples at the utterances' own offsets (ctu_engine_run_signal_host)
         sh.rows = r.pool.get((size_t)sh.total_samples * sizeof(int16_t));
         const int64_t *no = ctu_plan_out_samples(plan);
         sh.nout.assign(no, no + n);
-        if (ctu_engine_run_signal_host(eng, plan, static_cast<const int16_t *>(sh.arena.get()), static_cast<int16_t *>(sh.rows.get())) != CTU_OK)
-            throw Fatal(ctu_last_error(eng));
+        const int rc = r.wire_format >= 0 ? ctu_engine_run_signal_wire_host(eng, plan, sh.arena.get(), sh.eo.data(), &wire, static_cast<int16_t *>(sh.rows.get()))
+                                          : ctu_engine_run_signal_host(eng, plan, static_cast<const int16_t *>(sh.arena.get()), static_cast<int16_t *>(sh.rows.get()));
+        if (rc != CTU_OK) throw Fatal(ctu_last_error(eng));
         return;
     }
     sh.rows = r.pool.get((size_t)sh.total_frames * d.row_floats * sizeof(float));
@@ -338,8 +378,10 @@ void run_shard(Run &r, ctu_engine *eng, Shard &sh) {
         if (ctu_engine_run_rows_host(eng, plan, sh.arena.get(), static_cast<float *>(sh.rows.get())) != CTU_OK) throw Fatal(ctu_last_error(eng));
         return;
     }
-    if (ctu_engine_run_host(eng, plan, static_cast<const int16_t *>(sh.arena.get()), static_cast<float *>(sh.rows.get()), d.has_vad ? sh.vad.data() : nullptr, sh.kept.data()) != CTU_OK)
-        throw Fatal(ctu_last_error(eng));
+    uint8_t *vad = d.has_vad ? sh.vad.data() : nullptr;
+    const int rc = r.wire_format >= 0 ? ctu_engine_run_wire_host(eng, plan, sh.arena.get(), sh.eo.data(), &wire, static_cast<float *>(sh.rows.get()), vad, sh.kept.data())
+                                      : ctu_engine_run_host(eng, plan, static_cast<const int16_t *>(sh.arena.get()), static_cast<float *>(sh.rows.get()), vad, sh.kept.data());
+    if (rc != CTU_OK) throw Fatal(ctu_last_error(eng));
 }
 void run_batch(Run &r, Batch &b) {
     per_gpu(r.ngpu, [&](int g) {
@@ -670,8 +712,16 @@ int real_main(int argc, char **argv) {
     }
     r.signal_out = o.format_out == "raw" || o.format_out == "wave";
     if (!r.signal_out && o.format_out != "htk" && o.format_out != "ark" && o.format_out != "pfile") throw Fatal("OUT: Unknown output file format!");
-    r.items = read_items(o);
+    // --channels: refused ahead of the engine and of any input where a file is not N channels of samples
+    if (r.channels > 1 && o.pipe_in) throw Fatal("ENGINE: --channels above 1 with -online_in (a pipe is one stream: one set of streams per pipe is not built)");
+    if (r.channels > 1 && o.pipe_out) throw Fatal("ENGINE: --channels above 1 with -online_out (a pipe takes one file, --channels writes one per channel)");
+    if (r.channels > 1 && o.format_in == "htk") throw Fatal("ENGINE: --channels above 1 with -format_in htk (a feature file has rows, not channels)");
+    r.items = expand_channels(read_items(o), r.channels);
     if (o.pipe_in) return pipe_stage(r);
+    r.wire_format = wire_format_of(o.format_in, o.swap_in, r.channels);
+    // a WAVE header says how many channels it holds: the list's first file is asked ahead of the engine, so a wrong --channels (or a file
+    // that is not mono without it) needs no device to be told; the files behind it are asked where they always were (size_batch)
+    if (o.format_in == "wave" && !r.items.empty()) (void)probe_samples(o, r.items[0].fin, r.channels);
     // hwss / fwss / 2fwss chain the list through the noise seed (src/nr/nr.cc:212-221): one GPU, files in list order
     const bool chained = o.nr_mode == "hwss" || o.nr_mode == "fwss" || o.nr_mode == "2fwss";
     if (chained && r.ngpu > 1) {

@@ -471,6 +471,45 @@ int64_t ctu_wire_extent(const ctu_wire_layout *, int32_t n, const int64_t *elem_
  * Returns n_samples, or CTU_ERR_INPUT for a bad layout, a negative count or offset, or a NULL buffer with samples to expand. */
 int64_t ctu_wire_expand(const ctu_wire_layout *, const void *in, int64_t elem_off, int64_t n_samples, int16_t *out);
 
+/* ---- wire input, offline: a plan's utterances out of the same buffers -----------------------------------------------------------
+ * The offline twin of the wire pushes, for corpora that lie on disk as telephony left them - headerless a-law / mu-law files, PCM of the
+ * other byte order, stereo call recordings with one party per channel: the bytes go to the device as they lie (half the bytes of the
+ * samples for G.711, one upload for all channels of a file) and are expanded there, wire_unpack_kernel, into the plan's PCM arena.
+ *
+ * Addressing is that of ctu_streams_push_wire: sample k of utterance i is element elem_off[i] + k * stride of the buffer,
+ * k < utt_nsamples[i] of the plan; offsets count elements of the format; stride = n_channels with elem_off = base + channel is an
+ * interleaved file; ranges may interleave or overlap; the buffer is only read, and only at the elements named - it may end with the last
+ * of them.  elem_off is host memory (n_utt entries) and is read before the call returns.
+ *
+ * ctu_plan_unpack_wire writes exactly the utterances' samples - d_pcm[ctu_plan_sample_offsets()[i] + k] - and neither the gaps between
+ * utterances nor the 8 samples ahead of the first and the 512 behind the last, whose contents change no bit of a run.  d_pcm is an arena
+ * as ctu_engine_run takes it (2-byte aligned is enough; 16-byte aligned stores b128).  One launch, asynchronous on `stream`; then
+ * ctu_engine_run / ctu_engine_run_signal as ever, on the same stream or behind the caller's own synchronisation.  Calls on one plan
+ * are ordered by the caller, as its runs are.
+ *
+ * Kept: everything.  Rows, VAD bytes, samples and rows_per_utt are bit for bit those of the plain call on an arena that holds
+ * ctu_wire_expand's samples, for every configuration ctu_engine_create accepts on PCM - the hwss / fwss / 2fwss chain and
+ * ctu_engine_reset_chain, -vad file=, ctu_plan_set_vad_ring, drop, the large transforms, speech output - because the run behind the
+ * unpack is the plain one.
+ *
+ * The host forms are ctu_engine_run_host and ctu_engine_run_signal_host with the wire bytes going up in place of the arena: the
+ * covering range of the plan's utterances (ctu_wire_extent) - of each range's utterances where the 32 MiB rule, judged on the wire
+ * bytes, cuts the run into ranges on two streams; the hwss / fwss / 2fwss chain stays in one - a page-locked buffer as it lies, a
+ * pageable one through the runtime's staging.  A sparse layout - a few channels out of a long interleaved block - uploads its whole
+ * covering range: it belongs to the device form, which reads nothing but the elements named.  Synchronised on return.
+ *
+ * Refused with CTU_ERR_INPUT before anything is launched, uploaded or written, in words that name the fault: a NULL layout, a format
+ * outside CTU_WIRE_S16 .. CTU_WIRE_MULAW, a stride below 1, a negative elem_off of an utterance with samples (utterances without samples
+ * are not looked at), elem_off + (n - 1) * stride past int64_t, a buffer of 16-bit elements that is not 2-byte aligned, a NULL buffer on
+ * a plan with samples, a plan of another engine, an engine over feature files (use ctu_engine_run_rows...),
+ * ctu_engine_run_signal_wire_host on an engine without speech output and ctu_engine_run_wire_host on one with it. */
+int ctu_plan_unpack_wire(ctu_engine *, const ctu_plan *, const void *d_in, const int64_t *elem_off /* host, n_utt */,
+                         const ctu_wire_layout *, int16_t *d_pcm /* ctu_plan_total_samples() */, void *stream);
+int ctu_engine_run_wire_host(ctu_engine *, const ctu_plan *, const void *h_in, const int64_t *elem_off, const ctu_wire_layout *,
+                             float *h_rows, uint8_t *h_vad, int64_t *rows_per_utt);
+int ctu_engine_run_signal_wire_host(ctu_engine *, const ctu_plan *, const void *h_in, const int64_t *elem_off,
+                                    const ctu_wire_layout *, int16_t *h_out);
+
 /* -format_in alaw | mulaw on the device: n G.711 codes -> n int16 samples, the expansion of src/io/amulaw.h:20-53
  * (alaw2lin, called from src/io/in.cc:481-560) bit for bit.  The caller lays the codes of an utterance at the same offsets
  * as its samples (ctu_plan_sample_offsets) and may decode the whole arena at once.  Asynchronous on `stream`. */

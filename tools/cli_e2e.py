@@ -2,9 +2,10 @@
 """File-to-file throughput of the command-line host (bin/ctucopy): N seeded synthetic utterances written as raw PCM files,
 one `-S` list, wall time of the whole process (engine creation, reading, H2D, kernels, D2H, writing HTK files).
 
-  python tools/cli_e2e.py --utts 2000 [--bin bin/ctucopy] [--dir /tmp/ctu_e2e] [--set S-MFCC] [--runs 3] [-- extra CLI flags]
+  python tools/cli_e2e.py --utts 2000 [--bin bin/ctucopy] [--dir /tmp/ctu_e2e] [--set S-MFCC] [--format raw|alaw] [--runs 3] [-- extra CLI flags]
 
-Prints one JSON line per run.  The first run of a directory also pays for the page cache; later ones read cached files."""
+--format alaw: the files hold one a-law code per sample (the high byte of the synthetic sample: every byte is a code, and the rate does
+not depend on what the codes are worth) and the tool is given -format_in alaw.  Prints one JSON line per run.  The first run of a directory also pays for the page cache; later ones read cached files."""
 import argparse, json, os, subprocess, sys, time
 import numpy as np
 
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--dir", default="/tmp/ctu_e2e")
     ap.add_argument("--bin", default=os.path.join(ROOT, "bin", "ctucopy"))
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--format", default="raw", choices=("raw", "alaw"))
     ap.add_argument("extra", nargs="*")
     a = ap.parse_args()
     din, dout = os.path.join(a.dir, "in"), os.path.join(a.dir, "out")
@@ -42,8 +44,11 @@ def main():
     lst = os.path.join(a.dir, "list.scp")
     with open(lst, "w") as f:
         for i in idx:
-            p = os.path.join(din, "u%05d.raw" % i)
-            if not os.path.exists(p) or os.path.getsize(p) != 2 * ns[i]:
+            p = os.path.join(din, "u%05d.%s" % (i, a.format))
+            if a.format == "alaw":
+                if not os.path.exists(p) or os.path.getsize(p) != ns[i]:
+                    (arena[off[i]:off[i] + ns[i]].view(np.uint16) >> 8).astype(np.uint8).tofile(p)
+            elif not os.path.exists(p) or os.path.getsize(p) != 2 * ns[i]:
                 arena[off[i]:off[i] + ns[i]].tofile(p)
             if a.set.endswith("-VAD"):
                 f.write("%s %s spk %s\n" % (p, os.path.join(dout, "u%05d.htk" % i), os.path.join(dout, "u%05d.vad" % i)))
@@ -57,11 +62,13 @@ def main():
         for f in os.listdir(dout):
             os.unlink(os.path.join(dout, f))
         t = time.time()
-        cp = subprocess.run([a.bin] + FLAGS[a.set] + ["-S", lst] + a.extra, capture_output=True, text=True, env=dict(os.environ, CTU_HOST_TIMING="1"))
+        flags = list(FLAGS[a.set])
+        flags[flags.index("-format_in") + 1] = a.format
+        cp = subprocess.run([a.bin] + flags + ["-S", lst] + a.extra, capture_output=True, text=True, env=dict(os.environ, CTU_HOST_TIMING="1"))
         wall = time.time() - t
         nout = len(os.listdir(dout))
         size = sum(os.path.getsize(os.path.join(dout, f)) for f in os.listdir(dout))
-        print(json.dumps({"bin": os.path.basename(a.bin), "extra": a.extra, "run": r, "rc": cp.returncode, "wall_s": round(wall, 3), "files_out": nout,
+        print(json.dumps({"bin": os.path.basename(a.bin), "format_in": a.format, "extra": a.extra, "run": r, "rc": cp.returncode, "wall_s": round(wall, 3), "files_out": nout,
                           "bytes_out": size, "frames": frames, "frames_per_s": round(frames / wall), "pcm_MB_per_s": round(2 * sum(ns) / 1e6 / wall, 1),
                           "stderr": cp.stderr.strip()[-200:]}))
         sys.stdout.flush()
