@@ -660,11 +660,11 @@ void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows)
     const int ns = (tl + 3) / 4;
     if (e->tab.trap_bf16) {
         constexpr int NT16 = 2;  // fp16 terms per value (trap_kernel.h)
-        const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16;
+        const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16 + (size_t)(d.B * TB_BADW + 4) * 4;
         hipLaunchKernelGGL(trapdct_split16_kernel, dim3(std::max(pl->hp.n_chunks128, 1)), dim3(512), shm16, s,
-                           pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->hp.n_chunks128, d.B, nd, d.D);
+                           pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->hp.n_chunks128, d.B, tl, nd, d.D);
     } else {
-        const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float);
+        const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float) + (size_t)(d.B * TM_BADW + 1) * 4;
         lift<1, 2>(nd <= 16 ? 1 : 2, [&](auto nrb) {
             lift<26, 64>(ns <= 26 ? 26 : 64, [&](auto nsm) {
                 hipLaunchKernelGGL((trapdct_mfma_kernel<decltype(nrb)::value, decltype(nsm)::value>), dim3(pl->hp.n_chunks), dim3(256), shm, s, pl->logmel.p, d_rows,

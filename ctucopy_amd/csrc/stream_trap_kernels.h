@@ -37,8 +37,10 @@
 // the cut into pushes, not on the other streams; what is given up is bit identity with the offline kernel at those sizes, for rows
 // that are closer to the reference.  64 more registers (hi, lo) and 12 VALU operations per accumulator register and run.
 //
-// What is guarded: a tap beyond traplen (4 ceil(traplen/4) > traplen, traplen is odd) has a zero in G, as offline (areg), but its
-// operand must still be finite, and mid-stream the row it would name lies beyond the newest frame: the fetch index is clamped to
+// What is guarded: a tap beyond traplen (4 ceil(traplen/4) > traplen, traplen is odd) has a zero in G, as offline (areg), and a zero
+// for its operand too - the frame it would name is no part of the row's context, and on an all-zero frame (digital silence: the
+// logarithm of an empty band, -inf) 0 x -inf would make the row NaN where the reference's is finite.  Its fetch still needs an address
+// that exists, and mid-stream the row it would name lies beyond the newest frame: the fetch index is clamped to
 // [first frame in reach, newest frame], both of which exist.  That upper clamp is the right-hand clamp T-1 of a finish (the newest frame
 // is the file's last); mid-stream no real tap of a row that goes out reaches it.  The left clamp at frame 0 is applied to the index ahead
 // of the address: frames below 0 are in no history.  Idle columns (beyond the push's rows) neither load nor store.
@@ -114,10 +116,11 @@ __global__ __launch_bounds__(64) void stream_trap_kernel(const StreamTrapParams 
 #pragma unroll 1
     for (int s_ = 0; s_ < nsteps; s_++) {
         float x[BB], a[NRB];
-#pragma unroll
-        for (int bb = 0; bb < BB; bb++) x[bb] = xn[bb] - xc[bb];
-        // this lane's slice of G: A[i = lane&15][k = lane>>4] of the 16x4 block, zero beyond ndct and traplen (trapdct_mfma_kernel's areg)
         const int j = 4 * s_ + q;
+        // a tap beyond traplen is no tap: its operand is zero like its weight, whatever the frame it would name holds (0 x -inf is NaN)
+#pragma unroll
+        for (int bb = 0; bb < BB; bb++) x[bb] = j < p.traplen ? xn[bb] - xc[bb] : 0.f;
+        // this lane's slice of G: A[i = lane&15][k = lane>>4] of the 16x4 block, zero beyond ndct and traplen (trapdct_mfma_kernel's areg)
 #pragma unroll
         for (int rb = 0; rb < NRB; rb++) {
             const int k = rb * 16 + cn;

@@ -12,11 +12,33 @@ namespace {
 // value first (keeps the fp32 accumulation small).
 // One workgroup = 64 output frames of one utterance (4 waves x 16 frames), all bands.
 
+// Non-finite log-mel values (an all-zero frame is the logarithm of an empty band, -inf).  Both kernels pad the context with taps of
+// weight zero that fetch real neighbouring frames (to a multiple of four taps and to NSM tap groups here, to K = 128 taps in the 16-bit
+// kernel), and 0 x -inf = NaN would reach rows whose own traplen frames are finite; the 16-bit split holds no such value either (the low
+// term of -inf is -inf - -inf = NaN).  So such a value enters the tile as 0 and sets its frame's bit in a per-band mask in LDS (TM_BADW /
+// TB_BADW words a band over the tile's frames); a row whose own context - tile frames f0 .. f0 + traplen - 1 of the band - holds a marked
+// frame is written as NaN, which is what the reference's mean removal over the context makes of it (fea_trap.cc), and every other row is
+// the contraction of finite values.  A tile without such a value (speech: "never digitally silent") pays the test per element while
+// loading and one uniform branch behind the last row store; the MFMA loops and the stores are as they were.
+constexpr unsigned TRAP_NAN = 0xffc00000u;  // what -inf - -inf gives, here as in the reference's mean removal: the rows of a silent context stay what they were
+constexpr int TM_BADW = 10;  // trapdct_mfma_kernel: 64 + 4 * 64 = 320 tile frames at the most
+constexpr int TB_BADW = 8;   // trapdct_split16_kernel: 256 tile frames
+__device__ __forceinline__ bool f32_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ bool trap_context_marked(const unsigned *m, int f0, int n) {
+    bool bad = false;
+    for (int w = f0 >> 5; w <= (f0 + n - 1) >> 5; w++) {
+        const int lo = max(f0 - 32 * w, 0), hi = min(f0 + n - 32 * w, 32);  // bits lo .. hi - 1 of word w
+        const unsigned bits = (hi - lo == 32 ? ~0u : ((1u << (hi - lo)) - 1u)) << lo;
+        bad |= (m[w] & bits) != 0;
+    }
+    return bad;
+}
+
 template <int NRB, int NSM>  // row blocks of 16 DCT coefficients (ndct <= 16*NRB); NSM >= ceil(traplen/4) tap groups
 __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restrict__ logmel, float *__restrict__ rows,
                                                            const float *__restrict__ G, const int4 *__restrict__ utt_info,
                                                            const int *__restrict__ chunk_tab, int B, int traplen, int ndct, int D) {
-    extern __shared__ float tile[];  // [64 + 4*nsteps][Bs]
+    extern __shared__ float tile[];  // [64 + 4*nsteps][Bs], then bad[B][TM_BADW] + 1
     const int u = chunk_tab[blockIdx.x * 2], tc = chunk_tab[blockIdx.x * 2 + 1];
     const int4 ui = utt_info[u];
     const int64_t r0 = ((int64_t)ui.y << 32) | (uint32_t)ui.x;
@@ -24,12 +46,21 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
     const int half = (traplen - 1) / 2, nsteps = (traplen + 3) / 4;
     const int Bs = B | 1, nfr = 64 + 4 * (NSM <= 32 ? NSM : nsteps);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned *bad = reinterpret_cast<unsigned *>(tile + nfr * Bs);  // [B][TM_BADW], then the tile's flag
+    for (int e = tid; e <= B * TM_BADW; e += 256) bad[e] = 0u;
+    __syncthreads();
     // log-mel tile with the first / last frame replicated beyond the utterance (src/fea/fea_trap.cc:64-70,111-127)
     for (int e = tid; e < nfr * B; e += 256) {
         const int f = e / B, b = e - f * B;
         int t = tc - half + f;
         t = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
-        tile[f * Bs + b] = logmel[(r0 + t) * B + b];
+        float v = logmel[(r0 + t) * B + b];
+        if (f32_nonfinite(v)) {
+            atomicOr(&bad[b * TM_BADW + (f >> 5)], 1u << (f & 31));
+            bad[B * TM_BADW] = 1u;
+            v = 0.f;
+        }
+        tile[f * Bs + b] = v;
     }
     // this lane's slice of G: A[i = lane&15][k = lane>>4] of every 16x4 block
     const int ai = lane & 15, ak = lane >> 4;
@@ -71,6 +102,20 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
                 }
         }
     }
+    // A tile with marked frames (uniform over the workgroup): the lanes write NaN over what they stored above wherever the row's own
+    // context - tile frames tl .. tl + traplen - 1 of the band - holds one.  Behind the loop, so that the loop is as it was.
+    if (bad[B * TM_BADW] != 0u && t_out < T) {
+        const float nan = __uint_as_float(TRAP_NAN);
+        for (int b = 0; b < B; b++)
+            if (trap_context_marked(bad + b * TM_BADW, tl, traplen)) {
+                float *o = rows + (r0 + t_out) * D + b * ndct;
+                for (int rb = 0; rb < NRB; rb++)
+                    for (int r = 0; r < 4; r++) {
+                        const int k = rb * 16 + ak * 4 + r;
+                        if (k < ndct) o[k] = nan;
+                    }
+            }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -110,10 +155,10 @@ __device__ __forceinline__ void split16(float v, unsigned (&t)[2]) {
 #endif
 __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const float *__restrict__ logmel, float *__restrict__ rows,
                                                                 const uint4 *__restrict__ Gtab, const int4 *__restrict__ utt_info,
-                                                                const int *__restrict__ chunk_tab, int n_chunks, int B, int ndct, int D) {
+                                                                const int *__restrict__ chunk_tab, int n_chunks, int B, int traplen, int ndct, int D) {
     constexpr int NT = 2;                 // terms per operand
     constexpr int NA = 4 * NT * 64;       // uint4 fragments of a phase
-    extern __shared__ __align__(16) unsigned short xt[];  // [NT][B][TB_TT] terms, then x0[B] floats, then the fragment buffers
+    extern __shared__ __align__(16) unsigned short xt[];  // [NT][B][TB_TT] terms, then x0[B] floats, then the fragment buffers, then bad[B][TB_BADW] + 1
     if ((int)blockIdx.x >= n_chunks) return;
     const int u = chunk_tab[blockIdx.x * 2], tc = chunk_tab[blockIdx.x * 2 + 1];  // chunks of 128 frames
     const int4 ui = utt_info[u];
@@ -121,11 +166,14 @@ __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const floa
     const int T = ui.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *x0 = reinterpret_cast<float *>(xt + NT * B * TB_TT);
+    unsigned *bad = reinterpret_cast<unsigned *>(reinterpret_cast<uint4 *>(x0 + ((B + 3) & ~3)) + 2 * NA);  // [B][TB_BADW], then the tile's flag
     if (tid < B) {
         int t = tc + 64;
         t = t > T - 1 ? T - 1 : t;
-        x0[tid] = logmel[(r0 + t) * B + tid];
+        const float v = logmel[(r0 + t) * B + tid];
+        x0[tid] = f32_nonfinite(v) ? 0.f : v;  // (any constant serves: rows of G sum to zero)
     }
+    if (tid <= B * TB_BADW) bad[tid] = 0u;  // B <= 24: 193 words at the most
     __syncthreads();
     // log-mel tile with the first / last frame replicated beyond the utterance (src/fea/fea_trap.cc:64-70,111-127)
     unsigned *xt32 = reinterpret_cast<unsigned *>(xt);
@@ -149,8 +197,15 @@ __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const floa
             if (e < 128 * B) {
                 const int pr = e / B, b = e - pr * B;
                 unsigned ta[NT], tb[NT];
-                split16(v0[it] - x0[b], ta);
-                split16(v1[it] - x0[b], tb);
+                float d0 = v0[it] - x0[b], d1 = v1[it] - x0[b];
+                if (f32_nonfinite(d0) || f32_nonfinite(d1)) {  // tile frames 2 pr and 2 pr + 1 share a word of the mask
+                    atomicOr(&bad[b * TB_BADW + (pr >> 4)], (f32_nonfinite(d0) ? 1u : 0u) << (2 * pr & 31) | (f32_nonfinite(d1) ? 2u : 0u) << (2 * pr & 31));
+                    bad[B * TB_BADW] = 1u;
+                    d0 = f32_nonfinite(d0) ? 0.f : d0;
+                    d1 = f32_nonfinite(d1) ? 0.f : d1;
+                }
+                split16(d0, ta);
+                split16(d1, tb);
 #pragma unroll
                 for (int sp = 0; sp < NT; sp++) xt32[((sp * B + b) * TB_TT >> 1) + pr] = ta[sp] | (tb[sp] << 16);
             }
@@ -211,6 +266,22 @@ __global__ __launch_bounds__(512, TB_WGS) void trapdct_split16_kernel(const floa
         uint4 *an = abuf + ((c + 1) & 1) * NA;
         an[tid] = pre0;
         if (tid + 512 < NA) an[tid + 512] = pre1;
+    }
+    // A tile with marked frames (uniform over the workgroup): the lanes write NaN over what they stored above wherever the row's own
+    // context - tile frames 8 n + c + TB_OFF - half .. + traplen - 1 of the band - holds one.  Behind the phases, so that they are as they were.
+    if (bad[B * TB_BADW] != 0u) {
+        const float nan = __uint_as_float(TRAP_NAN);
+        const int half = (traplen - 1) / 2;
+        for (int c = 0; c < 8; c++) {
+            const int t_out = tc + 8 * n + c;
+            if (t_out >= T) continue;
+            for (int b = wave; b < B; b += 8)
+                if (trap_context_marked(bad + b * TB_BADW, 8 * n + c + TB_OFF - half, traplen)) {
+                    float *o = rows + (r0 + t_out) * D + b * ndct;
+                    for (int r = 0; r < 4; r++)
+                        if (q * 4 + r < ndct) o[q * 4 + r] = nan;
+                }
+        }
     }
 }
 

@@ -3,6 +3,7 @@
 
   make -C oracle ref && python tests/golden/make_ref_e2e_fixtures.py            # REF_E2E_CASES -> ref_e2e.npz
   make -C oracle ref && python tests/golden/make_ref_e2e_fixtures.py opts       # REF_E2E_OPT_CASES + ref_e2e_file_cases() -> ref_e2e_opts.npz
+  make -C oracle ref && python tests/golden/make_ref_e2e_fixtures.py silence    # REF_E2E_SILENCE_CASES -> ref_e2e_silence.npz
 
 oracle/Makefile's `ref` target compiles the sources of a reference tree (REF=<path>), unchanged and at -O0, against the FFTW stand-in
 (oracle/fftw_standin/fftw3.h, oracle/fftw_standin.cc) into oracle/_ref/ctucopy4_ref.  For every case this script writes the input
@@ -15,7 +16,9 @@ and runs the binary once over the whole list (`... -S list`), under `timeout` an
   <c>__<i>__pcm                int16 samples of -format_out raw
   <c>__file__<name>            (file cases) the bytes of output file <name> as uint8; <c>__input = CRC32 of every input file's bytes, in name order
 Conditions asserted here and again by tests/test_oracle_ref_e2e.py: every row of the first seven edge inputs is finite; on zeros_mid
-the non-finite rows are exactly the frames wholly inside the zero block, at most a quarter of the file's rows.
+the non-finite rows are exactly the frames wholly inside the zero block, at most a quarter of the file's rows.  On the silence table
+(tests/util.py's check_silence_conditions, asserted again by tests/test_oracle_ref_e2e_silence.py): the recorded non-finite rows of the first
+file, ten finite rows and more on either side of them, a finite second file.
 Neither this script nor the binary is run by a test: the tests read the .npz.
 """
 import os
@@ -30,10 +33,12 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-from tests.util import EDGE_INPUTS, REF_E2E_CASES, REF_E2E_OPT_CASES, ref_e2e_file_cases, ref_e2e_inputs, zeros_mid_parts  # noqa: E402
+from tests.util import (EDGE_INPUTS, REF_E2E_CASES, REF_E2E_OPT_CASES, REF_E2E_SILENCE_CASES, SILENCE_DIES, check_silence_conditions,  # noqa: E402
+                        ref_e2e_file_cases, ref_e2e_inputs, zeros_mid_parts)
 
 BIN = os.path.join(ROOT, "oracle", "_ref", "ctucopy4_ref")
-TABLES = {"base": (REF_E2E_CASES, False, "ref_e2e.npz"), "opts": (REF_E2E_OPT_CASES, True, "ref_e2e_opts.npz")}   # cases, file cases too, output
+TABLES = {"base": (REF_E2E_CASES, False, "ref_e2e.npz"), "opts": (REF_E2E_OPT_CASES, True, "ref_e2e_opts.npz"),   # cases, file cases too, output
+          "silence": (REF_E2E_SILENCE_CASES, False, "ref_e2e_silence.npz")}
 TIME_LIMIT = 300            # seconds per case; the direct transforms make a 2048-point frame a few milliseconds
 FILE_LIMIT = 64 << 20       # bytes: an -O2 build's endless VAD flush wrote gigabytes
 
@@ -148,6 +153,10 @@ def main():
             print(f"{name}: status {status}" + ("" if status else f", {sum(v.nbytes for v in got.values())} bytes"))
             if not status and inp.startswith("edge"):
                 check_edge_conditions(name, cfg, inputs, got)
+            if inp.startswith("sil"):
+                assert status == SILENCE_DIES.get(name, 0), (name, status)
+                if not status and f"{name}__0__rows" in got:
+                    check_silence_conditions(name, cfg, got[f"{name}__0__rows"], got[f"{name}__1__rows"])
             z.update(got)
         for name, case in (ref_e2e_file_cases() if with_files else {}).items():
             got = run_file_case(name, case, tmp)

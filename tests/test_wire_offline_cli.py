@@ -160,6 +160,50 @@ def test_channels_equal_the_mono_split_list(case, tmp_path):
                             f"{int((a[:min(a.size, b.size)] != b[:min(a.size, b.size)]).sum())} bytes in all; stderr: {r.stderr[-300:]!r}")
 
 
+def _htk_rows(path):
+    img = path.read_bytes()
+    n, size = int(np.frombuffer(img, "<u4", 1, 0)[0]), int(np.frombuffer(img, "<u2", 1, 8)[0])
+    assert size % 4 == 0 and len(img) == 12 + n * size, (str(path), n, size, len(img))
+    return np.frombuffer(img, "<f4", offset=12).reshape(n, size // 4)
+
+
+def test_an_idle_mu_law_channel_beside_a_speaking_one(tmp_path):
+    """A call recording with a party per channel: channel 1 speaks, channel 2 is the same speech with its middle quarter muted - a run of
+    code 0xFF, which expands to 0.  Behind the delta chain and the exponential CMS the all-zero frames' -inf / NaN stay to the end of the
+    idle channel's file (the recurrence never recovers; tests/golden/ref_e2e_silence.npz, sil_da_zexp_e) and must not reach the other
+    channel's: out_1 and out_2 hold the rows of Engine.extract on the two expanded channels, finite rows bit for bit, the same rows
+    non-finite, out_1 finite throughout."""
+    from ctucopy_amd import Engine
+    from tests.util import zeros_mid_parts
+    n = 8000
+    cfg = "-fs 8000 -format_in mulaw -format_out htk -preset mfcc -fea_delta d_a -fea_Z_exp 500".split()
+    speech = _codes("mulaw", synth_utt(3, n, fs=8000))
+    a, z, _ = zeros_mid_parts(n)
+    idle = speech.copy()
+    idle[a:a + z] = 0xFF
+    (tmp_path / "call.ul").write_bytes(np.stack([speech, idle], axis=1).tobytes())
+    (tmp_path / "list.scp").write_text("call.ul out\n")
+    x = [ceng.wire_expand(c, 0, n, fmt="mulaw") for c in (speech, idle)]
+    assert not (x[1][a:a + z] != 0).any() and np.array_equal(x[1][:a], x[0][:a]) and np.abs(x[0][a:a + z].astype(int)).max() > 1000
+    r = run(cfg + ["--channels", 2, "-S", "list.scp"], tmp_path)
+    assert r.returncode == 0, r.stderr
+    want = Engine(_with(cfg, "-format_in", "raw")).extract(x)
+    got = [_htk_rows(tmp_path / f"out_{c}") for c in (1, 2)]
+    for c, (g, w) in enumerate(zip(got, want), 1):
+        assert g.shape == w.shape == (98, 39), (c, g.shape, w.shape)
+        fg, fw = np.isfinite(g).all(axis=1), np.isfinite(w).all(axis=1)
+        print(f"idle mu-law channel, out_{c}: {g.shape[0]} rows, non-finite in the file {np.flatnonzero(~fg).tolist()}, from Engine.extract {np.flatnonzero(~fw).tolist()}; "
+              f"{int((g[fg & fw] != w[fg & fw]).any(axis=1).sum())} finite rows not bit-equal")
+        assert np.array_equal(fg, fw), (c, np.flatnonzero(fg != fw).tolist())
+        assert np.array_equal(g[fw], w[fw]), c
+    f1, f2 = (np.isfinite(g).all(axis=1) for g in got)
+    assert f1.all()
+    # the idle channel: finite up to the delta chain's reach ahead of the first all-zero frame (sample a + 1 on: pre-emphasis), then never again
+    first = -(-(a + 1) // 80) - 4
+    assert f2[:first].all() and not f2[first:].any() and first >= 10, (first, np.flatnonzero(~f2).tolist())
+    assert np.array_equal(got[0][:first - 4], got[1][:first - 4])      # what no window has reached yet is the speaking channel's
+
+
 def test_mono_alaw_list_is_the_raw_run_of_the_expanded_samples(tmp_path):
     """-format_in alaw / mulaw / raw big-endian, mono: the files the tool writes are those of the little-endian raw run of the samples
     the host expansion gives - what it wrote when the readers expanded them."""

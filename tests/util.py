@@ -130,7 +130,10 @@ REF_E2E_CASES = {
 
 
 def ref_e2e_inputs(name):
-    """The files of one input set of REF_E2E_CASES / REF_E2E_OPT_CASES, in list order."""
+    """The files of one input set of REF_E2E_CASES / REF_E2E_OPT_CASES / REF_E2E_SILENCE_CASES, in list order."""
+    if name.startswith("sil"):
+        n = int(name[len("sil"):])
+        return [zeros_mid(n), synth_utt(3, n // 2)]
     if name == "short3":
         a, b = ref_e2e_inputs("short")
         return [a, synth_utt(5, 300), b]
@@ -214,6 +217,91 @@ REF_E2E_OPT_CASES = {
     "post_dat_windows": (C2 + "-fea_delta d_a_t -d_win 3 -a_win 1 -t_win 2".split(), "short"),
     "post_dat": (C2 + ["-fea_delta", "d_a_t"], "short"),
 }
+
+
+# ---- digital silence through the stateful chains: tests/golden/ref_e2e_silence.npz (make_ref_e2e_fixtures.py silence)
+# Same shape and rules as REF_E2E_CASES.  "sil<n>" = zeros_mid(n) (3n/8 speech, n/4 zeros, 3n/8 speech: a muted telephone channel), then
+# synth_utt(3, n // 2), which shows what the first file hands on.  An all-zero frame is the logarithm of an empty band in the reference
+# (-inf / NaN), and every stage that carries state from frame to frame decides how far that spreads.
+REF_E2E_SILENCE_CASES = {
+    "sil_c4": (C4, "sil8000"),          # the reference dies on the first silent frame (Burg.h:72, den != 0.0): status only, DESIGN.md section 7
+    "sil_c4_novad": (C4_NOVAD, "sil8000"),
+    "sil_fwss": (C2 + "-nr_mode fwss -vad burg".split(), "sil12000"),
+    "sil_2fwss_8k": (M8 + "-nr_mode 2fwss -vad burg".split(), "sil8000"),
+    "sil_hwss_8k": (M8 + "-nr_mode hwss -vad burg".split(), "sil8000"),
+    "sil_trapdct51": (C2 + "-fb_definition 23filters -fea_kind trapdct,51,8".split(), "sil16000"),
+    "sil_da_zexp_e": (C2 + "-fea_delta d_a -fea_Z_exp 500 -fea_E on".split(), "sil12000"),
+    "sil_trap9": (C2 + ["-fea_trap", "9"], "sil12000"),
+    "sil_zblock30": (C2 + ["-fea_Z_block", "30"], "sil12000"),
+    "sil_vad_energy_dyn": (C2 + VAD_ENERGY + ["-vad_thr_mode", "dyn"], "sil12000"),
+    "sil_vad_energy_perc": (C2 + VAD_ENERGY + ["-vad_thr_mode", "perc"], "sil12000"),
+    "sil_vad_fea_adapt": (C2 + VAD_FEA + ["-vad_thr_mode", "adapt"], "sil12000"),
+    "sil_lpc12": (C2 + "-fea_kind lpc -fea_lporder 12".split(), "sil12000"),
+    "sil_plp": (C3 + ["-fb_inld", "off"], "sil12000"),          # the double tail
+    "sil_logspec_e": (C2 + "-fea_kind logspec -fea_E on".split(), "sil12000"),
+    "sil_spec": (C2 + "-fea_kind spec".split(), "sil12000"),
+    "sil_sig_fwss": (REF_E2E_CASES["sig_fwss"][0], "sil12000"),
+    "sil_m48_w64": (REF_E2E_CASES["m48_w64"][0], "sil25152"),   # 4096 points; 3072 + 23 x 960 samples: 24 rows, the fewest with ten finite ones on either side
+}
+SILENCE_DIES = {"sil_c4": 134}
+
+
+# What the reference does with the first file: (first, last non-finite row, rows); None for the first two where every row is finite, the
+# silent frames included (0 is a value to `spec`, and fwss / 2fwss floor what they subtract); hwss leaves empty bands on speech too, so its
+# entry is (number of non-finite rows, rows).  The smoothing chains spread the block: trapdct by half its context, -fea_trap and the deltas
+# by their windows, and the exponential CMS never recovers.
+REF_E2E_SILENCE_NONFINITE = {
+    "sil_c4_novad": (38, 60, 98), "sil_fwss": (None, None, 73), "sil_2fwss_8k": (None, None, 98), "sil_hwss_8k": (60, 98),
+    "sil_trapdct51": (13, 85, 98), "sil_da_zexp_e": (25, 72, 73), "sil_trap9": (25, 48, 73), "sil_zblock30": (29, 44, 73),
+    "sil_vad_energy_dyn": (29, 44, 73), "sil_vad_energy_perc": (29, 44, 73), "sil_vad_fea_adapt": (29, 44, 73), "sil_lpc12": (29, 44, 73),
+    "sil_plp": (29, 44, 73), "sil_logspec_e": (29, 44, 73), "sil_spec": (None, None, 73), "sil_m48_w64": (10, 13, 24),
+}
+SILENCE_VAD_ONES = {"sil_vad_energy_dyn": 31, "sil_vad_energy_perc": 42, "sil_vad_fea_adapt": 18}    # '1' bytes of the first file's 73
+
+
+def zero_block_frames(cfg, n, rows):
+    """Frames of zeros_mid(n) that lie wholly inside the zero block (with pre-emphasis: the sample in front of the frame too)."""
+    opt = {k: v for k, v in zip(cfg[:-1], cfg[1:]) if k.startswith("-")}
+    fs = int(opt["-fs"])
+    window, shift = int(float(opt.get("-w", 25)) * fs / 1000), int(float(opt.get("-s", 10)) * fs / 1000)
+    a, z, _ = zeros_mid_parts(n)
+    starts = np.arange(rows) * shift
+    return (starts - (1 if float(opt.get("-preem", 0)) > 0 else 0) >= a) & (starts + window <= a + z)
+
+
+def check_silence_conditions(name, cfg, rows0, rows1):
+    """What the GPU tests on REF_E2E_SILENCE_CASES rely on in the reference's rows of a case it survives: the recorded non-finite rows of
+    the first file, at least 10 finite rows ahead of the block, at least 10 behind it (not sil_da_zexp_e, whose recurrence stays non-finite
+    to the end of the file), and a second file that is finite throughout (not under hwss).  The block: the all-zero frames and every
+    non-finite row around them (under hwss the all-zero frames alone)."""
+    n = int(REF_E2E_SILENCE_CASES[name][1][len("sil"):])
+    hwss = "hwss" in cfg
+    bad = ~np.isfinite(rows0).all(axis=1)
+    idx, rows = np.flatnonzero(bad), rows0.shape[0]
+    silent = np.flatnonzero(zero_block_frames(cfg, n, rows))
+    assert silent.size >= 2, (name, silent)
+    want = REF_E2E_SILENCE_NONFINITE[name]
+    if hwss:
+        assert (int(bad.sum()), rows) == want and bad[silent].all(), (name, int(bad.sum()), rows)
+    elif want[0] is None:
+        assert not bad.any() and rows == want[2], (name, idx, rows)
+    else:
+        assert (int(idx[0]), int(idx[-1]), rows) == want and bad[idx[0]:idx[-1] + 1].all(), (name, idx, rows)
+        assert idx[0] <= silent[0] and silent[-1] <= idx[-1], (name, idx, silent)
+    lo, hi = int(silent[0]), int(silent[-1])
+    if idx.size and not hwss:
+        lo, hi = min(lo, int(idx[0])), max(hi, int(idx[-1]))
+    ahead, behind = int((~bad[:lo]).sum()), int((~bad[hi + 1:]).sum())
+    assert ahead >= 10 and (behind >= 10 or name == "sil_da_zexp_e"), (name, ahead, behind)
+    if name == "sil_da_zexp_e":
+        assert hi == rows - 1, (name, hi, rows)
+    assert rows1.shape[0] >= 10 and (hwss or np.isfinite(rows1).all()), name
+    return ahead, behind
+
+
+def ref_e2e_silence():
+    """What the compiled reference wrote for REF_E2E_SILENCE_CASES (make_ref_e2e_fixtures.py silence)."""
+    return np.load(os.path.join(GOLDEN, "ref_e2e_silence.npz"))
 
 
 def g711_codes(n=9000):
