@@ -194,9 +194,12 @@ std::string unsupported_reason(const Design &d) {
         if (o.fea_lporder > MAX_LP || o.fea_ncepcoefs > MAX_LP) return "LP order / cepstral order above 23 (the front end accumulates 24 lags per frame)";
     }
     if (d.B > 512) return "more than 512 filter bank channels";
-    if (d.kind == FeaKind::TrapDct && o.fea_trapdct_ndct > 32) return "more than 32 TRAP DCT coefficients";
-    if (d.kind == FeaKind::TrapDct && o.fea_trapdct_traplen > 255) return "TRAP longer than 255 frames";
-    if (d.kind == FeaKind::TrapDct && (size_t)(64 + 256) * (d.B | 1) * 4 > 64 * 1024) return "too many bands for the TRAP tile";
+    if (d.kind == FeaKind::TrapDct && o.fea_trapdct_ndct > TRAP_MAX_NDCT) return "more than 32 TRAP DCT coefficients";
+    if (d.kind == FeaKind::TrapDct && o.fea_trapdct_traplen > TRAP_MAX_LEN) return "TRAP longer than 255 frames";
+    // the launch shape (trap_path, layout_constants.h): the band limit is the tile's at the longest context; with the mask of non-finite
+    // frames behind it the request of 50 and 51 bands passes 64 KiB from 245 frames on, and stage_trap raises the kernel's limit there
+    if (d.kind == FeaKind::TrapDct && (!trap_bands_fit(d.B) || trap_path(d.B, o.fea_trapdct_traplen, o.fea_trapdct_ndct).lds_bytes > LDS_RAISED))
+        return "too many bands for the TRAP tile";
     return "";
 }
 

@@ -657,18 +657,18 @@ void stage_burg_vad(ctu_engine *e, const ctu_plan *pl, const RunExtent &x, hipSt
 void stage_trap(ctu_engine *e, const ctu_plan *pl, hipStream_t s, float *d_rows) {
     const ctu::Design &d = *e->design;
     const int tl = d.o.fea_trapdct_traplen, nd = d.o.fea_trapdct_ndct;
-    const int ns = (tl + 3) / 4;
-    if (e->tab.trap_bf16) {
-        constexpr int NT16 = 2;  // fp16 terms per value (trap_kernel.h)
-        const size_t shm16 = (size_t)NT16 * d.B * TB_TT * 2 + (size_t)((d.B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16 + (size_t)(d.B * TB_BADW + 4) * 4;
-        hipLaunchKernelGGL(trapdct_split16_kernel, dim3(std::max(pl->hp.n_chunks128, 1)), dim3(512), shm16, s,
-                           pl->logmel.p, d_rows, e->trapG16.p, pl->utt_info.p, pl->trap_chunks128.p, pl->hp.n_chunks128, d.B, tl, nd, d.D);
+    const TrapPath tp = trap_path(d.B, tl, nd);  // layout_constants.h: which kernel, its instantiation and its dynamic LDS
+    if (tp.split16 != (e->tab.trap_bf16 ? 1 : 0)) throw std::runtime_error("internal: the TRAP tables are not those of the kernel trap_path names");
+    if (tp.split16) {
+        launch_lds(e, &trapdct_split16_kernel, dim3(std::max(pl->hp.n_chunks128, 1)), dim3(512), (size_t)tp.lds_bytes, s, (const float *)pl->logmel.p, d_rows,
+                   (const uint4 *)e->trapG16.p, (const int4 *)pl->utt_info.p, (const int *)pl->trap_chunks128.p, pl->hp.n_chunks128, d.B, tl, nd, d.D);
     } else {
-        const size_t shm = (size_t)(64 + 4 * (ns <= 26 ? 26 : ns)) * (d.B | 1) * sizeof(float) + (size_t)(d.B * TM_BADW + 1) * 4;
-        lift<1, 2>(nd <= 16 ? 1 : 2, [&](auto nrb) {
-            lift<26, 64>(ns <= 26 ? 26 : 64, [&](auto nsm) {
-                hipLaunchKernelGGL((trapdct_mfma_kernel<decltype(nrb)::value, decltype(nsm)::value>), dim3(pl->hp.n_chunks), dim3(256), shm, s, pl->logmel.p, d_rows,
-                                   e->trapG.p, pl->utt_info.p, pl->trap_chunks.p, d.B, tl, nd, d.D);
+        // 50 and 51 bands on contexts of 245 frames and more ask for up to 67 324 bytes (tile and mask): launch_lds raises the limit there
+        lift<1, 2>(tp.nrb, [&](auto nrb) {
+            lift<TRAP_COMP_STEPS, 64>(tp.nsm, [&](auto nsm) {
+                launch_lds(e, &trapdct_mfma_kernel<decltype(nrb)::value, decltype(nsm)::value>, dim3(pl->hp.n_chunks), dim3(256), (size_t)tp.lds_bytes, s,
+                           (const float *)pl->logmel.p, d_rows, (const float *)e->trapG.p, (const int4 *)pl->utt_info.p, (const int *)pl->trap_chunks.p, d.B, tl, nd,
+                           d.D);
             });
         });
     }
@@ -878,6 +878,16 @@ int64_t ctu_config_table(int argc, const char *const *argv, const char *name, do
             const FeSel k = fe_select(d, d.signal_out ? nullptr : &t);
             v = {(double)k.nz, (double)k.feat, (double)k.mode, (double)k.vx, (double)k.nc, (double)k.gen, (double)k.lpo, (double)k.md, (double)k.vf,
                  (double)k.ss, (double)k.sy, (double)k.walk};
+        }
+        else if (n == "trap_path") {  // the launch of offline TRAP-DCT (trap_path, layout_constants.h), then whether ctu_engine_create takes the configuration
+            if (d.kind != ctu::FeaKind::TrapDct) {
+                g_create_error = "trap_path: not a trapdct configuration";
+                return CTU_ERR_INPUT;
+            }
+            spread_small_fft(d);
+            std::string why;
+            const TrapPath p = trap_path(d.B, d.o.fea_trapdct_traplen, d.o.fea_trapdct_ndct);
+            v = {(double)p.split16, (double)p.nrb, (double)p.nsm, (double)p.lds_bytes, (double)p.big_lds, ctu::create_check(d, why) == CTU_OK ? 1.0 : 0.0};
         }
         else if (n == "host_tables") v = host_tables_report(d);  // EngineTables and VadParams as ctu_engine_create builds them (include/ctu_engine.h)
         else if (n == "tile_frames") v = {(double)TILE};  // frames per tile record of a plan (offline, and of a stream set's pushes)

@@ -96,6 +96,45 @@ constexpr int VF0_STAGE = 4 * VF0_FSTRIDE;  // floats of staging per wave (behin
 
 constexpr int VAD_FEA_WIDE = 8;  // vad_kernels.h: entries per lane of the `fea` criterion on vectors of more than 32 entries: up to 512
 constexpr int TB_OFF = 56;       // trap_kernel.h: tile origin tc - 56: a multiple of 8 not below half = 50
+constexpr int TB_TT = 264;       // trapdct_split16_kernel: tile row in frames: 8 * 15 + 127 < 256 used; 528 bytes per row spreads the bands over the banks and keeps 16-byte alignment
+constexpr int TM_BADW = 10;      // trapdct_mfma_kernel: mask words a band over the tile's frames, 64 + 4 * 64 = 320 at the most
+constexpr int TB_BADW = 8;       // trapdct_split16_kernel: 256 tile frames
+constexpr int TRAP_COMP_STEPS = 26;  // tap groups of the short fp32 instantiations (traplen <= 104): one accumulator chain over the context
+constexpr int TRAP_COMP_RUN = 2;     // tap groups (8 taps) of one accumulator chain beyond that (trap_comp_close, trap_kernel.h, which says why 2)
+constexpr int TRAP_MAX_LEN = 255, TRAP_MAX_NDCT = 32;
+constexpr int LDS_DEFAULT = 64 * 1024, LDS_RAISED = 160 * 1024;  // dynamic LDS a launch gets as it is / behind allow_big_lds (engine.hip)
+
+// The launch shape of offline TRAP-DCT (trap_kernel.h), stated once: build_trap (tables.cc) builds the tables of the kernel named here,
+// stage_trap (engine.hip) launches it with these bytes, unsupported_reason (accept.cc) admits what it can launch, and
+// ctu_config_table(..., "trap_path") reports it.
+//   split16  trapdct_split16_kernel: at most 16 coefficients, a context that fits the 128 padded taps behind the tile origin tc - TB_OFF
+//            whatever the frame phase (traplen <= 113), at most 24 bands (NF = 6 loads per lane; 42 KB of LDS: two workgroups per CU)
+//   else     trapdct_mfma_kernel<nrb, nsm>: nrb row blocks of 16 coefficients; nsm = TRAP_COMP_STEPS tap groups compiled in for contexts
+//            of up to 104 frames, 64 guarded at run time (and summed in compensated runs) beyond
+// lds_bytes: the tile(s), then the mask of non-finite frames.  big_lds: more than a launch gets as it is - the launch raises the limit first.
+struct TrapPath {
+    int split16, nrb, nsm, lds_bytes, big_lds;
+};
+constexpr TrapPath trap_path(int B, int traplen, int ndct) {
+    const int half = (traplen - 1) / 2, ns = (traplen + 3) / 4;
+    TrapPath p{0, 0, 0, 0, 0};
+    p.split16 = ndct <= 16 && half <= TB_OFF && 7 + (TB_OFF - half) + traplen <= 128 && B <= 24;
+    if (p.split16) {
+        constexpr int NT16 = 2;  // fp16 terms per value
+        p.lds_bytes = NT16 * B * TB_TT * 2 + ((B + 3) & ~3) * 4 + 2 * (4 * NT16 * 64) * 16 + (B * TB_BADW + 4) * 4;
+    } else {
+        p.nrb = ndct <= 16 ? 1 : 2;
+        p.nsm = ns <= TRAP_COMP_STEPS ? TRAP_COMP_STEPS : 64;
+        p.lds_bytes = (64 + 4 * (p.nsm == 64 ? ns : p.nsm)) * (B | 1) * 4 + (B * TM_BADW + 1) * 4;
+    }
+    p.big_lds = p.lds_bytes > LDS_DEFAULT;
+    return p;
+}
+// The bands the fp32 kernel's tile takes at the longest context (64 + 256 frames of B | 1 floats in the default 64 KiB): B <= 51
+constexpr bool trap_bands_fit(int B) { return (64 + 4 * 64) * (B | 1) * 4 <= LDS_DEFAULT; }
+static_assert(trap_bands_fit(51) && !trap_bands_fit(52) && trap_path(51, TRAP_MAX_LEN, TRAP_MAX_NDCT).lds_bytes <= LDS_RAISED &&
+                  trap_path(51, TRAP_MAX_LEN, TRAP_MAX_NDCT).big_lds && !trap_path(24, 113, 16).big_lds,
+              "every accepted TRAP shape launches: behind allow_big_lds where the mask takes the request past 64 KiB");
 constexpr int DCTW_KC = 64, DCTW_MAX = 64;  // dctw_kernel.h: bands per chunk of the contraction, most values per frame (four row blocks of 16)
 
 // The DUAL instantiations of frontend_kernel (its phase 1).  They take their window table scaled by 1/2 (tables.cc asks this same function).

@@ -20,7 +20,7 @@
 // (stream_trap_columns, stream_plan.h); column c is row c of the caller's buffer.  A workgroup is one wave: 16 columns and a block of
 // BB bands (grid.y walks the band blocks: 8 bands with one row block, 4 with two), so a small push still spreads over the chip.
 // A column's result depends on nothing but its own traplen log-mel rows: not on which column of which wave computes it, not on how
-// the file was cut into pushes, not on the other streams - and, for contexts of up to 104 frames, it is the offline fp32 kernel's bit for bit when the log-mel rows are.
+// the file was cut into pushes, not on the other streams - and it is the offline fp32 kernel's bit for bit when the log-mel rows are.
 //
 // The B operand comes straight from the L2-resident rows, no LDS: per tap group a lane computes its row's address once (clamp, fresh or
 // history, 64-bit offset) and loads BB consecutive floats of it, one tap group ahead of the MFMAs that use them; the accumulators are
@@ -29,13 +29,12 @@
 //
 // Long contexts (COMP: more than TRAP_COMP_STEPS = 26 tap groups, traplen 105 .. 255).  Up to 26 tap groups the arithmetic is the
 // offline kernel's short instantiation and the rows are its rows bit for bit.  Beyond, one fp32 accumulator chain over the whole context
-// does not hold the engine's parity bound: at 255 taps the partial sums reach the hundreds for results below one, and on 140 frames of
-// speech the offline kernel's rows are 1.9e-4 of max(|oracle|, 1) from the oracle (bound 1e-4) where the same log-mel rows contracted in
-// float64 are 4.6e-5 from it.  So there the accumulator is closed every TRAP_COMP_RUN = 4 tap groups (16 taps): it joins a sum kept as two
-// floats by an error-free addition (two-sum, the addition's rounding error collected in the low word) and starts over from zero; the row
-// is hi + lo.  Taps still ascend and the operand is the same, so a column still depends on its own traplen log-mel rows alone - not on
-// the cut into pushes, not on the other streams; what is given up is bit identity with the offline kernel at those sizes, for rows
-// that are closer to the reference.  64 more registers (hi, lo) and 12 VALU operations per accumulator register and run.
+// does not hold the engine's parity bound (1.9e-4 of max(|oracle|, 1) on 140 frames of speech at 255 taps, against 1e-4), so there the
+// accumulator is closed every TRAP_COMP_RUN = 2 tap groups (8 taps) into a sum kept as two floats: trap_comp_close and trap_comp_row
+// of trap_kernel.h, which say how and why - and which the offline kernel's long instantiations (trapdct_mfma_kernel<NRB, 64>) call as
+// well, on the same ascending taps and the same centred operand, so the identity with the offline rows holds at these sizes too.  A
+// column still depends on its own traplen log-mel rows alone - not on the cut into pushes, not on the other streams.  64 more registers
+// (hi, lo) and 12 VALU operations per accumulator register and run.
 //
 // What is guarded: a tap beyond traplen (4 ceil(traplen/4) > traplen, traplen is odd) has a zero in G, as offline (areg), and a zero
 // for its operand too - the frame it would name is no part of the row's context, and on an all-zero frame (digital silence: the
@@ -48,14 +47,13 @@
 // appears once in a push.
 //
 // gfx950, hipcc -O3: stream_trap_kernel<1, false> 76 VGPRs, 32 AGPRs (the accumulators), 54 SGPRs; <2, false> 66 VGPRs, 32 AGPRs,
-// 48 SGPRs; four waves per SIMD each.  <1, true> 148 VGPRs, 32 AGPRs, 70 SGPRs (two waves per SIMD); <2, true> 124 VGPRs, 32 AGPRs,
+// 48 SGPRs; four waves per SIMD each.  <1, true> 144 VGPRs, 32 AGPRs, 70 SGPRs (two waves per SIMD); <2, true> 124 VGPRs, 32 AGPRs,
 // 54 SGPRs (three).  No spills, no scratch, no LDS in any of them.
 #pragma once
 
 namespace {
 
-constexpr int TRAP_COMP_STEPS = 26;  // tap groups of trapdct_mfma_kernel's short instantiation (traplen <= 104): up to here its arithmetic, bit for bit
-constexpr int TRAP_COMP_RUN = 4;     // tap groups (16 taps) of one accumulator chain beyond that
+// (TRAP_COMP_STEPS, TRAP_COMP_RUN: layout_constants.h)
 
 struct StreamTrapParams {
     const RowPush *push;
@@ -134,22 +132,14 @@ __global__ __launch_bounds__(64) void stream_trap_kernel(const StreamTrapParams 
                 for (int rb = 0; rb < NRB; rb++) acc[bb][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb], x[bb], acc[bb][rb], 0, 0, 0);
             }
         if constexpr (COMP) {
-            // every TRAP_COMP_RUN tap groups, and behind the last: the accumulator joins the sum by an error-free addition (two-sum:
-            // s = hi + a, the rounding error of that addition goes to lo) and starts over from zero, so no chain is longer than a run
-            if ((s_ & (TRAP_COMP_RUN - 1)) == TRAP_COMP_RUN - 1 || s_ + 1 == nsteps) {
+            // every TRAP_COMP_RUN tap groups, and behind the last: the accumulator joins the sum by an error-free addition and starts
+            // over from zero, so no chain is longer than a run (trap_comp_close, trap_kernel.h: the offline kernel's long contexts too)
+            if (trap_comp_closes(s_, nsteps)) {
 #pragma unroll
                 for (int bb = 0; bb < BB; bb++)
                     if (bb < nb) {
 #pragma unroll
-                        for (int rb = 0; rb < NRB; rb++)
-#pragma unroll
-                            for (int r = 0; r < 4; r++) {
-                                const float h = sum_hi[bb][rb][r], v = acc[bb][rb][r];
-                                const float t = h + v, vv = t - h;
-                                sum_lo[bb][rb][r] += (h - (t - vv)) + (v - vv);
-                                sum_hi[bb][rb][r] = t;
-                                acc[bb][rb][r] = 0.f;
-                            }
+                        for (int rb = 0; rb < NRB; rb++) trap_comp_close(acc[bb][rb], sum_hi[bb][rb], sum_lo[bb][rb]);
                     }
             }
         }
@@ -158,7 +148,7 @@ __global__ __launch_bounds__(64) void stream_trap_kernel(const StreamTrapParams 
 #pragma unroll
         for (int bb = 0; bb < BB; bb++)
 #pragma unroll
-            for (int rb = 0; rb < NRB; rb++) acc[bb][rb] = sum_hi[bb][rb] + sum_lo[bb][rb];
+            for (int rb = 0; rb < NRB; rb++) acc[bb][rb] = trap_comp_row(sum_hi[bb][rb], sum_lo[bb][rb]);
     }
     if (!live) return;
     float *out = p.rows + c * p.D;  // column c is row c of the caller's buffer (out0 is the prefix sum of nr)

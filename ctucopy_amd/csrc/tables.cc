@@ -382,7 +382,7 @@ namespace {
 void build_trap(const Design &d, EngineTables &e) {
     e.trapG.assign(d.trap.begin(), d.trap.end());
     const int tl = d.o.fea_trapdct_traplen, nd = d.o.fea_trapdct_ndct, half = (tl - 1) / 2;
-    e.trap_bf16 = nd <= 16 && half <= TB_OFF && 7 + (TB_OFF - half) + tl <= 128 && d.B <= 24;  // 24 bands: 62 KB of LDS (tile 38 KB + two fragment buffers 24 KB): two workgroups per CU
+    e.trap_bf16 = trap_path(d.B, tl, nd).split16 != 0;  // (layout_constants.h: the one statement of which kernel runs)
     if (!e.trap_bf16) return;
     const int NT = 2;
     e.trapG16.assign((size_t)8 * 4 * NT * 64 * 4, 0u);  // records of four words

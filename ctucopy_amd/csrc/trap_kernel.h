@@ -21,8 +21,7 @@ namespace {
 // the contraction of finite values.  A tile without such a value (speech: "never digitally silent") pays the test per element while
 // loading and one uniform branch behind the last row store; the MFMA loops and the stores are as they were.
 constexpr unsigned TRAP_NAN = 0xffc00000u;  // what -inf - -inf gives, here as in the reference's mean removal: the rows of a silent context stay what they were
-constexpr int TM_BADW = 10;  // trapdct_mfma_kernel: 64 + 4 * 64 = 320 tile frames at the most
-constexpr int TB_BADW = 8;   // trapdct_split16_kernel: 256 tile frames
+// (TM_BADW, TB_BADW and the tiles' sizes: layout_constants.h, where trap_path states the launch)
 __device__ __forceinline__ bool f32_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 __device__ __forceinline__ bool trap_context_marked(const unsigned *m, int f0, int n) {
     bool bad = false;
@@ -34,7 +33,32 @@ __device__ __forceinline__ bool trap_context_marked(const unsigned *m, int f0, i
     return bad;
 }
 
-template <int NRB, int NSM>  // row blocks of 16 DCT coefficients (ndct <= 16*NRB); NSM >= ceil(traplen/4) tap groups
+// Long contexts (more than TRAP_COMP_STEPS = 26 tap groups, traplen 105 .. 255): one fp32 accumulator chain over the whole context does
+// not hold the engine's parity bound - at 255 taps the partial sums reach the hundreds for results below one, and on speech the rows
+// were 1.9e-4 of max(|oracle|, 1) from the oracle (bound 1e-4) where the same log-mel rows contracted in float64 are 4.6e-5 from it.
+// So there the taps still ascend from a zero accumulator over the same centred operand, but the accumulator is closed every
+// TRAP_COMP_RUN = 2 tap groups (8 taps) and behind the last group: it joins a sum kept as two floats by an error-free addition
+// (two-sum: s = hi + a, the rounding error of that addition collected in lo) and starts over from zero; the row is hi + lo.
+// trapdct_mfma_kernel<NRB, 64> and stream_trap_kernel<NRB, true> (stream_trap_kernels.h) both sum this way, through these two
+// functions alone, so their rows are the same bit for bit when the log-mel rows are.  12 VALU operations per accumulator register and run.
+// Why runs of 2: measured on an MI355X against the float64 contraction of the device's own log-mel rows (tests/test_trapdct_shapes.py),
+// runs of 4 / 2 / 1 leave 3.5 - 5.8e-5 / 1.9 - 3.7e-5 / 1.4 - 2.3e-5 at 105 .. 255 taps, and that float64 contraction is itself 7e-5 (23
+// bands) to 1.0e-4 (51 bands) from the oracle at 201 .. 255 taps (bound 1e-4): with runs of 4 the 51-band rows came out at 1.11e-4.
+// gfx950, hipcc -O3: trapdct_mfma_kernel<1, 64> 194 VGPRs + 4 AGPRs, <2, 64> 247 + 8, two waves per SIMD, no scratch.
+__device__ __forceinline__ bool trap_comp_closes(int s_, int nsteps) { return (s_ & (TRAP_COMP_RUN - 1)) == TRAP_COMP_RUN - 1 || s_ + 1 == nsteps; }
+__device__ __forceinline__ void trap_comp_close(f32x4 &acc, f32x4 &sum_hi, f32x4 &sum_lo) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const float h = sum_hi[r], v = acc[r];
+        const float t = h + v, vv = t - h;
+        sum_lo[r] += (h - (t - vv)) + (v - vv);
+        sum_hi[r] = t;
+        acc[r] = 0.f;
+    }
+}
+__device__ __forceinline__ f32x4 trap_comp_row(const f32x4 &sum_hi, const f32x4 &sum_lo) { return sum_hi + sum_lo; }
+
+template <int NRB, int NSM>  // row blocks of 16 DCT coefficients (ndct <= 16*NRB); NSM >= ceil(traplen/4) tap groups; NSM > 32: summed in compensated runs
 __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restrict__ logmel, float *__restrict__ rows,
                                                            const float *__restrict__ G, const int4 *__restrict__ utt_info,
                                                            const int *__restrict__ chunk_tab, int B, int traplen, int ndct, int D) {
@@ -80,13 +104,32 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
         f32x4 acc[NRB];
 #pragma unroll
         for (int rb = 0; rb < NRB; rb++) acc[rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if constexpr (NSM <= 32) {
 #pragma unroll
-        for (int s_ = 0; s_ < NSM; s_++) {
-            if (NSM <= 32 || s_ < nsteps) {  // exact instantiations run unguarded (A is zero beyond traplen)
+            for (int s_ = 0; s_ < NSM; s_++) {  // exact instantiations run unguarded (A is zero beyond traplen)
                 const float bv = tile[(tl + 4 * s_ + ak) * Bs + b] - xc;
 #pragma unroll
                 for (int rb = 0; rb < NRB; rb++) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[rb][s_], bv, acc[rb], 0, 0, 0);
             }
+        } else {
+            // long contexts: the tap groups that exist (a uniform guard), closed in compensated runs (trap_comp_close above)
+            f32x4 sum_hi[NRB], sum_lo[NRB];
+#pragma unroll
+            for (int rb = 0; rb < NRB; rb++) sum_hi[rb] = sum_lo[rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s_ = 0; s_ < NSM; s_++) {
+                if (s_ < nsteps) {
+                    const float bv = tile[(tl + 4 * s_ + ak) * Bs + b] - xc;
+#pragma unroll
+                    for (int rb = 0; rb < NRB; rb++) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[rb][s_], bv, acc[rb], 0, 0, 0);
+                    if (trap_comp_closes(s_, nsteps)) {
+#pragma unroll
+                        for (int rb = 0; rb < NRB; rb++) trap_comp_close(acc[rb], sum_hi[rb], sum_lo[rb]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int rb = 0; rb < NRB; rb++) acc[rb] = trap_comp_row(sum_hi[rb], sum_lo[rb]);
         }
         if (t_out < T && ndct == 16 && NRB == 1 && (D & 3) == 0) {
             // C/D layout: this lane holds coefficients 4*(lane>>4)..+3 of frame column lane&15: one 16-byte store
@@ -134,7 +177,7 @@ __global__ __launch_bounds__(256) void trapdct_mfma_kernel(const float *__restri
 // One workgroup (8 waves, at most 128 VGPRs: two workgroups = four waves per SIMD on a CU) = 128 output frames x all
 // bands; wave w takes bands w, w+8, ...; A fragments of a phase (4 k-steps x NT terms) live in registers meanwhile.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr int TB_TT = 264;   // tile row in frames: 8 * 15 + 127 < 256 used; 528 bytes per row spreads the bands over the banks and keeps 16-byte alignment
+// (TB_TT, the tile row in frames: layout_constants.h)
 
 // Workgroup barrier for LDS hand-overs only: __syncthreads() also drains the vector-memory counter, which would put the
 // latency of a phase's row stores in front of the next phase.

@@ -96,7 +96,11 @@ int ctu_config_dims(int argc, const char *const *argv, ctu_dims *out);
  *          the 32 fields of the kernels' VAD parameter block (VadParams, layout_constants.h) in declaration order, as values.
  *        Not for HTK feature input, which has no tables.  tests/golden/host_tables.json pins it] |
  *        "tile_frames" [1: frames per tile record of a plan - an offline run's and a stream set's alike: a push that completes more
- *        frames of a stream than this spans two tiles].
+ *        frames of a stream than this spans two tiles] |
+ *        "trap_path" [6: the launch of offline TRAP-DCT for a -fea_kind trapdct configuration: 1 for the fp16-split kernel
+ *        (trapdct_split16_kernel) or 0 for the fp32 one (trapdct_mfma_kernel<NRB, NSM>), NRB, NSM (zeros for the split kernel), the
+ *        dynamic LDS bytes of the launch, whether the launch raises the kernel's LDS limit first (more than 64 KiB), and whether
+ *        ctu_engine_create takes the configuration; CTU_ERR_INPUT for another feature kind].
  * Returns the number of values (written up to cap), or a negative error code. */
 int64_t ctu_config_table(int argc, const char *const *argv, const char *name, double *out, int64_t cap);
 
@@ -269,10 +273,10 @@ int ctu_engine_run_rows_host(ctu_engine *, const ctu_plan *, const void *h_rows_
  * offline fp32 one (v_mfma_f32_16x16x4_f32 over the operand minus the column's own centre value), so a row depends on nothing but its
  * own traplen log-mel rows - not on the cut into pushes, not on the other streams - and is the row of ctu_engine_run bit for bit
  * wherever the log-mel rows are (every push a multiple of eight frames into the file) and the offline run launches its fp32 kernel
- * (more than 24 bands or more than 16 coefficients; elsewhere offline splits into fp16 terms and the two agree to rounding) on a context
- * of at most 104 frames.  Longer contexts (traplen 105 .. 255) are summed in compensated runs of 16 taps: a single fp32 chain over them
- * leaves the engine's parity bound (1.9e-4 of the reference at 255 taps, against 1e-4), so there a stream's rows are closer to the
- * reference than ctu_engine_run's and agree with them to that rounding; the independence of pushes and streams holds at every size.  Taken: the plain chain at every FFT size ctu_engine_create takes trapdct at, 1024 .. 4096 points included; with
+ * (more than 24 bands, more than 16 coefficients or a context of more than 113 frames; elsewhere offline splits into fp16 terms and the two agree to rounding),
+ * at every context length.  Contexts of more than 104 frames (traplen 105 .. 255) are summed in compensated runs of 8 taps, by the
+ * offline fp32 kernel and by a stream set alike (one device helper): a single fp32 chain over them leaves the engine's parity bound
+ * (1.9e-4 of the reference at 255 taps, against 1e-4).  The independence of pushes and streams holds at every size.  Taken: the plain chain at every FFT size ctu_engine_create takes trapdct at, 1024 .. 4096 points included; with
  * CTU_STREAMS_NR_STATE as well -nr_mode exten on the spectrum, and with CTU_STREAMS_LARGE_STATE beside that on 1024 .. 4096-point
  * frames.  Still refused by name with the flag: the VAD module beside trapdct (whatever the detector flag), -remove_dc1,
  * -nr_when afterFB behind exten, -s above -w; hwss / fwss / 2fwss and CMVN on trapdct are outside ctu_engine_create.  Without the flag

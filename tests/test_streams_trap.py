@@ -1,8 +1,8 @@
 """Stream sets with trap state on the GPU (Engine.streams(..., trap_state=True)): -fea_kind trapdct behind the streamed front end gives
 the rows of the offline run, row t with the push that brings frame t + half (half = (traplen - 1) / 2), the last half with finish.
 
-Bounds: bit identity with the offline run where it launches the exact-fp32 kernel (trapdct_mfma_kernel: more than 24 bands here; a
-context of at most 104 frames, beyond which the streamed kernel sums in compensated runs and is closer to the oracle than offline) and
+Bounds: bit identity with the offline run where it launches the fp32 kernel (trapdct_mfma_kernel: more than 24 bands, more than 16
+coefficients or a context of more than 113 frames; beyond 104 frames both kernels sum in compensated runs, through one device helper) and
 every push ends a multiple of eight frames into the file (the log-mel rows are bit-identical then, and a row of
 stream_trap_kernel depends on nothing but its own traplen log-mel rows); bit identity between two cuts of one file under the same
 condition, and between a stream alone and among others always; elsewhere the oracle bound of tests/test_gpu_parity.py (_assert_rows),
@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from ctucopy_amd import CtuError, streams_config_check, streams_rows_step
+from ctucopy_amd import CtuError, config_table, streams_config_check, streams_rows_step
 from ctucopy_amd import engine as ceng
 from oracle.oracle import Oracle
 from tests.test_gpu_parity import _assert_rows
@@ -67,15 +67,22 @@ def _eights(eng, x, frames=96):
     return [w + 7 * s] + [8 * s] * (frames // 8 - 1) + [x.size - (w + (frames // 8 * 8 - 1) * s)]
 
 
-@pytest.mark.parametrize("cfg", [C2 + T31, C2 + ["-w", "40"] + T31], ids=["512", "1024"])
-def test_pushes_of_eight_hops_are_bit_identical_to_the_offline_fp32_kernel(Engine, cfg):
-    eng = Engine(cfg)   # 26 bands: the offline run launches trapdct_mfma_kernel
-    assert streams_config_check(cfg, trap_state=True) == (ceng.CTU_OK, "", 15)
-    x = _signal(eng, 96)
+@pytest.mark.parametrize("cfg, frames", [
+    (C2 + T31, 96), (C2 + ["-w", "40"] + T31, 96),
+    (C2 + ["-fea_kind", "trapdct,103,16"], 96),         # the last short size: 26 tap groups, one accumulator chain
+    (C2 + ["-fea_kind", "trapdct,105,16"], 96),         # the first long size: both kernels close the accumulator every 8 taps (trap_comp_close)
+    (C2 + F23 + ["-fea_kind", "trapdct,255,16"], 144),  # the largest: 64 tap groups, 32 runs
+], ids=["512", "1024", "103_16", "105_16", "255_16"])
+def test_pushes_of_eight_hops_are_bit_identical_to_the_offline_fp32_kernel(Engine, cfg, frames):
+    eng = Engine(cfg)   # 26 bands, or a context of more than 113 frames: the offline run launches trapdct_mfma_kernel
+    half = _half(cfg)
+    assert config_table(cfg, "trap_path")[0] == 0
+    assert streams_config_check(cfg, trap_state=True) == (ceng.CTU_OK, "", half)
+    x = _signal(eng, frames)
     off = eng.extract([x])[0]
-    assert off.shape == (96, 26 * 8)
+    assert off.shape == (frames, eng.dims.nbands * (8 if half == 15 else 16))
     st = eng.streams(2, eng.dims.window + 8 * eng.dims.wshift, trap_state=True)
-    got = _stream(eng, st, 1, x, _eights(eng, x), cfg)
+    got = _stream(eng, st, 1, x, _eights(eng, x, frames), cfg)
     assert got.shape == off.shape and np.array_equal(got, off)
 
 
@@ -94,11 +101,11 @@ def test_arbitrary_chunking_agrees_with_the_oracle(Engine, cfg, frames, kw):
     51,20: two row blocks.  31,5: D = 115, the scalar store path.  exten: the noise state beside the trap state, at 512 and 1024 points.
     A padded tap that read a row nobody wrote would show here as a non-finite value.
 
-    Contexts of more than 104 frames (more tap groups than the offline kernel's short instantiation has) run the streamed kernel's
-    compensated form: 105_16 is the first such size (27 tap groups: six closed runs of four and a last one of three), 255_16 the
-    largest (sixteen runs).  With one fp32 accumulator chain over its 255 taps - the offline kernel's arithmetic, which Engine.extract
-    runs at this size - 255_16 is 1.914e-4 from the oracle on this input, outside the bound of 1e-4: partial sums in the hundreds for a
-    result below one.  The same log-mel rows contracted in float64 are 4.6e-5 from it."""
+    Contexts of more than 104 frames (more tap groups than the short instantiations have) run the compensated form: 105_16 is the
+    first such size (27 tap groups: thirteen closed runs of two and a last one of one), 255_16 the largest (32 runs).  With one fp32
+    accumulator chain over its 255 taps 255_16 was 1.914e-4 from the oracle on this input, outside the bound of 1e-4: partial sums in the
+    hundreds for a result below one.  The same log-mel rows contracted in float64 are 4.6e-5 from it.  Engine.extract sums the same way
+    at these sizes (tests/test_trapdct_shapes.py holds it to the same bound; the identity test above to the streamed rows bit for bit)."""
     eng = Engine(cfg)
     w, s = eng.dims.window, eng.dims.wshift
     x = _signal(eng, frames)
